@@ -12,10 +12,15 @@ timed region; each step copies the next staged batch into the graph's static inp
   python bench.py --gpus N ...          (no launcher: spawns one child process per GPU itself, before any GPU call)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+  python bench.py --full                 (the extra legs below)
+  python bench.py --dump-outputs DIR     (what the last timed step computed, as DIR/<name>.npy)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times the K steps and
+prints the line; with --full the line also carries, each measured after the timed region:
   roofline     dominant kernel class, live hipEvent timing vs the MFMA / HBM roof
+  fp32         the same workload at fp32 storage (the reference's precision), its own replica and timed region
   cpu_baseline the CPU oracle (oracle/nunet_oracle.py, kind "port") timed on this host
+(--no-roofline / --no-fp32 / --no-cpu-baseline leave one of them out of a --full run.)
 """
 import argparse
 import json
@@ -59,7 +64,15 @@ def parse(argv=None):
     ap.add_argument("--dist-dry-run", action="store_true",
                     help="rendezvous only: every rank joins a gloo group on the CPU, all-reduces its rank and rank 0 prints the ranks it saw "
                          "(exercises the launcher / self-spawn path without a GPU)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's timed region also run the roofline, fp32 and CPU-baseline legs (off: the line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step left to its caller (logits, loss, parameters, gradients, "
+                         "momentum, BatchNorm running statistics) as DIR/<name>.npy; rank 0 only")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port():
@@ -169,6 +182,35 @@ def kernel_source_hash():
     return _sha16([os.path.join(d, f) for f in KERNEL_SOURCES])
 
 
+DUMP_MAX_ELEMS = 1 << 21     # per array (8 MB as fp32): the arrays below stay under 64 MB in all at every size
+
+
+def dump_outputs(ts, out_dir):
+    """What the step's caller holds after the last step, as <name>.npy (fp32; the meters fp64). An array longer than
+    DUMP_MAX_ELEMS is reduced to a fixed sample: the same seeded, sorted flat indices for a given length in every run."""
+    import numpy as np
+    import torch
+    eng = ts.eng
+    arrays = {
+        "logits": ts.logits,            # [heads, N, classes, H, W] of the last step's forward
+        "loss": ts.loss_out,            # that step's loss per head, then their mean
+        "meters": ts.meters,            # loss / IoU sums over the steps since the meters were reset
+        "params": eng.flat_params,      # fp32 master weights after the last SGD update
+        "grads": eng.flat_grads,        # the last step's gradients (p.grad)
+        "momentum": ts.mom,
+        "bn_running": eng.bnbuf,        # BatchNorm running mean / var, state_dict order
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(a.size).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     argv = sys.argv[1:]
     args = parse(argv)
@@ -232,6 +274,8 @@ def main():
         return ts, dt
 
     ts, dt = timed_run(args.dtype, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ts, args.dump_outputs)     # before the --full legs: the roofline leg runs further steps on ts
     loss, iou = ts.epoch_stats()
     dp_info = None
     if world > 1 or force_dp:
@@ -247,7 +291,7 @@ def main():
                 "ms": {"%s/%s" % k: round(v, 4) for k, v in ts.executor_choice.items()} if ts.executor_choice else None}
 
     roofline = None
-    if not args.no_roofline and rank == 0 and world == 1:     # single-process leg: no collectives inside
+    if args.full and not args.no_roofline and rank == 0 and world == 1:     # single-process leg: no collectives inside
         # Live per-kernel timing of the same step: eager, single-lane issue (kernels alone on the device), every launch
         # through hipExtLaunchKernelGGL with a start/stop event pair = the dispatch's own begin/end timestamps (the
         # figures rocprofv3 --kernel-trace reports; profiles/r03_summary.md holds that trace of the same command).
@@ -313,7 +357,7 @@ def main():
     # finished/archs1.py:14-32 has no autocast anywhere, and north_star's 1e-4 parity bound is an fp32 bound): a second
     # timed region after the headline one, its own replica and graph, >= 20 steps. Reported beside the line, never as `value`.
     fp32 = None
-    if rank == 0 and world == 1 and not args.no_fp32 and args.dtype != "fp32":
+    if args.full and rank == 0 and world == 1 and not args.no_fp32 and args.dtype != "fp32":
         del ts
         torch.cuda.empty_cache()
         k32 = max(20, args.fp32_steps)
@@ -326,7 +370,7 @@ def main():
                 "note": "same workload and step, fp32 storage and exact-fp32 MFMA (v_mfma_f32_32x32x2_f32): the reference's precision"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, args.cpu_seconds)
 
     if rank == 0:

@@ -67,3 +67,30 @@ def test_decoded_uint8_set_is_the_float_set_before_the_sample_pipeline():
     ref = (((raw.astype(np.float64) / 255.0 - mean) / std) / 255.0).transpose(0, 3, 1, 2).astype(np.float32)   # dataset.py:66-74
     assert np.array_equal(ref, img)
     assert np.array_equal((m8 / 255.0).transpose(0, 3, 1, 2).astype(np.float32), msk)
+
+
+def test_bench_output_dump_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the same state gives the same files run after run (parameter-sized arrays through the same
+    seeded sample), every array fp32 / fp64, under 64 MB in all at the flagship's parameter count."""
+    from types import SimpleNamespace
+    spec = importlib.util.spec_from_file_location("nunet_bench_driver", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda: None)
+    g = torch.Generator().manual_seed(5)
+    npar = sum(p.numel() for p in nunet_amd.archs.NestedUNet(1, 3, False).parameters())
+    eng = SimpleNamespace(flat_params=torch.randn(npar, generator=g), flat_grads=torch.randn(npar, generator=g),
+                          bnbuf=torch.randn(3000, generator=g))
+    ts = SimpleNamespace(eng=eng, logits=torch.randn(1, 16, 1, 96, 96, generator=g), loss_out=torch.randn(2, generator=g),
+                         meters=torch.arange(4, dtype=torch.float64), mom=torch.randn(npar, generator=g))
+    bench.dump_outputs(ts, str(tmp_path / "a"))
+    bench.dump_outputs(ts, str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(n + ".npy" for n in ("logits", "loss", "meters", "params", "grads", "momentum", "bn_running"))
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) < 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    assert np.array_equal(np.load(tmp_path / "a" / "logits.npy"), ts.logits.numpy())
+    p = np.load(tmp_path / "a" / "params.npy")
+    assert p.size == bench.DUMP_MAX_ELEMS < npar and np.isin(p, ts.eng.flat_params.numpy()).all()

@@ -42,7 +42,18 @@ def test_oracle_matches_reference_goldens(name, synth):
     loss.backward()
     names = [str(s) for s in g["grad_names"]]
     assert names == list(net.params.keys())
+    net64 = None
     for k, nm in enumerate(names):
+        if nm.endswith("conv1.bias") or nm.endswith("conv2.bias"):
+            # analytically zero (a training-mode BatchNorm follows): the golden holds the reference's fp32 rounding noise, whose
+            # exact values follow the host's summation order (thread count, SIMD width). Asserted instead: the fp32 noise is of
+            # the reference's own size, and in fp64 the same gradient is zero far below any fp32 rounding.
+            if net64 is None:
+                net64 = O.OracleNet(synth.closed_form_state(ncls, cin, ds, fresh), ncls, cin, ds, dtype=torch.float64)
+                O.criterion_ds(net64(x.double()), t.double())[0].backward()
+            assert float(net.params[nm].grad.abs().max()) <= 10 * g["grad_amax"][k] + 1e-9, nm
+            assert float(net64.params[nm].grad.abs().max()) < 1e-10, nm
+            continue
         s, l2, smp = _summ(net.params[nm].grad)
         assert abs(l2 - g["grad_l2"][k]) <= 1e-4 * g["grad_l2"][k] + 1e-9, nm
         np.testing.assert_allclose(smp, g["grad_sample"][k], atol=1e-6 + 1e-4 * g["grad_amax"][k], err_msg=nm)

@@ -11,7 +11,7 @@ for lib in "" "$V"; do
   timeout -k 10 200 python tools/wgrad_layers.py >> $O 2>&1
   HW=256 NB=32 MAXLEV=3 timeout -k 10 200 python tools/conv_layers.py >> $O 2>&1
   HW=256 NB=32 timeout -k 10 200 python tools/wgrad_layers.py >> $O 2>&1
-  timeout -k 10 300 python bench.py --no-cpu-baseline --no-fp32 --steps 200 2>&1 | grep '^{' >> $O
-  timeout -k 10 300 python bench.py --no-cpu-baseline --no-fp32 --size 256 --batch 32 --steps 20 2>&1 | grep '^{' >> $O
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-fp32 --steps 200 2>&1 | grep '^{' >> $O
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-fp32 --size 256 --batch 32 --steps 20 2>&1 | grep '^{' >> $O
 done
 grep -v amdgpu.ids $O | grep "^sum\|^===\|^{" | cut -c1-260
