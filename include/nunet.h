@@ -294,6 +294,36 @@ int nunet_sgd_step(float* p, const float* g, float* mom, int64_t n, const float*
                    float grad_scale, nunet_stream_t s);
 
 /* ------------------------------------------------------------------------ */
+/* Generic optimiser step: SGD as above, or optim.Adam (trains.py:225-227)   */
+/* ------------------------------------------------------------------------ */
+enum { NUNET_OPT_SGD = 0, NUNET_OPT_ADAM = 1 };
+/* kind NUNET_OPT_SGD: torch.optim.SGD(momentum, weight_decay, nesterov); state0 = momentum buffer, lr = device lr.
+ * kind NUNET_OPT_ADAM: torch.optim.Adam(betas, eps, weight_decay), amsgrad off, L2 decay added to the gradient (not AdamW);
+ *   state0 / state1 = exp_avg / exp_avg_sq (flat fp32, parameter order); adam_scal = the two floats
+ *   {lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)} that nunet_adam_prepare leaves for step t. Per element:
+ *     g += wd * p;  m = lerp(m, g, 1 - beta1);  v = beta2 * v + (1 - beta2) * g * g;
+ *     p -= adam_scal[0] * (m / (sqrt(v) * adam_scal[1] + eps))
+ *   beta1 / beta2 are doubles (torch's Python floats): 1 - beta is formed in double and rounded to fp32 once, as torch does. */
+typedef struct {
+  int32_t kind;
+  float momentum;
+  double beta1, beta2;
+  float eps, weight_decay;
+  int32_t nesterov;
+  const float* lr;         /* SGD: device learning rate */
+  const float* adam_scal;  /* Adam: device {step_size, 1/sqrt(bias_correction2)} (nunet_adam_prepare) */
+  float* state0;
+  float* state1;
+} nunet_optim;
+/* Adam bookkeeping of one step, a 1-thread kernel: *step_dev += 1 (fp32, torch's capturable step), then adam_scal for that
+ * step from the device lr (bias corrections in double, rounded to fp32 once). Kernel arguments are frozen when a step is
+ * captured, so t and lr live on the device; issue it on the caller's stream ahead of the step's forward pass, so that every
+ * update launch of the step - in-pass ones included - sees the same t. */
+int nunet_adam_prepare(const float* lr_dev, double beta1, double beta2, float* step_dev, float* adam_scal, nunet_stream_t s);
+/* Flat Adam step over n fp32 elements (p, g and the state in the same flat order); g is read as g * grad_scale. */
+int nunet_adam_step(float* p, const float* g, const nunet_optim* opt, int64_t n, float grad_scale, nunet_stream_t s);
+
+/* ------------------------------------------------------------------------ */
 /* layout helpers                                                            */
 /* ------------------------------------------------------------------------ */
 /* Device-side input pipeline (reference dataset.py:66-74 + trains.py:258-259,266): uint8 HWC batch ->
@@ -391,6 +421,13 @@ int nunet_plan_set_inpass_update(nunet_plan* p, float* params, float* momentum, 
  * one launch instead of unpack + nunet_sgd_step, no OIHW gradient round trip unless `grads` is given. */
 int nunet_plan_sgd(nunet_plan* p, float* params, float* momentum, void* arena, size_t arena_bytes, const float* lr_dev, float mom, float wd,
                    int32_t nesterov, float grad_scale, float* grads, nunet_stream_t s);
+/* The fused steps above with any optimiser (nunet_optim): repack = 0 is nunet_plan_sgd's launch (the next forward repacks),
+ * repack = 1 is nunet_plan_update's (both packed layouts written). With an SGD `opt` the results are those of
+ * nunet_plan_sgd / nunet_plan_update bit for bit. */
+int nunet_plan_opt_step(nunet_plan* p, float* params, const nunet_optim* opt, void* arena, size_t arena_bytes, float grad_scale,
+                        float* grads, int32_t repack, nunet_stream_t s);
+/* nunet_plan_set_inpass_update with any optimiser (the struct is copied; params = NULL: off). */
+int nunet_plan_set_inpass_opt(nunet_plan* p, float* params, const nunet_optim* opt, float grad_scale, float* grads);
 /* Repack the weight layouts from the fp32 parameters (what nunet_plan_forward does first unless told they are current). */
 int nunet_plan_repack(nunet_plan* p, const float* params, void* arena, size_t arena_bytes, nunet_stream_t s);
 /* Multi-lane issue (default on; env NUNET_MULTISTREAM=0 disables): the plan forks onto

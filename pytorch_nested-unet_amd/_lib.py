@@ -98,6 +98,16 @@ class ProfEntry(C.Structure):
                 ("bytes", C.c_double)]
 
 
+OPT_SGD, OPT_ADAM = 0, 1    # NUNET_OPT_* in include/nunet.h
+
+
+class Optim(C.Structure):
+    """nunet_optim: which optimiser a generic step entry runs, its hyper-parameters and state pointers."""
+    _fields_ = [("kind", _i32), ("momentum", _f32), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", _f32), ("weight_decay", _f32), ("nesterov", _i32),
+                ("lr", _vp), ("adam_scal", _vp), ("state0", _vp), ("state1", _vp)]
+
+
 class PlanCfg(C.Structure):
     _fields_ = [("N", _i32), ("H", _i32), ("W", _i32),
                 ("input_channels", _i32), ("num_classes", _i32), ("deep_supervision", _i32),
@@ -136,6 +146,8 @@ _SIG = {
     "nunet_iou_counts": (_i32, [_vp, _vp, _i64, _f32, _vp, _vp]),
     "nunet_sigmoid_u8": (_i32, [_vp, _vp, _vp, _i64, _vp]),
     "nunet_sgd_step": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32, _f32, _i32, _i32, _f32, _vp]),
+    "nunet_adam_prepare": (_i32, [_vp, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "nunet_adam_step": (_i32, [_vp, _vp, C.POINTER(Optim), _i64, _f32, _vp]),
     "nunet_preprocess_u8": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
     "nunet_nchw_to_nhwc": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "nunet_plan_create": (_vp, [C.POINTER(PlanCfg)]),
@@ -154,6 +166,8 @@ _SIG = {
     "nunet_plan_bucket0_wait": (_i32, [_vp, _vp]),
     "nunet_plan_update": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _f32, _f32, _i32, _f32, _vp, _vp]),
     "nunet_plan_set_inpass_update": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _i32, _f32, _vp]),
+    "nunet_plan_opt_step": (_i32, [_vp, _vp, C.POINTER(Optim), _vp, _sz, _f32, _vp, _i32, _vp]),
+    "nunet_plan_set_inpass_opt": (_i32, [_vp, _vp, C.POINTER(Optim), _f32, _vp]),
     "nunet_plan_repack": (_i32, [_vp, _vp, _vp, _sz, _vp]),
     "nunet_plan_sgd": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _f32, _f32, _i32, _f32, _vp, _vp]),
     "nunet_plan_feature": (_i64, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

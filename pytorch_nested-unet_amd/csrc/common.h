@@ -338,3 +338,55 @@ __device__ __forceinline__ float wave_sum(float v) {
    : (dt) == NUNET_BF16 ? FN<bf16_t>(__VA_ARGS__)                     \
    : (dt) == NUNET_F16  ? FN<f16_t>(__VA_ARGS__)                      \
                         : (nunet_set_error("bad dtype %d", (int)(dt)), NUNET_EINVAL))
+
+// ---------------------------------------------------------------------------
+// Optimiser functors of the fused update kernels (plan.hip) and the flat Adam step (elementwise.hip): the per-element step
+// with its state pointers (NS fp32 buffers in flat parameter order). begin() reads the device scalars once per thread;
+// one(p, g, s) takes the (scaled, undecayed) gradient and the element's state, updates the state in place and returns the
+// new parameter. Built on the host from a nunet_optim by opt_from() (plan.hip) / the flat entry (elementwise.hip).
+// ---------------------------------------------------------------------------
+struct OptSgd {   // torch.optim.SGD (reference trains.py:229-231): the arithmetic the SGD kernels always had, bit for bit
+  static constexpr int NS = 1;
+  float* st[1];
+  const float* lr_dev;
+  float momc, wd;
+  int nesterov;
+  float lr;
+  __device__ __forceinline__ void begin() { lr = lr_dev[0]; }
+  __device__ __forceinline__ float one(float p, float g, float* s) const {
+    float gv = g + wd * p;
+    if (momc != 0.f) {
+      const float b = momc * s[0] + gv;
+      s[0] = b;
+      gv = nesterov ? gv + momc * b : b;
+    }
+    return p - lr * gv;
+  }
+};
+struct OptAdam {  // torch.optim.Adam, amsgrad=False, maximize=False, L2 decay in the gradient (reference trains.py:225-227)
+  static constexpr int NS = 2;
+  float* st[2];             // exp_avg, exp_avg_sq
+  const float* scal_dev;    // {lr / (1 - b1^t), 1 / sqrt(1 - b2^t)}, written by adam_prepare_kernel for this step
+  float omb1, b2, omb2, eps, wd;   // 1 - beta1, beta2, 1 - beta2 rounded from double once (torch's Python-float scalars)
+  float step_size, inv_sqrt_bc2;
+  __device__ __forceinline__ void begin() { step_size = scal_dev[0]; inv_sqrt_bc2 = scal_dev[1]; }
+  __device__ __forceinline__ float one(float p, float g, float* s) const {
+    const float gd = g + wd * p;                            // grad.add(param, alpha=wd)
+    const float m = s[0] + omb1 * (gd - s[0]);              // exp_avg.lerp_(grad, 1 - beta1)
+    const float v = s[1] * b2 + omb2 * (gd * gd);           // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+    s[0] = m;
+    s[1] = v;
+    const float denom = sqrtf(v) * inv_sqrt_bc2 + eps;     // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
+    return p - step_size * (m / denom);                     // param.addcdiv_(exp_avg, denom, value=-step_size)
+  }
+};
+// one element at flat index idx: state in, step, state out; returns the new parameter (the caller stores it)
+template <typename O> __device__ __forceinline__ float opt_elem(const O& o, float p, float g, long long idx) {
+  float s[O::NS];
+#pragma unroll
+  for (int k = 0; k < O::NS; ++k) s[k] = o.st[k][idx];
+  const float pn = o.one(p, g, s);
+#pragma unroll
+  for (int k = 0; k < O::NS; ++k) o.st[k][idx] = s[k];
+  return pn;
+}

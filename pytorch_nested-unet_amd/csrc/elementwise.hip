@@ -1264,3 +1264,62 @@ extern "C" int nunet_sgd_step(float* p, const float* g, float* mom, int64_t n, c
   NUNET_LAUNCH(sgd_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, (hipStream_t)s, p, g, mom, n, lr_dev, momentum, weight_decay, nesterov, first, grad_scale);
   return nunet_check_launch("sgd_step");
 }
+
+// ---------------------------------------------------------------------------
+// Adam (torch.optim.Adam semantics, amsgrad off; the per-element arithmetic is OptAdam in common.h)
+// ---------------------------------------------------------------------------
+// One thread: t = ++step (fp32, torch's capturable step), then the step's two scalars from the device lr. torch forms the
+// bias corrections from Python floats (double) and hands fp32 kernels scalars rounded once: so does this.
+__global__ void adam_prepare_kernel(const float* __restrict__ lr_dev, double b1, double b2, float* __restrict__ step, float* __restrict__ scal) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const float t = step[0] + 1.f;
+  step[0] = t;
+  const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
+  scal[0] = (float)((double)lr_dev[0] / bc1);
+  scal[1] = (float)(1.0 / sqrt(bc2));
+}
+extern "C" int nunet_adam_prepare(const float* lr_dev, double beta1, double beta2, float* step_dev, float* adam_scal, nunet_stream_t s) {
+  NUNET_REQUIRE(lr_dev && step_dev && adam_scal, "adam_prepare: null pointer");
+  NUNET_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adam_prepare: betas must lie in [0, 1)");
+  NUNET_LAUNCH(adam_prepare_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, lr_dev, beta1, beta2, step_dev, adam_scal);
+  return nunet_check_launch("adam_prepare");
+}
+
+// Flat step: four elements per thread as 16-byte runs when every array is 16-byte aligned, scalar tail for n % 4
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, OptAdam o, int64_t n, float gscale, int vec) {
+  o.begin();
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+  const int64_t n4 = vec ? n / 4 : 0;
+  for (int64_t i = tid; i < n4; i += nth) {
+    f32x4 pv = reinterpret_cast<const f32x4*>(p)[i];
+    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+    f32x4 mv = reinterpret_cast<const f32x4*>(o.st[0])[i], vv = reinterpret_cast<const f32x4*>(o.st[1])[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float s[2] = {mv[j], vv[j]};
+      pv[j] = o.one(pv[j], gv[j] * gscale, s);
+      mv[j] = s[0];
+      vv[j] = s[1];
+    }
+    reinterpret_cast<f32x4*>(o.st[0])[i] = mv;
+    reinterpret_cast<f32x4*>(o.st[1])[i] = vv;
+    reinterpret_cast<f32x4*>(p)[i] = pv;
+  }
+  for (int64_t i = 4 * n4 + tid; i < n; i += nth) p[i] = opt_elem(o, p[i], g[i] * gscale, i);
+}
+extern "C" int nunet_adam_step(float* p, const float* g, const nunet_optim* opt, int64_t n, float grad_scale, nunet_stream_t s) {
+  NUNET_REQUIRE(p && g && opt && n > 0, "adam_step: bad args");
+  NUNET_REQUIRE(opt->kind == NUNET_OPT_ADAM, "adam_step: optimiser kind %d is not NUNET_OPT_ADAM", (int)opt->kind);
+  NUNET_REQUIRE(opt->adam_scal && opt->state0 && opt->state1, "adam_step: Adam needs adam_scal, state0 and state1");
+  NUNET_REQUIRE(opt->beta1 >= 0.0 && opt->beta1 < 1.0 && opt->beta2 >= 0.0 && opt->beta2 < 1.0, "adam_step: betas must lie in [0, 1)");
+  NUNET_REQUIRE(opt->eps > 0.f, "adam_step: eps must be > 0");
+  OptAdam o;
+  memset(&o, 0, sizeof(o));
+  o.st[0] = opt->state0; o.st[1] = opt->state1; o.scal_dev = opt->adam_scal;
+  o.omb1 = (float)(1.0 - opt->beta1); o.b2 = (float)opt->beta2; o.omb2 = (float)(1.0 - opt->beta2);
+  o.eps = opt->eps; o.wd = opt->weight_decay;
+  const int vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)opt->state0 | (uintptr_t)opt->state1) & 15) == 0;
+  ProfScope ps(PC_SGD, 0, (double)n * 28, (hipStream_t)s);
+  NUNET_LAUNCH(adam_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, (hipStream_t)s, p, g, o, n, grad_scale, vec);
+  return nunet_check_launch("adam_step");
+}

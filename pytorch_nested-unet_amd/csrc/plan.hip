@@ -262,24 +262,14 @@ __global__ __launch_bounds__(256) void unpack_tiled_kernel(const float* __restri
 // also steps the layer's conv bias and BatchNorm gamma / beta; blocks past the last tile own the 1x1 heads
 // (sum of their gradient slabs, then the same step). torch.optim.SGD semantics (reference trains.py:229-231).
 // ---------------------------------------------------------------------------------------------------------
-struct UpdP { float* params; float* mom; const float* scratch; float* grads; const float* lr; float momc, wd, gscale; int nesterov; int nconv;
+struct UpdP { float* params; const float* scratch; float* grads; float gscale; int nconv;
               int bid_off; };   // first block's index in the whole-model block numbering (a launch may cover one VGGBlock's tiles, or the heads)
 
-__device__ __forceinline__ float sgd_one(float p, float g, float* m, const UpdP& u, float lr) {
-  float gv = g + u.wd * p;
-  if (u.momc != 0.f) {
-    const float b = u.momc * (*m) + gv;
-    *m = b;
-    gv = u.nesterov ? gv + u.momc * b : b;
-  }
-  return p - lr * gv;
-}
-
-template <typename T>
-__global__ __launch_bounds__(512) void update_kernel(UpdP u, T* __restrict__ arena, PackTab tab, UnpackTab ut) {
+template <typename T, typename O>
+__global__ __launch_bounds__(512) void update_kernel(UpdP u, O o, T* __restrict__ arena, PackTab tab, UnpackTab ut) {
   __shared__ float s_t[32][32 * 9 + 1];
   __shared__ float s_g[32][32 * 9 + 1];
-  const float lr = u.lr[0];
+  o.begin();
   const int bid = (int)blockIdx.x + u.bid_off;
   if (bid >= tab.ntiles) {
     // ---- 1x1 head: sum the gradient slabs (fixed order), then the step; <= 264 elements
@@ -304,9 +294,7 @@ __global__ __launch_bounds__(512) void update_kernel(UpdP u, T* __restrict__ are
         g *= u.gscale;
         const long long idx = en.dst + e0 + threadIdx.x;
         if (u.grads) u.grads[idx] = g;
-        float m = u.mom[idx];
-        const float pn = sgd_one(u.params[idx], g, &m, u, lr);
-        u.mom[idx] = m; u.params[idx] = pn;
+        u.params[idx] = opt_elem(o, u.params[idx], g, idx);
       }
       __syncthreads();
     }
@@ -345,9 +333,8 @@ __global__ __launch_bounds__(512) void update_kernel(UpdP u, T* __restrict__ are
       const long long idx = en.src + ((long long)(co0 + ro) * en.cin + ci0) * 9 + k;
       const float g = s_g[ro][k] * u.gscale;
       if (u.grads) u.grads[idx] = g;
-      float m = u.mom[idx];
-      const float pn = sgd_one(s_t[ro][k], g, &m, u, lr);
-      u.mom[idx] = m; u.params[idx] = pn;
+      const float pn = opt_elem(o, s_t[ro][k], g, idx);
+      u.params[idx] = pn;
       s_t[ro][k] = pn;
     }
   }
@@ -359,9 +346,7 @@ __global__ __launch_bounds__(512) void update_kernel(UpdP u, T* __restrict__ are
       const long long idx = ue.dst + nw + (long long)v * en.cout + c;
       const float g = dw[9LL * en.cout * en.cinpad + (long long)v * en.cout + c] * u.gscale;
       if (u.grads) u.grads[idx] = g;
-      float m = u.mom[idx];
-      const float pn = sgd_one(u.params[idx], g, &m, u, lr);
-      u.mom[idx] = m; u.params[idx] = pn;
+      u.params[idx] = opt_elem(o, u.params[idx], g, idx);
     }
   }
   __syncthreads();
@@ -461,7 +446,7 @@ struct PlanRt {  // runtime objects owned by the plan (host side only)
   // so the real timeline of an (unprofiled) hipGraph replay can be read back (tools/stamp_timeline.py)
   unsigned long long* stamps;              // device, [2][STAMP_CAP]
   // nunet_plan_set_inpass_update: the optimiser step of every VGGBlock as an op of the backward pass (params == NULL: off)
-  struct { float* params; float* mom; const float* lr; float momc, wd, gscale; int nesterov; float* grads; } upd;
+  struct { float* params; float gscale; float* grads; int kind; OptSgd sgd; OptAdam adam; } upd;
   int lane_low_priority;                   // side lanes of the flag-synchronised program at the lowest stream priority (default 1)
   int calibrating;                         // nunet_plan_calibrate: single lane + stamps, to measure every op's isolated cost
   std::map<std::string, float> op_cost[2]; // measured cost (us) by op name, per pass; empty: the built-in estimates
@@ -1484,6 +1469,57 @@ extern "C" int nunet_plan_grad_scratch(const nunet_plan* P, int64_t* byte_offset
   return NUNET_OK;
 }
 
+// Optimiser functor of a nunet_optim (validated first: every entry refuses a bad one before touching the device)
+static int opt_check(const nunet_optim* o, const char* what) {
+  NUNET_REQUIRE(o, "%s: null optimiser", what);
+  if (o->kind == NUNET_OPT_SGD) {
+    NUNET_REQUIRE(o->lr && o->state0, "%s: SGD needs lr and state0 (momentum buffer)", what);
+  } else if (o->kind == NUNET_OPT_ADAM) {
+    NUNET_REQUIRE(o->adam_scal && o->state0 && o->state1, "%s: Adam needs adam_scal, state0 (exp_avg) and state1 (exp_avg_sq)", what);
+    NUNET_REQUIRE(o->beta1 >= 0.0 && o->beta1 < 1.0 && o->beta2 >= 0.0 && o->beta2 < 1.0, "%s: betas must lie in [0, 1)", what);
+    NUNET_REQUIRE(o->eps > 0.f, "%s: eps must be > 0", what);
+  } else {
+    NUNET_REQUIRE(false, "%s: unknown optimiser kind %d", what, (int)o->kind);
+  }
+  return NUNET_OK;
+}
+static OptSgd opt_sgd(const float* lr, float* mom, float momc, float wd, int nesterov) {
+  OptSgd o; memset(&o, 0, sizeof(o));
+  o.st[0] = mom; o.lr_dev = lr; o.momc = momc; o.wd = wd; o.nesterov = nesterov;
+  return o;
+}
+static OptAdam opt_adam(const nunet_optim* d) {
+  OptAdam o; memset(&o, 0, sizeof(o));
+  o.st[0] = d->state0; o.st[1] = d->state1; o.scal_dev = d->adam_scal;
+  o.omb1 = (float)(1.0 - d->beta1); o.b2 = (float)d->beta2; o.omb2 = (float)(1.0 - d->beta2);
+  o.eps = d->eps; o.wd = d->weight_decay;
+  return o;
+}
+
+static void update_tiles(nunet_plan* P) {
+  PackTab& tab = P->ptab;
+  int nt = 0;
+  for (int i = 0; i < tab.n; ++i) { tab.tile0[i] = nt; nt += ((tab.e[i].cout + 31) / 32) * ((tab.e[i].cinpad + 31) / 32); }
+  tab.tile0[tab.n] = nt; tab.ntiles = nt;
+}
+
+// blocks [bid0, bid0 + nblocks) of update_kernel's whole-model numbering: all of it (nunet_plan_update), one VGGBlock's
+// tiles or the heads (the in-pass step)
+template <typename O> static int launch_update_kernel(nunet_plan* P, void* arena, float* params, const O& o, float grad_scale, float* grads,
+                                                      int bid0, int nblocks, double bytes, hipStream_t st) {
+  if (nblocks <= 0) return NUNET_OK;
+  UpdP u;
+  u.params = params; u.scratch = (const float*)AB(arena, P->off_gs); u.grads = grads;
+  u.gscale = grad_scale; u.nconv = P->ptab.n; u.bid_off = bid0;
+  void* wp = AB(arena, P->off_wpack);
+  const dim3 grid(nblocks), blk(512);
+  ProfScope ps(PC_SGD, 0, bytes, st);
+  if (P->cfg.dtype == NUNET_F32) NUNET_LAUNCH((update_kernel<float, O>), grid, blk, 0, st, u, o, (float*)wp, P->ptab, P->utab);
+  else if (P->cfg.dtype == NUNET_BF16) NUNET_LAUNCH((update_kernel<bf16_t, O>), grid, blk, 0, st, u, o, (bf16_t*)wp, P->ptab, P->utab);
+  else NUNET_LAUNCH((update_kernel<f16_t, O>), grid, blk, 0, st, u, o, (f16_t*)wp, P->ptab, P->utab);
+  return nunet_check_launch(bid0 == 0 && nblocks == P->ptab.ntiles + P->utab.n - P->ptab.n ? "plan_update" : "plan update (in pass)");
+}
+
 // Fused optimiser step on the plan's own buffers (update_kernel above): scratch -> SGD -> repacked weights.
 // `grads` (flat OIHW arena) is optional: when given it receives the (scaled) gradients as nunet_plan_backward would
 // have left them. Afterwards the packed weights in `arena` are current: the next nunet_plan_forward may be called
@@ -1492,37 +1528,15 @@ extern "C" int nunet_plan_update(nunet_plan* P, float* params, float* momentum, 
                                  int32_t nesterov, float grad_scale, float* grads, nunet_stream_t s) {
   NUNET_REQUIRE(P && params && momentum && arena && lr_dev, "plan_update: null pointer");
   ARENA_CHECK("plan_update");
-  hipStream_t st = (hipStream_t)s;
-  PackTab& tab = P->ptab;
-  int nt = 0;
-  for (int i = 0; i < tab.n; ++i) { tab.tile0[i] = nt; nt += ((tab.e[i].cout + 31) / 32) * ((tab.e[i].cinpad + 31) / 32); }
-  tab.tile0[tab.n] = nt; tab.ntiles = nt;
-  UpdP u;
-  u.params = params; u.mom = momentum; u.scratch = (const float*)AB(arena, P->off_gs); u.grads = grads; u.lr = lr_dev;
-  u.momc = mom; u.wd = wd; u.gscale = grad_scale; u.nesterov = nesterov; u.nconv = tab.n; u.bid_off = 0;
-  const int nheads = P->utab.n - tab.n;
-  ProfScope ps(PC_SGD, 0, (double)P->nparams * (grads ? 28.0 : 24.0), st);
-  void* wp = AB(arena, P->off_wpack);
-  const dim3 grid(nt + nheads), blk(512);
-  if (P->cfg.dtype == NUNET_F32) NUNET_LAUNCH((update_kernel<float>), grid, blk, 0, st, u, (float*)wp, tab, P->utab);
-  else if (P->cfg.dtype == NUNET_BF16) NUNET_LAUNCH((update_kernel<bf16_t>), grid, blk, 0, st, u, (bf16_t*)wp, tab, P->utab);
-  else NUNET_LAUNCH((update_kernel<f16_t>), grid, blk, 0, st, u, (f16_t*)wp, tab, P->utab);
-  return nunet_check_launch("plan_update");
+  update_tiles(P);
+  return launch_update_kernel(P, arena, params, opt_sgd(lr_dev, momentum, mom, wd, nesterov), grad_scale, grads, 0,
+                              P->ptab.ntiles + P->utab.n - P->ptab.n, (double)P->nparams * (grads ? 28.0 : 24.0), (hipStream_t)s);
 }
 
-// A slice of the same launch: blocks [bid0, bid0 + nblocks) of the whole-model numbering (one VGGBlock's tiles, or the heads)
+// In-pass step of blocks [bid0, bid0 + nblocks) with the optimiser nunet_plan_set_inpass_* left in the plan
 template <typename U> static int launch_update(nunet_plan* P, void* arena, const U& s, int bid0, int nblocks, hipStream_t st) {
-  if (nblocks <= 0) return NUNET_OK;
-  UpdP u;
-  u.params = s.params; u.mom = s.mom; u.scratch = (const float*)AB(arena, P->off_gs); u.grads = s.grads; u.lr = s.lr;
-  u.momc = s.momc; u.wd = s.wd; u.gscale = s.gscale; u.nesterov = s.nesterov; u.nconv = P->ptab.n; u.bid_off = bid0;
-  void* wp = AB(arena, P->off_wpack);
-  const dim3 grid(nblocks), blk(512);
-  ProfScope ps(PC_SGD, 0, 0.0, st);
-  if (P->cfg.dtype == NUNET_F32) NUNET_LAUNCH((update_kernel<float>), grid, blk, 0, st, u, (float*)wp, P->ptab, P->utab);
-  else if (P->cfg.dtype == NUNET_BF16) NUNET_LAUNCH((update_kernel<bf16_t>), grid, blk, 0, st, u, (bf16_t*)wp, P->ptab, P->utab);
-  else NUNET_LAUNCH((update_kernel<f16_t>), grid, blk, 0, st, u, (f16_t*)wp, P->ptab, P->utab);
-  return nunet_check_launch("plan update (in pass)");
+  if (s.kind == NUNET_OPT_ADAM) return launch_update_kernel(P, arena, s.params, s.adam, s.gscale, s.grads, bid0, nblocks, 0.0, st);
+  return launch_update_kernel(P, arena, s.params, s.sgd, s.gscale, s.grads, bid0, nblocks, 0.0, st);
 }
 
 // The optimiser step as part of the backward pass: with parameters set here, every whole pass (nunet_plan_backward, or
@@ -1534,23 +1548,39 @@ extern "C" int nunet_plan_set_inpass_update(nunet_plan* P, float* params, float*
                                             int32_t nesterov, float grad_scale, float* grads) {
   NUNET_REQUIRE(P && (!params || (momentum && lr_dev)), "plan_set_inpass_update: null pointer");
   auto& s = rt_of(P)->upd;
-  s.params = params; s.mom = momentum; s.lr = lr_dev; s.momc = mom; s.wd = wd; s.gscale = grad_scale; s.nesterov = nesterov; s.grads = grads;
+  memset(&s, 0, sizeof(s));
+  s.params = params; s.gscale = grad_scale; s.grads = grads; s.kind = NUNET_OPT_SGD;
+  s.sgd = opt_sgd(lr_dev, momentum, mom, wd, nesterov);
+  return NUNET_OK;
+}
+
+extern "C" int nunet_plan_set_inpass_opt(nunet_plan* P, float* params, const nunet_optim* opt, float grad_scale, float* grads) {
+  NUNET_REQUIRE(P, "plan_set_inpass_opt: null plan");
+  if (params) {
+    const int rc = opt_check(opt, "plan_set_inpass_opt");
+    if (rc != NUNET_OK) return rc;
+  }
+  auto& s = rt_of(P)->upd;
+  memset(&s, 0, sizeof(s));
+  if (!params) return NUNET_OK;
+  s.params = params; s.gscale = grad_scale; s.grads = grads; s.kind = opt->kind;
+  if (opt->kind == NUNET_OPT_ADAM) s.adam = opt_adam(opt);
+  else s.sgd = opt_sgd(opt->lr, opt->state0, opt->momentum, opt->weight_decay, opt->nesterov);
   return NUNET_OK;
 }
 
 // Optimiser step straight from the gradient scratch: replaces nunet_plan_backward_phase bit 2 +
 // nunet_sgd_step; the weights are repacked by the next nunet_plan_forward as usual.
 // unpack_tiled_kernel with the optimiser step as the epilogue of its store phase: the tile's gradients meet the OIHW
-// parameters and momentum as 16-byte runs, the flat gradient arena is written only when the caller wants it.
-__global__ __launch_bounds__(256) void unpack_sgd_tiled_kernel(UpdP u, PackTab tab, UnpackTab ut) {
+// parameters and the optimiser state as 16-byte runs, the flat gradient arena is written only when the caller wants it.
+template <typename O>
+__global__ __launch_bounds__(256) void unpack_sgd_tiled_kernel(UpdP u, O o, PackTab tab, UnpackTab ut) {
   __shared__ float s_t[32][32 * 9 + 1];
-  const float lr = u.lr[0];
+  o.begin();
   auto step1 = [&](long long idx, float g) {
     g *= u.gscale;
     if (u.grads) u.grads[idx] = g;
-    float m = u.mom[idx];
-    const float pn = sgd_one(u.params[idx], g, &m, u, lr);
-    u.mom[idx] = m; u.params[idx] = pn;
+    u.params[idx] = opt_elem(o, u.params[idx], g, idx);
   };
   if ((int)blockIdx.x >= tab.ntiles) {
     const UnpackEnt en = ut.e[(int)blockIdx.x - tab.ntiles];
@@ -1610,18 +1640,31 @@ __global__ __launch_bounds__(256) void unpack_sgd_tiled_kernel(UpdP u, PackTab t
     }
   }
   __syncthreads();
-  const bool al = ((uintptr_t)(u.params + row0) & 15) == 0 && ((uintptr_t)(u.mom + row0) & 15) == 0 && (!u.grads || ((uintptr_t)(u.grads + row0) & 15) == 0);
+  bool al = ((uintptr_t)(u.params + row0) & 15) == 0 && (!u.grads || ((uintptr_t)(u.grads + row0) & 15) == 0);
+#pragma unroll
+  for (int q = 0; q < O::NS; ++q) al = al && ((uintptr_t)(o.st[q] + row0) & 15) == 0;
   if (full && en.cin % 4 == 0 && al) {
     for (int i = threadIdx.x; i < 32 * 72; i += blockDim.x) {
       const int ro = i / 72, k4 = i - ro * 72;
       const long long idx = row0 + (long long)ro * en.cin * 9 + k4 * 4;
       const float* sp = &s_t[ro][k4 * 4];
       f32x4 g = {sp[0] * u.gscale, sp[1] * u.gscale, sp[2] * u.gscale, sp[3] * u.gscale};
-      f32x4 pv = *reinterpret_cast<const f32x4*>(u.params + idx), mv = *reinterpret_cast<const f32x4*>(u.mom + idx);
+      f32x4 pv = *reinterpret_cast<const f32x4*>(u.params + idx);
+      f32x4 sv[O::NS];
+#pragma unroll
+      for (int q = 0; q < O::NS; ++q) sv[q] = *reinterpret_cast<const f32x4*>(o.st[q] + idx);
       if (u.grads) *reinterpret_cast<f32x4*>(u.grads + idx) = g;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { float m = mv[j]; pv[j] = sgd_one(pv[j], g[j], &m, u, lr); mv[j] = m; }
-      *reinterpret_cast<f32x4*>(u.mom + idx) = mv;
+      for (int j = 0; j < 4; ++j) {
+        float s[O::NS];
+#pragma unroll
+        for (int q = 0; q < O::NS; ++q) s[q] = sv[q][j];
+        pv[j] = o.one(pv[j], g[j], s);
+#pragma unroll
+        for (int q = 0; q < O::NS; ++q) sv[q][j] = s[q];
+      }
+#pragma unroll
+      for (int q = 0; q < O::NS; ++q) *reinterpret_cast<f32x4*>(o.st[q] + idx) = sv[q];
       *reinterpret_cast<f32x4*>(u.params + idx) = pv;
     }
   } else {
@@ -1632,21 +1675,46 @@ __global__ __launch_bounds__(256) void unpack_sgd_tiled_kernel(UpdP u, PackTab t
   }
 }
 
+template <typename O> static int launch_unpack_step(nunet_plan* P, void* arena, float* params, const O& o, float grad_scale, float* grads,
+                                                    double bytes, hipStream_t st) {
+  UpdP u;
+  u.params = params; u.scratch = (const float*)AB(arena, P->off_gs); u.grads = grads;
+  u.gscale = grad_scale; u.nconv = P->ptab.n; u.bid_off = 0;
+  ProfScope ps(PC_SGD, 0, bytes, st);
+  update_tiles(P);
+  NUNET_LAUNCH((unpack_sgd_tiled_kernel<O>), dim3(P->ptab.ntiles + P->utab.n), dim3(256), 0, st, u, o, P->ptab, P->utab);
+  return nunet_check_launch("plan_sgd");
+}
+
 extern "C" int nunet_plan_sgd(nunet_plan* P, float* params, float* momentum, void* arena, size_t arena_bytes, const float* lr_dev, float mom, float wd,
                               int32_t nesterov, float grad_scale, float* grads, nunet_stream_t s) {
   NUNET_REQUIRE(P && params && momentum && arena && lr_dev, "plan_sgd: null pointer");
   ARENA_CHECK("plan_sgd");
+  return launch_unpack_step(P, arena, params, opt_sgd(lr_dev, momentum, mom, wd, nesterov), grad_scale, grads,
+                            (double)P->nparams * (grads ? 24.0 : 20.0), (hipStream_t)s);
+}
+
+// nunet_plan_sgd (repack 0) / nunet_plan_update (repack 1) with any optimiser; Adam streams its second state buffer on top
+extern "C" int nunet_plan_opt_step(nunet_plan* P, float* params, const nunet_optim* opt, void* arena, size_t arena_bytes, float grad_scale,
+                                   float* grads, int32_t repack, nunet_stream_t s) {
+  NUNET_REQUIRE(P && params && arena, "plan_opt_step: null pointer");
+  const int rc = opt_check(opt, "plan_opt_step");
+  if (rc != NUNET_OK) return rc;
+  ARENA_CHECK("plan_opt_step");
   hipStream_t st = (hipStream_t)s;
-  UpdP u;
-  u.params = params; u.mom = momentum; u.scratch = (const float*)AB(arena, P->off_gs); u.grads = grads; u.lr = lr_dev;
-  u.momc = mom; u.wd = wd; u.gscale = grad_scale; u.nesterov = nesterov; u.nconv = P->ptab.n; u.bid_off = 0;
-  ProfScope ps(PC_SGD, 0, (double)P->nparams * (grads ? 24.0 : 20.0), st);
-  PackTab& tab = P->ptab;
-  int nt = 0;
-  for (int i = 0; i < tab.n; ++i) { tab.tile0[i] = nt; nt += ((tab.e[i].cout + 31) / 32) * ((tab.e[i].cinpad + 31) / 32); }
-  tab.tile0[tab.n] = nt; tab.ntiles = nt;
-  NUNET_LAUNCH(unpack_sgd_tiled_kernel, dim3(nt + P->utab.n), dim3(256), 0, st, u, tab, P->utab);
-  return nunet_check_launch("plan_sgd");
+  const double extra = opt->kind == NUNET_OPT_ADAM ? 8.0 : 0.0;
+  if (repack) {
+    update_tiles(P);
+    const int nb = P->ptab.ntiles + P->utab.n - P->ptab.n;
+    const double bytes = (double)P->nparams * ((grads ? 28.0 : 24.0) + extra);
+    if (opt->kind == NUNET_OPT_ADAM) return launch_update_kernel(P, arena, params, opt_adam(opt), grad_scale, grads, 0, nb, bytes, st);
+    return launch_update_kernel(P, arena, params, opt_sgd(opt->lr, opt->state0, opt->momentum, opt->weight_decay, opt->nesterov),
+                                grad_scale, grads, 0, nb, bytes, st);
+  }
+  const double bytes = (double)P->nparams * ((grads ? 24.0 : 20.0) + extra);
+  if (opt->kind == NUNET_OPT_ADAM) return launch_unpack_step(P, arena, params, opt_adam(opt), grad_scale, grads, bytes, st);
+  return launch_unpack_step(P, arena, params, opt_sgd(opt->lr, opt->state0, opt->momentum, opt->weight_decay, opt->nesterov),
+                            grad_scale, grads, bytes, st);
 }
 
 // Repack the 16-bit weight layouts from the fp32 master parameters (what nunet_plan_forward does first unless told

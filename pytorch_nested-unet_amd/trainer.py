@@ -1,13 +1,13 @@
 """Fused training step: the loop body of reference trains.py:113-135
 (forward, BCEDiceLoss (mean over heads under deep supervision, :118-124), IoU on
-the last head, backward, SGD(momentum, wd) :229-231,133) enqueued as ONE hipGraph
+the last head, backward, SGD(momentum, wd) :229-231,133 or Adam :225-227) enqueued as ONE hipGraph
 replay per step, with no host synchronisation: loss and IoU counts stay on the
 device and are read back only when the caller asks (AverageMeter semantics of
 utils.py:17-33 are kept by `epoch_stats`).
 
 Data parallel (new capability): one process per GPU, one gradient
 all-reduce per step over RCCL, buckets in gradient-ready order. Replica state:
-  * parameters, momentum and BatchNorm buffers are broadcast from rank 0 when the
+  * parameters, optimiser state and BatchNorm buffers are broadcast from rank 0 when the
     TrainStep is built (what DistributedDataParallel does at construction), so ranks
     that initialised differently or loaded a checkpoint on rank 0 only start identical;
   * BatchNorm batch statistics stay LOCAL to a replica (plain nn.BatchNorm2d semantics,
@@ -17,6 +17,7 @@ all-reduce per step over RCCL, buckets in gradient-ready order. Replica state:
     broadcasts them before validation / checkpointing (train.py does);
   * p.grad holds the rank-MEAN gradient in every step layout (as DDP leaves it).
 """
+import ctypes as C
 import math
 import os
 
@@ -24,13 +25,14 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
+from .optim_state import flat_to_torch_state, torch_state_to_flat
 from .parallel import allreduce_flat_, broadcast_flat_
 
 
 class TrainStep:
     def __init__(self, model, batch_shape, lr=1e-3, momentum=0.9, weight_decay=1e-4, nesterov=False,
                  use_graph=True, process_group=None, keep_grads=True, fused_update=None, loss="BCEDiceLoss", input_u8=False,
-                 schedule=None, segmented=None):
+                 schedule=None, segmented=None, optimizer="SGD", betas=(0.9, 0.999), eps=1e-8):
         """loss: 'BCEDiceLoss' (reference losses.py:103-117, the default of trains.py:58) or 'LovaszHingeLoss'
         (losses.py:120-129, the loss of the reference's published table README.md:102-108; one class only) - both run
         inside the step's graph and under data parallel.
@@ -46,7 +48,12 @@ class TrainStep:
                     True - single-stream graph segments with events between graph launches
         Both None (default): single-process training times (False, 'lanes') against ('flags', 'list') on the captured step and
         keeps the faster (self.executor_choice); data-parallel training keeps (False, 'lanes'), whose graph can hold the RCCL
-        exchange. NUNET_SCHEDULE / NUNET_SEGMENTED force a form (tools)."""
+        exchange. NUNET_SCHEDULE / NUNET_SEGMENTED force a form (tools).
+        optimizer: 'SGD' (momentum, weight_decay, nesterov; reference trains.py:229-231) or 'Adam' (betas, eps, weight_decay as
+        L2 decay in the gradient, amsgrad off; trains.py:225-227). Either runs inside the step in every fused_update layout;
+        Adam keeps flat exp_avg / exp_avg_sq, a device step counter and the step's two bias-correction scalars, refreshed by a
+        1-thread launch at the head of every step (nunet_adam_prepare). optimizer_state_dict() / load_optimizer_state_dict()
+        speak torch.optim's state-dict format."""
         self.model = model
         self.eng = model.engine()
         dev = self.eng.device
@@ -95,8 +102,24 @@ class TrainStep:
         # device-side epoch meters: [sum of step losses, sum of step IoUs, last intersection, last union]
         self.meters = torch.zeros(4, dtype=torch.float64, device=dev)
         self.lr = torch.full((1,), lr, dtype=torch.float32, device=dev)
-        self.mom = torch.zeros_like(self.eng.flat_params)
+        if optimizer not in ("SGD", "Adam"):
+            raise L.NunetError("TrainStep: optimizer %r is not 'SGD' or 'Adam'" % (optimizer,))
+        self.optimizer = optimizer
         self.momentum, self.wd, self.nesterov = momentum, weight_decay, nesterov
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        if optimizer == "SGD":
+            self.mom = torch.zeros_like(self.eng.flat_params)
+            self.opt_state = [self.mom]
+        else:
+            self.mom = None
+            self.exp_avg = torch.zeros_like(self.eng.flat_params)
+            self.exp_avg_sq = torch.zeros_like(self.eng.flat_params)
+            self.adam_step = torch.zeros(1, dtype=torch.float32, device=dev)      # torch's step, as its capturable form keeps it
+            self.adam_scal = torch.zeros(2, dtype=torch.float32, device=dev)      # {lr / (1 - b1^t), 1 / sqrt(1 - b2^t)} of this step
+            self.opt_state = [self.exp_avg, self.exp_avg_sq, self.adam_step]
+            self._optim = L.Optim(kind=L.OPT_ADAM, momentum=0.0, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
+                                  weight_decay=weight_decay, nesterov=0, lr=L.ptr(self.lr).value, adam_scal=L.ptr(self.adam_scal).value,
+                                  state0=L.ptr(self.exp_avg).value, state1=L.ptr(self.exp_avg_sq).value)
         self.steps = 0
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (process_group is not None or dist.is_initialized()) else 1
@@ -156,10 +179,10 @@ class TrainStep:
         self._b0_armed = L.lib().nunet_plan_bucket0_enable(self.pl.handle, 1 if on else 0) == 1
 
     def broadcast_state(self, src=0):
-        """Rank `src`'s parameters, momentum and BatchNorm buffers become every rank's (construction time; also after
-        loading a checkpoint on one rank)."""
+        """Rank `src`'s parameters, optimiser state (momentum; Adam's moments and step) and BatchNorm buffers become every
+        rank's (construction time; also after loading a checkpoint on one rank)."""
         eng = self.eng
-        for t in (eng.flat_params, self.mom, eng.bnbuf):
+        for t in [eng.flat_params] + self.opt_state + [eng.bnbuf]:
             broadcast_flat_(t, src, self.pg)
         nbt = eng.nbt.to(torch.float64)          # (gloo / RCCL both take floating tensors; counts are exact in fp64)
         broadcast_flat_(nbt, src, self.pg)
@@ -181,6 +204,11 @@ class TrainStep:
         lib, eng, pl = L.lib(), self.eng, self.pl
         st = L.stream()
         flags = 3 if (self.fused_update in (1, 3) and self._packed) else 1
+        if self.optimizer == "Adam":
+            # t += 1 and this step's bias corrections, ahead of the forward pass: every update launch of the step (in-pass ones on
+            # any lane included) is ordered behind it
+            L.check(lib.nunet_adam_prepare(L.ptr(self.lr), self.betas[0], self.betas[1], L.ptr(self.adam_step), L.ptr(self.adam_scal), st),
+                    "adam_prepare")
         if self.input_u8:
             # the sample pipeline on the device: image -> the plan's padded NHWC tile, mask -> {0,1} fp32 NCHW target
             L.check(lib.nunet_plan_stage_u8(pl.handle, L.ptr(self.x_u8), L.ptr(self._mean), L.ptr(self._std), L.ptr(self.aug), 1.0 / 255.0,
@@ -208,6 +236,11 @@ class TrainStep:
         eng, pl = self.eng, self.pl
         if self.fused_update == 3:      # already done, block by block, inside the backward pass
             return
+        if self.optimizer == "Adam":    # layout 2: repack 0, layout 1: repack 1 (the same launches, Adam instantiations)
+            L.check(L.lib().nunet_plan_opt_step(pl.handle, L.ptr(eng.flat_params), C.byref(self._optim), L.ptr(pl.arena), L.nbytes(pl.arena),
+                                                1.0 / self.world, L.ptr(eng.flat_grads) if self.keep_grads else None,
+                                                1 if self.fused_update == 1 else 0, L.stream()), "plan_opt_step")
+            return
         if self.fused_update == 2:      # gradient scratch -> SGD in one launch; the next forward repacks
             L.check(L.lib().nunet_plan_sgd(pl.handle, L.ptr(eng.flat_params), L.ptr(self.mom), L.ptr(pl.arena), L.nbytes(pl.arena), L.ptr(self.lr),
                                            self.momentum, self.wd, 1 if self.nesterov else 0, 1.0 / self.world,
@@ -231,7 +264,11 @@ class TrainStep:
         if on == self._inpass_set:
             return
         eng = self.eng
-        if on:
+        if self.optimizer == "Adam":
+            L.check(L.lib().nunet_plan_set_inpass_opt(self.pl.handle, L.ptr(eng.flat_params) if on else None, C.byref(self._optim),
+                                                      1.0 / self.world, L.ptr(eng.flat_grads) if self.keep_grads else None),
+                    "plan_set_inpass_opt")
+        elif on:
             L.check(L.lib().nunet_plan_set_inpass_update(self.pl.handle, L.ptr(eng.flat_params), L.ptr(self.mom), L.ptr(self.lr), self.momentum,
                                                          self.wd, 1 if self.nesterov else 0, 1.0 / self.world,
                                                          L.ptr(eng.flat_grads) if self.keep_grads else None), "plan_set_inpass_update")
@@ -245,6 +282,10 @@ class TrainStep:
         eng = self.eng
         if self.world > 1:
             eng.flat_grads.mul_(1.0 / self.world)      # p.grad = rank mean in every layout
+        if self.optimizer == "Adam":
+            L.check(L.lib().nunet_adam_step(L.ptr(eng.flat_params), L.ptr(eng.flat_grads), C.byref(self._optim),
+                                            eng.flat_params.numel(), 1.0, L.stream()), "adam_step")
+            return
         L.check(L.lib().nunet_sgd_step(L.ptr(eng.flat_params), L.ptr(eng.flat_grads), L.ptr(self.mom),
                                        eng.flat_params.numel(), L.ptr(self.lr), self.momentum, self.wd,
                                        1 if self.nesterov else 0, 0, 1.0, L.stream()), "sgd_step")
@@ -358,7 +399,8 @@ class TrainStep:
         else:
             self.x.copy_(inp)
             self.t.copy_(target)
-        snap = [t.clone() for t in (eng.flat_params, eng.bnbuf, eng.nbt, self.mom, self.meters)]
+        state = [eng.flat_params, eng.bnbuf, eng.nbt, self.meters] + self.opt_state
+        snap = [t.clone() for t in state]
         steps0 = self.steps
         self.sync_weights()            # from here on every step leaves the packed weights current
         s = torch.cuda.Stream()
@@ -402,7 +444,7 @@ class TrainStep:
                 self._opt()
         torch.cuda.synchronize()
         with torch.no_grad():
-            for dst, src in zip((eng.flat_params, eng.bnbuf, eng.nbt, self.mom, self.meters), snap):
+            for dst, src in zip(state, snap):
                 dst.copy_(src)
         self.steps = steps0
         self.sync_weights()            # the restored parameters, repacked
@@ -640,6 +682,40 @@ class TrainStep:
 
     def set_lr(self, lr):
         self.lr.fill_(lr)
+
+    def _hyper(self):
+        lr = float(self.lr.item())
+        if self.optimizer == "Adam":
+            return dict(lr=lr, betas=self.betas, eps=self.eps, weight_decay=self.wd, amsgrad=False)
+        return dict(lr=lr, momentum=self.momentum, dampening=0, weight_decay=self.wd, nesterov=self.nesterov)
+
+    def _trainable(self):
+        """(offset into the flat arena, shape) of the module's trainable parameters, in filter(requires_grad, model.parameters())
+        order"""
+        return [(off, p.shape) for p, off in zip(self.eng.module_params, self.eng.param_off) if p.requires_grad]
+
+    def optimizer_state_dict(self):
+        """The optimiser state in the format of torch.optim.Adam / torch.optim.SGD.state_dict(), keyed by the index of a parameter
+        in filter(requires_grad, model.parameters()): a stock optimiser over those parameters loads it (one host sync)."""
+        torch.cuda.current_stream().synchronize()
+        if self.optimizer == "Adam":
+            flat = {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}
+            step = float(self.adam_step.item())
+        else:
+            flat = {"momentum_buffer": self.mom}
+            step = None
+        return flat_to_torch_state(self._trainable(), flat, step, self._hyper())
+
+    def load_optimizer_state_dict(self, sd):
+        """Inverse of optimizer_state_dict(): the state (and lr) of a torch.optim.Adam / SGD state dict of the same kind, over the
+        same parameters, becomes this step's. The next step continues it (graphs read the same buffers)."""
+        names = ("exp_avg", "exp_avg_sq") if self.optimizer == "Adam" else ("momentum_buffer",)
+        flat = {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq} if self.optimizer == "Adam" else {"momentum_buffer": self.mom}
+        step, lr = torch_state_to_flat(sd, self._trainable(), {k: flat[k] for k in names})
+        if self.optimizer == "Adam":
+            self.adam_step.fill_(0.0 if step is None else step)
+        if lr is not None:
+            self.set_lr(lr)
 
     def reset_meters(self):
         self.meters.zero_()

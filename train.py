@@ -160,14 +160,18 @@ def main():
     val = tuple(v.cuda() for v in make_split(config['val_size'], h, w, config['input_channels'], config['num_classes'], 2000))
     steps = config['train_size'] // (bs * world)          # drop_last=True (trains.py:296); global batch = world x bs
 
-    fused = config['optimizer'] == 'SGD' and not (config['loss'] == 'LovaszHingeLoss' and config['num_classes'] != 1)   # TrainStep: SGD, either loss
+    fused = not (config['loss'] == 'LovaszHingeLoss' and config['num_classes'] != 1)   # TrainStep: SGD or Adam, either loss
     if world > 1 and not fused:
-        raise SystemExit('data parallel runs the fused step: --optimizer SGD')
+        raise SystemExit('data parallel runs the fused step: multi-class LovaszHingeLoss is not fused')
     u8 = fused and config['device_pipeline'] and config['input_channels'] == 3 and config['num_classes'] == 1
     if fused:
         model.train()
-        ts = TrainStep(model, (bs, config['input_channels'], h, w), lr=config['lr'], momentum=config['momentum'],
-                       weight_decay=config['weight_decay'], nesterov=config['nesterov'], loss=config['loss'], input_u8=u8)
+        if config['optimizer'] == 'Adam':      # torch.optim.Adam(params, lr, weight_decay) with its default betas / eps (trains.py:225-227)
+            ts = TrainStep(model, (bs, config['input_channels'], h, w), lr=config['lr'], weight_decay=config['weight_decay'],
+                           loss=config['loss'], input_u8=u8, optimizer='Adam')
+        else:
+            ts = TrainStep(model, (bs, config['input_channels'], h, w), lr=config['lr'], momentum=config['momentum'],
+                           weight_decay=config['weight_decay'], nesterov=config['nesterov'], loss=config['loss'], input_u8=u8)
         if u8:
             # the decoded set (what the reference's Dataset holds after cv2.imread, dataset.py:56-64) lives in HBM as uint8
             raw, m8 = nunet_amd.synth.synth_blob_pairs_u8(config['train_size'], h, w, seed=1000)
@@ -176,6 +180,8 @@ def main():
             aug_gen = torch.Generator().manual_seed(config['seed'] + 1)
         else:
             ts.capture(train[0][:bs], train[1][:bs])
+        if rank == 0:
+            print('=> fused training step (TrainStep): %s, %s' % (config['optimizer'], config['loss']))
     else:
         params = filter(lambda p: p.requires_grad, model.parameters())
         if config['optimizer'] == 'Adam':
