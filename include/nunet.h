@@ -314,6 +314,7 @@ typedef struct {
   const float* adam_scal;  /* Adam: device {step_size, 1/sqrt(bias_correction2)} (nunet_adam_prepare) */
   float* state0;
   float* state1;
+  const struct nunet_scaler* scaler;   /* dynamic loss scaling (nunet_scaler below); NULL: none, the arithmetic of no scaling */
 } nunet_optim;
 /* Adam bookkeeping of one step, a 1-thread kernel: *step_dev += 1 (fp32, torch's capturable step), then adam_scal for that
  * step from the device lr (bias corrections in double, rounded to fp32 once). Kernel arguments are frozen when a step is
@@ -322,6 +323,46 @@ typedef struct {
 int nunet_adam_prepare(const float* lr_dev, double beta1, double beta2, float* step_dev, float* adam_scal, nunet_stream_t s);
 /* Flat Adam step over n fp32 elements (p, g and the state in the same flat order); g is read as g * grad_scale. */
 int nunet_adam_step(float* p, const float* g, const nunet_optim* opt, int64_t n, float grad_scale, nunet_stream_t s);
+
+/* ------------------------------------------------------------------------ */
+/* Dynamic loss scaling: torch.amp.GradScaler on the device                  */
+/* ------------------------------------------------------------------------ */
+/* The scaler's state, 32 bytes of DEVICE memory. A step with loss scaling:
+ *   1. nunet_loss_step_scaled(seed_scale = &scaler->scale): dlogits = scale * dL/dlogits (the multiply is the last operation);
+ *   2. backward pass (and, data parallel, the exchange of the gradient scratch);
+ *   3. nunet_scaler_check over the final fp32 gradient scratch: found_inf |= any element is inf or NaN;
+ *   4. the update launches with nunet_optim.scaler set: gradients are read as g * grad_scale * inv_scale; when found_inf is set
+ *      they write neither parameters, nor optimiser state, nor packed weights (the optional flat `grads` still receive the
+ *      unscaled, non-finite gradients, what torch's unscale_ leaves in p.grad); Adam's bookkeeping is nunet_adam_prepare_scaled,
+ *      issued after the check;
+ *   5. nunet_scaler_update: torch's _amp_update_scale_ (backoff on found_inf, growth after growth_interval clean steps),
+ *      inv_scale recomputed, skipped counted, found_inf cleared.
+ * A captured step replays with a changing scale: every launch reads the state from device memory. */
+typedef struct nunet_scaler {
+  float scale;              /* the loss scale of the next step */
+  float inv_scale;          /* float(1.0 / (double)scale), as torch forms it */
+  int32_t growth_tracker;   /* clean steps since the last growth or backoff */
+  uint32_t found_inf;       /* nonzero: a non-finite gradient was found in this step (cleared by nunet_scaler_update) */
+  int32_t skipped;          /* steps skipped since the caller last zeroed it */
+  int32_t reserved[3];
+} nunet_scaler;
+/* nunet_loss_step whose dlogits are multiplied by seed_scale[0] (device) as their last operation: a power-of-two scale is exact,
+ * a scale of 1 changes nothing. loss_out and meters stay unscaled. */
+int nunet_loss_step_scaled(const float* logits, const float* target, int32_t N, int64_t per_sample,
+                           int32_t heads, int32_t loss_kind, float* ws, size_t ws_bytes, float* dlogits, float* loss_out,
+                           double* meters, float iou_logit_threshold, const float* seed_scale, nunet_stream_t s);
+/* found_inf |= (any of g[0, n) is inf or NaN): a read-only pass, one atomic OR per workgroup that found one. */
+int nunet_scaler_check(const float* g, int64_t n, nunet_scaler* scaler, nunet_stream_t s);
+/* The end of a scaled step, a 1-thread kernel: torch's _amp_update_scale_ with these factors, then inv_scale, skipped, found_inf. */
+int nunet_scaler_update(nunet_scaler* scaler, double growth_factor, double backoff_factor, int32_t growth_interval, nunet_stream_t s);
+/* nunet_adam_prepare that does nothing when scaler->found_inf is set (torch does not call optimizer.step() on a skipped step):
+ * issue it after nunet_scaler_check and before the update launches. */
+int nunet_adam_prepare_scaled(const float* lr_dev, double beta1, double beta2, float* step_dev, float* adam_scal,
+                              const nunet_scaler* scaler, nunet_stream_t s);
+/* Flat optimiser step of any kind over n fp32 elements (SGD: nunet_sgd_step's arithmetic; Adam: nunet_adam_step's); g is read
+ * as g * grad_scale. With opt->scaler set, the step is skipped on found_inf and g is left holding g * grad_scale * inv_scale
+ * (the unscaled gradient) in any case. */
+int nunet_opt_step(float* p, float* g, const nunet_optim* opt, int64_t n, float grad_scale, nunet_stream_t s);
 
 /* ------------------------------------------------------------------------ */
 /* layout helpers                                                            */
@@ -423,10 +464,12 @@ int nunet_plan_sgd(nunet_plan* p, float* params, float* momentum, void* arena, s
                    int32_t nesterov, float grad_scale, float* grads, nunet_stream_t s);
 /* The fused steps above with any optimiser (nunet_optim): repack = 0 is nunet_plan_sgd's launch (the next forward repacks),
  * repack = 1 is nunet_plan_update's (both packed layouts written). With an SGD `opt` the results are those of
- * nunet_plan_sgd / nunet_plan_update bit for bit. */
+ * nunet_plan_sgd / nunet_plan_update bit for bit. With opt->scaler set (loss scaling) the gradients are read as
+ * g * grad_scale * inv_scale, and a step with found_inf set writes only `grads` (nunet_scaler). */
 int nunet_plan_opt_step(nunet_plan* p, float* params, const nunet_optim* opt, void* arena, size_t arena_bytes, float grad_scale,
                         float* grads, int32_t repack, nunet_stream_t s);
-/* nunet_plan_set_inpass_update with any optimiser (the struct is copied; params = NULL: off). */
+/* nunet_plan_set_inpass_update with any optimiser (the struct is copied; params = NULL: off). No scaler: a step already half
+ * applied inside the pass cannot be skipped. */
 int nunet_plan_set_inpass_opt(nunet_plan* p, float* params, const nunet_optim* opt, float grad_scale, float* grads);
 /* Repack the weight layouts from the fp32 parameters (what nunet_plan_forward does first unless told they are current). */
 int nunet_plan_repack(nunet_plan* p, const float* params, void* arena, size_t arena_bytes, nunet_stream_t s);

@@ -105,7 +105,10 @@ class Optim(C.Structure):
     """nunet_optim: which optimiser a generic step entry runs, its hyper-parameters and state pointers."""
     _fields_ = [("kind", _i32), ("momentum", _f32), ("beta1", C.c_double), ("beta2", C.c_double),
                 ("eps", _f32), ("weight_decay", _f32), ("nesterov", _i32),
-                ("lr", _vp), ("adam_scal", _vp), ("state0", _vp), ("state1", _vp)]
+                ("lr", _vp), ("adam_scal", _vp), ("state0", _vp), ("state1", _vp), ("scaler", _vp)]
+
+
+SCALER_WORDS = 8    # nunet_scaler: 32 bytes of device memory, [scale f32, inv_scale f32, growth_tracker i32, found_inf u32, skipped i32, 3 reserved]
 
 
 class PlanCfg(C.Structure):
@@ -148,6 +151,11 @@ _SIG = {
     "nunet_sgd_step": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32, _f32, _i32, _i32, _f32, _vp]),
     "nunet_adam_prepare": (_i32, [_vp, C.c_double, C.c_double, _vp, _vp, _vp]),
     "nunet_adam_step": (_i32, [_vp, _vp, C.POINTER(Optim), _i64, _f32, _vp]),
+    "nunet_loss_step_scaled": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _sz, _vp, _vp, _vp, _f32, _vp, _vp]),
+    "nunet_scaler_check": (_i32, [_vp, _i64, _vp, _vp]),
+    "nunet_scaler_update": (_i32, [_vp, C.c_double, C.c_double, _i32, _vp]),
+    "nunet_adam_prepare_scaled": (_i32, [_vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
+    "nunet_opt_step": (_i32, [_vp, _vp, C.POINTER(Optim), _i64, _f32, _vp]),
     "nunet_preprocess_u8": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
     "nunet_nchw_to_nhwc": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "nunet_plan_create": (_vp, [C.POINTER(PlanCfg)]),

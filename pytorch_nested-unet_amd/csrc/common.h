@@ -341,18 +341,29 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 // ---------------------------------------------------------------------------
 // Optimiser functors of the fused update kernels (plan.hip) and the flat Adam step (elementwise.hip): the per-element step
-// with its state pointers (NS fp32 buffers in flat parameter order). begin() reads the device scalars once per thread;
+// with its state pointers (NS fp32 buffers in flat parameter order). begin(gscale) reads the device scalars once per thread;
 // one(p, g, s) takes the (scaled, undecayed) gradient and the element's state, updates the state in place and returns the
 // new parameter. Built on the host from a nunet_optim by opt_from() (plan.hip) / the flat entry (elementwise.hip).
+// Loss scaling (sc != NULL, nunet_scaler): begin() returns false when the step is skipped (found_inf) - every thread of the
+// launch reads the same word, written by an earlier launch, so the decision is uniform and the caller's workgroup stores no
+// parameter, state or packed weight - and otherwise folds inv_scale into the caller's gradient scale. sc == NULL leaves the
+// gradient scale untouched: the arithmetic of an unscaled step is unchanged.
 // ---------------------------------------------------------------------------
+__device__ __forceinline__ bool scaler_begin(const nunet_scaler* sc, float& gscale) {
+  if (!sc) return true;
+  if (sc->found_inf) return false;
+  gscale *= sc->inv_scale;
+  return true;
+}
 struct OptSgd {   // torch.optim.SGD (reference trains.py:229-231): the arithmetic the SGD kernels always had, bit for bit
   static constexpr int NS = 1;
   float* st[1];
   const float* lr_dev;
   float momc, wd;
   int nesterov;
+  const nunet_scaler* sc;
   float lr;
-  __device__ __forceinline__ void begin() { lr = lr_dev[0]; }
+  __device__ __forceinline__ bool begin(float& gscale) { lr = lr_dev[0]; return scaler_begin(sc, gscale); }
   __device__ __forceinline__ float one(float p, float g, float* s) const {
     float gv = g + wd * p;
     if (momc != 0.f) {
@@ -368,8 +379,12 @@ struct OptAdam {  // torch.optim.Adam, amsgrad=False, maximize=False, L2 decay i
   float* st[2];             // exp_avg, exp_avg_sq
   const float* scal_dev;    // {lr / (1 - b1^t), 1 / sqrt(1 - b2^t)}, written by adam_prepare_kernel for this step
   float omb1, b2, omb2, eps, wd;   // 1 - beta1, beta2, 1 - beta2 rounded from double once (torch's Python-float scalars)
+  const nunet_scaler* sc;
   float step_size, inv_sqrt_bc2;
-  __device__ __forceinline__ void begin() { step_size = scal_dev[0]; inv_sqrt_bc2 = scal_dev[1]; }
+  __device__ __forceinline__ bool begin(float& gscale) {
+    step_size = scal_dev[0]; inv_sqrt_bc2 = scal_dev[1];
+    return scaler_begin(sc, gscale);
+  }
   __device__ __forceinline__ float one(float p, float g, float* s) const {
     const float gd = g + wd * p;                            // grad.add(param, alpha=wd)
     const float m = s[0] + omb1 * (gd - s[0]);              // exp_avg.lerp_(grad, 1 - beta1)

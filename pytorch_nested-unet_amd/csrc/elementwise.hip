@@ -4,6 +4,7 @@
 //   1x1 heads fwd/bwd, BCEDiceLoss fwd/bwd, IoU counts, SGD, layout helpers.
 // Reference arithmetic: finished/archs1.py:17-21,82-83,105-111; losses.py:103-117;
 // metrics.py:6-18; trains.py:229-231.
+#include <cmath>
 #include <stdlib.h>
 #include <string.h>
 
@@ -1074,7 +1075,8 @@ __global__ __launch_bounds__(256) void loss_step_partial_kernel(const float* __r
   if (threadIdx.x < 6)    // (counts <= 256 * trip count per wave: exact in fp32 up to 2^24 per block)
     ws[((((size_t)hd * N + n) * LOSS_GX) + blockIdx.x) * 6 + threadIdx.x] = s_f[0][threadIdx.x] + s_f[1][threadIdx.x] + s_f[2][threadIdx.x] + s_f[3][threadIdx.x];
 }
-__global__ __launch_bounds__(256) void loss_step_bwd_kernel(const float* __restrict__ x, const float* __restrict__ t, int64_t per, const float* __restrict__ ws, int gx, int N, int heads, float* __restrict__ dx, float* __restrict__ loss_out, double* __restrict__ meters) {
+__global__ __launch_bounds__(256) void loss_step_bwd_kernel(const float* __restrict__ x, const float* __restrict__ t, int64_t per, const float* __restrict__ ws, int gx, int N, int heads, float* __restrict__ dx, float* __restrict__ loss_out, double* __restrict__ meters,
+                                                            const float* __restrict__ seed_scale) {
   const int n = blockIdx.y, hd = blockIdx.z;
   const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
   const bool on = l < gx;
@@ -1141,6 +1143,7 @@ __global__ __launch_bounds__(256) void loss_step_bwd_kernel(const float* __restr
   const float num = 2.f * I + 1e-5f;
   const float invD2 = 1.f / (D * D);
   const float invN = 1.f / (float)N;
+  const float sc = seed_scale ? seed_scale[0] : 1.f;   // loss scaling: the last multiply (exact for powers of two; 1 changes nothing)
   const float* xs = x + ((int64_t)hd * N + n) * per;
   const float* ts = t + (int64_t)n * per;
   float* ds = dx + ((int64_t)hd * N + n) * per;
@@ -1148,31 +1151,42 @@ __global__ __launch_bounds__(256) void loss_step_bwd_kernel(const float* __restr
     const float xv = xs[i], tv = ts[i];
     const float pv = sigmoidf_(xv);
     const float ddice = (2.f * tv * D - num) * invD2 * pv * (1.f - pv);
-    ds[i] = g * (kb * (pv - tv) - invN * ddice);
+    ds[i] = g * (kb * (pv - tv) - invN * ddice) * sc;
   }
 }
 size_t lovasz_step_ws_bytes(int32_t N, int64_t per, int32_t heads);    // lovasz.hip
 int lovasz_loss_step(const float* logits, const float* target, int32_t N, int64_t per, int32_t heads, float* ws, float* dlogits,
-                     float* loss_out, double* meters, float iou_thr, hipStream_t st);
+                     float* loss_out, double* meters, float iou_thr, const float* seed_scale, hipStream_t st);
 extern "C" size_t nunet_loss_step_ws_bytes(int32_t N, int64_t per, int32_t heads, int32_t loss_kind) {
   if (N <= 0 || per <= 0 || heads < 1) return 0;
   if (loss_kind == NUNET_LOSS_LOVASZ_HINGE) return lovasz_step_ws_bytes(N, per, heads);
   return (size_t)heads * N * LOSS_GX * 6 * sizeof(float);
 }
-extern "C" int nunet_loss_step(const float* logits, const float* target, int32_t N, int64_t per, int32_t heads, int32_t loss_kind, float* ws, size_t ws_bytes,
-                               float* dlogits, float* loss_out, double* meters, float iou_logit_threshold, nunet_stream_t s) {
+static int loss_step(const float* logits, const float* target, int32_t N, int64_t per, int32_t heads, int32_t loss_kind, float* ws, size_t ws_bytes,
+                     float* dlogits, float* loss_out, double* meters, float iou_logit_threshold, const float* seed_scale, nunet_stream_t s) {
   NUNET_REQUIRE(logits && target && ws && dlogits && loss_out && N > 0 && per > 0 && heads >= 1 && heads <= 8, "loss_step: bad args");
   NUNET_REQUIRE(loss_kind == NUNET_LOSS_BCE_DICE || loss_kind == NUNET_LOSS_LOVASZ_HINGE, "loss_step: loss_kind %d", (int)loss_kind);
   NUNET_REQUIRE(per <= (1ll << 24), "loss_step: image too large");    // per-image IoU counts stay exact in fp32
   NUNET_REQUIRE(ws_bytes >= nunet_loss_step_ws_bytes(N, per, heads, loss_kind), "loss_step: workspace of %zu bytes, nunet_loss_step_ws_bytes = %zu",
                 ws_bytes, nunet_loss_step_ws_bytes(N, per, heads, loss_kind));
   hipStream_t st = (hipStream_t)s;
-  if (loss_kind == NUNET_LOSS_LOVASZ_HINGE) return lovasz_loss_step(logits, target, N, per, heads, ws, dlogits, loss_out, meters, iou_logit_threshold, st);
+  if (loss_kind == NUNET_LOSS_LOVASZ_HINGE)
+    return lovasz_loss_step(logits, target, N, per, heads, ws, dlogits, loss_out, meters, iou_logit_threshold, seed_scale, st);
   const int gx = grid_for(per, 256, LOSS_GX);     // one element per thread up to 128x128 images: the step waits on this pair of launches
   ProfScope ps(PC_LOSS, 0, (double)N * per * heads * 16, st);
   NUNET_LAUNCH(loss_step_partial_kernel, dim3(gx, N, heads), dim3(256), 0, st, logits, target, per, ws, N, heads, iou_logit_threshold);
-  NUNET_LAUNCH(loss_step_bwd_kernel, dim3(gx, N, heads), dim3(256), 0, st, logits, target, per, ws, gx, N, heads, dlogits, loss_out, meters);
+  NUNET_LAUNCH(loss_step_bwd_kernel, dim3(gx, N, heads), dim3(256), 0, st, logits, target, per, ws, gx, N, heads, dlogits, loss_out, meters, seed_scale);
   return nunet_check_launch("loss_step");
+}
+extern "C" int nunet_loss_step(const float* logits, const float* target, int32_t N, int64_t per, int32_t heads, int32_t loss_kind, float* ws, size_t ws_bytes,
+                               float* dlogits, float* loss_out, double* meters, float iou_logit_threshold, nunet_stream_t s) {
+  return loss_step(logits, target, N, per, heads, loss_kind, ws, ws_bytes, dlogits, loss_out, meters, iou_logit_threshold, nullptr, s);
+}
+extern "C" int nunet_loss_step_scaled(const float* logits, const float* target, int32_t N, int64_t per, int32_t heads, int32_t loss_kind, float* ws,
+                                      size_t ws_bytes, float* dlogits, float* loss_out, double* meters, float iou_logit_threshold,
+                                      const float* seed_scale, nunet_stream_t s) {
+  NUNET_REQUIRE(seed_scale, "loss_step_scaled: null seed_scale");
+  return loss_step(logits, target, N, per, heads, loss_kind, ws, ws_bytes, dlogits, loss_out, meters, iou_logit_threshold, seed_scale, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -1245,8 +1259,10 @@ extern "C" int nunet_sigmoid_u8(const float* logits, const float* thresholds, ui
 // ---------------------------------------------------------------------------
 // SGD with momentum / weight decay / nesterov (torch.optim.SGD semantics)
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, int64_t n, const float* __restrict__ lr_dev, float mom, float wd, int nesterov, int first, float gscale) {
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, int64_t n, const float* __restrict__ lr_dev, float mom, float wd, int nesterov, int first, float gscale,
+                                                  const nunet_scaler* __restrict__ sc) {
   const float lr = lr_dev[0];
+  if (!scaler_begin(sc, gscale)) return;     // loss scaling: a skipped step writes nothing
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float pv = p[i];
     float gv = g[i] * gscale + wd * pv;
@@ -1261,7 +1277,8 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
 extern "C" int nunet_sgd_step(float* p, const float* g, float* mom, int64_t n, const float* lr_dev, float momentum, float weight_decay, int32_t nesterov, int32_t first, float grad_scale, nunet_stream_t s) {
   NUNET_REQUIRE(p && g && lr_dev && n > 0 && (momentum == 0.f || mom), "sgd_step: bad args");
   ProfScope ps(PC_SGD, 0, (double)n * 20, (hipStream_t)s);
-  NUNET_LAUNCH(sgd_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, (hipStream_t)s, p, g, mom, n, lr_dev, momentum, weight_decay, nesterov, first, grad_scale);
+  NUNET_LAUNCH(sgd_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, (hipStream_t)s, p, g, mom, n, lr_dev, momentum, weight_decay, nesterov, first, grad_scale,
+               (const nunet_scaler*)nullptr);
   return nunet_check_launch("sgd_step");
 }
 
@@ -1270,8 +1287,10 @@ extern "C" int nunet_sgd_step(float* p, const float* g, float* mom, int64_t n, c
 // ---------------------------------------------------------------------------
 // One thread: t = ++step (fp32, torch's capturable step), then the step's two scalars from the device lr. torch forms the
 // bias corrections from Python floats (double) and hands fp32 kernels scalars rounded once: so does this.
-__global__ void adam_prepare_kernel(const float* __restrict__ lr_dev, double b1, double b2, float* __restrict__ step, float* __restrict__ scal) {
+__global__ void adam_prepare_kernel(const float* __restrict__ lr_dev, double b1, double b2, float* __restrict__ step, float* __restrict__ scal,
+                                    const nunet_scaler* __restrict__ sc) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  if (sc && sc->found_inf) return;           // a step skipped by loss scaling does not count
   const float t = step[0] + 1.f;
   step[0] = t;
   const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
@@ -1281,13 +1300,20 @@ __global__ void adam_prepare_kernel(const float* __restrict__ lr_dev, double b1,
 extern "C" int nunet_adam_prepare(const float* lr_dev, double beta1, double beta2, float* step_dev, float* adam_scal, nunet_stream_t s) {
   NUNET_REQUIRE(lr_dev && step_dev && adam_scal, "adam_prepare: null pointer");
   NUNET_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adam_prepare: betas must lie in [0, 1)");
-  NUNET_LAUNCH(adam_prepare_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, lr_dev, beta1, beta2, step_dev, adam_scal);
+  NUNET_LAUNCH(adam_prepare_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, lr_dev, beta1, beta2, step_dev, adam_scal, (const nunet_scaler*)nullptr);
   return nunet_check_launch("adam_prepare");
+}
+extern "C" int nunet_adam_prepare_scaled(const float* lr_dev, double beta1, double beta2, float* step_dev, float* adam_scal,
+                                         const nunet_scaler* scaler, nunet_stream_t s) {
+  NUNET_REQUIRE(lr_dev && step_dev && adam_scal && scaler, "adam_prepare_scaled: null pointer");
+  NUNET_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adam_prepare_scaled: betas must lie in [0, 1)");
+  NUNET_LAUNCH(adam_prepare_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, lr_dev, beta1, beta2, step_dev, adam_scal, scaler);
+  return nunet_check_launch("adam_prepare_scaled");
 }
 
 // Flat step: four elements per thread as 16-byte runs when every array is 16-byte aligned, scalar tail for n % 4
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, OptAdam o, int64_t n, float gscale, int vec) {
-  o.begin();
+  if (!o.begin(gscale)) return;              // loss scaling: a skipped step writes nothing
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
   const int64_t n4 = vec ? n / 4 : 0;
   for (int64_t i = tid; i < n4; i += nth) {
@@ -1307,19 +1333,116 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
   for (int64_t i = 4 * n4 + tid; i < n; i += nth) p[i] = opt_elem(o, p[i], g[i] * gscale, i);
 }
-extern "C" int nunet_adam_step(float* p, const float* g, const nunet_optim* opt, int64_t n, float grad_scale, nunet_stream_t s) {
-  NUNET_REQUIRE(p && g && opt && n > 0, "adam_step: bad args");
-  NUNET_REQUIRE(opt->kind == NUNET_OPT_ADAM, "adam_step: optimiser kind %d is not NUNET_OPT_ADAM", (int)opt->kind);
-  NUNET_REQUIRE(opt->adam_scal && opt->state0 && opt->state1, "adam_step: Adam needs adam_scal, state0 and state1");
-  NUNET_REQUIRE(opt->beta1 >= 0.0 && opt->beta1 < 1.0 && opt->beta2 >= 0.0 && opt->beta2 < 1.0, "adam_step: betas must lie in [0, 1)");
-  NUNET_REQUIRE(opt->eps > 0.f, "adam_step: eps must be > 0");
+static int adam_args(const nunet_optim* opt, const char* what) {
+  NUNET_REQUIRE(opt->adam_scal && opt->state0 && opt->state1, "%s: Adam needs adam_scal, state0 and state1", what);
+  NUNET_REQUIRE(opt->beta1 >= 0.0 && opt->beta1 < 1.0 && opt->beta2 >= 0.0 && opt->beta2 < 1.0, "%s: betas must lie in [0, 1)", what);
+  NUNET_REQUIRE(opt->eps > 0.f, "%s: eps must be > 0", what);
+  return NUNET_OK;
+}
+static void launch_adam(float* p, const float* g, const nunet_optim* opt, int64_t n, float grad_scale, hipStream_t st) {
   OptAdam o;
   memset(&o, 0, sizeof(o));
   o.st[0] = opt->state0; o.st[1] = opt->state1; o.scal_dev = opt->adam_scal;
   o.omb1 = (float)(1.0 - opt->beta1); o.b2 = (float)opt->beta2; o.omb2 = (float)(1.0 - opt->beta2);
-  o.eps = opt->eps; o.wd = opt->weight_decay;
+  o.eps = opt->eps; o.wd = opt->weight_decay; o.sc = opt->scaler;
   const int vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)opt->state0 | (uintptr_t)opt->state1) & 15) == 0;
-  ProfScope ps(PC_SGD, 0, (double)n * 28, (hipStream_t)s);
-  NUNET_LAUNCH(adam_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, (hipStream_t)s, p, g, o, n, grad_scale, vec);
+  ProfScope ps(PC_SGD, 0, (double)n * 28, st);
+  NUNET_LAUNCH(adam_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, st, p, g, o, n, grad_scale, vec);
+}
+extern "C" int nunet_adam_step(float* p, const float* g, const nunet_optim* opt, int64_t n, float grad_scale, nunet_stream_t s) {
+  NUNET_REQUIRE(p && g && opt && n > 0, "adam_step: bad args");
+  NUNET_REQUIRE(opt->kind == NUNET_OPT_ADAM, "adam_step: optimiser kind %d is not NUNET_OPT_ADAM", (int)opt->kind);
+  NUNET_REQUIRE(!opt->scaler, "adam_step: loss scaling goes through nunet_opt_step");
+  const int rc = adam_args(opt, "adam_step");
+  if (rc != NUNET_OK) return rc;
+  launch_adam(p, g, opt, n, grad_scale, (hipStream_t)s);
   return nunet_check_launch("adam_step");
+}
+
+// ---------------------------------------------------------------------------
+// Dynamic loss scaling (torch.amp.GradScaler on the device; include/nunet.h nunet_scaler)
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t nonfinite(uint32_t bits) { return (bits & 0x7f800000u) == 0x7f800000u ? 1u : 0u; }
+// found_inf |= any element of g is inf / NaN: 16-byte loads, the exponent test on the raw bits, one workgroup-wide OR, and one
+// device-scope atomic per workgroup that found one (none in a clean step)
+__global__ __launch_bounds__(256) void scaler_check_kernel(const float* __restrict__ g, int64_t n, int vec, nunet_scaler* __restrict__ sc) {
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+  const int64_t n4 = vec ? n / 4 : 0;
+  const u32x4* g4 = reinterpret_cast<const u32x4*>(g);
+  uint32_t bad = 0;
+  for (int64_t i = tid; i < n4; i += nth) {
+    const u32x4 v = g4[i];
+    bad |= nonfinite(v[0]) | nonfinite(v[1]) | nonfinite(v[2]) | nonfinite(v[3]);
+  }
+  for (int64_t i = 4 * n4 + tid; i < n; i += nth) bad |= nonfinite(__float_as_uint(g[i]));
+  if (__syncthreads_or((int)bad) && threadIdx.x == 0) atomicOr(&sc->found_inf, 1u);
+}
+extern "C" int nunet_scaler_check(const float* g, int64_t n, nunet_scaler* scaler, nunet_stream_t s) {
+  NUNET_REQUIRE(g && scaler && n > 0, "scaler_check: bad args");
+  const int vec = ((uintptr_t)g & 15) == 0;
+  ProfScope ps(PC_SGD, 0, (double)n * 4, (hipStream_t)s);
+  NUNET_LAUNCH(scaler_check_kernel, dim3(grid_for(vec ? (n + 3) / 4 : n, 256 * 4, 2048)), dim3(256), 0, (hipStream_t)s, g, n, vec, scaler);
+  return nunet_check_launch("scaler_check");
+}
+
+// One thread, torch's _amp_update_scale_ (the factors are doubles, the products rounded to fp32 once), then the next step's
+// inv_scale as torch's unscale_ forms it (double reciprocal, rounded to fp32), the skip count, and found_inf cleared.
+__global__ void scaler_update_kernel(nunet_scaler* __restrict__ sc, double growth, double backoff, int interval) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  float scale = sc->scale;
+  if (sc->found_inf) {
+    scale = (float)((double)scale * backoff);
+    sc->growth_tracker = 0;
+    sc->skipped = sc->skipped + 1;
+  } else {
+    const int t = sc->growth_tracker + 1;
+    if (t == interval) {
+      const float grown = (float)((double)scale * growth);
+      if (isfinite(grown)) scale = grown;
+      sc->growth_tracker = 0;
+    } else {
+      sc->growth_tracker = t;
+    }
+  }
+  sc->scale = scale;
+  sc->inv_scale = (float)(1.0 / (double)scale);
+  sc->found_inf = 0u;
+}
+extern "C" int nunet_scaler_update(nunet_scaler* scaler, double growth_factor, double backoff_factor, int32_t growth_interval, nunet_stream_t s) {
+  NUNET_REQUIRE(scaler, "scaler_update: null scaler");
+  NUNET_REQUIRE(growth_factor > 1.0 && std::isfinite(growth_factor), "scaler_update: growth_factor must be > 1 (got %g)", growth_factor);
+  NUNET_REQUIRE(backoff_factor > 0.0 && backoff_factor < 1.0, "scaler_update: backoff_factor must lie in (0, 1) (got %g)", backoff_factor);
+  NUNET_REQUIRE(growth_interval > 0, "scaler_update: growth_interval must be > 0 (got %d)", (int)growth_interval);
+  NUNET_LAUNCH(scaler_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, scaler, growth_factor, backoff_factor, (int)growth_interval);
+  return nunet_check_launch("scaler_update");
+}
+
+// g *= grad_scale * inv_scale in every step, skipped ones included: what torch's unscale_ leaves in p.grad
+__global__ __launch_bounds__(256) void unscale_kernel(float* __restrict__ g, int64_t n, float gscale, const nunet_scaler* __restrict__ sc, int vec) {
+  const float f = gscale * sc->inv_scale;
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+  const int64_t n4 = vec ? n / 4 : 0;
+  for (int64_t i = tid; i < n4; i += nth) reinterpret_cast<f32x4*>(g)[i] = reinterpret_cast<const f32x4*>(g)[i] * f;
+  for (int64_t i = 4 * n4 + tid; i < n; i += nth) g[i] = g[i] * f;
+}
+extern "C" int nunet_opt_step(float* p, float* g, const nunet_optim* opt, int64_t n, float grad_scale, nunet_stream_t s) {
+  NUNET_REQUIRE(p && g && opt && n > 0, "opt_step: bad args");
+  hipStream_t st = (hipStream_t)s;
+  if (opt->kind == NUNET_OPT_SGD) {
+    NUNET_REQUIRE(opt->lr && (opt->momentum == 0.f || opt->state0), "opt_step: SGD needs lr and state0 (momentum buffer)");
+    ProfScope ps(PC_SGD, 0, (double)n * 20, st);
+    NUNET_LAUNCH(sgd_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, st, p, g, opt->state0, n, opt->lr, opt->momentum, opt->weight_decay,
+                 opt->nesterov, 0, grad_scale, opt->scaler);
+  } else if (opt->kind == NUNET_OPT_ADAM) {
+    const int rc = adam_args(opt, "opt_step");
+    if (rc != NUNET_OK) return rc;
+    launch_adam(p, g, opt, n, grad_scale, st);
+  } else {
+    NUNET_REQUIRE(false, "opt_step: unknown optimiser kind %d", (int)opt->kind);
+  }
+  if (opt->scaler) {   // after the step, which read the scaled gradients
+    const int vec = ((uintptr_t)g & 15) == 0;
+    NUNET_LAUNCH(unscale_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, st, g, n, grad_scale, opt->scaler, vec);
+  }
+  return nunet_check_launch("opt_step");
 }

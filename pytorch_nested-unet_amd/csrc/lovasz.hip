@@ -322,12 +322,15 @@ extern "C" int nunet_lovasz_hinge_bwd(const float* dlogits_unit, const float* gs
 static size_t lovasz_head_ws(int32_t N, int64_t per) { return (nunet_lovasz_ws_bytes(N, per) + 255) / 256 * 256; }
 size_t lovasz_step_ws_bytes(int32_t N, int64_t per, int32_t heads) { return (size_t)heads * lovasz_head_ws(N, per) + 256; }
 
-// dlogits (unit gradients of every head) *= 1 / heads; IoU counts of the last head (integer atomics: order-independent)
+// dlogits (unit gradients of every head) *= 1 / heads, then (loss scaling) * seed_scale[0] as the last multiply; IoU counts
+// of the last head (integer atomics: order-independent)
 __global__ __launch_bounds__(256) void lovasz_step_scale_kernel(float* __restrict__ dx, const float* __restrict__ x_last, const float* __restrict__ t,
-                                                                int64_t n_all, int64_t n_img, float inv_heads, float thr, unsigned long long* __restrict__ cnt) {
+                                                                int64_t n_all, int64_t n_img, float inv_heads, float thr, unsigned long long* __restrict__ cnt,
+                                                                const float* __restrict__ seed_scale) {
   unsigned ci = 0, cu = 0;
+  const float sc = seed_scale ? seed_scale[0] : 1.f;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n_all; i += (int64_t)gridDim.x * blockDim.x) {
-    dx[i] *= inv_heads;
+    dx[i] = dx[i] * inv_heads * sc;
     if (i < n_img) { const bool a = x_last[i] >= thr, b = t[i] > 0.5f; ci += (a && b) ? 1u : 0u; cu += (a || b) ? 1u : 0u; }
   }
 #pragma unroll
@@ -347,7 +350,7 @@ __global__ void lovasz_step_final_kernel(float* __restrict__ loss_out, int heads
   }
 }
 int lovasz_loss_step(const float* logits, const float* target, int32_t N, int64_t per, int32_t heads, float* ws, float* dlogits,
-                     float* loss_out, double* meters, float iou_thr, hipStream_t st) {
+                     float* loss_out, double* meters, float iou_thr, const float* seed_scale, hipStream_t st) {
   const size_t hw = lovasz_head_ws(N, per);
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>((char*)ws + (size_t)heads * hw);
   int rc = nunet_zero_async(cnt, 16, st);
@@ -359,7 +362,7 @@ int lovasz_loss_step(const float* logits, const float* target, int32_t N, int64_
   int64_t g = (n_all + 1023) / 1024;
   if (g > 1024) g = 1024;
   NUNET_LAUNCH(lovasz_step_scale_kernel, dim3((unsigned)g), dim3(256), 0, st, dlogits, logits + (size_t)(heads - 1) * N * per, target, n_all, n_img,
-               1.f / (float)heads, iou_thr, cnt);
+               1.f / (float)heads, iou_thr, cnt, seed_scale);
   NUNET_LAUNCH(lovasz_step_final_kernel, dim3(1), dim3(1), 0, st, loss_out, (int)heads, cnt, meters);
   return nunet_check_launch("loss_step (lovasz hinge)");
 }

@@ -269,7 +269,9 @@ template <typename T, typename O>
 __global__ __launch_bounds__(512) void update_kernel(UpdP u, O o, T* __restrict__ arena, PackTab tab, UnpackTab ut) {
   __shared__ float s_t[32][32 * 9 + 1];
   __shared__ float s_g[32][32 * 9 + 1];
-  o.begin();
+  float gs = u.gscale;
+  const bool live = o.begin(gs);   // false: a step skipped by loss scaling, which stores the unscaled gradients only
+  if (!live && !u.grads) return;
   const int bid = (int)blockIdx.x + u.bid_off;
   if (bid >= tab.ntiles) {
     // ---- 1x1 head: sum the gradient slabs (fixed order), then the step; <= 264 elements
@@ -291,10 +293,10 @@ __global__ __launch_bounds__(512) void update_kernel(UpdP u, O o, T* __restrict_
       if ((int)threadIdx.x < ne) {
         float g = 0.f;
         for (int q = 0; q < parts; ++q) g += (&s_t[0][0])[q * ne + threadIdx.x];
-        g *= u.gscale;
+        g *= gs;
         const long long idx = en.dst + e0 + threadIdx.x;
         if (u.grads) u.grads[idx] = g;
-        u.params[idx] = opt_elem(o, u.params[idx], g, idx);
+        if (live) u.params[idx] = opt_elem(o, u.params[idx], g, idx);
       }
       __syncthreads();
     }
@@ -331,11 +333,13 @@ __global__ __launch_bounds__(512) void update_kernel(UpdP u, O o, T* __restrict_
     const int ro = i / 288, k = i - ro * 288;
     if (ro < rw && k < cw * 9) {
       const long long idx = en.src + ((long long)(co0 + ro) * en.cin + ci0) * 9 + k;
-      const float g = s_g[ro][k] * u.gscale;
+      const float g = s_g[ro][k] * gs;
       if (u.grads) u.grads[idx] = g;
-      const float pn = opt_elem(o, s_t[ro][k], g, idx);
-      u.params[idx] = pn;
-      s_t[ro][k] = pn;
+      if (live) {
+        const float pn = opt_elem(o, s_t[ro][k], g, idx);
+        u.params[idx] = pn;
+        s_t[ro][k] = pn;
+      }
     }
   }
   if (ci0 == 0) {
@@ -344,12 +348,13 @@ __global__ __launch_bounds__(512) void update_kernel(UpdP u, O o, T* __restrict_
     for (int i = threadIdx.x; i < ue.nvec * rw; i += blockDim.x) {
       const int v = i / rw, c = co0 + (i - v * rw);
       const long long idx = ue.dst + nw + (long long)v * en.cout + c;
-      const float g = dw[9LL * en.cout * en.cinpad + (long long)v * en.cout + c] * u.gscale;
+      const float g = dw[9LL * en.cout * en.cinpad + (long long)v * en.cout + c] * gs;
       if (u.grads) u.grads[idx] = g;
-      u.params[idx] = opt_elem(o, u.params[idx], g, idx);
+      if (live) u.params[idx] = opt_elem(o, u.params[idx], g, idx);
     }
   }
   __syncthreads();
+  if (!live) return;               // (uniform) the packed weights keep matching the unchanged parameters
   T* wf = arena + en.wf;
 #pragma unroll 6
   for (int i = threadIdx.x; i < 9 * 32 * 32; i += blockDim.x) {   // wf[tap][co][ci], ci fastest
@@ -1559,6 +1564,7 @@ extern "C" int nunet_plan_set_inpass_opt(nunet_plan* P, float* params, const nun
   if (params) {
     const int rc = opt_check(opt, "plan_set_inpass_opt");
     if (rc != NUNET_OK) return rc;
+    NUNET_REQUIRE(!opt->scaler, "plan_set_inpass_opt: a step applied inside the backward pass cannot be skipped by loss scaling");
   }
   auto& s = rt_of(P)->upd;
   memset(&s, 0, sizeof(s));
@@ -1576,11 +1582,13 @@ extern "C" int nunet_plan_set_inpass_opt(nunet_plan* P, float* params, const nun
 template <typename O>
 __global__ __launch_bounds__(256) void unpack_sgd_tiled_kernel(UpdP u, O o, PackTab tab, UnpackTab ut) {
   __shared__ float s_t[32][32 * 9 + 1];
-  o.begin();
+  float gs = u.gscale;
+  const bool live = o.begin(gs);   // false: a step skipped by loss scaling, which stores the unscaled gradients only
+  if (!live && !u.grads) return;
   auto step1 = [&](long long idx, float g) {
-    g *= u.gscale;
+    g *= gs;
     if (u.grads) u.grads[idx] = g;
-    u.params[idx] = opt_elem(o, u.params[idx], g, idx);
+    if (live) u.params[idx] = opt_elem(o, u.params[idx], g, idx);
   };
   if ((int)blockIdx.x >= tab.ntiles) {
     const UnpackEnt en = ut.e[(int)blockIdx.x - tab.ntiles];
@@ -1648,7 +1656,11 @@ __global__ __launch_bounds__(256) void unpack_sgd_tiled_kernel(UpdP u, O o, Pack
       const int ro = i / 72, k4 = i - ro * 72;
       const long long idx = row0 + (long long)ro * en.cin * 9 + k4 * 4;
       const float* sp = &s_t[ro][k4 * 4];
-      f32x4 g = {sp[0] * u.gscale, sp[1] * u.gscale, sp[2] * u.gscale, sp[3] * u.gscale};
+      f32x4 g = {sp[0] * gs, sp[1] * gs, sp[2] * gs, sp[3] * gs};
+      if (!live) {
+        *reinterpret_cast<f32x4*>(u.grads + idx) = g;
+        continue;
+      }
       f32x4 pv = *reinterpret_cast<const f32x4*>(u.params + idx);
       f32x4 sv[O::NS];
 #pragma unroll
@@ -1703,18 +1715,19 @@ extern "C" int nunet_plan_opt_step(nunet_plan* P, float* params, const nunet_opt
   ARENA_CHECK("plan_opt_step");
   hipStream_t st = (hipStream_t)s;
   const double extra = opt->kind == NUNET_OPT_ADAM ? 8.0 : 0.0;
+  OptAdam adam = opt_adam(opt);
+  OptSgd sgd = opt_sgd(opt->lr, opt->state0, opt->momentum, opt->weight_decay, opt->nesterov);
+  adam.sc = sgd.sc = opt->scaler;
   if (repack) {
     update_tiles(P);
     const int nb = P->ptab.ntiles + P->utab.n - P->ptab.n;
     const double bytes = (double)P->nparams * ((grads ? 28.0 : 24.0) + extra);
-    if (opt->kind == NUNET_OPT_ADAM) return launch_update_kernel(P, arena, params, opt_adam(opt), grad_scale, grads, 0, nb, bytes, st);
-    return launch_update_kernel(P, arena, params, opt_sgd(opt->lr, opt->state0, opt->momentum, opt->weight_decay, opt->nesterov),
-                                grad_scale, grads, 0, nb, bytes, st);
+    if (opt->kind == NUNET_OPT_ADAM) return launch_update_kernel(P, arena, params, adam, grad_scale, grads, 0, nb, bytes, st);
+    return launch_update_kernel(P, arena, params, sgd, grad_scale, grads, 0, nb, bytes, st);
   }
   const double bytes = (double)P->nparams * ((grads ? 24.0 : 20.0) + extra);
-  if (opt->kind == NUNET_OPT_ADAM) return launch_unpack_step(P, arena, params, opt_adam(opt), grad_scale, grads, bytes, st);
-  return launch_unpack_step(P, arena, params, opt_sgd(opt->lr, opt->state0, opt->momentum, opt->weight_decay, opt->nesterov),
-                            grad_scale, grads, bytes, st);
+  if (opt->kind == NUNET_OPT_ADAM) return launch_unpack_step(P, arena, params, adam, grad_scale, grads, bytes, st);
+  return launch_unpack_step(P, arena, params, sgd, grad_scale, grads, bytes, st);
 }
 
 // Repack the 16-bit weight layouts from the fp32 master parameters (what nunet_plan_forward does first unless told

@@ -25,6 +25,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
+from . import loss_scale as LS
 from .optim_state import flat_to_torch_state, torch_state_to_flat
 from .parallel import allreduce_flat_, broadcast_flat_
 
@@ -32,7 +33,7 @@ from .parallel import allreduce_flat_, broadcast_flat_
 class TrainStep:
     def __init__(self, model, batch_shape, lr=1e-3, momentum=0.9, weight_decay=1e-4, nesterov=False,
                  use_graph=True, process_group=None, keep_grads=True, fused_update=None, loss="BCEDiceLoss", input_u8=False,
-                 schedule=None, segmented=None, optimizer="SGD", betas=(0.9, 0.999), eps=1e-8):
+                 schedule=None, segmented=None, optimizer="SGD", betas=(0.9, 0.999), eps=1e-8, loss_scale=None):
         """loss: 'BCEDiceLoss' (reference losses.py:103-117, the default of trains.py:58) or 'LovaszHingeLoss'
         (losses.py:120-129, the loss of the reference's published table README.md:102-108; one class only) - both run
         inside the step's graph and under data parallel.
@@ -53,7 +54,13 @@ class TrainStep:
         L2 decay in the gradient, amsgrad off; trains.py:225-227). Either runs inside the step in every fused_update layout;
         Adam keeps flat exp_avg / exp_avg_sq, a device step counter and the step's two bias-correction scalars, refreshed by a
         1-thread launch at the head of every step (nunet_adam_prepare). optimizer_state_dict() / load_optimizer_state_dict()
-        speak torch.optim's state-dict format."""
+        speak torch.optim's state-dict format.
+        loss_scale: None (default: no scaling), "dynamic" (torch.amp.GradScaler's defaults) or a dict of GradScaler's constructor
+        settings (init_scale, growth_factor, backoff_factor, growth_interval). Dynamic loss scaling on the device, inside the
+        captured step: the loss gradient is seeded with the scale, the final gradient scratch is checked for inf / NaN, the update
+        unscales it - or, on an overflow, writes nothing (the step is skipped) - and a 1-thread launch backs the scale off or grows
+        it as torch's scaler.update() does. No host synchronisation per step; scaler_stats() / scaler_state_dict() read the state.
+        Under scaling the in-pass update (fused_update 3) falls back to 2: a step half applied inside the pass cannot be skipped."""
         self.model = model
         self.eng = model.engine()
         dev = self.eng.device
@@ -120,6 +127,16 @@ class TrainStep:
             self._optim = L.Optim(kind=L.OPT_ADAM, momentum=0.0, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
                                   weight_decay=weight_decay, nesterov=0, lr=L.ptr(self.lr).value, adam_scal=L.ptr(self.adam_scal).value,
                                   state0=L.ptr(self.exp_avg).value, state1=L.ptr(self.exp_avg_sq).value)
+        # dynamic loss scaling: the nunet_scaler words on the device (scale, inv_scale, growth tracker, found_inf, skipped steps)
+        self.scaler_cfg = LS.scaler_settings(loss_scale)
+        self._scaler = None
+        if self.scaler_cfg is not None:
+            self._scaler = torch.zeros(L.SCALER_WORDS, dtype=torch.int32, device=dev)
+            self._write_scaler(self.scaler_cfg["init_scale"], 0, 0)
+            if optimizer == "SGD":      # scaled SGD goes through the generic entries (bit-identical to the SGD ones)
+                self._optim = L.Optim(kind=L.OPT_SGD, momentum=momentum, beta1=0.0, beta2=0.0, eps=0.0, weight_decay=weight_decay,
+                                      nesterov=1 if nesterov else 0, lr=L.ptr(self.lr).value, state0=L.ptr(self.mom).value)
+            self._optim.scaler = L.ptr(self._scaler).value
         self.steps = 0
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (process_group is not None or dist.is_initialized()) else 1
@@ -157,7 +174,7 @@ class TrainStep:
         # as an op of the pass behind its weight gradients, beside the rest of the pass; single-process training only (a
         # data-parallel step exchanges the gradients before the update: it falls back to 2).
         self.fused_update = int(os.environ.get("NUNET_FUSED_UPDATE", "2")) if fused_update is None else int(fused_update)   
-        if self.fused_update == 3 and self.dp:
+        if self.fused_update == 3 and (self.dp or self.scaler_cfg is not None):
             self.fused_update = 2
         self.keep_grads = keep_grads
         self._inpass_set = False
@@ -166,6 +183,8 @@ class TrainStep:
         self.g_b2 = None
         self.g_opt = None
         self._buckets = self._grad_scratch() if self.dp else None
+        if self.scaler_cfg is not None and not self.dp:
+            self._grad_scratch()             # (self._scratch: what the overflow check reads)
         self._b0_armed = False
         self._comm = torch.cuda.Stream() if self.dp else None
         if self.dp and self.dp_mode == 2:
@@ -179,10 +198,10 @@ class TrainStep:
         self._b0_armed = L.lib().nunet_plan_bucket0_enable(self.pl.handle, 1 if on else 0) == 1
 
     def broadcast_state(self, src=0):
-        """Rank `src`'s parameters, optimiser state (momentum; Adam's moments and step) and BatchNorm buffers become every
-        rank's (construction time; also after loading a checkpoint on one rank)."""
+        """Rank `src`'s parameters, optimiser state (momentum; Adam's moments and step), loss-scaler state and BatchNorm buffers
+        become every rank's (construction time; also after loading a checkpoint on one rank)."""
         eng = self.eng
-        for t in [eng.flat_params] + self.opt_state + [eng.bnbuf]:
+        for t in [eng.flat_params] + self.opt_state + [eng.bnbuf] + ([self._scaler] if self._scaler is not None else []):
             broadcast_flat_(t, src, self.pg)
         nbt = eng.nbt.to(torch.float64)          # (gloo / RCCL both take floating tensors; counts are exact in fp64)
         broadcast_flat_(nbt, src, self.pg)
@@ -204,7 +223,7 @@ class TrainStep:
         lib, eng, pl = L.lib(), self.eng, self.pl
         st = L.stream()
         flags = 3 if (self.fused_update in (1, 3) and self._packed) else 1
-        if self.optimizer == "Adam":
+        if self.optimizer == "Adam" and self._scaler is None:     # (under loss scaling: behind the overflow check, _scaled_opt)
             # t += 1 and this step's bias corrections, ahead of the forward pass: every update launch of the step (in-pass ones on
             # any lane included) is ordered behind it
             L.check(lib.nunet_adam_prepare(L.ptr(self.lr), self.betas[0], self.betas[1], L.ptr(self.adam_step), L.ptr(self.adam_scal), st),
@@ -218,8 +237,13 @@ class TrainStep:
             flags |= 4
         L.check(lib.nunet_plan_forward(pl.handle, L.ptr(eng.flat_params), L.ptr(eng.bnbuf), L.ptr(eng.nbt),
                                        L.ptr(self.x), L.ptr(pl.arena), L.nbytes(pl.arena), L.ptr(self.logits), flags, st), "plan_forward")
-        L.check(lib.nunet_loss_step(L.ptr(self.logits), L.ptr(self.t), self.n, self.per, self.heads, self.loss_kind, L.ptr(self.loss_ws), L.nbytes(self.loss_ws),
-                                    L.ptr(self.dlogits), L.ptr(self.loss_out), L.ptr(self.meters), self.iou_thr, st), "loss_step")
+        if self._scaler is not None:    # dlogits seeded with the loss scale (the scaler's first word)
+            L.check(lib.nunet_loss_step_scaled(L.ptr(self.logits), L.ptr(self.t), self.n, self.per, self.heads, self.loss_kind, L.ptr(self.loss_ws),
+                                               L.nbytes(self.loss_ws), L.ptr(self.dlogits), L.ptr(self.loss_out), L.ptr(self.meters), self.iou_thr,
+                                               L.ptr(self._scaler), st), "loss_step_scaled")
+        else:
+            L.check(lib.nunet_loss_step(L.ptr(self.logits), L.ptr(self.t), self.n, self.per, self.heads, self.loss_kind, L.ptr(self.loss_ws), L.nbytes(self.loss_ws),
+                                        L.ptr(self.dlogits), L.ptr(self.loss_out), L.ptr(self.meters), self.iou_thr, st), "loss_step")
         pl.trained_forward = True
 
     def _bwd(self, phases):
@@ -276,7 +300,30 @@ class TrainStep:
             L.check(L.lib().nunet_plan_set_inpass_update(self.pl.handle, None, None, None, 0.0, 0.0, 0, 1.0, None), "plan_set_inpass_update")
         self._inpass_set = on
 
+    def _scaled_opt(self):
+        """The optimiser step under loss scaling, behind the complete (exchanged) gradient scratch: overflow check, Adam's
+        bookkeeping unless skipped, the update (unscaled by inv_scale; nothing written on a skipped step), the scale update."""
+        lib, eng, pl, st = L.lib(), self.eng, self.pl, L.stream()
+        sc = L.ptr(self._scaler)
+        L.check(lib.nunet_scaler_check(L.ptr(self._scratch), self._scratch.numel(), sc, st), "scaler_check")
+        if self.optimizer == "Adam":
+            L.check(lib.nunet_adam_prepare_scaled(L.ptr(self.lr), self.betas[0], self.betas[1], L.ptr(self.adam_step), L.ptr(self.adam_scal),
+                                                  sc, st), "adam_prepare_scaled")
+        if self.fused_update:           # layout 2: repack 0, layout 1: repack 1
+            L.check(lib.nunet_plan_opt_step(pl.handle, L.ptr(eng.flat_params), C.byref(self._optim), L.ptr(pl.arena), L.nbytes(pl.arena),
+                                            1.0 / self.world, L.ptr(eng.flat_grads) if self.keep_grads else None,
+                                            1 if self.fused_update == 1 else 0, st), "plan_opt_step")
+        else:
+            if self.world > 1:
+                eng.flat_grads.mul_(1.0 / self.world)
+            L.check(lib.nunet_opt_step(L.ptr(eng.flat_params), L.ptr(eng.flat_grads), C.byref(self._optim), eng.flat_params.numel(), 1.0, st),
+                    "opt_step")
+        cfg = self.scaler_cfg
+        L.check(lib.nunet_scaler_update(sc, cfg["growth_factor"], cfg["backoff_factor"], cfg["growth_interval"], st), "scaler_update")
+
     def _opt(self):
+        if self._scaler is not None:
+            return self._scaled_opt()
         if self.fused_update:
             return self._update()
         eng = self.eng
@@ -399,7 +446,7 @@ class TrainStep:
         else:
             self.x.copy_(inp)
             self.t.copy_(target)
-        state = [eng.flat_params, eng.bnbuf, eng.nbt, self.meters] + self.opt_state
+        state = [eng.flat_params, eng.bnbuf, eng.nbt, self.meters] + self.opt_state + ([self._scaler] if self._scaler is not None else [])
         snap = [t.clone() for t in state]
         steps0 = self.steps
         self.sync_weights()            # from here on every step leaves the packed weights current
@@ -719,7 +766,54 @@ class TrainStep:
 
     def reset_meters(self):
         self.meters.zero_()
+        if self._scaler is not None:
+            self._scaler[4:5].zero_()        # skipped steps
         self.steps = 0
+
+    # -- loss scaling ----------------------------------------------------------------
+    def _write_scaler(self, scale, tracker, skipped=None):
+        """Set the device scaler words (scale, its inverse as torch forms it, growth tracker; found_inf cleared)."""
+        w = self._scaler.cpu()
+        w[0:2] = torch.tensor([scale, LS.inv_scale(scale)], dtype=torch.float32).view(torch.int32)
+        w[2] = int(tracker)
+        w[3] = 0
+        if skipped is not None:
+            w[4] = int(skipped)
+        self._scaler.copy_(w)
+
+    def _read_scaler(self):
+        torch.cuda.current_stream().synchronize()
+        w = self._scaler.cpu()
+        return w[0:1].view(torch.float32).item(), int(w[2]), int(w[4])
+
+    def scaler_stats(self):
+        """(current loss scale, steps skipped for overflow since reset_meters()); one host sync. None without loss scaling."""
+        if self._scaler is None:
+            return None
+        scale, _, skipped = self._read_scaler()
+        return scale, skipped
+
+    def scaler_state_dict(self):
+        """The loss scaler's state in torch.amp.GradScaler.state_dict()'s format (one host sync); {} without loss scaling, as a
+        disabled GradScaler returns."""
+        if self._scaler is None:
+            return {}
+        scale, tracker, _ = self._read_scaler()
+        return LS.to_state_dict(scale, tracker, self.scaler_cfg)
+
+    def load_scaler_state_dict(self, sd):
+        """Inverse of scaler_state_dict() (also takes a torch.amp.GradScaler's): scale and growth tracker become this step's; the
+        factors and interval too, as GradScaler.load_state_dict() does - once a step is captured they are part of its graph and
+        must equal this TrainStep's. Under data parallel, call it on every rank (or on one, then broadcast_state())."""
+        if self._scaler is None:
+            raise L.NunetError("this TrainStep was built without loss scaling (loss_scale=None)")
+        scale, tracker, cfg = LS.from_state_dict(sd)
+        keys = ("growth_factor", "backoff_factor", "growth_interval")
+        if self.g_fb is not None and any(cfg[k] != self.scaler_cfg[k] for k in keys):
+            raise L.NunetError("load_scaler_state_dict: growth_factor / backoff_factor / growth_interval %s differ from the captured step's %s"
+                               % ([cfg[k] for k in keys], [self.scaler_cfg[k] for k in keys]))
+        self.scaler_cfg.update({k: cfg[k] for k in keys})
+        self._write_scaler(scale, tracker)
 
     def epoch_stats(self):
         """(mean loss, mean IoU) over the steps since reset_meters(); one host sync.

@@ -67,6 +67,10 @@ def parse_args():
     p.add_argument('--num_workers', default=0, type=int, help='accepted for compatibility; data is generated in-process')
     # additions
     p.add_argument('--dtype', default='bf16', choices=['fp32', 'bf16', 'fp16'])
+    p.add_argument('--loss_scale', default='none', choices=['none', 'dynamic'],
+                   help='dynamic loss scaling (torch.amp.GradScaler semantics; inside the fused step on the device)')
+    p.add_argument('--init_scale', default=65536.0, type=float, help='initial loss scale (--loss_scale dynamic)')
+    p.add_argument('--growth_interval', default=2000, type=int, help='clean steps between scale growths (--loss_scale dynamic)')
     p.add_argument('--train_size', default=512, type=int)
     p.add_argument('--val_size', default=128, type=int)
     p.add_argument('--seed', default=41, type=int)
@@ -164,14 +168,16 @@ def main():
     if world > 1 and not fused:
         raise SystemExit('data parallel runs the fused step: multi-class LovaszHingeLoss is not fused')
     u8 = fused and config['device_pipeline'] and config['input_channels'] == 3 and config['num_classes'] == 1
+    scaling = None if config['loss_scale'] == 'none' else dict(init_scale=config['init_scale'], growth_interval=config['growth_interval'])
     if fused:
         model.train()
         if config['optimizer'] == 'Adam':      # torch.optim.Adam(params, lr, weight_decay) with its default betas / eps (trains.py:225-227)
             ts = TrainStep(model, (bs, config['input_channels'], h, w), lr=config['lr'], weight_decay=config['weight_decay'],
-                           loss=config['loss'], input_u8=u8, optimizer='Adam')
+                           loss=config['loss'], input_u8=u8, optimizer='Adam', loss_scale=scaling)
         else:
             ts = TrainStep(model, (bs, config['input_channels'], h, w), lr=config['lr'], momentum=config['momentum'],
-                           weight_decay=config['weight_decay'], nesterov=config['nesterov'], loss=config['loss'], input_u8=u8)
+                           weight_decay=config['weight_decay'], nesterov=config['nesterov'], loss=config['loss'], input_u8=u8,
+                           loss_scale=scaling)
         if u8:
             # the decoded set (what the reference's Dataset holds after cv2.imread, dataset.py:56-64) lives in HBM as uint8
             raw, m8 = nunet_amd.synth.synth_blob_pairs_u8(config['train_size'], h, w, seed=1000)
@@ -181,7 +187,8 @@ def main():
         else:
             ts.capture(train[0][:bs], train[1][:bs])
         if rank == 0:
-            print('=> fused training step (TrainStep): %s, %s' % (config['optimizer'], config['loss']))
+            print('=> fused training step (TrainStep): %s, %s%s' % (config['optimizer'], config['loss'],
+                                                                    ', dynamic loss scaling' if scaling else ''))
     else:
         params = filter(lambda p: p.requires_grad, model.parameters())
         if config['optimizer'] == 'Adam':
@@ -189,6 +196,7 @@ def main():
         else:
             optimizer = torch.optim.SGD(params, lr=config['lr'], momentum=config['momentum'], nesterov=config['nesterov'],
                                         weight_decay=config['weight_decay'])
+        scaler = torch.amp.GradScaler('cuda', **scaling) if scaling else None
 
     log = OrderedDict([(k, []) for k in ('epoch', 'lr', 'loss', 'iou', 'val_loss', 'val_iou', 'images_per_sec')])
     best_iou, trigger = 0, 0
@@ -219,6 +227,7 @@ def main():
                 else:
                     ts.step(train[0][idx], train[1][idx])
             tl, ti = ts.epoch_stats()
+            scale_info = ts.scaler_stats()
             if world > 1:                                                # epoch means over all ranks' (equal-sized) batches
                 m = torch.tensor([tl, ti], dtype=torch.float64, device='cuda')
                 dist.all_reduce(m)
@@ -228,6 +237,7 @@ def main():
             for gpar in optimizer.param_groups:
                 gpar['lr'] = lr
             ml, mi = AverageMeter(), AverageMeter()
+            skipped = 0
             for k in range(steps):                                       # reference trains.py:113-135
                 idx = perm[k * bs:(k + 1) * bs]
                 xb, tb = train[0][idx], train[1][idx]
@@ -239,11 +249,19 @@ def main():
                     loss = criterion(out, tb)
                     last = out
                 optimizer.zero_grad()
-                loss.backward()
-                optimizer.step()
+                if scaler is not None:
+                    scaler.scale(loss).backward()
+                    scaler.step(optimizer)
+                    s0 = scaler.get_scale()
+                    scaler.update()
+                    skipped += int(scaler.get_scale() < s0)       # (a backoff: this step found an inf / NaN and was skipped)
+                else:
+                    loss.backward()
+                    optimizer.step()
                 ml.update(loss.item(), bs)
                 mi.update(iou_from_counts(iou_counts(last.detach().contiguous(), tb)), bs)
             tl, ti = ml.avg, mi.avg
+            scale_info = (scaler.get_scale(), skipped) if scaler is not None else None
         torch.cuda.synchronize()
         ips = steps * bs * world / (time.perf_counter() - t0)
         val_log = validate(config, val, model, criterion)                # every rank: identical replicas, identical numbers
@@ -253,7 +271,8 @@ def main():
         improved = val_log['iou'] > best_iou
         if rank == 0:
             print('Epoch [%d/%d] loss %.4f - iou %.4f - val_loss %.4f - val_iou %.4f - %.0f img/s'
-                  % (epoch, config['epochs'], tl, ti, val_log['loss'], val_log['iou'], ips))
+                  % (epoch, config['epochs'], tl, ti, val_log['loss'], val_log['iou'], ips)
+                  + (' - loss scale %g, %d steps skipped' % scale_info if scale_info is not None else ''))
             for k, v in zip(log, (epoch, lr, tl, ti, val_log['loss'], val_log['iou'], ips)):
                 log[k].append(v)
             with open('models/%s/log.csv' % config['name'], 'w') as f:
