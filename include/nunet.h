@@ -315,13 +315,15 @@ typedef struct {
   float* state0;
   float* state1;
   const struct nunet_scaler* scaler;   /* dynamic loss scaling (nunet_scaler below); NULL: none, the arithmetic of no scaling */
+  const struct nunet_clip* clip;       /* gradient-norm clipping (nunet_clip below); NULL: none, no arithmetic changes */
 } nunet_optim;
 /* Adam bookkeeping of one step, a 1-thread kernel: *step_dev += 1 (fp32, torch's capturable step), then adam_scal for that
  * step from the device lr (bias corrections in double, rounded to fp32 once). Kernel arguments are frozen when a step is
  * captured, so t and lr live on the device; issue it on the caller's stream ahead of the step's forward pass, so that every
  * update launch of the step - in-pass ones included - sees the same t. */
 int nunet_adam_prepare(const float* lr_dev, double beta1, double beta2, float* step_dev, float* adam_scal, nunet_stream_t s);
-/* Flat Adam step over n fp32 elements (p, g and the state in the same flat order); g is read as g * grad_scale. */
+/* Flat Adam step over n fp32 elements (p, g and the state in the same flat order); g is read as g * grad_scale. Refuses a
+ * scaler or a clip: those go through nunet_opt_step. */
 int nunet_adam_step(float* p, const float* g, const nunet_optim* opt, int64_t n, float grad_scale, nunet_stream_t s);
 
 /* ------------------------------------------------------------------------ */
@@ -361,8 +363,41 @@ int nunet_adam_prepare_scaled(const float* lr_dev, double beta1, double beta2, f
                               const nunet_scaler* scaler, nunet_stream_t s);
 /* Flat optimiser step of any kind over n fp32 elements (SGD: nunet_sgd_step's arithmetic; Adam: nunet_adam_step's); g is read
  * as g * grad_scale. With opt->scaler set, the step is skipped on found_inf and g is left holding g * grad_scale * inv_scale
- * (the unscaled gradient) in any case. */
+ * (the unscaled gradient) in any case. With opt->clip set, the gradient is read as that times clip->coef, and g is left holding
+ * the clipped (unscaled) gradient, as torch's in-place clip leaves p.grad. */
 int nunet_opt_step(float* p, float* g, const nunet_optim* opt, int64_t n, float grad_scale, nunet_stream_t s);
+
+/* ------------------------------------------------------------------------ */
+/* Gradient-norm clipping: torch.nn.utils.clip_grad_norm_ on the device      */
+/* ------------------------------------------------------------------------ */
+/* clip_grad_norm_(params, max_norm, norm_type=2, error_if_nonfinite=False) over all parameters, inside the step:
+ *   total_norm = ||g||_2 of the gradient the optimiser would otherwise consume (g * grad_scale, * inv_scale under loss scaling);
+ *   coef = min(1, max_norm / (total_norm + 1e-6)) in fp32; the update launches with nunet_optim.clip set read g * coef
+ *   (weight decay is added after clipping, as in torch).
+ * A clipped step: the square norm of the final (exchanged) gradient - nunet_plan_grad_sqnorm over the plan's native-layout
+ * scratch, or nunet_grad_sqnorm over flat gradients - leaves one double partial per workgroup in `ws` (plain stores);
+ * nunet_clip_finalize sums them in index order, writes coef and the statistics; then the update. No atomics anywhere: the norm,
+ * and every parameter after the step, is bit-identical from run to run. Under loss scaling the order is torch's:
+ * nunet_scaler_check, (nunet_adam_prepare_scaled,) the norm, the update, nunet_scaler_update; on a skipped step (found_inf)
+ * coef = 1 and the statistics are left untouched. max_norm = +inf measures and never clips (coef == 1.0f exactly).
+ * The state, 32 bytes of DEVICE memory: */
+typedef struct nunet_clip {
+  float max_norm;           /* read every step: changing it needs no recapture */
+  float coef;               /* this step's factor, written by nunet_clip_finalize */
+  float norm;               /* total_norm of the last applied step */
+  float norm_peak;          /* max since the caller last zeroed the statistics */
+  double norm_sum;          /* sum of total_norm over counted steps (epoch mean) */
+  int32_t clipped, steps;   /* steps with coef < 1 / steps counted */
+} nunet_clip;
+/* Workspace of nunet_grad_sqnorm over n values: one double per workgroup (the grid is a function of n alone). */
+size_t nunet_grad_sqnorm_ws_bytes(int64_t n);
+/* ws[b] = sum of (double)g[i] * (double)g[i] over workgroup b's elements of g[0, n), for b < ws_bytes(n) / 8: a read-only pass
+ * with 16-byte loads (scalar head / tail where g is not 16-byte aligned), each partial summed by a fixed tree. */
+int nunet_grad_sqnorm(const float* g, int64_t n, double* ws, size_t ws_bytes, nunet_stream_t s);
+/* One workgroup: sum = ws[0] + ... + ws[nparts - 1] by a fixed tree; total_norm = float(sqrt(sum) * grad_scale * (scaler ?
+ * scaler->inv_scale : 1)); clip->coef, norm, norm_peak, norm_sum, steps, clipped - or, with scaler->found_inf set, coef = 1 only. */
+int nunet_clip_finalize(const double* ws, int32_t nparts, float grad_scale, const nunet_scaler* scaler, nunet_clip* clip,
+                        nunet_stream_t s);
 
 /* ------------------------------------------------------------------------ */
 /* layout helpers                                                            */
@@ -465,12 +500,19 @@ int nunet_plan_sgd(nunet_plan* p, float* params, float* momentum, void* arena, s
 /* The fused steps above with any optimiser (nunet_optim): repack = 0 is nunet_plan_sgd's launch (the next forward repacks),
  * repack = 1 is nunet_plan_update's (both packed layouts written). With an SGD `opt` the results are those of
  * nunet_plan_sgd / nunet_plan_update bit for bit. With opt->scaler set (loss scaling) the gradients are read as
- * g * grad_scale * inv_scale, and a step with found_inf set writes only `grads` (nunet_scaler). */
+ * g * grad_scale * inv_scale, and a step with found_inf set writes only `grads` (nunet_scaler). With opt->clip set they are
+ * read as that times clip->coef (nunet_clip), and `grads` receive the clipped gradient. */
 int nunet_plan_opt_step(nunet_plan* p, float* params, const nunet_optim* opt, void* arena, size_t arena_bytes, float grad_scale,
                         float* grads, int32_t repack, nunet_stream_t s);
-/* nunet_plan_set_inpass_update with any optimiser (the struct is copied; params = NULL: off). No scaler: a step already half
- * applied inside the pass cannot be skipped. */
+/* nunet_plan_set_inpass_update with any optimiser (the struct is copied; params = NULL: off). No scaler and no clip: a step
+ * already half applied inside the pass can neither be skipped nor rescaled. */
 int nunet_plan_set_inpass_opt(nunet_plan* p, float* params, const nunet_optim* opt, float grad_scale, float* grads);
+/* Square norm of the gradient in the plan's native-layout scratch (after the backward pass and, data parallel, the exchange):
+ * one double partial per workgroup in `ws`, for nunet_clip_finalize with nparts = nunet_plan_grad_sqnorm_ws_bytes / 8. Only
+ * real parameters count: the [tap][co][ci] entries with ci < cin (not the padding up to cinpad), conv bias / gamma / beta, and
+ * each head's gradient as the sum of its slabs (nunet_plan_sgd's summation order) before it is squared. Read-only on the arena. */
+size_t nunet_plan_grad_sqnorm_ws_bytes(const nunet_plan* p);
+int nunet_plan_grad_sqnorm(nunet_plan* p, const void* arena, size_t arena_bytes, double* ws, size_t ws_bytes, nunet_stream_t s);
 /* Repack the weight layouts from the fp32 parameters (what nunet_plan_forward does first unless told they are current). */
 int nunet_plan_repack(nunet_plan* p, const float* params, void* arena, size_t arena_bytes, nunet_stream_t s);
 /* Multi-lane issue (default on; env NUNET_MULTISTREAM=0 disables): the plan forks onto

@@ -105,10 +105,13 @@ class Optim(C.Structure):
     """nunet_optim: which optimiser a generic step entry runs, its hyper-parameters and state pointers."""
     _fields_ = [("kind", _i32), ("momentum", _f32), ("beta1", C.c_double), ("beta2", C.c_double),
                 ("eps", _f32), ("weight_decay", _f32), ("nesterov", _i32),
-                ("lr", _vp), ("adam_scal", _vp), ("state0", _vp), ("state1", _vp), ("scaler", _vp)]
+                ("lr", _vp), ("adam_scal", _vp), ("state0", _vp), ("state1", _vp), ("scaler", _vp), ("clip", _vp)]
 
 
 SCALER_WORDS = 8    # nunet_scaler: 32 bytes of device memory, [scale f32, inv_scale f32, growth_tracker i32, found_inf u32, skipped i32, 3 reserved]
+
+
+CLIP_WORDS = 8      # nunet_clip: 32 bytes of device memory, [max_norm f32, coef f32, norm f32, norm_peak f32, norm_sum f64 (2 words), clipped i32, steps i32]
 
 
 class PlanCfg(C.Structure):
@@ -156,6 +159,9 @@ _SIG = {
     "nunet_scaler_update": (_i32, [_vp, C.c_double, C.c_double, _i32, _vp]),
     "nunet_adam_prepare_scaled": (_i32, [_vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
     "nunet_opt_step": (_i32, [_vp, _vp, C.POINTER(Optim), _i64, _f32, _vp]),
+    "nunet_grad_sqnorm_ws_bytes": (C.c_size_t, [_i64]),
+    "nunet_grad_sqnorm": (_i32, [_vp, _i64, _vp, _sz, _vp]),
+    "nunet_clip_finalize": (_i32, [_vp, _i32, _f32, _vp, _vp, _vp]),
     "nunet_preprocess_u8": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
     "nunet_nchw_to_nhwc": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "nunet_plan_create": (_vp, [C.POINTER(PlanCfg)]),
@@ -176,6 +182,8 @@ _SIG = {
     "nunet_plan_set_inpass_update": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _i32, _f32, _vp]),
     "nunet_plan_opt_step": (_i32, [_vp, _vp, C.POINTER(Optim), _vp, _sz, _f32, _vp, _i32, _vp]),
     "nunet_plan_set_inpass_opt": (_i32, [_vp, _vp, C.POINTER(Optim), _f32, _vp]),
+    "nunet_plan_grad_sqnorm_ws_bytes": (C.c_size_t, [_vp]),
+    "nunet_plan_grad_sqnorm": (_i32, [_vp, _vp, _sz, _vp, _sz, _vp]),
     "nunet_plan_repack": (_i32, [_vp, _vp, _vp, _sz, _vp]),
     "nunet_plan_sgd": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _f32, _f32, _i32, _f32, _vp, _vp]),
     "nunet_plan_feature": (_i64, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

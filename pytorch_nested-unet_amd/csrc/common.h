@@ -332,6 +332,20 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// Sum of one double per thread over a 256-thread workgroup by a fixed tree: xor butterfly inside each wave (every lane ends
+// with the same total), the four wave totals through LDS, added in wave order. Every thread returns the total.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ double block256_sum_f64(double v, double* s_w4) {
+  v = wave_sum_f64(v);
+  if ((threadIdx.x & 63) == 0) s_w4[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((s_w4[0] + s_w4[1]) + s_w4[2]) + s_w4[3];
+}
+
 // dispatch a templated launcher on dtype
 #define NUNET_DISPATCH(dt, FN, ...)                                   \
   ((dt) == NUNET_F32    ? FN<float>(__VA_ARGS__)                      \
@@ -348,11 +362,18 @@ __device__ __forceinline__ float wave_sum(float v) {
 // launch reads the same word, written by an earlier launch, so the decision is uniform and the caller's workgroup stores no
 // parameter, state or packed weight - and otherwise folds inv_scale into the caller's gradient scale. sc == NULL leaves the
 // gradient scale untouched: the arithmetic of an unscaled step is unchanged.
+// Gradient clipping (cl != NULL, nunet_clip): this step's coef, written by clip_finalize_kernel in an earlier launch, is folded
+// into the gradient scale behind inv_scale (1.0f exactly when nothing is clipped). cl == NULL: nothing changes.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ bool scaler_begin(const nunet_scaler* sc, float& gscale) {
   if (!sc) return true;
   if (sc->found_inf) return false;
   gscale *= sc->inv_scale;
+  return true;
+}
+__device__ __forceinline__ bool scale_begin(const nunet_scaler* sc, const nunet_clip* cl, float& gscale) {
+  if (!scaler_begin(sc, gscale)) return false;
+  if (cl) gscale *= cl->coef;
   return true;
 }
 struct OptSgd {   // torch.optim.SGD (reference trains.py:229-231): the arithmetic the SGD kernels always had, bit for bit
@@ -362,8 +383,9 @@ struct OptSgd {   // torch.optim.SGD (reference trains.py:229-231): the arithmet
   float momc, wd;
   int nesterov;
   const nunet_scaler* sc;
+  const nunet_clip* cl;
   float lr;
-  __device__ __forceinline__ bool begin(float& gscale) { lr = lr_dev[0]; return scaler_begin(sc, gscale); }
+  __device__ __forceinline__ bool begin(float& gscale) { lr = lr_dev[0]; return scale_begin(sc, cl, gscale); }
   __device__ __forceinline__ float one(float p, float g, float* s) const {
     float gv = g + wd * p;
     if (momc != 0.f) {
@@ -380,10 +402,11 @@ struct OptAdam {  // torch.optim.Adam, amsgrad=False, maximize=False, L2 decay i
   const float* scal_dev;    // {lr / (1 - b1^t), 1 / sqrt(1 - b2^t)}, written by adam_prepare_kernel for this step
   float omb1, b2, omb2, eps, wd;   // 1 - beta1, beta2, 1 - beta2 rounded from double once (torch's Python-float scalars)
   const nunet_scaler* sc;
+  const nunet_clip* cl;
   float step_size, inv_sqrt_bc2;
   __device__ __forceinline__ bool begin(float& gscale) {
     step_size = scal_dev[0]; inv_sqrt_bc2 = scal_dev[1];
-    return scaler_begin(sc, gscale);
+    return scale_begin(sc, cl, gscale);
   }
   __device__ __forceinline__ float one(float p, float g, float* s) const {
     const float gd = g + wd * p;                            // grad.add(param, alpha=wd)

@@ -1260,9 +1260,9 @@ extern "C" int nunet_sigmoid_u8(const float* logits, const float* thresholds, ui
 // SGD with momentum / weight decay / nesterov (torch.optim.SGD semantics)
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, int64_t n, const float* __restrict__ lr_dev, float mom, float wd, int nesterov, int first, float gscale,
-                                                  const nunet_scaler* __restrict__ sc) {
+                                                  const nunet_scaler* __restrict__ sc, const nunet_clip* __restrict__ cl) {
   const float lr = lr_dev[0];
-  if (!scaler_begin(sc, gscale)) return;     // loss scaling: a skipped step writes nothing
+  if (!scale_begin(sc, cl, gscale)) return;  // loss scaling: a skipped step writes nothing; clipping: coef folded in
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float pv = p[i];
     float gv = g[i] * gscale + wd * pv;
@@ -1278,7 +1278,7 @@ extern "C" int nunet_sgd_step(float* p, const float* g, float* mom, int64_t n, c
   NUNET_REQUIRE(p && g && lr_dev && n > 0 && (momentum == 0.f || mom), "sgd_step: bad args");
   ProfScope ps(PC_SGD, 0, (double)n * 20, (hipStream_t)s);
   NUNET_LAUNCH(sgd_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, (hipStream_t)s, p, g, mom, n, lr_dev, momentum, weight_decay, nesterov, first, grad_scale,
-               (const nunet_scaler*)nullptr);
+               (const nunet_scaler*)nullptr, (const nunet_clip*)nullptr);
   return nunet_check_launch("sgd_step");
 }
 
@@ -1344,7 +1344,7 @@ static void launch_adam(float* p, const float* g, const nunet_optim* opt, int64_
   memset(&o, 0, sizeof(o));
   o.st[0] = opt->state0; o.st[1] = opt->state1; o.scal_dev = opt->adam_scal;
   o.omb1 = (float)(1.0 - opt->beta1); o.b2 = (float)opt->beta2; o.omb2 = (float)(1.0 - opt->beta2);
-  o.eps = opt->eps; o.wd = opt->weight_decay; o.sc = opt->scaler;
+  o.eps = opt->eps; o.wd = opt->weight_decay; o.sc = opt->scaler; o.cl = opt->clip;
   const int vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)opt->state0 | (uintptr_t)opt->state1) & 15) == 0;
   ProfScope ps(PC_SGD, 0, (double)n * 28, st);
   NUNET_LAUNCH(adam_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, st, p, g, o, n, grad_scale, vec);
@@ -1353,6 +1353,7 @@ extern "C" int nunet_adam_step(float* p, const float* g, const nunet_optim* opt,
   NUNET_REQUIRE(p && g && opt && n > 0, "adam_step: bad args");
   NUNET_REQUIRE(opt->kind == NUNET_OPT_ADAM, "adam_step: optimiser kind %d is not NUNET_OPT_ADAM", (int)opt->kind);
   NUNET_REQUIRE(!opt->scaler, "adam_step: loss scaling goes through nunet_opt_step");
+  NUNET_REQUIRE(!opt->clip, "adam_step: gradient clipping goes through nunet_opt_step");
   const int rc = adam_args(opt, "adam_step");
   if (rc != NUNET_OK) return rc;
   launch_adam(p, g, opt, n, grad_scale, (hipStream_t)s);
@@ -1417,9 +1418,13 @@ extern "C" int nunet_scaler_update(nunet_scaler* scaler, double growth_factor, d
   return nunet_check_launch("scaler_update");
 }
 
-// g *= grad_scale * inv_scale in every step, skipped ones included: what torch's unscale_ leaves in p.grad
-__global__ __launch_bounds__(256) void unscale_kernel(float* __restrict__ g, int64_t n, float gscale, const nunet_scaler* __restrict__ sc, int vec) {
-  const float f = gscale * sc->inv_scale;
+// g *= grad_scale * inv_scale in every step, skipped ones included: what torch's unscale_ leaves in p.grad; with a clip,
+// * coef on top (1 on a skipped step): what clip_grad_norm_ leaves there. The factor is formed as the functors' begin() forms it.
+__global__ __launch_bounds__(256) void unscale_kernel(float* __restrict__ g, int64_t n, float gscale, const nunet_scaler* __restrict__ sc,
+                                                      const nunet_clip* __restrict__ cl, int vec) {
+  float f = gscale;
+  if (sc) f *= sc->inv_scale;
+  if (cl) f *= cl->coef;
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
   const int64_t n4 = vec ? n / 4 : 0;
   for (int64_t i = tid; i < n4; i += nth) reinterpret_cast<f32x4*>(g)[i] = reinterpret_cast<const f32x4*>(g)[i] * f;
@@ -1432,7 +1437,7 @@ extern "C" int nunet_opt_step(float* p, float* g, const nunet_optim* opt, int64_
     NUNET_REQUIRE(opt->lr && (opt->momentum == 0.f || opt->state0), "opt_step: SGD needs lr and state0 (momentum buffer)");
     ProfScope ps(PC_SGD, 0, (double)n * 20, st);
     NUNET_LAUNCH(sgd_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, st, p, g, opt->state0, n, opt->lr, opt->momentum, opt->weight_decay,
-                 opt->nesterov, 0, grad_scale, opt->scaler);
+                 opt->nesterov, 0, grad_scale, opt->scaler, opt->clip);
   } else if (opt->kind == NUNET_OPT_ADAM) {
     const int rc = adam_args(opt, "opt_step");
     if (rc != NUNET_OK) return rc;
@@ -1440,9 +1445,82 @@ extern "C" int nunet_opt_step(float* p, float* g, const nunet_optim* opt, int64_
   } else {
     NUNET_REQUIRE(false, "opt_step: unknown optimiser kind %d", (int)opt->kind);
   }
-  if (opt->scaler) {   // after the step, which read the scaled gradients
+  if (opt->scaler || opt->clip) {   // after the step, which read the scaled, unclipped gradients
     const int vec = ((uintptr_t)g & 15) == 0;
-    NUNET_LAUNCH(unscale_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, st, g, n, grad_scale, opt->scaler, vec);
+    NUNET_LAUNCH(unscale_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, st, g, n, grad_scale, opt->scaler, opt->clip, vec);
   }
   return nunet_check_launch("opt_step");
+}
+
+// ---------------------------------------------------------------------------
+// Gradient-norm clipping (torch.nn.utils.clip_grad_norm_ on the device; include/nunet.h nunet_clip)
+// ---------------------------------------------------------------------------
+// Square norm of n fp32 values, one double partial per workgroup. The products (double)g * (double)g are exact (48 bits), the
+// sums are in double in a fixed order: a thread's grid-stride elements in index order (16-byte loads over the aligned middle,
+// then the `head` scalars in front of it and the < 4 behind it), then block256_sum_f64. Plain stores, no atomics.
+#define SQNORM_PER_WG (256 * 32)      // values a workgroup takes before the grid stops growing with n
+#define SQNORM_MAX_WGS 1024
+static int sqnorm_grid(int64_t n) {
+  const int64_t g = (n + SQNORM_PER_WG - 1) / SQNORM_PER_WG;
+  return (int)(g < 1 ? 1 : g > SQNORM_MAX_WGS ? SQNORM_MAX_WGS : g);
+}
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const float* __restrict__ g, int64_t n, int64_t head, double* __restrict__ ws) {
+  __shared__ double s_w[4];
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+  const int64_t n4 = (n - head) / 4;
+  const f32x4* g4 = reinterpret_cast<const f32x4*>(g + head);
+  double acc = 0.0;
+  for (int64_t i = tid; i < n4; i += nth) {
+    const f32x4 v = g4[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc += (double)v[j] * (double)v[j];
+  }
+  for (int64_t i = tid; i < head; i += nth) acc += (double)g[i] * (double)g[i];
+  for (int64_t i = head + 4 * n4 + tid; i < n; i += nth) acc += (double)g[i] * (double)g[i];
+  const double tot = block256_sum_f64(acc, s_w);
+  if (threadIdx.x == 0) ws[blockIdx.x] = tot;
+}
+extern "C" size_t nunet_grad_sqnorm_ws_bytes(int64_t n) { return n > 0 ? (size_t)sqnorm_grid(n) * sizeof(double) : 0; }
+extern "C" int nunet_grad_sqnorm(const float* g, int64_t n, double* ws, size_t ws_bytes, nunet_stream_t s) {
+  NUNET_REQUIRE(g && ws && n > 0, "grad_sqnorm: bad args");
+  NUNET_REQUIRE(((uintptr_t)g & 3) == 0 && ((uintptr_t)ws & 7) == 0, "grad_sqnorm: g must be 4-byte aligned, ws 8-byte aligned");
+  NUNET_REQUIRE(ws_bytes >= nunet_grad_sqnorm_ws_bytes(n), "grad_sqnorm: workspace of %zu bytes, nunet_grad_sqnorm_ws_bytes = %zu",
+                ws_bytes, nunet_grad_sqnorm_ws_bytes(n));
+  int64_t head = (int64_t)(((16 - ((uintptr_t)g & 15)) & 15) / 4);     // scalars in front of the first 16-byte boundary
+  if (head > n) head = n;
+  ProfScope ps(PC_SGD, 0, (double)n * 4, (hipStream_t)s);
+  NUNET_LAUNCH(grad_sqnorm_kernel, dim3(sqnorm_grid(n)), dim3(256), 0, (hipStream_t)s, g, n, head, ws);
+  return nunet_check_launch("grad_sqnorm");
+}
+
+// One workgroup: the partials summed by a fixed tree (thread t takes ws[t], ws[t + 256], ... in order, then
+// block256_sum_f64), then thread 0 forms total_norm, coef as torch forms it (fp32: max_norm / (total_norm + 1e-6), clamped
+// to 1; a NaN passes through like torch.clamp's) and the statistics. A step skipped by loss scaling gets coef = 1 and
+// counts nowhere.
+__global__ __launch_bounds__(256) void clip_finalize_kernel(const double* __restrict__ ws, int nparts, float gscale,
+                                                            const nunet_scaler* __restrict__ sc, nunet_clip* __restrict__ cl) {
+  __shared__ double s_w[4];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += 256) acc += ws[i];
+  const double tot = block256_sum_f64(acc, s_w);
+  if (threadIdx.x != 0) return;
+  if (sc && sc->found_inf) { cl->coef = 1.f; return; }
+  const double f = (double)gscale * (sc ? (double)sc->inv_scale : 1.0);
+  const float norm = (float)(sqrt(tot) * f);
+  float coef = cl->max_norm / (norm + 1e-6f);
+  coef = coef > 1.f ? 1.f : coef;
+  cl->coef = coef;
+  cl->norm = norm;
+  if (!(cl->norm_peak >= norm)) cl->norm_peak = norm;
+  cl->norm_sum = cl->norm_sum + (double)norm;
+  cl->steps = cl->steps + 1;
+  if (coef < 1.f) cl->clipped = cl->clipped + 1;
+}
+extern "C" int nunet_clip_finalize(const double* ws, int32_t nparts, float grad_scale, const nunet_scaler* scaler, nunet_clip* clip,
+                                   nunet_stream_t s) {
+  NUNET_REQUIRE(ws && clip && nparts > 0, "clip_finalize: bad args");
+  NUNET_REQUIRE(((uintptr_t)ws & 7) == 0 && ((uintptr_t)clip & 7) == 0, "clip_finalize: ws and clip must be 8-byte aligned");
+  NUNET_REQUIRE(grad_scale > 0.f && std::isfinite(grad_scale), "clip_finalize: grad_scale must be positive and finite (got %g)", (double)grad_scale);
+  NUNET_LAUNCH(clip_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, ws, (int)nparts, grad_scale, scaler, clip);
+  return nunet_check_launch("clip_finalize");
 }

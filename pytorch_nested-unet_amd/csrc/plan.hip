@@ -1565,6 +1565,7 @@ extern "C" int nunet_plan_set_inpass_opt(nunet_plan* P, float* params, const nun
     const int rc = opt_check(opt, "plan_set_inpass_opt");
     if (rc != NUNET_OK) return rc;
     NUNET_REQUIRE(!opt->scaler, "plan_set_inpass_opt: a step applied inside the backward pass cannot be skipped by loss scaling");
+    NUNET_REQUIRE(!opt->clip, "plan_set_inpass_opt: a step applied inside the backward pass cannot be rescaled by gradient clipping");
   }
   auto& s = rt_of(P)->upd;
   memset(&s, 0, sizeof(s));
@@ -1718,6 +1719,7 @@ extern "C" int nunet_plan_opt_step(nunet_plan* P, float* params, const nunet_opt
   OptAdam adam = opt_adam(opt);
   OptSgd sgd = opt_sgd(opt->lr, opt->state0, opt->momentum, opt->weight_decay, opt->nesterov);
   adam.sc = sgd.sc = opt->scaler;
+  adam.cl = sgd.cl = opt->clip;
   if (repack) {
     update_tiles(P);
     const int nb = P->ptab.ntiles + P->utab.n - P->ptab.n;
@@ -1728,6 +1730,94 @@ extern "C" int nunet_plan_opt_step(nunet_plan* P, float* params, const nunet_opt
   const double bytes = (double)P->nparams * ((grads ? 24.0 : 20.0) + extra);
   if (opt->kind == NUNET_OPT_ADAM) return launch_unpack_step(P, arena, params, adam, grad_scale, grads, bytes, st);
   return launch_unpack_step(P, arena, params, sgd, grad_scale, grads, bytes, st);
+}
+
+// Square norm of the gradient scratch for gradient clipping (include/nunet.h nunet_clip): unpack_sgd_tiled_kernel's
+// block -> (layer, 32 x 32 tile | vector tail | head) map, read-only. A conv tile sums the squares of its real [tap][co][ci]
+// entries (ci < cin: the padding up to cinpad does not count) straight from the scratch, 16-byte loads along ci; a tail block
+// takes the layer's conv bias, gamma and beta; a head block sums the slabs first, in unpack_sgd_tiled_kernel's order, and
+// squares the sum. Products exact in double, a thread's elements in index order, then block256_sum_f64: one partial per
+// workgroup, plain store (a pure-padding tile stores 0).
+__global__ __launch_bounds__(256) void plan_sqnorm_kernel(const float* __restrict__ scratch, PackTab tab, UnpackTab ut, double* __restrict__ ws) {
+  __shared__ float s_p[256];
+  __shared__ double s_w[4];
+  double acc = 0.0;
+  if ((int)blockIdx.x >= tab.ntiles) {
+    const UnpackEnt en = ut.e[(int)blockIdx.x - tab.ntiles];
+    const float* dw = scratch + en.src;
+    const int nw = en.cout * en.cin * en.taps;
+    if (en.nslab > 1) {
+      const int tot = nw + en.nvec * en.cout;
+      for (int e0 = 0; e0 < tot; e0 += 256) {
+        const int ne = min(256, tot - e0);
+        const int parts = 256 / ne;
+        const int e = threadIdx.x % ne, part = threadIdx.x / ne;
+        float v = 0.f;
+        if (part < parts) {
+#pragma unroll 8
+          for (int sl = part; sl < en.nslab; sl += parts) v += dw[(long long)sl * tot + e0 + e];
+        }
+        s_p[threadIdx.x] = part < parts ? v : 0.f;
+        __syncthreads();
+        if ((int)threadIdx.x < ne) {
+          float g = 0.f;
+          for (int q = 0; q < parts; ++q) g += s_p[q * ne + threadIdx.x];
+          acc += (double)g * (double)g;
+        }
+        __syncthreads();
+      }
+    } else {
+      const float* vsrc = dw + (long long)en.taps * en.cout * en.cinpad;
+      for (int i = threadIdx.x; i < en.nvec * en.cout; i += blockDim.x) acc += (double)vsrc[i] * (double)vsrc[i];
+    }
+  } else {
+    int e = 0;
+    while (e + 1 < tab.n && (int)blockIdx.x >= tab.tile0[e + 1]) ++e;
+    const PackEnt en = tab.e[e];
+    const int t = blockIdx.x - tab.tile0[e];
+    const int nci = (en.cinpad + 31) / 32;
+    const int co0 = (t / nci) * 32, ci0 = (t % nci) * 32;
+    const int cw = min(32, en.cin - ci0), rw = min(32, en.cout - co0);
+    const float* dw = scratch + ut.e[e].src;
+    if (cw > 0 && en.cinpad % 4 == 0 && ((uintptr_t)dw & 15) == 0) {
+      for (int i = threadIdx.x; i < 9 * 32 * 8; i += blockDim.x) {
+        const int c4 = i & 7, ro = (i >> 3) & 31, tap = i >> 8;
+        if (ro >= rw || c4 * 4 >= cw) continue;      // (ci0 + c4 * 4 < cin <= cinpad, a multiple of 4: the run is inside the row)
+        const f32x4 v = *reinterpret_cast<const f32x4*>(dw + ((long long)tap * en.cout + co0 + ro) * en.cinpad + ci0 + c4 * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (c4 * 4 + j < cw) acc += (double)v[j] * (double)v[j];
+      }
+    } else if (cw > 0) {
+      for (int i = threadIdx.x; i < 9 * 32 * 32; i += blockDim.x) {
+        const int ci = i & 31, ro = (i >> 5) & 31, tap = i >> 10;
+        if (ro < rw && ci < cw) {
+          const float v = dw[((long long)tap * en.cout + co0 + ro) * en.cinpad + ci0 + ci];
+          acc += (double)v * (double)v;
+        }
+      }
+    }
+  }
+  const double tot = block256_sum_f64(acc, s_w);
+  if (threadIdx.x == 0) ws[blockIdx.x] = tot;
+}
+static int sqnorm_blocks(const nunet_plan* P) {
+  int nt = 0;
+  for (int i = 0; i < P->ptab.n; ++i) nt += ((P->ptab.e[i].cout + 31) / 32) * ((P->ptab.e[i].cinpad + 31) / 32);
+  return nt + P->utab.n;
+}
+extern "C" size_t nunet_plan_grad_sqnorm_ws_bytes(const nunet_plan* P) { return P ? (size_t)sqnorm_blocks(P) * sizeof(double) : 0; }
+extern "C" int nunet_plan_grad_sqnorm(nunet_plan* P, const void* arena, size_t arena_bytes, double* ws, size_t ws_bytes, nunet_stream_t s) {
+  NUNET_REQUIRE(P && arena && ws, "plan_grad_sqnorm: null pointer");
+  ARENA_CHECK("plan_grad_sqnorm");
+  NUNET_REQUIRE(((uintptr_t)ws & 7) == 0, "plan_grad_sqnorm: ws must be 8-byte aligned");
+  NUNET_REQUIRE(ws_bytes >= nunet_plan_grad_sqnorm_ws_bytes(P), "plan_grad_sqnorm: workspace of %zu bytes, nunet_plan_grad_sqnorm_ws_bytes = %zu",
+                ws_bytes, nunet_plan_grad_sqnorm_ws_bytes(P));
+  update_tiles(P);
+  ProfScope ps(PC_SGD, 0, (double)P->nparams * 4, (hipStream_t)s);
+  NUNET_LAUNCH(plan_sqnorm_kernel, dim3(P->ptab.ntiles + P->utab.n), dim3(256), 0, (hipStream_t)s,
+               (const float*)AB(const_cast<void*>(arena), P->off_gs), P->ptab, P->utab, ws);
+  return nunet_check_launch("plan_grad_sqnorm");
 }
 
 // Repack the 16-bit weight layouts from the fp32 master parameters (what nunet_plan_forward does first unless told

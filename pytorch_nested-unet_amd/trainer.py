@@ -33,7 +33,8 @@ from .parallel import allreduce_flat_, broadcast_flat_
 class TrainStep:
     def __init__(self, model, batch_shape, lr=1e-3, momentum=0.9, weight_decay=1e-4, nesterov=False,
                  use_graph=True, process_group=None, keep_grads=True, fused_update=None, loss="BCEDiceLoss", input_u8=False,
-                 schedule=None, segmented=None, optimizer="SGD", betas=(0.9, 0.999), eps=1e-8, loss_scale=None):
+                 schedule=None, segmented=None, optimizer="SGD", betas=(0.9, 0.999), eps=1e-8, loss_scale=None,
+                 clip_grad_norm=None):
         """loss: 'BCEDiceLoss' (reference losses.py:103-117, the default of trains.py:58) or 'LovaszHingeLoss'
         (losses.py:120-129, the loss of the reference's published table README.md:102-108; one class only) - both run
         inside the step's graph and under data parallel.
@@ -60,7 +61,13 @@ class TrainStep:
         captured step: the loss gradient is seeded with the scale, the final gradient scratch is checked for inf / NaN, the update
         unscales it - or, on an overflow, writes nothing (the step is skipped) - and a 1-thread launch backs the scale off or grows
         it as torch's scaler.update() does. No host synchronisation per step; scaler_stats() / scaler_state_dict() read the state.
-        Under scaling the in-pass update (fused_update 3) falls back to 2: a step half applied inside the pass cannot be skipped."""
+        Under scaling the in-pass update (fused_update 3) falls back to 2: a step half applied inside the pass cannot be skipped.
+        clip_grad_norm: None (default: no clipping, today's launches) or max_norm > 0 of torch.nn.utils.clip_grad_norm_(params,
+        max_norm) over all parameters, applied inside the captured step between the unscale and the optimiser step: one read-only
+        pass takes the 2-norm of the final (rank-mean, unscaled) gradient in double, in a fixed summation order; a one-workgroup
+        launch forms coef = min(1, max_norm / (norm + 1e-6)) and the statistics; the update reads g * coef. float('inf')
+        measures and never clips (bit-identical to None). set_clip_grad_norm() changes the threshold of a captured step,
+        grad_norm_stats() reads the norms. Like scaling, clipping turns fused_update 3 into 2."""
         self.model = model
         self.eng = model.engine()
         dev = self.eng.device
@@ -133,10 +140,21 @@ class TrainStep:
         if self.scaler_cfg is not None:
             self._scaler = torch.zeros(L.SCALER_WORDS, dtype=torch.int32, device=dev)
             self._write_scaler(self.scaler_cfg["init_scale"], 0, 0)
-            if optimizer == "SGD":      # scaled SGD goes through the generic entries (bit-identical to the SGD ones)
-                self._optim = L.Optim(kind=L.OPT_SGD, momentum=momentum, beta1=0.0, beta2=0.0, eps=0.0, weight_decay=weight_decay,
-                                      nesterov=1 if nesterov else 0, lr=L.ptr(self.lr).value, state0=L.ptr(self.mom).value)
+        # gradient-norm clipping: the nunet_clip words on the device (max_norm, coef, last norm, peak, fp64 sum, clipped, steps)
+        self._clip = None
+        if clip_grad_norm is not None:
+            if not float(clip_grad_norm) > 0.0:
+                raise L.NunetError("TrainStep: clip_grad_norm must be > 0 or None (got %r)" % (clip_grad_norm,))
+            self._clip = torch.zeros(L.CLIP_WORDS, dtype=torch.int32, device=dev)
+            self._clip[0:2] = torch.tensor([float(clip_grad_norm), 1.0], dtype=torch.float32).view(torch.int32).to(dev)
+        if optimizer == "SGD" and (self._scaler is not None or self._clip is not None):
+            # scaled / clipped SGD goes through the generic entries (bit-identical to the SGD ones)
+            self._optim = L.Optim(kind=L.OPT_SGD, momentum=momentum, beta1=0.0, beta2=0.0, eps=0.0, weight_decay=weight_decay,
+                                  nesterov=1 if nesterov else 0, lr=L.ptr(self.lr).value, state0=L.ptr(self.mom).value)
+        if self._scaler is not None:
             self._optim.scaler = L.ptr(self._scaler).value
+        if self._clip is not None:
+            self._optim.clip = L.ptr(self._clip).value
         self.steps = 0
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (process_group is not None or dist.is_initialized()) else 1
@@ -174,8 +192,12 @@ class TrainStep:
         # as an op of the pass behind its weight gradients, beside the rest of the pass; single-process training only (a
         # data-parallel step exchanges the gradients before the update: it falls back to 2).
         self.fused_update = int(os.environ.get("NUNET_FUSED_UPDATE", "2")) if fused_update is None else int(fused_update)   
-        if self.fused_update == 3 and (self.dp or self.scaler_cfg is not None):
+        if self.fused_update == 3 and (self.dp or self.scaler_cfg is not None or self._clip is not None):
             self.fused_update = 2
+        if self._clip is not None:       # one double per workgroup of the square-norm launch of this layout
+            nb = (L.lib().nunet_plan_grad_sqnorm_ws_bytes(self.pl.handle) if self.fused_update
+                  else L.lib().nunet_grad_sqnorm_ws_bytes(self.eng.flat_params.numel()))
+            self._clip_ws = torch.zeros(nb // 8, dtype=torch.float64, device=dev)
         self.keep_grads = keep_grads
         self._inpass_set = False
         self._packed = False          # the arena's packed weights match the fp32 parameters
@@ -198,10 +220,10 @@ class TrainStep:
         self._b0_armed = L.lib().nunet_plan_bucket0_enable(self.pl.handle, 1 if on else 0) == 1
 
     def broadcast_state(self, src=0):
-        """Rank `src`'s parameters, optimiser state (momentum; Adam's moments and step), loss-scaler state and BatchNorm buffers
-        become every rank's (construction time; also after loading a checkpoint on one rank)."""
+        """Rank `src`'s parameters, optimiser state (momentum; Adam's moments and step), loss-scaler state, clip state (max_norm
+        and statistics) and BatchNorm buffers become every rank's (construction time; also after loading a checkpoint on one rank)."""
         eng = self.eng
-        for t in [eng.flat_params] + self.opt_state + [eng.bnbuf] + ([self._scaler] if self._scaler is not None else []):
+        for t in [eng.flat_params] + self.opt_state + [eng.bnbuf] + self._aux_state():
             broadcast_flat_(t, src, self.pg)
         nbt = eng.nbt.to(torch.float64)          # (gloo / RCCL both take floating tensors; counts are exact in fp64)
         broadcast_flat_(nbt, src, self.pg)
@@ -300,29 +322,51 @@ class TrainStep:
             L.check(L.lib().nunet_plan_set_inpass_update(self.pl.handle, None, None, None, 0.0, 0.0, 0, 1.0, None), "plan_set_inpass_update")
         self._inpass_set = on
 
+    def _aux_state(self):
+        """The scaler and clip words, where present: snapshotted by capture() and broadcast with the replica state."""
+        return [t for t in (self._scaler, self._clip) if t is not None]
+
+    def _clip_coef(self, plan, grad_scale):
+        """This step's clip factor: the square norm of the plan's gradient scratch (plan=True) or of the flat gradients, one
+        double per workgroup, then the one-workgroup launch that forms the norm, coef and the statistics."""
+        lib, eng, pl, st = L.lib(), self.eng, self.pl, L.stream()
+        ws = self._clip_ws
+        if plan:
+            L.check(lib.nunet_plan_grad_sqnorm(pl.handle, L.ptr(pl.arena), L.nbytes(pl.arena), L.ptr(ws), L.nbytes(ws), st), "plan_grad_sqnorm")
+        else:
+            L.check(lib.nunet_grad_sqnorm(L.ptr(eng.flat_grads), eng.flat_grads.numel(), L.ptr(ws), L.nbytes(ws), st), "grad_sqnorm")
+        L.check(lib.nunet_clip_finalize(L.ptr(ws), ws.numel(), grad_scale, L.ptr(self._scaler), L.ptr(self._clip), st), "clip_finalize")
+
     def _scaled_opt(self):
-        """The optimiser step under loss scaling, behind the complete (exchanged) gradient scratch: overflow check, Adam's
-        bookkeeping unless skipped, the update (unscaled by inv_scale; nothing written on a skipped step), the scale update."""
+        """The optimiser step under loss scaling and / or gradient clipping, behind the complete (exchanged) gradient scratch, in
+        torch's order: overflow check, Adam's bookkeeping unless skipped, the norm of the unscaled gradient and the clip factor,
+        the update (unscaled by inv_scale, clipped by coef; nothing written on a skipped step), the scale update."""
         lib, eng, pl, st = L.lib(), self.eng, self.pl, L.stream()
         sc = L.ptr(self._scaler)
-        L.check(lib.nunet_scaler_check(L.ptr(self._scratch), self._scratch.numel(), sc, st), "scaler_check")
-        if self.optimizer == "Adam":
-            L.check(lib.nunet_adam_prepare_scaled(L.ptr(self.lr), self.betas[0], self.betas[1], L.ptr(self.adam_step), L.ptr(self.adam_scal),
-                                                  sc, st), "adam_prepare_scaled")
+        if sc is not None:
+            L.check(lib.nunet_scaler_check(L.ptr(self._scratch), self._scratch.numel(), sc, st), "scaler_check")
+            if self.optimizer == "Adam":
+                L.check(lib.nunet_adam_prepare_scaled(L.ptr(self.lr), self.betas[0], self.betas[1], L.ptr(self.adam_step), L.ptr(self.adam_scal),
+                                                      sc, st), "adam_prepare_scaled")
         if self.fused_update:           # layout 2: repack 0, layout 1: repack 1
+            if self._clip is not None:
+                self._clip_coef(True, 1.0 / self.world)
             L.check(lib.nunet_plan_opt_step(pl.handle, L.ptr(eng.flat_params), C.byref(self._optim), L.ptr(pl.arena), L.nbytes(pl.arena),
                                             1.0 / self.world, L.ptr(eng.flat_grads) if self.keep_grads else None,
                                             1 if self.fused_update == 1 else 0, st), "plan_opt_step")
         else:
             if self.world > 1:
                 eng.flat_grads.mul_(1.0 / self.world)
+            if self._clip is not None:
+                self._clip_coef(False, 1.0)
             L.check(lib.nunet_opt_step(L.ptr(eng.flat_params), L.ptr(eng.flat_grads), C.byref(self._optim), eng.flat_params.numel(), 1.0, st),
                     "opt_step")
-        cfg = self.scaler_cfg
-        L.check(lib.nunet_scaler_update(sc, cfg["growth_factor"], cfg["backoff_factor"], cfg["growth_interval"], st), "scaler_update")
+        if sc is not None:
+            cfg = self.scaler_cfg
+            L.check(lib.nunet_scaler_update(sc, cfg["growth_factor"], cfg["backoff_factor"], cfg["growth_interval"], st), "scaler_update")
 
     def _opt(self):
-        if self._scaler is not None:
+        if self._scaler is not None or self._clip is not None:
             return self._scaled_opt()
         if self.fused_update:
             return self._update()
@@ -446,7 +490,7 @@ class TrainStep:
         else:
             self.x.copy_(inp)
             self.t.copy_(target)
-        state = [eng.flat_params, eng.bnbuf, eng.nbt, self.meters] + self.opt_state + ([self._scaler] if self._scaler is not None else [])
+        state = [eng.flat_params, eng.bnbuf, eng.nbt, self.meters] + self.opt_state + self._aux_state()
         snap = [t.clone() for t in state]
         steps0 = self.steps
         self.sync_weights()            # from here on every step leaves the packed weights current
@@ -768,7 +812,30 @@ class TrainStep:
         self.meters.zero_()
         if self._scaler is not None:
             self._scaler[4:5].zero_()        # skipped steps
+        if self._clip is not None:
+            self._clip[2:].zero_()           # last norm, peak, sum, clipped, steps (max_norm and coef stay)
         self.steps = 0
+
+    # -- gradient clipping -----------------------------------------------------------
+    def set_clip_grad_norm(self, value):
+        """A new max_norm (float('inf'): measure only) for the steps that follow; a captured step reads it from the device."""
+        if self._clip is None:
+            raise L.NunetError("this TrainStep was built without gradient clipping (clip_grad_norm=None)")
+        if not float(value) > 0.0:
+            raise L.NunetError("set_clip_grad_norm: max_norm must be > 0 (got %r)" % (value,))
+        self._clip[0:1].view(torch.float32).fill_(float(value))
+
+    def grad_norm_stats(self):
+        """dict(last, mean, peak, clipped, steps) of the total gradient norm over the applied steps since reset_meters() (steps
+        skipped by loss scaling do not count); one host sync. None without gradient clipping."""
+        if self._clip is None:
+            return None
+        torch.cuda.current_stream().synchronize()
+        w = self._clip.cpu()
+        f = w.view(torch.float32)
+        steps = int(w[7])
+        return dict(last=float(f[2]), mean=float(w[4:6].view(torch.float64).item()) / max(steps, 1), peak=float(f[3]),
+                    clipped=int(w[6]), steps=steps)
 
     # -- loss scaling ----------------------------------------------------------------
     def _write_scaler(self, scale, tracker, skipped=None):

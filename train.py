@@ -71,6 +71,8 @@ def parse_args():
                    help='dynamic loss scaling (torch.amp.GradScaler semantics; inside the fused step on the device)')
     p.add_argument('--init_scale', default=65536.0, type=float, help='initial loss scale (--loss_scale dynamic)')
     p.add_argument('--growth_interval', default=2000, type=int, help='clean steps between scale growths (--loss_scale dynamic)')
+    p.add_argument('--clip_grad_norm', default=0.0, type=float,
+                   help='max_norm of torch.nn.utils.clip_grad_norm_ over all parameters, inside the fused step (0: off)')
     p.add_argument('--train_size', default=512, type=int)
     p.add_argument('--val_size', default=128, type=int)
     p.add_argument('--seed', default=41, type=int)
@@ -169,15 +171,17 @@ def main():
         raise SystemExit('data parallel runs the fused step: multi-class LovaszHingeLoss is not fused')
     u8 = fused and config['device_pipeline'] and config['input_channels'] == 3 and config['num_classes'] == 1
     scaling = None if config['loss_scale'] == 'none' else dict(init_scale=config['init_scale'], growth_interval=config['growth_interval'])
+    clip = config['clip_grad_norm'] if config['clip_grad_norm'] > 0 else None
     if fused:
         model.train()
         if config['optimizer'] == 'Adam':      # torch.optim.Adam(params, lr, weight_decay) with its default betas / eps (trains.py:225-227)
             ts = TrainStep(model, (bs, config['input_channels'], h, w), lr=config['lr'], weight_decay=config['weight_decay'],
-                           loss=config['loss'], input_u8=u8, optimizer='Adam', loss_scale=scaling)
+                           loss=config['loss'], input_u8=u8, optimizer='Adam', loss_scale=scaling,
+                           clip_grad_norm=clip)
         else:
             ts = TrainStep(model, (bs, config['input_channels'], h, w), lr=config['lr'], momentum=config['momentum'],
                            weight_decay=config['weight_decay'], nesterov=config['nesterov'], loss=config['loss'], input_u8=u8,
-                           loss_scale=scaling)
+                           loss_scale=scaling, clip_grad_norm=clip)
         if u8:
             # the decoded set (what the reference's Dataset holds after cv2.imread, dataset.py:56-64) lives in HBM as uint8
             raw, m8 = nunet_amd.synth.synth_blob_pairs_u8(config['train_size'], h, w, seed=1000)
@@ -187,8 +191,9 @@ def main():
         else:
             ts.capture(train[0][:bs], train[1][:bs])
         if rank == 0:
-            print('=> fused training step (TrainStep): %s, %s%s' % (config['optimizer'], config['loss'],
-                                                                    ', dynamic loss scaling' if scaling else ''))
+            print('=> fused training step (TrainStep): %s, %s%s%s' % (config['optimizer'], config['loss'],
+                                                                      ', dynamic loss scaling' if scaling else '',
+                                                                      ', grad norm clipped at %g' % clip if clip else ''))
     else:
         params = filter(lambda p: p.requires_grad, model.parameters())
         if config['optimizer'] == 'Adam':
@@ -197,6 +202,7 @@ def main():
             optimizer = torch.optim.SGD(params, lr=config['lr'], momentum=config['momentum'], nesterov=config['nesterov'],
                                         weight_decay=config['weight_decay'])
         scaler = torch.amp.GradScaler('cuda', **scaling) if scaling else None
+        clip_params = [p for p in model.parameters() if p.requires_grad]
 
     log = OrderedDict([(k, []) for k in ('epoch', 'lr', 'loss', 'iou', 'val_loss', 'val_iou', 'images_per_sec')])
     best_iou, trigger = 0, 0
@@ -228,6 +234,7 @@ def main():
                     ts.step(train[0][idx], train[1][idx])
             tl, ti = ts.epoch_stats()
             scale_info = ts.scaler_stats()
+            norm_info = ts.grad_norm_stats()
             if world > 1:                                                # epoch means over all ranks' (equal-sized) batches
                 m = torch.tensor([tl, ti], dtype=torch.float64, device='cuda')
                 dist.all_reduce(m)
@@ -238,6 +245,7 @@ def main():
                 gpar['lr'] = lr
             ml, mi = AverageMeter(), AverageMeter()
             skipped = 0
+            norms = []
             for k in range(steps):                                       # reference trains.py:113-135
                 idx = perm[k * bs:(k + 1) * bs]
                 xb, tb = train[0][idx], train[1][idx]
@@ -251,17 +259,28 @@ def main():
                 optimizer.zero_grad()
                 if scaler is not None:
                     scaler.scale(loss).backward()
+                    if clip:
+                        scaler.unscale_(optimizer)
+                        norms.append(torch.nn.utils.clip_grad_norm_(clip_params, clip))
                     scaler.step(optimizer)
                     s0 = scaler.get_scale()
                     scaler.update()
                     skipped += int(scaler.get_scale() < s0)       # (a backoff: this step found an inf / NaN and was skipped)
                 else:
                     loss.backward()
+                    if clip:
+                        norms.append(torch.nn.utils.clip_grad_norm_(clip_params, clip))
                     optimizer.step()
                 ml.update(loss.item(), bs)
                 mi.update(iou_from_counts(iou_counts(last.detach().contiguous(), tb)), bs)
             tl, ti = ml.avg, mi.avg
             scale_info = (scaler.get_scale(), skipped) if scaler is not None else None
+            norm_info = None
+            if clip:
+                nv = torch.stack(norms)
+                nv = nv[torch.isfinite(nv)]                       # (steps skipped by the scaler do not count)
+                norm_info = dict(mean=float(nv.mean()) if nv.numel() else 0.0, peak=float(nv.max()) if nv.numel() else 0.0,
+                                 clipped=int((nv > clip).sum()))
         torch.cuda.synchronize()
         ips = steps * bs * world / (time.perf_counter() - t0)
         val_log = validate(config, val, model, criterion)                # every rank: identical replicas, identical numbers
@@ -272,7 +291,9 @@ def main():
         if rank == 0:
             print('Epoch [%d/%d] loss %.4f - iou %.4f - val_loss %.4f - val_iou %.4f - %.0f img/s'
                   % (epoch, config['epochs'], tl, ti, val_log['loss'], val_log['iou'], ips)
-                  + (' - loss scale %g, %d steps skipped' % scale_info if scale_info is not None else ''))
+                  + (' - loss scale %g, %d steps skipped' % scale_info if scale_info is not None else '')
+                  + (' - grad norm %.4g/%.4g, %d steps clipped' % (norm_info['mean'], norm_info['peak'], norm_info['clipped'])
+                     if norm_info is not None else ''))
             for k, v in zip(log, (epoch, lr, tl, ti, val_log['loss'], val_log['iou'], ips)):
                 log[k].append(v)
             with open('models/%s/log.csv' % config['name'], 'w') as f:
