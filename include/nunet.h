@@ -110,8 +110,10 @@ typedef struct {
   float* tf_dgamma; float* tf_dbeta; float* tf_dbias;
   void* tf_store; int32_t tf_ps;
   int32_t tile;                     /* workgroup tile, pixels x output channels: 0 = chosen from the shape (the measured policy), 1 = 128 x 32,
-                                     * 2 = 128 x 64, 3 = 256 x 32, 4 = 256 x 64 (2 and 4 need Cout % 64 == 0). Results do not depend on it
-                                     * except through the K-split (fp32 summation order) of grid-starved layers. */
+                                     * 2 = 128 x 64, 3 = 256 x 32, 4 = 256 x 64 (2 and 4 need Cout % 64 == 0). The stored OUTPUTS do not depend
+                                     * on it except through the K-split (fp32 summation order) of grid-starved layers. The `stats` / `bn_sums`
+                                     * totals do, in their last bits: a workgroup sums the pixels of its own tile in fp32 before its fixed-point
+                                     * add, and the tile decides which pixels meet in a lane, a wave and a workgroup. */
 } nunet_conv_desc;
 
 /* y = conv(cat(src0,src1)) + bias. Also used as dgrad with the flipped,

@@ -24,6 +24,35 @@ int nunet_debug_stamp(uint64_t* dst, nunet_stream_t stream);
 /* Diagnostic (tools/graph_sched_probe.py): `tag` workgroups, the first spins `us` microseconds. */
 int nunet_debug_spin(int32_t us, int32_t tag, nunet_stream_t stream);
 
+/* Launch geometry of a 3x3 convolution / weight-gradient descriptor, from the very code the launch runs (tile policy, tile
+ * chooser, K-split and persistent-grid rules). Pure host functions: no GPU call, and no pointer of the descriptor is
+ * dereferenced or required - only compared with NULL where the launch itself does (splitk_ws enables the K-split, bn_y the
+ * fused BatchNorm-backward reduce, whose tables take LDS and so change the grid). The tests use them to state which kernel
+ * instantiation and which loop regime a case reaches. */
+typedef struct {
+  int32_t tile;                     /* 1 = 128 x 32, 2 = 128 x 64, 3 = 256 x 32, 4 = 256 x 64 (the policy's choice when the descriptor says 0) */
+  int32_t BM, BN, HPMAX, NT;        /* pixels, output channels, halo-pixel capacity and threads of a workgroup */
+  int32_t NI, TH, TW, SH;           /* images x rows x columns of a pixel tile; SH = H + 1 with stacked-rows tiling, else 0 */
+  int32_t tilesX, tilesY, tilesG;   /* pixel tiles along x, y (virtual rows when stacked) and over the batch */
+  int32_t nCoT;                     /* Cout / BN */
+  int32_t S, nch;                   /* K-split slices (1: none) and 64-byte channel chunks of the input */
+  int32_t items;                    /* nCoT * tilesX * tilesY * tilesG * S */
+  int32_t grid;                     /* workgroups of the launch; workgroup b runs items b, b + grid, ... (after the XCD remap) */
+  int32_t per_cu;                   /* workgroups assumed resident per CU when the grid was sized */
+} nunet_conv_launch_info;
+int nunet_conv3x3_launch_info(const nunet_conv_desc* d, nunet_conv_launch_info* out);
+
+typedef struct {
+  int32_t A, B;                     /* a work item covers 32 A output x 32 B input channels */
+  int32_t NI, TH, TW, SH;           /* pixel tile (at most 128 pixels, 192 with halo), as above */
+  int32_t tilesX, tilesY, tilesG;
+  int32_t nMT;                      /* pixel tiles = tilesX * tilesY * tilesG */
+  int32_t nCoT, nCiT;               /* output / input channel tiles */
+  int32_t ksplit;                   /* slices of the pixel-tile loop = nunet_conv3x3_wgrad_slabs(d); slice s walks tiles s, s + ksplit, ... */
+  int32_t grid;                     /* nCoT * nCiT * ksplit workgroups */
+} nunet_wgrad_launch_info;
+int nunet_conv3x3_wgrad_launch_info(const nunet_wgrad_desc* d, nunet_wgrad_launch_info* out);
+
 #ifdef __cplusplus
 }
 #endif

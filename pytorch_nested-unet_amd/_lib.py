@@ -71,6 +71,18 @@ class WgradDesc(C.Structure):
                 ("dw", _vp), ("slab_stride", _i64), ("max_slabs", _i32), ("target_wgs", _i32), ("dw_floats", _i64), ("item_shape", _i32)]
 
 
+class ConvLaunchInfo(C.Structure):
+    """nunet_conv_launch_info (include/nunet_diag.h): what a ConvDesc would launch."""
+    _fields_ = [(k, _i32) for k in ("tile", "BM", "BN", "HPMAX", "NT", "NI", "TH", "TW", "SH", "tilesX", "tilesY", "tilesG",
+                                    "nCoT", "S", "nch", "items", "grid", "per_cu")]
+
+
+class WgradLaunchInfo(C.Structure):
+    """nunet_wgrad_launch_info (include/nunet_diag.h): what a WgradDesc would launch."""
+    _fields_ = [(k, _i32) for k in ("A", "B", "NI", "TH", "TW", "SH", "tilesX", "tilesY", "tilesG", "nMT", "nCoT", "nCiT",
+                                    "ksplit", "grid")]
+
+
 class BnFwdDesc(C.Structure):
     _fields_ = [("dtype", _i32), ("N", _i32), ("H", _i32), ("W", _i32), ("C", _i32),
                 ("y", _vp), ("PY", _i32),
@@ -197,6 +209,8 @@ _SIG = {
     "nunet_profile_end": (_i32, [C.POINTER(ProfEntry), _i32, C.POINTER(_i32)]),
     "nunet_debug_spin": (_i32, [_i32, _i32, _vp]),
     "nunet_debug_stamp": (_i32, [_vp, _vp]),
+    "nunet_conv3x3_launch_info": (_i32, [C.POINTER(ConvDesc), C.POINTER(ConvLaunchInfo)]),
+    "nunet_conv3x3_wgrad_launch_info": (_i32, [C.POINTER(WgradDesc), C.POINTER(WgradLaunchInfo)]),
     "nunet_graph_begin": (_i32, [_vp]),
     "nunet_graph_end": (_i32, [_vp, C.POINTER(_vp)]),
     "nunet_graph_launch": (_i32, [_vp, _vp]),

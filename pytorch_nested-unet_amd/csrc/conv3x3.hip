@@ -914,7 +914,7 @@ static void launch_conv_lt(int lt, unsigned grid, size_t dyn, hipStream_t st, co
 }
 
 // everything a launch of one problem needs, for one tile configuration
-struct ConvSetup { ConvP p; long grid; size_t dyn; bool bnr; int lt; double flops, bytes; };
+struct ConvSetup { ConvP p; long grid; long per_cu; size_t dyn; bool bnr; int lt; double flops, bytes; };
 template <typename T, int WM, int WN, int SM, int SN>
 static void conv_setup(const nunet_conv_desc* d, ConvSetup& S) {
   typedef ConvCfg<T, WM, WN, SM, SN> C;
@@ -967,6 +967,7 @@ static void conv_setup(const nunet_conv_desc* d, ConvSetup& S) {
   long per_cu = (long)(160 * 1024 / lds_bytes);
   if (per_cu < 1) per_cu = 1;
   if (per_cu > 2048 / C::NT) per_cu = 2048 / C::NT;
+  S.per_cu = per_cu;
   const long resident = 256 * per_cu;
   const long rounds = (items + resident - 1) / resident;
   S.grid = (items + rounds - 1) / rounds;
@@ -1079,7 +1080,7 @@ template <typename T> static int conv_is_split(const nunet_conv_desc* d) {
   return S.p.S > 1 ? 1 : 0;
 }
 
-static int conv_check(const nunet_conv_desc* d);
+static int conv_check(const nunet_conv_desc* d, bool ptrs = true);
 // Grouping key of a problem: problems with equal keys (>= 0) may share a launch. -1: launch it alone.
 int nunet_conv_group_key(const nunet_conv_desc* d) {
   if (!d || conv_check(d) != NUNET_OK) return -1;
@@ -1095,16 +1096,17 @@ int nunet_conv3x3_group(const nunet_conv_desc* const* ds, int n, hipStream_t st)
   return NUNET_DISPATCH(ds[0]->dtype, launch_conv_n, ds, n, st);
 }
 
-static int conv_check(const nunet_conv_desc* d) {
-  NUNET_REQUIRE(d && d->src0 && d->wpack && d->dst0, "conv3x3: null pointer");
+// ptrs == false (nunet_conv3x3_launch_info): the shape rules only, no pointer is required
+static int conv_check(const nunet_conv_desc* d, bool ptrs) {
+  NUNET_REQUIRE(d && (!ptrs || (d->src0 && d->wpack && d->dst0)), "conv3x3: null pointer");
   const int cin = d->C0 + d->C1, cout = d->D0 + d->D1;
   NUNET_REQUIRE(d->dtype >= 0 && d->dtype <= 2, "conv3x3: bad dtype %d", d->dtype);
   const int kc = 64 / dtype_size(d->dtype);
   NUNET_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0, "conv3x3: bad extent %dx%dx%d", d->N, d->H, d->W);
   NUNET_REQUIRE(d->C0 > 0 && d->C0 % kc == 0 && d->C1 % kc == 0, "conv3x3: C0=%d C1=%d must be multiples of %d (64-byte channel chunks)", d->C0, d->C1, kc);
-  NUNET_REQUIRE(d->C1 == 0 || d->src1, "conv3x3: src1 null with C1=%d", d->C1);
+  NUNET_REQUIRE(!ptrs || d->C1 == 0 || d->src1, "conv3x3: src1 null with C1=%d", d->C1);
   NUNET_REQUIRE(cout % 32 == 0 && d->D0 % 32 == 0 && d->D1 % 32 == 0, "conv3x3: D0=%d D1=%d must be multiples of 32", d->D0, d->D1);
-  NUNET_REQUIRE(d->D1 == 0 || d->dst1, "conv3x3: dst1 null with D1=%d", d->D1);
+  NUNET_REQUIRE(!ptrs || d->D1 == 0 || d->dst1, "conv3x3: dst1 null with D1=%d", d->D1);
   NUNET_REQUIRE(d->P0 >= d->C0 && (d->C1 == 0 || d->P1 >= d->C1) && d->Q0 >= d->D0 && (d->D1 == 0 || d->Q1 >= d->D1), "conv3x3: pitch smaller than channels");
   const int epv = 16 / dtype_size(d->dtype);
   NUNET_REQUIRE(d->P0 % epv == 0 && (d->C1 == 0 || d->P1 % epv == 0), "conv3x3: source pitch must keep 16-byte alignment");
@@ -1117,7 +1119,7 @@ static int conv_check(const nunet_conv_desc* d) {
                   (d->in_tf != 2 || px * d->tf_py * es < lim), "conv3x3: problem too large (every input tensor must span < 4 GB)");
   }
   if (d->bn_y) {
-    NUNET_REQUIRE(d->bn_mean_invstd && d->bn_gamma && d->bn_beta && d->bn_sums, "conv3x3: fused BN-backward reduce needs mean/invstd, gamma, beta and sums");
+    NUNET_REQUIRE(!ptrs || (d->bn_mean_invstd && d->bn_gamma && d->bn_beta && d->bn_sums), "conv3x3: fused BN-backward reduce needs mean/invstd, gamma, beta and sums");
     NUNET_REQUIRE(d->D1 == 0 && d->Q0 == d->D0 && d->acc0_mask == 0 && d->bn_py % epv == 0 && cout <= 512,
                   "conv3x3: fused BN-backward reduce needs one dense, assign-only destination");
   }
@@ -1125,13 +1127,13 @@ static int conv_check(const nunet_conv_desc* d) {
   NUNET_REQUIRE(d->tile >= 0 && d->tile <= 4 && ((d->tile != 2 && d->tile != 4) || cout % 64 == 0), "conv3x3: tile %d with Cout=%d", d->tile, cout);
   if (d->in_tf) {
     NUNET_REQUIRE(d->C1 == 0 && cin <= 1024, "conv3x3: an input transform needs a single source (C1 == 0) of at most 1024 channels");
-    NUNET_REQUIRE(d->tf_gamma && d->tf_beta, "conv3x3: input transform needs gamma and beta");
+    NUNET_REQUIRE(!ptrs || (d->tf_gamma && d->tf_beta), "conv3x3: input transform needs gamma and beta");
     NUNET_REQUIRE(!d->tf_store || d->tf_ps % epv == 0, "conv3x3: tf_store pitch alignment");
     if (d->in_tf == 1) {
-      if (d->tf_training) NUNET_REQUIRE(d->tf_fx, "conv3x3: BN input transform in training mode needs the producing conv's sums");
-      else NUNET_REQUIRE(d->tf_running_mean && d->tf_running_var, "conv3x3: BN input transform in eval mode needs running statistics");
+      if (d->tf_training) NUNET_REQUIRE(!ptrs || d->tf_fx, "conv3x3: BN input transform in training mode needs the producing conv's sums");
+      else NUNET_REQUIRE(!ptrs || (d->tf_running_mean && d->tf_running_var), "conv3x3: BN input transform in eval mode needs running statistics");
     } else {
-      NUNET_REQUIRE(d->tf_y && d->tf_fx && d->tf_mean_invstd && d->tf_py % epv == 0, "conv3x3: BN-backward input transform needs y, sums and saved mean/invstd");
+      NUNET_REQUIRE((!ptrs || (d->tf_y && d->tf_fx && d->tf_mean_invstd)) && d->tf_py % epv == 0, "conv3x3: BN-backward input transform needs y, sums and saved mean/invstd");
     }
   }
   return NUNET_OK;
@@ -1140,6 +1142,33 @@ extern "C" int nunet_conv3x3_fwd(const nunet_conv_desc* d, nunet_stream_t s) {
   const int rc = conv_check(d);
   if (rc) return rc;
   return NUNET_DISPATCH(d->dtype, launch_conv, d, (hipStream_t)s);
+}
+
+// Diagnostic (include/nunet_diag.h): what launch_conv_n would launch for this descriptor, from the same policy and setup code
+template <typename T, int WM, int WN, int SM, int SN>
+static int conv_info_cfg(const nunet_conv_desc* d, int cfg, nunet_conv_launch_info* o) {
+  typedef ConvCfg<T, WM, WN, SM, SN> C;
+  ConvSetup S;
+  conv_setup<T, WM, WN, SM, SN>(d, S);
+  const ConvP& p = S.p;
+  o->tile = cfg + 1; o->BM = C::BM; o->BN = C::BN; o->HPMAX = C::HPMAX; o->NT = C::NT;
+  o->NI = p.NI; o->TH = p.TH; o->TW = p.TW; o->SH = p.SH;
+  o->tilesX = p.tilesX; o->tilesY = p.tilesY; o->tilesG = p.tilesG; o->nCoT = p.nCoT;
+  o->S = p.S; o->nch = p.nch; o->items = p.nItems; o->grid = (int32_t)S.grid; o->per_cu = (int32_t)S.per_cu;
+  return NUNET_OK;
+}
+template <typename T> static int conv_info(const nunet_conv_desc* d, nunet_conv_launch_info* o) {
+  const int cfg = conv_cfg_of(d);
+  if (cfg == 0) return conv_info_cfg<T, 4, 1, 1, 1>(d, cfg, o);
+  if (cfg == 1) return conv_info_cfg<T, 2, 2, 2, 1>(d, cfg, o);
+  if (cfg == 3) return conv_info_cfg<T, 4, 1, 2, 2>(d, cfg, o);
+  return conv_info_cfg<T, 4, 1, 2, 1>(d, cfg, o);
+}
+extern "C" int nunet_conv3x3_launch_info(const nunet_conv_desc* d, nunet_conv_launch_info* out) {
+  NUNET_REQUIRE(out, "conv3x3 launch info: null output");
+  const int rc = conv_check(d, false);
+  if (rc) return rc;
+  return NUNET_DISPATCH(d->dtype, conv_info, d, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -1600,11 +1629,12 @@ template <typename T> static int launch_wgrad_pair(const WgPairArgs* w, hipStrea
   return nunet_check_launch("wgrad3x3 (pair)");
 }
 
-static int wgrad_check(const nunet_wgrad_desc* d) {
-  NUNET_REQUIRE(d && d->src0 && d->dy && d->dw, "wgrad: null pointer");
+// ptrs == false (nunet_conv3x3_wgrad_launch_info): the shape rules only, no pointer or slab capacity is required
+static int wgrad_check(const nunet_wgrad_desc* d, bool ptrs = true) {
+  NUNET_REQUIRE(d && (!ptrs || (d->src0 && d->dy && d->dw)), "wgrad: null pointer");
   NUNET_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0, "wgrad: bad extent");
   NUNET_REQUIRE(d->C0 > 0 && d->C0 % 16 == 0 && d->C1 % 16 == 0, "wgrad: C0=%d C1=%d must be multiples of 16", d->C0, d->C1);
-  NUNET_REQUIRE(d->C1 == 0 || d->src1, "wgrad: src1 null");
+  NUNET_REQUIRE(!ptrs || d->C1 == 0 || d->src1, "wgrad: src1 null");
   NUNET_REQUIRE(d->Cout % 32 == 0, "wgrad: Cout=%d must be a multiple of 32", d->Cout);
   const int epv = 16 / dtype_size(d->dtype);
   NUNET_REQUIRE(d->P0 % epv == 0 && (d->C1 == 0 || d->P1 % epv == 0) && d->PY % epv == 0, "wgrad: pitch alignment");
@@ -1616,7 +1646,7 @@ static int wgrad_check(const nunet_wgrad_desc* d) {
   NUNET_REQUIRE(d->slab_stride == 0 || d->slab_stride >= 9LL * d->Cout * (d->C0 + d->C1), "wgrad: slab_stride smaller than one slab");
   NUNET_REQUIRE(d->max_slabs >= 0 && d->target_wgs >= 0, "wgrad: max_slabs / target_wgs");
   NUNET_REQUIRE(d->item_shape == 0 || d->item_shape == 11 || d->item_shape == 12 || d->item_shape == 21, "wgrad: item_shape %d (0 | 11 | 12 | 21)", d->item_shape);
-  {
+  if (ptrs) {
     // every slab the launch will write must fit what the caller says `dw` holds
     const long long stride = d->slab_stride > 0 ? d->slab_stride : 9LL * d->Cout * (d->C0 + d->C1);
     const long long need = (long long)(nunet_conv3x3_wgrad_slabs(d) - 1) * stride + 9LL * d->Cout * (d->C0 + d->C1);
@@ -1637,6 +1667,24 @@ extern "C" int nunet_conv3x3_wgrad_pair(const nunet_wgrad_desc* a, const nunet_w
   NUNET_REQUIRE(a->dtype == b->dtype, "wgrad_pair: the two problems must share the dtype");
   WgPairArgs w{a, b};
   return NUNET_DISPATCH(a->dtype, launch_wgrad_pair, &w, (hipStream_t)s);
+}
+
+// Diagnostic (include/nunet_diag.h): the geometry launch_wgrad would use, from wgrad_setup itself
+template <typename T> static int wgrad_info(const nunet_wgrad_desc* d, nunet_wgrad_launch_info* o) {
+  WgP p;
+  const long grid = wgrad_setup<T>(d, p);
+  const WgTile wt = wgrad_tile(d);
+  o->A = wt.A; o->B = wt.B;
+  o->NI = p.NI; o->TH = p.TH; o->TW = p.TW; o->SH = p.SH;
+  o->tilesX = p.tilesX; o->tilesY = p.tilesY; o->tilesG = p.tilesG; o->nMT = p.nMT;
+  o->nCoT = p.nCoT; o->nCiT = p.nCiT; o->ksplit = p.ksplit; o->grid = (int32_t)grid;
+  return NUNET_OK;
+}
+extern "C" int nunet_conv3x3_wgrad_launch_info(const nunet_wgrad_desc* d, nunet_wgrad_launch_info* out) {
+  NUNET_REQUIRE(out, "wgrad launch info: null output");
+  const int rc = wgrad_check(d, false);
+  if (rc) return rc;
+  return NUNET_DISPATCH(d->dtype, wgrad_info, d, out);
 }
 
 // Sum of the K-split slabs of a weight gradient (fixed order: bit-reproducible): out[i] (+)= sum_s slabs[s * stride + i].

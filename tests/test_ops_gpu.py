@@ -68,15 +68,17 @@ def conv_desc(dt, n, h, w, src0, c0, p0, wpack, dst0, d0, q0, src1=None, c1=0, p
 
 @pytest.mark.parametrize("dt", [L.F32, L.BF16, L.F16])
 @pytest.mark.parametrize("shape", [
-    (2, 20, 24, 32, 0, 32),     # BN=32 config, ragged tiles
-    (1, 16, 16, 64, 64, 64),    # two sources, BN=64 config
-    (5, 6, 6, 32, 0, 64),       # multi-image tiles
-    (2, 8, 40, 96, 0, 32),      # three channel chunks from one source
-    (1, 2, 2, 64, 32, 96),      # tiny spatial, Cout = 96 -> BN=32 config
-    (3, 1, 1, 32, 0, 32),       # 1x1 images (level 4 of a 16x16 input)
-    (16, 12, 12, 64, 32, 64),   # 12x12 images: stacked-rows tiling (level 3 of the 96x96 workload)
-    (5, 12, 12, 32, 0, 32),     # stacked rows, BM=256 config, ragged last tile
-    (7, 3, 5, 32, 0, 64),       # stacked rows on odd tiny images
+    # every shape here has fewer than 256 standard items, so the policy gives all of them the 128 x 32 tile, one work item
+    # per workgroup (nunet_conv3x3_launch_info); the other three tiles and the multi-item loop: tests/test_conv_tiles_gpu.py
+    (2, 20, 24, 32, 0, 32),     # 10 x 12 pixel tiles: 8 unused rows per tile
+    (1, 16, 16, 64, 64, 64),    # two sources, two Cout tiles
+    (5, 6, 6, 32, 0, 64),       # multi-image tiles (3 images each, the second one ragged)
+    (2, 8, 40, 96, 0, 32),      # three channel chunks from one source, ragged tile columns
+    (1, 2, 2, 64, 32, 96),      # tiny spatial (stacked rows), Cout = 96: three Cout tiles
+    (3, 1, 1, 32, 0, 32),       # 1x1 images (level 4 of a 16x16 input): stacked rows, one item
+    (16, 12, 12, 64, 32, 64),   # 12x12 images: stacked-rows tiling (level 3 of the 96x96 workload), 21 tiles of 10 virtual rows
+    (5, 12, 12, 32, 0, 32),     # stacked rows, ragged last tile
+    (7, 3, 5, 32, 0, 64),       # odd tiny images: regular tiling, 4 images per tile, the second tile ragged
 ])
 def test_conv3x3_fwd(dt, shape):
     n, h, w, c0, c1, cout = shape
@@ -131,13 +133,15 @@ def test_conv3x3_dgrad_split_accumulate(dt):
 
 @pytest.mark.parametrize("dt", [L.F32, L.BF16, L.F16])
 @pytest.mark.parametrize("shape", [
-    (2, 20, 24, 32, 0, 32, 32),
+    # the default K-split gives every one of these shapes one pixel tile per slice (ksplit == nMT, nunet_conv3x3_wgrad_launch_info):
+    # the tile loop's body runs once; slices that walk several tiles: tests/test_conv_tiles_gpu.py
+    (2, 20, 24, 32, 0, 32, 32),     # 8 pixel tiles of 10 x 12
     (1, 16, 16, 64, 64, 64, 64),
-    (5, 6, 6, 64, 32, 64, 32),      # Cin = 96: ci tile straddles the two sources
+    (5, 6, 6, 64, 32, 64, 32),      # Cin = 96: input tiles 0, 1 from source 0, tile 2 from source 1; multi-image pixel tiles
     (2, 8, 8, 32, 0, 32, 32),       # first-layer style: real Cin=3 padded to 32 handled by caller
-    (3, 1, 1, 32, 0, 64, 32),
-    (16, 12, 12, 64, 32, 64, 32),   # stacked-rows tiling
-    (7, 3, 5, 32, 0, 32, 32),
+    (3, 1, 1, 32, 0, 64, 32),       # stacked rows, a single pixel tile
+    (16, 12, 12, 64, 32, 64, 32),   # stacked-rows tiling, 21 pixel tiles
+    (7, 3, 5, 32, 0, 32, 32),       # 4 images per pixel tile
 ])
 def test_conv3x3_wgrad(dt, shape):
     n, h, w, c0, c1, cout, _ = shape
