@@ -40,7 +40,7 @@ enum {
   NUNET_ENODEV = -3   /* no gfx950 device / code object */
 };
 
-int nunet_version(void);
+int nunet_version(void);   /* 101: the SGD-only plan entries of 100 are gone, nunet_plan_opt_step / nunet_plan_set_inpass_opt take SGD too */
 const char* nunet_last_error(void);
 
 /* ------------------------------------------------------------------------ */
@@ -442,7 +442,8 @@ int32_t nunet_plan_num_heads(const nunet_plan* p);
  * input:  NCHW fp32. logits: [heads][N][K][H][W] fp32.
  * arena / arena_bytes: the caller's buffer of at least nunet_plan_arena_bytes(p) bytes (NUNET_EINVAL when smaller), 256-byte aligned.
  * training: bit 0 = training mode (batch statistics, running-stat update); bit 1 = the packed weights in `arena`
- * are current (left so by nunet_plan_update / nunet_plan_repack on these parameters): skip the repack; bit 2 = the image
+ * are current (left so by nunet_plan_opt_step with repack = 1, the in-pass step or nunet_plan_repack on these parameters): skip
+ * the repack; bit 2 = the image
  * was staged into the arena by nunet_plan_stage_u8 (`input` is ignored and may be NULL). */
 int nunet_plan_forward(nunet_plan* p, const float* params, float* bnbuf, int64_t* nbt,
                        const float* input, void* arena, size_t arena_bytes, float* logits, int32_t training,
@@ -481,38 +482,26 @@ int nunet_plan_grad_scratch(const nunet_plan* p, int64_t* byte_offset, int64_t* 
  * producing kernels directly (inside a capture `s` must be a stream the capture has not used yet). */
 int nunet_plan_bucket0_enable(nunet_plan* p, int32_t on);
 int nunet_plan_bucket0_wait(nunet_plan* p, nunet_stream_t s);
-/* Fused optimiser step on the plan's buffers, replacing unpack (nunet_plan_backward_phase bit 2) + nunet_sgd_step +
- * the repack of the next forward: gradient scratch (optionally exchanged between ranks) -> torch.optim.SGD step
- * (reference trains.py:229-231; lr from device memory, momentum buffer `momentum`, weight decay, nesterov,
- * grad_scale = 1/world) on the fp32 master parameters -> both packed weight layouts. `grads` (flat OIHW, may be NULL)
- * receives the scaled gradients. */
-int nunet_plan_update(nunet_plan* p, float* params, float* momentum, void* arena, size_t arena_bytes, const float* lr_dev, float mom, float wd,
-                      int32_t nesterov, float grad_scale, float* grads, nunet_stream_t s);
-/* The optimiser step INSIDE the backward pass: once parameters are set here, every whole backward pass steps each VGGBlock's
- * parameters (scratch -> SGD -> both packed 16-bit layouts, the arithmetic of nunet_plan_update) as an op scheduled behind that
- * block's weight gradients, beside the rest of the pass, and the heads at its end. The caller then calls neither
- * nunet_plan_update nor nunet_plan_sgd and sets bit 1 of the next forward's training flags (weights current).
- * Single-process training only (a data-parallel step exchanges the gradients before the update). params = NULL: off. */
-int nunet_plan_set_inpass_update(nunet_plan* p, float* params, float* momentum, const float* lr_dev, float mom, float wd,
-                                 int32_t nesterov, float grad_scale, float* grads);
-/* The same optimiser step without the repack (the next nunet_plan_forward repacks as usual): gradient scratch -> SGD,
- * one launch instead of unpack + nunet_sgd_step, no OIHW gradient round trip unless `grads` is given. */
-int nunet_plan_sgd(nunet_plan* p, float* params, float* momentum, void* arena, size_t arena_bytes, const float* lr_dev, float mom, float wd,
-                   int32_t nesterov, float grad_scale, float* grads, nunet_stream_t s);
-/* The fused steps above with any optimiser (nunet_optim): repack = 0 is nunet_plan_sgd's launch (the next forward repacks),
- * repack = 1 is nunet_plan_update's (both packed layouts written). With an SGD `opt` the results are those of
- * nunet_plan_sgd / nunet_plan_update bit for bit. With opt->scaler set (loss scaling) the gradients are read as
+/* Fused optimiser step (any nunet_optim) on the plan's buffers, one launch replacing unpack (nunet_plan_backward_phase bit 2) +
+ * nunet_opt_step: gradient scratch (optionally exchanged between ranks) -> the step on the fp32 master parameters (lr from
+ * device memory, grad_scale = 1/world). repack = 0: the next nunet_plan_forward repacks as usual; repack = 1: both packed weight
+ * layouts are written too, and the next forward may set bit 1 of `training`. `grads` (flat OIHW, may be NULL) receives the
+ * scaled gradients. SGD needs state0 whatever the momentum. With opt->scaler set (loss scaling) the gradients are read as
  * g * grad_scale * inv_scale, and a step with found_inf set writes only `grads` (nunet_scaler). With opt->clip set they are
  * read as that times clip->coef (nunet_clip), and `grads` receive the clipped gradient. */
 int nunet_plan_opt_step(nunet_plan* p, float* params, const nunet_optim* opt, void* arena, size_t arena_bytes, float grad_scale,
                         float* grads, int32_t repack, nunet_stream_t s);
-/* nunet_plan_set_inpass_update with any optimiser (the struct is copied; params = NULL: off). No scaler and no clip: a step
- * already half applied inside the pass can neither be skipped nor rescaled. */
+/* The optimiser step INSIDE the backward pass: once parameters are set here, every whole backward pass steps each VGGBlock's
+ * parameters (the arithmetic of nunet_plan_opt_step with repack = 1) as an op scheduled behind that block's weight gradients,
+ * beside the rest of the pass, and the heads at its end. The caller then does not call nunet_plan_opt_step and sets bit 1 of the
+ * next forward's training flags (weights current). Single-process training only (a data-parallel step exchanges the gradients
+ * before the update). The struct is copied. params = NULL: off, whatever `opt` is (NULL included). No scaler and no clip: a
+ * step already half applied inside the pass can neither be skipped nor rescaled. */
 int nunet_plan_set_inpass_opt(nunet_plan* p, float* params, const nunet_optim* opt, float grad_scale, float* grads);
 /* Square norm of the gradient in the plan's native-layout scratch (after the backward pass and, data parallel, the exchange):
  * one double partial per workgroup in `ws`, for nunet_clip_finalize with nparts = nunet_plan_grad_sqnorm_ws_bytes / 8. Only
  * real parameters count: the [tap][co][ci] entries with ci < cin (not the padding up to cinpad), conv bias / gamma / beta, and
- * each head's gradient as the sum of its slabs (nunet_plan_sgd's summation order) before it is squared. Read-only on the arena. */
+ * each head's gradient as the sum of its slabs (the summation order of nunet_plan_opt_step) before it is squared. Read-only on the arena. */
 size_t nunet_plan_grad_sqnorm_ws_bytes(const nunet_plan* p);
 int nunet_plan_grad_sqnorm(nunet_plan* p, const void* arena, size_t arena_bytes, double* ws, size_t ws_bytes, nunet_stream_t s);
 /* Repack the weight layouts from the fp32 parameters (what nunet_plan_forward does first unless told they are current). */

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <string.h>
 #include <type_traits>
 
 #include "../../include/nunet.h"
@@ -357,7 +358,8 @@ __device__ __forceinline__ double block256_sum_f64(double v, double* s_w4) {
 // Optimiser functors of the fused update kernels (plan.hip) and the flat Adam step (elementwise.hip): the per-element step
 // with its state pointers (NS fp32 buffers in flat parameter order). begin(gscale) reads the device scalars once per thread;
 // one(p, g, s) takes the (scaled, undecayed) gradient and the element's state, updates the state in place and returns the
-// new parameter. Built on the host from a nunet_optim by opt_from() (plan.hip) / the flat entry (elementwise.hip).
+// new parameter. Built on the host from a nunet_optim by opt_sgd() / opt_adam() below, which every entry reaches through
+// opt_check() + opt_dispatch().
 // Loss scaling (sc != NULL, nunet_scaler): begin() returns false when the step is skipped (found_inf) - every thread of the
 // launch reads the same word, written by an earlier launch, so the decision is uniform and the caller's workgroup stores no
 // parameter, state or packed weight - and otherwise folds inv_scale into the caller's gradient scale. sc == NULL leaves the
@@ -427,4 +429,32 @@ template <typename O> __device__ __forceinline__ float opt_elem(const O& o, floa
 #pragma unroll
   for (int k = 0; k < O::NS; ++k) o.st[k][idx] = s[k];
   return pn;
+}
+
+// Host side of the functors: one validator, one builder per functor, one dispatcher over nunet_optim.kind. Every entry that
+// takes a nunet_optim refuses a bad one here, before it touches the device. need_sgd_state: the plan kernels load the
+// momentum buffer unconditionally (opt_elem), the flat sgd_kernel only when momentum != 0.
+static inline int opt_check(const nunet_optim* o, const char* what, bool need_sgd_state) {
+  NUNET_REQUIRE(o, "%s: null optimiser", what);
+  const bool sgd = o->kind == NUNET_OPT_SGD;
+  NUNET_REQUIRE(sgd || o->kind == NUNET_OPT_ADAM, "%s: unknown optimiser kind %d", what, (int)o->kind);
+  NUNET_REQUIRE(!sgd || (o->lr && (o->state0 || (!need_sgd_state && o->momentum == 0.f))), "%s: SGD needs lr and state0 (momentum buffer)", what);
+  NUNET_REQUIRE(sgd || (o->adam_scal && o->state0 && o->state1), "%s: Adam needs adam_scal, state0 (exp_avg) and state1 (exp_avg_sq)", what);
+  NUNET_REQUIRE(sgd || (o->beta1 >= 0.0 && o->beta1 < 1.0 && o->beta2 >= 0.0 && o->beta2 < 1.0), "%s: betas must lie in [0, 1)", what);
+  NUNET_REQUIRE(sgd || o->eps > 0.f, "%s: eps must be > 0", what);
+  return NUNET_OK;
+}
+static inline OptSgd opt_sgd(const nunet_optim* d) {
+  OptSgd o; memset(&o, 0, sizeof(o));
+  o.st[0] = d->state0; o.lr_dev = d->lr; o.momc = d->momentum; o.wd = d->weight_decay; o.nesterov = d->nesterov; o.sc = d->scaler; o.cl = d->clip;
+  return o;
+}
+static inline OptAdam opt_adam(const nunet_optim* d) {
+  OptAdam o; memset(&o, 0, sizeof(o));
+  o.st[0] = d->state0; o.st[1] = d->state1; o.scal_dev = d->adam_scal; o.eps = d->eps; o.wd = d->weight_decay; o.sc = d->scaler; o.cl = d->clip;
+  o.omb1 = (float)(1.0 - d->beta1); o.b2 = (float)d->beta2; o.omb2 = (float)(1.0 - d->beta2);
+  return o;
+}
+template <class F> static inline int opt_dispatch(const nunet_optim* o, F&& f) {   // f(functor of o->kind); `o` has passed opt_check
+  return o->kind == NUNET_OPT_ADAM ? f(opt_adam(o)) : f(opt_sgd(o));
 }

@@ -36,7 +36,7 @@ int nunet_check_launch(const char* what) {
   return NUNET_OK;
 }
 extern "C" const char* nunet_last_error(void) { return g_err; }
-extern "C" int nunet_version(void) { return 100; }
+extern "C" int nunet_version(void) { return 101; }
 
 static inline int grid_for(int64_t items, int block, int cap = 256 * 16) {
   int64_t g = ceil_div64(items, block);
@@ -1274,13 +1274,6 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     p[i] = pv - lr * gv;
   }
 }
-extern "C" int nunet_sgd_step(float* p, const float* g, float* mom, int64_t n, const float* lr_dev, float momentum, float weight_decay, int32_t nesterov, int32_t first, float grad_scale, nunet_stream_t s) {
-  NUNET_REQUIRE(p && g && lr_dev && n > 0 && (momentum == 0.f || mom), "sgd_step: bad args");
-  ProfScope ps(PC_SGD, 0, (double)n * 20, (hipStream_t)s);
-  NUNET_LAUNCH(sgd_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, (hipStream_t)s, p, g, mom, n, lr_dev, momentum, weight_decay, nesterov, first, grad_scale,
-               (const nunet_scaler*)nullptr, (const nunet_clip*)nullptr);
-  return nunet_check_launch("sgd_step");
-}
 
 // ---------------------------------------------------------------------------
 // Adam (torch.optim.Adam semantics, amsgrad off; the per-element arithmetic is OptAdam in common.h)
@@ -1333,30 +1326,36 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
   for (int64_t i = 4 * n4 + tid; i < n; i += nth) p[i] = opt_elem(o, p[i], g[i] * gscale, i);
 }
-static int adam_args(const nunet_optim* opt, const char* what) {
-  NUNET_REQUIRE(opt->adam_scal && opt->state0 && opt->state1, "%s: Adam needs adam_scal, state0 and state1", what);
-  NUNET_REQUIRE(opt->beta1 >= 0.0 && opt->beta1 < 1.0 && opt->beta2 >= 0.0 && opt->beta2 < 1.0, "%s: betas must lie in [0, 1)", what);
-  NUNET_REQUIRE(opt->eps > 0.f, "%s: eps must be > 0", what);
-  return NUNET_OK;
+
+// The flat step (layout 0) of a validated nunet_optim, either kind: one launch of sgd_kernel / adam_kernel
+static void launch_flat(float* p, const float* g, const nunet_optim* opt, int64_t n, float grad_scale, int first, hipStream_t st) {
+  const dim3 grid(grid_for(n, 256 * 4, 2048)), blk(256);
+  opt_dispatch(opt, [&](auto o) {
+    ProfScope ps(PC_SGD, 0, (double)n * (o.NS == 2 ? 28 : 20), st);
+    if constexpr (std::is_same<decltype(o), OptSgd>::value) {
+      NUNET_LAUNCH(sgd_kernel, grid, blk, 0, st, p, g, o.st[0], n, o.lr_dev, o.momc, o.wd, o.nesterov, first, grad_scale, o.sc, o.cl);
+    } else {
+      const int vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)o.st[0] | (uintptr_t)o.st[1]) & 15) == 0;
+      NUNET_LAUNCH(adam_kernel, grid, blk, 0, st, p, g, o, n, grad_scale, vec);
+    }
+    return (int)NUNET_OK;
+  });
 }
-static void launch_adam(float* p, const float* g, const nunet_optim* opt, int64_t n, float grad_scale, hipStream_t st) {
-  OptAdam o;
-  memset(&o, 0, sizeof(o));
-  o.st[0] = opt->state0; o.st[1] = opt->state1; o.scal_dev = opt->adam_scal;
-  o.omb1 = (float)(1.0 - opt->beta1); o.b2 = (float)opt->beta2; o.omb2 = (float)(1.0 - opt->beta2);
-  o.eps = opt->eps; o.wd = opt->weight_decay; o.sc = opt->scaler; o.cl = opt->clip;
-  const int vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)opt->state0 | (uintptr_t)opt->state1) & 15) == 0;
-  ProfScope ps(PC_SGD, 0, (double)n * 28, st);
-  NUNET_LAUNCH(adam_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, st, p, g, o, n, grad_scale, vec);
+extern "C" int nunet_sgd_step(float* p, const float* g, float* mom, int64_t n, const float* lr_dev, float momentum, float weight_decay, int32_t nesterov, int32_t first, float grad_scale, nunet_stream_t s) {
+  NUNET_REQUIRE(p && g && n > 0, "sgd_step: bad args");
+  nunet_optim o; memset(&o, 0, sizeof(o));
+  o.kind = NUNET_OPT_SGD; o.momentum = momentum; o.weight_decay = weight_decay; o.nesterov = nesterov; o.lr = lr_dev; o.state0 = mom;
+  if (const int rc = opt_check(&o, "sgd_step", false)) return rc;
+  launch_flat(p, g, &o, n, grad_scale, first, (hipStream_t)s);
+  return nunet_check_launch("sgd_step");
 }
 extern "C" int nunet_adam_step(float* p, const float* g, const nunet_optim* opt, int64_t n, float grad_scale, nunet_stream_t s) {
   NUNET_REQUIRE(p && g && opt && n > 0, "adam_step: bad args");
   NUNET_REQUIRE(opt->kind == NUNET_OPT_ADAM, "adam_step: optimiser kind %d is not NUNET_OPT_ADAM", (int)opt->kind);
   NUNET_REQUIRE(!opt->scaler, "adam_step: loss scaling goes through nunet_opt_step");
   NUNET_REQUIRE(!opt->clip, "adam_step: gradient clipping goes through nunet_opt_step");
-  const int rc = adam_args(opt, "adam_step");
-  if (rc != NUNET_OK) return rc;
-  launch_adam(p, g, opt, n, grad_scale, (hipStream_t)s);
+  if (const int rc = opt_check(opt, "adam_step", false)) return rc;
+  launch_flat(p, g, opt, n, grad_scale, 0, (hipStream_t)s);
   return nunet_check_launch("adam_step");
 }
 
@@ -1431,20 +1430,11 @@ __global__ __launch_bounds__(256) void unscale_kernel(float* __restrict__ g, int
   for (int64_t i = 4 * n4 + tid; i < n; i += nth) g[i] = g[i] * f;
 }
 extern "C" int nunet_opt_step(float* p, float* g, const nunet_optim* opt, int64_t n, float grad_scale, nunet_stream_t s) {
-  NUNET_REQUIRE(p && g && opt && n > 0, "opt_step: bad args");
+  NUNET_REQUIRE(p && g && opt, "opt_step: bad args");
+  if (const int rc = opt_check(opt, "opt_step", false)) return rc;
+  NUNET_REQUIRE(n > 0, "opt_step: bad args");
   hipStream_t st = (hipStream_t)s;
-  if (opt->kind == NUNET_OPT_SGD) {
-    NUNET_REQUIRE(opt->lr && (opt->momentum == 0.f || opt->state0), "opt_step: SGD needs lr and state0 (momentum buffer)");
-    ProfScope ps(PC_SGD, 0, (double)n * 20, st);
-    NUNET_LAUNCH(sgd_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, st, p, g, opt->state0, n, opt->lr, opt->momentum, opt->weight_decay,
-                 opt->nesterov, 0, grad_scale, opt->scaler, opt->clip);
-  } else if (opt->kind == NUNET_OPT_ADAM) {
-    const int rc = adam_args(opt, "opt_step");
-    if (rc != NUNET_OK) return rc;
-    launch_adam(p, g, opt, n, grad_scale, st);
-  } else {
-    NUNET_REQUIRE(false, "opt_step: unknown optimiser kind %d", (int)opt->kind);
-  }
+  launch_flat(p, g, opt, n, grad_scale, 0, st);
   if (opt->scaler || opt->clip) {   // after the step, which read the scaled, unclipped gradients
     const int vec = ((uintptr_t)g & 15) == 0;
     NUNET_LAUNCH(unscale_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, st, g, n, grad_scale, opt->scaler, opt->clip, vec);

@@ -373,15 +373,19 @@ __global__ __launch_bounds__(512) void update_kernel(UpdP u, O o, T* __restrict_
   }
 }
 
-template <typename T> static int launch_pack(const float* params, void* arena_t, PackTab& tab, long long maxn, hipStream_t st) {
-  (void)maxn;
+// block -> tile prefix table of a PackTab: entry i owns blocks [tile0[i], tile0[i + 1]) of the tile kernels, one per 32 x 32
+// (cout, cinpad) tile. Filled once, when the table is built.
+static void pack_tiles(PackTab& tab) {
   int nt = 0;
   for (int i = 0; i < tab.n; ++i) { tab.tile0[i] = nt; nt += ((tab.e[i].cout + 31) / 32) * ((tab.e[i].cinpad + 31) / 32); }
   tab.tile0[tab.n] = nt; tab.ntiles = nt;
+}
+
+template <typename T> static int launch_pack(const float* params, void* arena_t, const PackTab& tab, hipStream_t st) {
   double pb = 0;
   for (int i = 0; i < tab.n; ++i) pb += 9.0 * tab.e[i].cout * tab.e[i].cin * (4 + (tab.e[i].wd >= 0 ? 2 : 1) * sizeof(T));
   ProfScope ps(PC_PACK, 0, pb, st);
-  NUNET_LAUNCH((pack_kernel<T>), dim3(nt), dim3(256), 0, st, params, (T*)arena_t, tab);
+  NUNET_LAUNCH((pack_kernel<T>), dim3(tab.ntiles), dim3(256), 0, st, params, (T*)arena_t, tab);
   return nunet_check_launch("pack_weights");
 }
 
@@ -397,7 +401,8 @@ extern "C" int nunet_pack_weights(const float* w, int32_t cout, int32_t cin, int
   tab.e[0].wf = ((char*)wf - base) / es;
   tab.e[0].wd = wd ? ((char*)wd - base) / es : -1;
   tab.e[0].cout = cout; tab.e[0].cin = cin; tab.e[0].cinpad = cin_pad;
-  return NUNET_DISPATCH(dtype, launch_pack, w, (void*)base, tab, 9LL * cout * cin_pad, (hipStream_t)s);
+  pack_tiles(tab);
+  return NUNET_DISPATCH(dtype, launch_pack, w, (void*)base, tab, (hipStream_t)s);
 }
 
 extern "C" int nunet_unpack_wgrad(const float* dw, int32_t cout, int32_t cin, int32_t cin_pad, float* g, int32_t accumulate, nunet_stream_t s) {
@@ -450,8 +455,8 @@ struct PlanRt {  // runtime objects owned by the plan (host side only)
   // NUNET_STAMPS=1 diagnostic: a 1-thread kernel after every scheduled op writes the 100 MHz wall clock,
   // so the real timeline of an (unprofiled) hipGraph replay can be read back (tools/stamp_timeline.py)
   unsigned long long* stamps;              // device, [2][STAMP_CAP]
-  // nunet_plan_set_inpass_update: the optimiser step of every VGGBlock as an op of the backward pass (params == NULL: off)
-  struct { float* params; float gscale; float* grads; int kind; OptSgd sgd; OptAdam adam; } upd;
+  // nunet_plan_set_inpass_opt: the optimiser step of every VGGBlock as an op of the backward pass (params == NULL: off)
+  struct { float* params; float gscale; float* grads; nunet_optim opt; } upd;
   int lane_low_priority;                   // side lanes of the flag-synchronised program at the lowest stream priority (default 1)
   int calibrating;                         // nunet_plan_calibrate: single lane + stamps, to measure every op's isolated cost
   std::map<std::string, float> op_cost[2]; // measured cost (us) by op name, per pass; empty: the built-in estimates
@@ -492,9 +497,8 @@ struct nunet_plan {
   size_t off_sk[16]; long long sk_floats[16];   // per-BLOCK fp32 K-split slabs (blocks of the grid-starved levels; 0: none)   // per-level backward scratch (dY ping-pong)
   struct PlanRt* rt;
   size_t total;
-  PackTab ptab; long long pack_maxn;
-  PackTab ptab_lvl[5]; long long pack_maxn_lvl[5];   // the same entries grouped by pyramid level (issued per lane)
-  UnpackTab utab; long long unpack_maxn;
+  PackTab ptab;
+  UnpackTab utab;
 };
 
 static size_t fx_region_bytes(const nunet_plan* P) { return P->stats_floats * NUNET_BN_SUM_REPLICAS * NUNET_FX_WORDS * sizeof(long long); }
@@ -663,28 +667,15 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
 
   // ---- pack / unpack tables ------------------------------------------------------
   memset(&P->ptab, 0, sizeof(P->ptab)); memset(&P->utab, 0, sizeof(P->utab));
-  P->pack_maxn = 0; P->unpack_maxn = 0;
   auto add_conv = [&](const ConvL& c) {
     PackEnt& pe = P->ptab.e[P->ptab.n++];
     pe.src = c.w_off; pe.wf = c.wf; pe.wd = c.wd; pe.cout = c.cout; pe.cin = c.cin; pe.cinpad = c.cinpad;
-    if (9LL * c.cout * c.cinpad > P->pack_maxn) P->pack_maxn = 9LL * c.cout * c.cinpad;
     UnpackEnt& ue = P->utab.e[P->utab.n++];
     ue.src = c.gs; ue.dst = c.w_off; ue.cout = c.cout; ue.cin = c.cin; ue.cinpad = c.cinpad; ue.taps = 9; ue.nvec = 3; ue.nslab = 1;
     ue.inv_taps = dec_inv(9); ue.inv_cin = dec_inv(c.cin); ue.fast = 9LL * c.cout * c.cin * (c.cin > 9 ? c.cin : 9) < (1ll << 32);
-    if (9LL * c.cout * c.cin + 3 * c.cout > P->unpack_maxn) P->unpack_maxn = 9LL * c.cout * c.cin + 3 * c.cout;
   };
   for (size_t r = 0; r < P->reg.size(); ++r) { add_conv(P->exec[P->reg[r]].c1); add_conv(P->exec[P->reg[r]].c2); }
-  for (int l = 0; l < 5; ++l) { memset(&P->ptab_lvl[l], 0, sizeof(PackTab)); P->pack_maxn_lvl[l] = 0; }
-  for (size_t k = 0; k < P->exec.size(); ++k) {
-    const Node& n = P->exec[k];
-    for (int cv = 0; cv < 2; ++cv) {
-      const ConvL& c = cv ? n.c2 : n.c1;
-      PackTab& t = P->ptab_lvl[n.i];
-      PackEnt& pe = t.e[t.n++];
-      pe.src = c.w_off; pe.wf = c.wf; pe.wd = c.wd; pe.cout = c.cout; pe.cin = c.cin; pe.cinpad = c.cinpad;
-      if (9LL * c.cout * c.cinpad > P->pack_maxn_lvl[n.i]) P->pack_maxn_lvl[n.i] = 9LL * c.cout * c.cinpad;
-    }
-  }
+  pack_tiles(P->ptab);
   for (size_t k = 0; k < P->heads.size(); ++k) {
     UnpackEnt& ue = P->utab.e[P->utab.n++];
     ue.src = P->heads[k].gs; ue.dst = P->heads[k].w_off; ue.cout = cfg->num_classes; ue.cin = NBF[0]; ue.cinpad = NBF[0]; ue.taps = 1; ue.nvec = 1; ue.nslab = HEAD_SLABS; ue.inv_taps = 0; ue.inv_cin = dec_inv(NBF[0]); ue.fast = 1;
@@ -697,7 +688,6 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
   rt->calibrating = 0;
   rt->lane_low_priority = 1;
   memset(&rt->upd, 0, sizeof(rt->upd));
-  { PackTab& tab = P->ptab; int nt = 0; for (int i = 0; i < tab.n; ++i) { tab.tile0[i] = nt; nt += ((tab.e[i].cout + 31) / 32) * ((tab.e[i].cinpad + 31) / 32); } tab.tile0[tab.n] = nt; tab.ntiles = nt; }
   rt->b0_event = nullptr; rt->b0_enabled = false; rt->open_sched = nullptr;
   rt->seg_lanes[0] = rt->seg_lanes[1] = rt->seg_lanes[2] = nullptr;
   rt->events_used[0] = rt->events_used[1] = 0;
@@ -1296,13 +1286,11 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
 
   Sched S; S.init(P, st, 0);
   int rc = NUNET_OK;
-  const bool skip_pack = (training_flags & 2) != 0;   // the caller vouches that nunet_plan_update / _repack left the packed weights current
+  const bool skip_pack = (training_flags & 2) != 0;   // the caller vouches that nunet_plan_opt_step(repack 1) / _repack left the packed weights current
   if (!skip_pack) {
     S.name("pack");
     S.add(0, 0, 15.f, {}, {R_WP + 0, R_WP + 1, R_WP + 2, R_WP + 3, R_WP + 4}, [=](hipStream_t ls) {
-      if (dt == NUNET_F32) return launch_pack<float>(params, wpack, P->ptab, P->pack_maxn, ls);
-      if (dt == NUNET_BF16) return launch_pack<bf16_t>(params, wpack, P->ptab, P->pack_maxn, ls);
-      return launch_pack<f16_t>(params, wpack, P->ptab, P->pack_maxn, ls);
+      return NUNET_DISPATCH(dt, launch_pack, params, wpack, P->ptab, ls);
     });
   }
   // (The x2 upsample of a block output can ride in the producer's BatchNorm launch as a second block role - nunet_bn_fwd_desc.up,
@@ -1474,41 +1462,7 @@ extern "C" int nunet_plan_grad_scratch(const nunet_plan* P, int64_t* byte_offset
   return NUNET_OK;
 }
 
-// Optimiser functor of a nunet_optim (validated first: every entry refuses a bad one before touching the device)
-static int opt_check(const nunet_optim* o, const char* what) {
-  NUNET_REQUIRE(o, "%s: null optimiser", what);
-  if (o->kind == NUNET_OPT_SGD) {
-    NUNET_REQUIRE(o->lr && o->state0, "%s: SGD needs lr and state0 (momentum buffer)", what);
-  } else if (o->kind == NUNET_OPT_ADAM) {
-    NUNET_REQUIRE(o->adam_scal && o->state0 && o->state1, "%s: Adam needs adam_scal, state0 (exp_avg) and state1 (exp_avg_sq)", what);
-    NUNET_REQUIRE(o->beta1 >= 0.0 && o->beta1 < 1.0 && o->beta2 >= 0.0 && o->beta2 < 1.0, "%s: betas must lie in [0, 1)", what);
-    NUNET_REQUIRE(o->eps > 0.f, "%s: eps must be > 0", what);
-  } else {
-    NUNET_REQUIRE(false, "%s: unknown optimiser kind %d", what, (int)o->kind);
-  }
-  return NUNET_OK;
-}
-static OptSgd opt_sgd(const float* lr, float* mom, float momc, float wd, int nesterov) {
-  OptSgd o; memset(&o, 0, sizeof(o));
-  o.st[0] = mom; o.lr_dev = lr; o.momc = momc; o.wd = wd; o.nesterov = nesterov;
-  return o;
-}
-static OptAdam opt_adam(const nunet_optim* d) {
-  OptAdam o; memset(&o, 0, sizeof(o));
-  o.st[0] = d->state0; o.st[1] = d->state1; o.scal_dev = d->adam_scal;
-  o.omb1 = (float)(1.0 - d->beta1); o.b2 = (float)d->beta2; o.omb2 = (float)(1.0 - d->beta2);
-  o.eps = d->eps; o.wd = d->weight_decay;
-  return o;
-}
-
-static void update_tiles(nunet_plan* P) {
-  PackTab& tab = P->ptab;
-  int nt = 0;
-  for (int i = 0; i < tab.n; ++i) { tab.tile0[i] = nt; nt += ((tab.e[i].cout + 31) / 32) * ((tab.e[i].cinpad + 31) / 32); }
-  tab.tile0[tab.n] = nt; tab.ntiles = nt;
-}
-
-// blocks [bid0, bid0 + nblocks) of update_kernel's whole-model numbering: all of it (nunet_plan_update), one VGGBlock's
+// blocks [bid0, bid0 + nblocks) of update_kernel's whole-model numbering: all of it (nunet_plan_opt_step, repack 1), one VGGBlock's
 // tiles or the heads (the in-pass step)
 template <typename O> static int launch_update_kernel(nunet_plan* P, void* arena, float* params, const O& o, float grad_scale, float* grads,
                                                       int bid0, int nblocks, double bytes, hipStream_t st) {
@@ -1522,62 +1476,35 @@ template <typename O> static int launch_update_kernel(nunet_plan* P, void* arena
   if (P->cfg.dtype == NUNET_F32) NUNET_LAUNCH((update_kernel<float, O>), grid, blk, 0, st, u, o, (float*)wp, P->ptab, P->utab);
   else if (P->cfg.dtype == NUNET_BF16) NUNET_LAUNCH((update_kernel<bf16_t, O>), grid, blk, 0, st, u, o, (bf16_t*)wp, P->ptab, P->utab);
   else NUNET_LAUNCH((update_kernel<f16_t, O>), grid, blk, 0, st, u, o, (f16_t*)wp, P->ptab, P->utab);
-  return nunet_check_launch(bid0 == 0 && nblocks == P->ptab.ntiles + P->utab.n - P->ptab.n ? "plan_update" : "plan update (in pass)");
+  return nunet_check_launch(bid0 == 0 && nblocks == P->ptab.ntiles + P->utab.n - P->ptab.n ? "plan_opt_step" : "plan_opt_step (in pass)");
 }
 
-// Fused optimiser step on the plan's own buffers (update_kernel above): scratch -> SGD -> repacked weights.
-// `grads` (flat OIHW arena) is optional: when given it receives the (scaled) gradients as nunet_plan_backward would
-// have left them. Afterwards the packed weights in `arena` are current: the next nunet_plan_forward may be called
-// with bit 1 of `training` set (skip the repack).
-extern "C" int nunet_plan_update(nunet_plan* P, float* params, float* momentum, void* arena, size_t arena_bytes, const float* lr_dev, float mom, float wd,
-                                 int32_t nesterov, float grad_scale, float* grads, nunet_stream_t s) {
-  NUNET_REQUIRE(P && params && momentum && arena && lr_dev, "plan_update: null pointer");
-  ARENA_CHECK("plan_update");
-  update_tiles(P);
-  return launch_update_kernel(P, arena, params, opt_sgd(lr_dev, momentum, mom, wd, nesterov), grad_scale, grads, 0,
-                              P->ptab.ntiles + P->utab.n - P->ptab.n, (double)P->nparams * (grads ? 28.0 : 24.0), (hipStream_t)s);
-}
-
-// In-pass step of blocks [bid0, bid0 + nblocks) with the optimiser nunet_plan_set_inpass_* left in the plan
+// In-pass step of blocks [bid0, bid0 + nblocks) with the optimiser nunet_plan_set_inpass_opt left in the plan
 template <typename U> static int launch_update(nunet_plan* P, void* arena, const U& s, int bid0, int nblocks, hipStream_t st) {
-  if (s.kind == NUNET_OPT_ADAM) return launch_update_kernel(P, arena, s.params, s.adam, s.gscale, s.grads, bid0, nblocks, 0.0, st);
-  return launch_update_kernel(P, arena, s.params, s.sgd, s.gscale, s.grads, bid0, nblocks, 0.0, st);
+  return opt_dispatch(&s.opt, [&](const auto& o) { return launch_update_kernel(P, arena, s.params, o, s.gscale, s.grads, bid0, nblocks, 0.0, st); });
 }
 
 // The optimiser step as part of the backward pass: with parameters set here, every whole pass (nunet_plan_backward, or
 // nunet_plan_backward_phase with bits 0 and 1) steps each VGGBlock's parameters - and repacks its 16-bit weights - as an op of
-// the pass, scheduled behind that block's weight gradients, and the heads at the end. The caller then calls neither
-// nunet_plan_update / nunet_plan_sgd nor lets the next forward repack (training flag bit 1). Single-process training only: a
-// data-parallel step exchanges the gradients first. params == NULL switches it off.
-extern "C" int nunet_plan_set_inpass_update(nunet_plan* P, float* params, float* momentum, const float* lr_dev, float mom, float wd,
-                                            int32_t nesterov, float grad_scale, float* grads) {
-  NUNET_REQUIRE(P && (!params || (momentum && lr_dev)), "plan_set_inpass_update: null pointer");
-  auto& s = rt_of(P)->upd;
-  memset(&s, 0, sizeof(s));
-  s.params = params; s.gscale = grad_scale; s.grads = grads; s.kind = NUNET_OPT_SGD;
-  s.sgd = opt_sgd(lr_dev, momentum, mom, wd, nesterov);
-  return NUNET_OK;
-}
-
+// the pass, scheduled behind that block's weight gradients, and the heads at the end. The caller then neither calls
+// nunet_plan_opt_step nor lets the next forward repack (training flag bit 1). Single-process training only: a
+// data-parallel step exchanges the gradients first. params == NULL switches it off (`opt` is then not looked at).
 extern "C" int nunet_plan_set_inpass_opt(nunet_plan* P, float* params, const nunet_optim* opt, float grad_scale, float* grads) {
   NUNET_REQUIRE(P, "plan_set_inpass_opt: null plan");
   if (params) {
-    const int rc = opt_check(opt, "plan_set_inpass_opt");
-    if (rc != NUNET_OK) return rc;
+    CK(opt_check(opt, "plan_set_inpass_opt", true));
     NUNET_REQUIRE(!opt->scaler, "plan_set_inpass_opt: a step applied inside the backward pass cannot be skipped by loss scaling");
     NUNET_REQUIRE(!opt->clip, "plan_set_inpass_opt: a step applied inside the backward pass cannot be rescaled by gradient clipping");
   }
   auto& s = rt_of(P)->upd;
   memset(&s, 0, sizeof(s));
   if (!params) return NUNET_OK;
-  s.params = params; s.gscale = grad_scale; s.grads = grads; s.kind = opt->kind;
-  if (opt->kind == NUNET_OPT_ADAM) s.adam = opt_adam(opt);
-  else s.sgd = opt_sgd(opt->lr, opt->state0, opt->momentum, opt->weight_decay, opt->nesterov);
+  s.params = params; s.gscale = grad_scale; s.grads = grads; s.opt = *opt;
   return NUNET_OK;
 }
 
 // Optimiser step straight from the gradient scratch: replaces nunet_plan_backward_phase bit 2 +
-// nunet_sgd_step; the weights are repacked by the next nunet_plan_forward as usual.
+// nunet_opt_step; the weights are repacked by the next nunet_plan_forward as usual.
 // unpack_tiled_kernel with the optimiser step as the epilogue of its store phase: the tile's gradients meet the OIHW
 // parameters and the optimiser state as 16-byte runs, the flat gradient arena is written only when the caller wants it.
 template <typename O>
@@ -1694,42 +1621,24 @@ template <typename O> static int launch_unpack_step(nunet_plan* P, void* arena, 
   u.params = params; u.scratch = (const float*)AB(arena, P->off_gs); u.grads = grads;
   u.gscale = grad_scale; u.nconv = P->ptab.n; u.bid_off = 0;
   ProfScope ps(PC_SGD, 0, bytes, st);
-  update_tiles(P);
   NUNET_LAUNCH((unpack_sgd_tiled_kernel<O>), dim3(P->ptab.ntiles + P->utab.n), dim3(256), 0, st, u, o, P->ptab, P->utab);
-  return nunet_check_launch("plan_sgd");
+  return nunet_check_launch("plan_opt_step");
 }
 
-extern "C" int nunet_plan_sgd(nunet_plan* P, float* params, float* momentum, void* arena, size_t arena_bytes, const float* lr_dev, float mom, float wd,
-                              int32_t nesterov, float grad_scale, float* grads, nunet_stream_t s) {
-  NUNET_REQUIRE(P && params && momentum && arena && lr_dev, "plan_sgd: null pointer");
-  ARENA_CHECK("plan_sgd");
-  return launch_unpack_step(P, arena, params, opt_sgd(lr_dev, momentum, mom, wd, nesterov), grad_scale, grads,
-                            (double)P->nparams * (grads ? 24.0 : 20.0), (hipStream_t)s);
-}
-
-// nunet_plan_sgd (repack 0) / nunet_plan_update (repack 1) with any optimiser; Adam streams its second state buffer on top
+// The fused step on the plan's own buffers with any optimiser, gradient scratch -> step -> fp32 master parameters: repack 0 is
+// unpack_sgd_tiled_kernel (the next forward repacks), repack 1 is update_kernel, which also writes both packed weight layouts
+// (the next nunet_plan_forward may then be called with bit 1 of `training` set). `grads` (flat OIHW arena) is optional: when
+// given it receives the (scaled) gradients as nunet_plan_backward would have left them. Adam streams its second state buffer on top.
 extern "C" int nunet_plan_opt_step(nunet_plan* P, float* params, const nunet_optim* opt, void* arena, size_t arena_bytes, float grad_scale,
                                    float* grads, int32_t repack, nunet_stream_t s) {
   NUNET_REQUIRE(P && params && arena, "plan_opt_step: null pointer");
-  const int rc = opt_check(opt, "plan_opt_step");
-  if (rc != NUNET_OK) return rc;
+  CK(opt_check(opt, "plan_opt_step", true));
   ARENA_CHECK("plan_opt_step");
-  hipStream_t st = (hipStream_t)s;
-  const double extra = opt->kind == NUNET_OPT_ADAM ? 8.0 : 0.0;
-  OptAdam adam = opt_adam(opt);
-  OptSgd sgd = opt_sgd(opt->lr, opt->state0, opt->momentum, opt->weight_decay, opt->nesterov);
-  adam.sc = sgd.sc = opt->scaler;
-  adam.cl = sgd.cl = opt->clip;
-  if (repack) {
-    update_tiles(P);
-    const int nb = P->ptab.ntiles + P->utab.n - P->ptab.n;
-    const double bytes = (double)P->nparams * ((grads ? 28.0 : 24.0) + extra);
-    if (opt->kind == NUNET_OPT_ADAM) return launch_update_kernel(P, arena, params, adam, grad_scale, grads, 0, nb, bytes, st);
-    return launch_update_kernel(P, arena, params, sgd, grad_scale, grads, 0, nb, bytes, st);
-  }
-  const double bytes = (double)P->nparams * ((grads ? 24.0 : 20.0) + extra);
-  if (opt->kind == NUNET_OPT_ADAM) return launch_unpack_step(P, arena, params, adam, grad_scale, grads, bytes, st);
-  return launch_unpack_step(P, arena, params, sgd, grad_scale, grads, bytes, st);
+  return opt_dispatch(opt, [&](const auto& o) {
+    const double bytes = (double)P->nparams * ((repack ? 24.0 : 20.0) + (grads ? 4.0 : 0.0) + 8.0 * (o.NS - 1));
+    if (repack) return launch_update_kernel(P, arena, params, o, grad_scale, grads, 0, P->ptab.ntiles + P->utab.n - P->ptab.n, bytes, (hipStream_t)s);
+    return launch_unpack_step(P, arena, params, o, grad_scale, grads, bytes, (hipStream_t)s);
+  });
 }
 
 // Square norm of the gradient scratch for gradient clipping (include/nunet.h nunet_clip): unpack_sgd_tiled_kernel's
@@ -1801,19 +1710,13 @@ __global__ __launch_bounds__(256) void plan_sqnorm_kernel(const float* __restric
   const double tot = block256_sum_f64(acc, s_w);
   if (threadIdx.x == 0) ws[blockIdx.x] = tot;
 }
-static int sqnorm_blocks(const nunet_plan* P) {
-  int nt = 0;
-  for (int i = 0; i < P->ptab.n; ++i) nt += ((P->ptab.e[i].cout + 31) / 32) * ((P->ptab.e[i].cinpad + 31) / 32);
-  return nt + P->utab.n;
-}
-extern "C" size_t nunet_plan_grad_sqnorm_ws_bytes(const nunet_plan* P) { return P ? (size_t)sqnorm_blocks(P) * sizeof(double) : 0; }
+extern "C" size_t nunet_plan_grad_sqnorm_ws_bytes(const nunet_plan* P) { return P ? (size_t)(P->ptab.ntiles + P->utab.n) * sizeof(double) : 0; }
 extern "C" int nunet_plan_grad_sqnorm(nunet_plan* P, const void* arena, size_t arena_bytes, double* ws, size_t ws_bytes, nunet_stream_t s) {
   NUNET_REQUIRE(P && arena && ws, "plan_grad_sqnorm: null pointer");
   ARENA_CHECK("plan_grad_sqnorm");
   NUNET_REQUIRE(((uintptr_t)ws & 7) == 0, "plan_grad_sqnorm: ws must be 8-byte aligned");
   NUNET_REQUIRE(ws_bytes >= nunet_plan_grad_sqnorm_ws_bytes(P), "plan_grad_sqnorm: workspace of %zu bytes, nunet_plan_grad_sqnorm_ws_bytes = %zu",
                 ws_bytes, nunet_plan_grad_sqnorm_ws_bytes(P));
-  update_tiles(P);
   ProfScope ps(PC_SGD, 0, (double)P->nparams * 4, (hipStream_t)s);
   NUNET_LAUNCH(plan_sqnorm_kernel, dim3(P->ptab.ntiles + P->utab.n), dim3(256), 0, (hipStream_t)s,
                (const float*)AB(const_cast<void*>(arena), P->off_gs), P->ptab, P->utab, ws);
@@ -1821,15 +1724,13 @@ extern "C" int nunet_plan_grad_sqnorm(nunet_plan* P, const void* arena, size_t a
 }
 
 // Repack the 16-bit weight layouts from the fp32 master parameters (what nunet_plan_forward does first unless told
-// that they are current): needed once before a loop that relies on nunet_plan_update, and after the parameters were
+// that they are current): needed once before a loop that relies on nunet_plan_opt_step(repack 1), and after the parameters were
 // changed by anything else (checkpoint load, a stock optimiser).
 extern "C" int nunet_plan_repack(nunet_plan* P, const float* params, void* arena, size_t arena_bytes, nunet_stream_t s) {
   NUNET_REQUIRE(P && params && arena, "plan_repack: null pointer");
   ARENA_CHECK("plan_repack");
   char* wpack = AB(arena, P->off_wpack);
-  if (P->cfg.dtype == NUNET_F32) return launch_pack<float>(params, wpack, P->ptab, P->pack_maxn, (hipStream_t)s);
-  if (P->cfg.dtype == NUNET_BF16) return launch_pack<bf16_t>(params, wpack, P->ptab, P->pack_maxn, (hipStream_t)s);
-  return launch_pack<f16_t>(params, wpack, P->ptab, P->pack_maxn, (hipStream_t)s);
+  return NUNET_DISPATCH(P->cfg.dtype, launch_pack, params, wpack, P->ptab, (hipStream_t)s);
 }
 
 // Sum of the weight gradients' K-split slabs into the native-layout gradient scratch, all layers of a phase in one
@@ -2121,7 +2022,7 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
               return r ? r : launch_reduce(P, arena, k, k, ls);
             });
     }
-    // ---- in-pass optimiser step (nunet_plan_set_inpass_update): this block's two convolutions are stepped - scratch -> SGD ->
+    // ---- in-pass optimiser step (nunet_plan_set_inpass_opt): this block's two convolutions are stepped - scratch -> step ->
     // both packed 16-bit layouts - as soon as their gradients are complete, beside the rest of the backward pass, instead of in
     // one launch over all layers after it (43 us) plus the next forward's repack (15 us), with nothing to overlap either
     if (inpass) {
@@ -2191,10 +2092,6 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
   if (!(phases & 4)) return NUNET_OK;
   P->utab.accumulate = accumulate;
   ProfScope ps(PC_UNPACK, 0, (double)P->nparams * (accumulate ? 12 : 8), st);
-  PackTab& tab = P->ptab;
-  int nt = 0;
-  for (int i = 0; i < tab.n; ++i) { tab.tile0[i] = nt; nt += ((tab.e[i].cout + 31) / 32) * ((tab.e[i].cinpad + 31) / 32); }
-  tab.tile0[tab.n] = nt; tab.ntiles = nt;
   NUNET_LAUNCH(unpack_tiled_kernel, dim3(P->ptab.ntiles + P->utab.n), dim3(256), 0, st, gsr, grads, P->ptab, P->utab);
   return nunet_check_launch("unpack_grads");
 }

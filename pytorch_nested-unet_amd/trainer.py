@@ -124,6 +124,8 @@ class TrainStep:
         if optimizer == "SGD":
             self.mom = torch.zeros_like(self.eng.flat_params)
             self.opt_state = [self.mom]
+            self._optim = L.Optim(kind=L.OPT_SGD, momentum=momentum, beta1=0.0, beta2=0.0, eps=0.0, weight_decay=weight_decay,
+                                  nesterov=1 if nesterov else 0, lr=L.ptr(self.lr).value, state0=L.ptr(self.mom).value)
         else:
             self.mom = None
             self.exp_avg = torch.zeros_like(self.eng.flat_params)
@@ -147,10 +149,6 @@ class TrainStep:
                 raise L.NunetError("TrainStep: clip_grad_norm must be > 0 or None (got %r)" % (clip_grad_norm,))
             self._clip = torch.zeros(L.CLIP_WORDS, dtype=torch.int32, device=dev)
             self._clip[0:2] = torch.tensor([float(clip_grad_norm), 1.0], dtype=torch.float32).view(torch.int32).to(dev)
-        if optimizer == "SGD" and (self._scaler is not None or self._clip is not None):
-            # scaled / clipped SGD goes through the generic entries (bit-identical to the SGD ones)
-            self._optim = L.Optim(kind=L.OPT_SGD, momentum=momentum, beta1=0.0, beta2=0.0, eps=0.0, weight_decay=weight_decay,
-                                  nesterov=1 if nesterov else 0, lr=L.ptr(self.lr).value, state0=L.ptr(self.mom).value)
         if self._scaler is not None:
             self._optim.scaler = L.ptr(self._scaler).value
         if self._clip is not None:
@@ -184,11 +182,11 @@ class TrainStep:
         self.dp_choice = None        # {layout: ms per step} when the layout was chosen by measurement
         self.use_graph = use_graph
         # optimiser step layout: 0 = unpack, SGD, (next forward's) pack as three streaming launches; 2 (default) = unpack
-        # with the SGD step as its epilogue (nunet_plan_sgd, 46 us against 59 us for the pair); 1 = one tile kernel that
-        # also repacks the weights (nunet_plan_update). The flat OIHW gradients (p.grad views) are materialised with
+        # with the SGD step as its epilogue (nunet_plan_opt_step, repack 0: 46 us against 59 us for the pair); 1 = one tile kernel
+        # that also repacks the weights (nunet_plan_opt_step, repack 1). The flat OIHW gradients (p.grad views) are materialised with
         # keep_grads=True in the fused layouts; in every layout they hold the rank-MEAN gradient (as
         # DistributedDataParallel leaves p.grad).
-        # 3 = the optimiser step INSIDE the backward pass (nunet_plan_set_inpass_update): every VGGBlock is stepped and repacked
+        # 3 = the optimiser step INSIDE the backward pass (nunet_plan_set_inpass_opt): every VGGBlock is stepped and repacked
         # as an op of the pass behind its weight gradients, beside the rest of the pass; single-process training only (a
         # data-parallel step exchanges the gradients before the update: it falls back to 2).
         self.fused_update = int(os.environ.get("NUNET_FUSED_UPDATE", "2")) if fused_update is None else int(fused_update)   
@@ -245,7 +243,7 @@ class TrainStep:
         lib, eng, pl = L.lib(), self.eng, self.pl
         st = L.stream()
         flags = 3 if (self.fused_update in (1, 3) and self._packed) else 1
-        if self.optimizer == "Adam" and self._scaler is None:     # (under loss scaling: behind the overflow check, _scaled_opt)
+        if self.optimizer == "Adam" and self._scaler is None:     # (under loss scaling: behind the overflow check, _opt)
             # t += 1 and this step's bias corrections, ahead of the forward pass: every update launch of the step (in-pass ones on
             # any lane included) is ordered behind it
             L.check(lib.nunet_adam_prepare(L.ptr(self.lr), self.betas[0], self.betas[1], L.ptr(self.adam_step), L.ptr(self.adam_scal), st),
@@ -277,25 +275,6 @@ class TrainStep:
         self._fwd_loss()
         self._bwd(3 if self.fused_update else 7)
 
-    def _update(self):
-        """scratch -> SGD -> repacked weights in one launch (replaces unpack + sgd + the next forward's repack)."""
-        eng, pl = self.eng, self.pl
-        if self.fused_update == 3:      # already done, block by block, inside the backward pass
-            return
-        if self.optimizer == "Adam":    # layout 2: repack 0, layout 1: repack 1 (the same launches, Adam instantiations)
-            L.check(L.lib().nunet_plan_opt_step(pl.handle, L.ptr(eng.flat_params), C.byref(self._optim), L.ptr(pl.arena), L.nbytes(pl.arena),
-                                                1.0 / self.world, L.ptr(eng.flat_grads) if self.keep_grads else None,
-                                                1 if self.fused_update == 1 else 0, L.stream()), "plan_opt_step")
-            return
-        if self.fused_update == 2:      # gradient scratch -> SGD in one launch; the next forward repacks
-            L.check(L.lib().nunet_plan_sgd(pl.handle, L.ptr(eng.flat_params), L.ptr(self.mom), L.ptr(pl.arena), L.nbytes(pl.arena), L.ptr(self.lr),
-                                           self.momentum, self.wd, 1 if self.nesterov else 0, 1.0 / self.world,
-                                           L.ptr(eng.flat_grads) if self.keep_grads else None, L.stream()), "plan_sgd")
-            return
-        L.check(L.lib().nunet_plan_update(pl.handle, L.ptr(eng.flat_params), L.ptr(self.mom), L.ptr(pl.arena), L.nbytes(pl.arena), L.ptr(self.lr),
-                                          self.momentum, self.wd, 1 if self.nesterov else 0, 1.0 / self.world,
-                                          L.ptr(eng.flat_grads) if self.keep_grads else None, L.stream()), "plan_update")
-
     def sync_weights(self):
         """Repack the plan's 16-bit weights from the fp32 parameters: call after changing the parameters by anything
         other than step() (load_state_dict, a stock optimiser) when fused_update is on."""
@@ -310,16 +289,8 @@ class TrainStep:
         if on == self._inpass_set:
             return
         eng = self.eng
-        if self.optimizer == "Adam":
-            L.check(L.lib().nunet_plan_set_inpass_opt(self.pl.handle, L.ptr(eng.flat_params) if on else None, C.byref(self._optim),
-                                                      1.0 / self.world, L.ptr(eng.flat_grads) if self.keep_grads else None),
-                    "plan_set_inpass_opt")
-        elif on:
-            L.check(L.lib().nunet_plan_set_inpass_update(self.pl.handle, L.ptr(eng.flat_params), L.ptr(self.mom), L.ptr(self.lr), self.momentum,
-                                                         self.wd, 1 if self.nesterov else 0, 1.0 / self.world,
-                                                         L.ptr(eng.flat_grads) if self.keep_grads else None), "plan_set_inpass_update")
-        else:
-            L.check(L.lib().nunet_plan_set_inpass_update(self.pl.handle, None, None, None, 0.0, 0.0, 0, 1.0, None), "plan_set_inpass_update")
+        L.check(L.lib().nunet_plan_set_inpass_opt(self.pl.handle, L.ptr(eng.flat_params) if on else None, C.byref(self._optim),
+                                                  1.0 / self.world, L.ptr(eng.flat_grads) if self.keep_grads else None), "plan_set_inpass_opt")
         self._inpass_set = on
 
     def _aux_state(self):
@@ -337,8 +308,8 @@ class TrainStep:
             L.check(lib.nunet_grad_sqnorm(L.ptr(eng.flat_grads), eng.flat_grads.numel(), L.ptr(ws), L.nbytes(ws), st), "grad_sqnorm")
         L.check(lib.nunet_clip_finalize(L.ptr(ws), ws.numel(), grad_scale, L.ptr(self._scaler), L.ptr(self._clip), st), "clip_finalize")
 
-    def _scaled_opt(self):
-        """The optimiser step under loss scaling and / or gradient clipping, behind the complete (exchanged) gradient scratch, in
+    def _opt(self):
+        """The optimiser step, behind the complete (exchanged) gradient scratch. Under loss scaling and / or gradient clipping in
         torch's order: overflow check, Adam's bookkeeping unless skipped, the norm of the unscaled gradient and the clip factor,
         the update (unscaled by inv_scale, clipped by coef; nothing written on a skipped step), the scale update."""
         lib, eng, pl, st = L.lib(), self.eng, self.pl, L.stream()
@@ -348,15 +319,16 @@ class TrainStep:
             if self.optimizer == "Adam":
                 L.check(lib.nunet_adam_prepare_scaled(L.ptr(self.lr), self.betas[0], self.betas[1], L.ptr(self.adam_step), L.ptr(self.adam_scal),
                                                       sc, st), "adam_prepare_scaled")
-        if self.fused_update:           # layout 2: repack 0, layout 1: repack 1
+        # (layout 3: already done, block by block, inside the backward pass)
+        if self.fused_update in (1, 2):    # gradient scratch -> step in one launch; layout 1 (repack 1) also repacks the weights
             if self._clip is not None:
                 self._clip_coef(True, 1.0 / self.world)
             L.check(lib.nunet_plan_opt_step(pl.handle, L.ptr(eng.flat_params), C.byref(self._optim), L.ptr(pl.arena), L.nbytes(pl.arena),
                                             1.0 / self.world, L.ptr(eng.flat_grads) if self.keep_grads else None,
                                             1 if self.fused_update == 1 else 0, st), "plan_opt_step")
-        else:
+        elif not self.fused_update:        # layout 0: the flat gradients that backward phase 4 unpacked
             if self.world > 1:
-                eng.flat_grads.mul_(1.0 / self.world)
+                eng.flat_grads.mul_(1.0 / self.world)      # p.grad = rank mean in every layout
             if self._clip is not None:
                 self._clip_coef(False, 1.0)
             L.check(lib.nunet_opt_step(L.ptr(eng.flat_params), L.ptr(eng.flat_grads), C.byref(self._optim), eng.flat_params.numel(), 1.0, st),
@@ -364,22 +336,6 @@ class TrainStep:
         if sc is not None:
             cfg = self.scaler_cfg
             L.check(lib.nunet_scaler_update(sc, cfg["growth_factor"], cfg["backoff_factor"], cfg["growth_interval"], st), "scaler_update")
-
-    def _opt(self):
-        if self._scaler is not None or self._clip is not None:
-            return self._scaled_opt()
-        if self.fused_update:
-            return self._update()
-        eng = self.eng
-        if self.world > 1:
-            eng.flat_grads.mul_(1.0 / self.world)      # p.grad = rank mean in every layout
-        if self.optimizer == "Adam":
-            L.check(L.lib().nunet_adam_step(L.ptr(eng.flat_params), L.ptr(eng.flat_grads), C.byref(self._optim),
-                                            eng.flat_params.numel(), 1.0, L.stream()), "adam_step")
-            return
-        L.check(L.lib().nunet_sgd_step(L.ptr(eng.flat_params), L.ptr(eng.flat_grads), L.ptr(self.mom),
-                                       eng.flat_params.numel(), L.ptr(self.lr), self.momentum, self.wd,
-                                       1 if self.nesterov else 0, 0, 1.0, L.stream()), "sgd_step")
 
     def _grad_scratch(self):
         """The plan's native-layout gradient scratch as two fp32 views in gradient-ready order."""
@@ -557,7 +513,7 @@ class TrainStep:
                     for _ in range(3):
                         g.replay()
                 torch.cuda.synchronize()
-                self._single_lane_ms = self._time_program(g, 5)     # (with the stamp kernels: an upper bound of the one-lane step)
+                self._single_lane_ms = self._time(self._as_step_runs(g), 2, 5)     # (with the stamp kernels: an upper bound of the one-lane step)
             finally:
                 L.check(L.lib().nunet_plan_calibrate(self.pl.handle, 0), "plan_calibrate")
             # (kept alive while the program below picks its lanes: with the calibration graph - and its launch stream - destroyed
@@ -573,7 +529,7 @@ class TrainStep:
             prog = None
             for attempt in range(3):
                 prog = _SegProgram(s, body, flags=True)
-                ms = self._time_program(prog, 8)
+                ms = self._time(self._as_step_runs(prog), 2, 8)
                 if ms < 0.9 * self._single_lane_ms:
                     break
                 print("[nunet] flag-synchronised program came up at %.2f ms per step (one lane: %.2f): picking new lanes (%d)"
@@ -586,23 +542,28 @@ class TrainStep:
         self._calib_graph = None
         return prog
 
-    def _time_program(self, g, reps):
-        """ms per replay of a recorded program, issued the way step() issues it (batch copy + replay from the caller's stream)."""
+    @staticmethod
+    def _time(run, warm, reps):
+        """ms per call of run(): `warm` untimed calls, then `reps` between two events on the caller's stream."""
+        for _ in range(warm):
+            run()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            run()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    def _as_step_runs(self, g):
+        """A recorded program issued the way step() issues it: batch copy + replay from the caller's stream."""
         buf = self.x_u8 if self.input_u8 else self.x
         fresh = buf.clone()
         def one():
             buf.copy_(fresh, non_blocking=True)
             g.replay()
-        for _ in range(2):
-            one()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            one()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / reps
+        return one
 
     def _choose_executor(self, s, body, reps=20):
         """Time the two executable forms of the captured step on this device and keep the faster: the multi-branch hipGraph
@@ -617,23 +578,11 @@ class TrainStep:
                 # timed the way step() will run it: from the caller's stream, behind the copies of a fresh batch (a stream that
                 # shares a hardware queue with one of the lanes shows here, not after the choice)
                 torch.cuda.current_stream().wait_stream(s)
-                buf = self.x_u8 if self.input_u8 else self.x
-                fresh = buf.clone()
-                def one():
-                    buf.copy_(fresh, non_blocking=True)
-                    g.replay()
-                for _ in range(3):
-                    one()
-                torch.cuda.synchronize()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(reps):
-                    one()
-                e1.record()
-                torch.cuda.synchronize()
+                one = self._as_step_runs(g)
+                ms = self._time(one, 3, reps)
                 one()                            # (a cross-lane wait that timed out fails the NEXT launch)
                 torch.cuda.synchronize()
-                progs[form], times[form] = g, e0.elapsed_time(e1) / reps
+                progs[form], times[form] = g, ms
             except Exception as e:
                 if form == forms[0]:
                     raise
@@ -708,16 +657,7 @@ class TrainStep:
                       % (mode, ex[0], ex[1], ": %s" % err if err is not None else ""))
                 times.append(float("inf"))
                 continue
-            for _ in range(2):
-                run()
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(reps):
-                run()
-            e1.record()
-            torch.cuda.synchronize()
-            times.append(e0.elapsed_time(e1) / reps)
+            times.append(self._time(run, 2, reps))
         t = torch.tensor(times, dtype=torch.float64, device=self.eng.device)
         t = torch.nan_to_num(t, posinf=1e30)
         if dist.get_backend(self.pg) == "gloo":

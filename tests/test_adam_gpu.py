@@ -99,7 +99,7 @@ def test_fused_adam_layouts_equal_unpack_plus_flat_adam(dtype, mode, synth):
     ts._fwd_loss(); ts._bwd(3)                     # t = 6 prepared, gradient scratch complete, not yet unpacked
     eng = ts.eng
     p0, m0, v0 = eng.flat_params.clone(), ts.exp_avg.clone(), ts.exp_avg_sq.clone()
-    ts._bwd(4); ts._opt()                          # reference: unpack + nunet_adam_step
+    ts._bwd(4); ts._opt()                          # reference: unpack + nunet_opt_step
     torch.cuda.synchronize()
     pa, ma, va, ga = eng.flat_params.clone(), ts.exp_avg.clone(), ts.exp_avg_sq.clone(), eng.flat_grads.clone()
     eng.flat_params.copy_(p0); ts.exp_avg.copy_(m0); ts.exp_avg_sq.copy_(v0); eng.flat_grads.zero_()

@@ -523,8 +523,8 @@ def test_training_step_is_bit_reproducible(dtype, synth):
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 @pytest.mark.parametrize("mode", [1, 2])
 def test_fused_update_equals_unpack_sgd_pack(dtype, mode, synth):
-    """nunet_plan_update (mode 1: scratch -> SGD -> repacked weights in one launch) and nunet_plan_sgd (mode 2: scratch ->
-    SGD) against the launches they replace (unpack into the OIHW gradient arena + nunet_sgd_step), applied to the SAME
+    """nunet_plan_opt_step with repack 1 (mode 1: scratch -> SGD -> repacked weights in one launch) and repack 0 (mode 2: scratch ->
+    SGD) against the launches they replace (unpack into the OIHW gradient arena + nunet_opt_step), applied to the SAME
     gradient scratch from the SAME state: parameters, momentum and gradients agree to rounding (momentum, weight decay,
     nesterov on); after mode 1 the next forward with the repack skipped gives the logits of a forward that repacks."""
     from nunet_amd.trainer import TrainStep
@@ -537,12 +537,12 @@ def test_fused_update_equals_unpack_sgd_pack(dtype, mode, synth):
     ts._fwd_loss(); ts._bwd(3)                     # gradient scratch complete, not yet unpacked
     eng = ts.eng
     p0, m0 = eng.flat_params.clone(), ts.mom.clone()
-    ts._bwd(4); ts._opt()                          # reference: unpack + nunet_sgd_step
+    ts._bwd(4); ts._opt()                          # reference: unpack + nunet_opt_step
     torch.cuda.synchronize()
     pa, ma, ga = eng.flat_params.clone(), ts.mom.clone(), eng.flat_grads.clone()
     eng.flat_params.copy_(p0); ts.mom.copy_(m0); eng.flat_grads.zero_()
     ts.fused_update = mode
-    ts._opt()                                      # nunet_plan_update / nunet_plan_sgd on the same scratch
+    ts._opt()                                      # nunet_plan_opt_step (repack 1 / 0) on the same scratch
     torch.cuda.synchronize()
     pb, mb, gb = eng.flat_params.clone(), ts.mom.clone(), eng.flat_grads.clone()
     assert float((ga - gb).abs().max()) <= 1e-5 * float(ga.abs().max())     # (the head slabs are summed in a different order)
@@ -560,8 +560,8 @@ def test_fused_update_equals_unpack_sgd_pack(dtype, mode, synth):
 @pytest.mark.parametrize("dtype", ["bf16", "fp32"])
 @pytest.mark.parametrize("ds", [False, True])
 def test_optimiser_step_inside_the_backward_pass(dtype, ds, synth):
-    """fused_update=3 (nunet_plan_set_inpass_update): every VGGBlock - and the heads - stepped and repacked as an op of the backward
-    pass, behind its weight gradients. It is the arithmetic of nunet_plan_update (mode 1), launched in slices: after three captured
+    """fused_update=3 (nunet_plan_set_inpass_opt): every VGGBlock - and the heads - stepped and repacked as an op of the backward
+    pass, behind its weight gradients. It is the arithmetic of nunet_plan_opt_step with repack 1 (mode 1), launched in slices: after three captured
     steps parameters, momentum, p.grad, BatchNorm buffers and losses are BIT-identical to mode 1's, under every executor."""
     from nunet_amd.trainer import TrainStep
     n, hw = 16, 96

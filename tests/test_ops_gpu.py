@@ -565,6 +565,49 @@ def test_sgd_matches_torch(nesterov):
     np.testing.assert_allclose(p.cpu().numpy(), ref.detach().numpy(), rtol=1e-6, atol=1e-7)
 
 
+@pytest.mark.parametrize("n,offset", [(3, 0), (1027, 0), (1027, 1)])
+def test_flat_opt_step_equals_the_sgd_and_adam_entries(n, offset):
+    """nunet_opt_step (what TrainStep's layout 0 calls) leaves the bits of the per-optimiser flat entries. SGD: against
+    nunet_sgd_step(first=0) from the same p, g and a non-zero momentum buffer, three steps, nesterov off and on. Adam: against
+    nunet_adam_step, each after one nunet_adam_prepare from the same step count. g is left alone by both (no scaler, no clip: no
+    unscale launch). n = 3: scalar tail only; n = 1027: 16-byte body + tail; offset 1: every buffer one float off a 16-byte
+    boundary, adam_kernel's non-vector path - and a buffer that ends where its allocation ends, in front of the guard band."""
+    lib = L.lib()
+    gen = torch.Generator().manual_seed(100 * n + offset)
+
+    def dev(x):
+        buf = torch.zeros(n + offset, device=DEV)
+        buf[offset:].copy_(x)
+        return buf[offset:]
+
+    p0, g0 = torch.randn(n, generator=gen) * 0.1, torch.randn(n, generator=gen) * 1e-2
+    m0, v0 = torch.randn(n, generator=gen) * 1e-2, (torch.randn(n, generator=gen) * 1e-3) ** 2 + 1e-8
+    lr = torch.full((1,), 1e-2, device=DEV)
+    for nesterov in (0, 1):
+        pa, pb, ga, gb, ma, mb = dev(p0), dev(p0), dev(g0), dev(g0), dev(m0), dev(m0)
+        opt = L.Optim(kind=L.OPT_SGD, momentum=0.9, weight_decay=1e-4, nesterov=nesterov, lr=L.ptr(lr).value, state0=L.ptr(ma).value)
+        for _ in range(3):
+            L.check(lib.nunet_opt_step(L.ptr(pa), L.ptr(ga), C.byref(opt), n, 0.5, L.stream()), "opt_step")
+            L.check(lib.nunet_sgd_step(L.ptr(pb), L.ptr(gb), L.ptr(mb), n, L.ptr(lr), 0.9, 1e-4, nesterov, 0, 0.5, L.stream()), "sgd_step")
+        assert torch.equal(pa, pb) and torch.equal(ma, mb), nesterov
+        assert not torch.equal(pa.cpu(), p0) and not torch.equal(ma.cpu(), m0)          # (the steps were taken)
+        assert torch.equal(ga.cpu(), g0) and torch.equal(gb.cpu(), g0)
+    pa, pb, ga, gb, ma, mb, va, vb = dev(p0), dev(p0), dev(g0), dev(g0), dev(m0), dev(m0), dev(v0), dev(v0)
+    for p, g, m, v, generic in ((pa, ga, ma, va, True), (pb, gb, mb, vb, False)):
+        step, scal = torch.full((1,), 5.0, device=DEV), torch.zeros(2, device=DEV)
+        opt = L.Optim(kind=L.OPT_ADAM, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-4, lr=L.ptr(lr).value,
+                      adam_scal=L.ptr(scal).value, state0=L.ptr(m).value, state1=L.ptr(v).value)
+        L.check(lib.nunet_adam_prepare(L.ptr(lr), 0.9, 0.999, L.ptr(step), L.ptr(scal), L.stream()), "adam_prepare")
+        if generic:
+            L.check(lib.nunet_opt_step(L.ptr(p), L.ptr(g), C.byref(opt), n, 0.5, L.stream()), "opt_step")
+        else:
+            L.check(lib.nunet_adam_step(L.ptr(p), L.ptr(g), C.byref(opt), n, 0.5, L.stream()), "adam_step")
+        assert float(step) == 6.0
+    assert torch.equal(pa, pb) and torch.equal(ma, mb) and torch.equal(va, vb)
+    assert not torch.equal(pa.cpu(), p0) and not torch.equal(ma.cpu(), m0) and not torch.equal(va.cpu(), v0)
+    assert torch.equal(ga.cpu(), g0) and torch.equal(gb.cpu(), g0)
+
+
 def test_nchw_to_nhwc_pad():
     x = torch.randn(2, 3, 5, 7)
     y = torch.full((2, 5, 7, 32), 9.0, dtype=torch.bfloat16, device=DEV)
@@ -910,8 +953,9 @@ def test_undersized_workspaces_are_refused_without_a_launch():
         assert b"nunet_plan_arena_bytes" in lib.nunet_last_error()
         assert lib.nunet_plan_backward(p, L.ptr(params), L.ptr(logits), L.ptr(arena), L.nbytes(arena), L.ptr(params), 0, L.stream()) == -1
         lr = torch.zeros(1, device=DEV)
-        assert lib.nunet_plan_sgd(p, L.ptr(params), L.ptr(bnb), L.ptr(arena), L.nbytes(arena), L.ptr(lr), 0.9, 1e-4, 0, 1.0, None, L.stream()) == -1
-        assert lib.nunet_plan_update(p, L.ptr(params), L.ptr(bnb), L.ptr(arena), L.nbytes(arena), L.ptr(lr), 0.9, 1e-4, 0, 1.0, None, L.stream()) == -1
+        opt = L.Optim(kind=L.OPT_SGD, momentum=0.9, weight_decay=1e-4, nesterov=0, lr=L.ptr(lr).value, state0=L.ptr(bnb).value)
+        assert lib.nunet_plan_opt_step(p, L.ptr(params), C.byref(opt), L.ptr(arena), L.nbytes(arena), 1.0, None, 0, L.stream()) == -1
+        assert lib.nunet_plan_opt_step(p, L.ptr(params), C.byref(opt), L.ptr(arena), L.nbytes(arena), 1.0, None, 1, L.stream()) == -1
         assert lib.nunet_plan_repack(p, L.ptr(params), L.ptr(arena), L.nbytes(arena), L.stream()) == -1
     finally:
         lib.nunet_plan_destroy(p)
