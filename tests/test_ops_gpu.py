@@ -394,7 +394,7 @@ def test_conv3x3_fused_bn_bwd_reduce(dt, shape, sk):
     assert float((tot - rtot).abs().max()) < 2e-4 * scale + 1e-5, (DT[dt], shape)
 
 
-@pytest.mark.parametrize("dt", [L.F32, L.BF16])
+@pytest.mark.parametrize("dt", [L.F32, L.BF16, L.F16])
 def test_maxpool(dt):
     n, h, w, c = 2, 8, 12, 32
     g = torch.Generator().manual_seed(6)
@@ -419,7 +419,7 @@ def test_maxpool(dt):
         assert rel_err(to_nchw(dxb, c), exp) < TOL[dt]
 
 
-@pytest.mark.parametrize("dt", [L.F32, L.BF16])
+@pytest.mark.parametrize("dt", [L.F32, L.BF16, L.F16])
 @pytest.mark.parametrize("hw", [(6, 10), (1, 1), (3, 2), (4, 4), (4, 7), (5, 9), (12, 6), (24, 4), (48, 48), (3, 8), (8, 3)])
 def test_upsample(dt, hw):
     h, w = hw
@@ -445,7 +445,7 @@ def test_upsample(dt, hw):
         assert rel_err(to_nchw(dxb, c, off=64), exp) < TOL[dt]
 
 
-@pytest.mark.parametrize("dt", [L.F32, L.BF16])
+@pytest.mark.parametrize("dt", [L.F32, L.BF16, L.F16])
 @pytest.mark.parametrize("k", [1, 4])
 def test_head(dt, k):
     n, h, w, c = 2, 12, 20, 32
