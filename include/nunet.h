@@ -40,7 +40,7 @@ enum {
   NUNET_ENODEV = -3   /* no gfx950 device / code object */
 };
 
-int nunet_version(void);   /* 101: the SGD-only plan entries of 100 are gone, nunet_plan_opt_step / nunet_plan_set_inpass_opt take SGD too */
+int nunet_version(void);   /* 102: schedule 1 (single-stream) and recording mode 0 (event segments) of 101 are refused, nunet_graph_info reports nodes, edges, lanes */
 const char* nunet_last_error(void);
 
 /* ------------------------------------------------------------------------ */
@@ -512,15 +512,14 @@ int nunet_plan_repack(nunet_plan* p, const float* params, void* arena, size_t ar
  * before anything the caller enqueues on `s` afterwards, and a capture of `s` records the
  * lanes as parallel branches of the same hipGraph. */
 int nunet_plan_set_multistream(nunet_plan* p, int32_t enable);
-/* How the plan issues its ops. NUNET_SCHEDULE_LANES (default): forked streams, captured as parallel branches of one hipGraph.
- * NUNET_SCHEDULE_WAVE: ONE stream, dependency order from a critical-path list scheduler, every ready 3x3 convolution of the same
- * kernel variant grouped into one launch - a single-stream graph (ROCm replays those as one batch of pre-built packets) whose
- * concurrency lives inside the launches. Bit-identical results; set before the first forward / capture. */
-/* NUNET_SCHEDULE_LIST: the lane of every op is chosen by a list scheduler over the hazard graph of the program order (critical-path
+/* How the plan issues its ops; bit-identical results; set before the first forward / capture.
+ * NUNET_SCHEDULE_LANES (default): every op on the lane of its block - forked streams, captured as parallel branches of one hipGraph.
+ * NUNET_SCHEDULE_LIST: the lane of every op is chosen by a list scheduler over the hazard graph of the program order (critical-path
  * priority, earliest start in a simulation with per-op costs) instead of following the op's block; meant for lanes that are real
  * in-order streams (NUNET_SEG_FLAGS). nunet_plan_calibrate(p, 1) ... one captured step replayed on one lane ...
- * nunet_plan_calibrate(p, 0) replaces the built-in cost estimates by the measured isolated cost of every op. */
-enum { NUNET_SCHEDULE_LANES = 0, NUNET_SCHEDULE_WAVE = 1, NUNET_SCHEDULE_LIST = 2 };
+ * nunet_plan_calibrate(p, 0) replaces the built-in cost estimates by the measured isolated cost of every op.
+ * (1 was a single-stream schedule with grouped convolution launches, measured slower and removed: NUNET_EINVAL, never another schedule.) */
+enum { NUNET_SCHEDULE_LANES = 0, NUNET_SCHEDULE_LIST = 2 };
 int nunet_plan_calibrate(nunet_plan* p, int32_t begin);
 /* Side lanes of the flag-synchronised program at the lowest stream priority (default 1: the chain lane's workgroups are dispatched
  * first) or at the default priority (0: needed when another library's high-priority stream lives in the process - RCCL's -,
@@ -561,22 +560,23 @@ typedef struct nunet_graph nunet_graph;
 int nunet_graph_begin(nunet_stream_t stream);
 int nunet_graph_end(nunet_stream_t stream, nunet_graph** out);
 int nunet_graph_launch(nunet_graph* graph, nunet_stream_t stream);
-int nunet_graph_info(const nunet_graph* graph, int32_t* nodes, int32_t* edges_captured, int32_t* edges_final, int32_t* padding, int32_t* lanes);
+int nunet_graph_info(const nunet_graph* graph, int32_t* nodes, int32_t* edges, int32_t* lanes);
 void nunet_graph_destroy(nunet_graph* graph);
 
 /* ------------------------------------------------------------------------ */
 /* Segmented step (csrc/graph.hip): the same captured step as a PROGRAM of    */
-/* single-stream graph segments on the plan's real streams, with the          */
-/* cross-lane dependencies as event records / waits between graph launches.   */
+/* single-stream graphs, one per lane, on the plan's real streams, with the    */
+/* cross-lane dependencies as device-side flags inside the graphs.            */
 /* ROCm 7.2 replays a hipGraph that has parallel branches node by node        */
 /* (2.6-5 us of launch + synchronisation per node) but a single-stream graph  */
 /* as one batch of pre-built packets (0.7 us per node); the step has ~160     */
 /* nodes, ~75 of them on its critical chain.                                   */
 /* Recording takes two passes over the same body (every launch made through   */
 /* this library on `stream` or on the plan's lanes between begin and end):    */
-/* dry = 1 launches nothing and finds the events that are waited on across     */
-/* streams; dry = 0 records. nunet_seg_end returns the program (NULL after a   */
-/* dry pass). The stream must outlive the program: it replays on it.           */
+/* NUNET_SEG_DRY launches nothing and finds the events that are waited on      */
+/* across streams; NUNET_SEG_FLAGS records. nunet_seg_end returns the program  */
+/* (NULL after a dry pass). The stream must outlive the program: it replays    */
+/* on it.                                                                      */
 /* ------------------------------------------------------------------------ */
 /* mode NUNET_SEG_FLAGS: every lane stream captures ONE single-stream graph for  */
 /* the whole step and the cross-lane dependencies become device-side flags      */
@@ -584,12 +584,15 @@ void nunet_graph_destroy(nunet_graph* graph);
 /* on the consumer lane; csrc/graph.hip). Needs the lanes on distinct hardware   */
 /* queues (the plan picks them by measurement); a wait that is not satisfied     */
 /* within 4 s sets an error word and the NEXT nunet_seg_launch fails.            */
-enum { NUNET_SEG_RECORD = 0, NUNET_SEG_DRY = 1, NUNET_SEG_FLAGS = 2 };
+/* (mode 0 recorded graph segments with events between their launches, measured  */
+/* slower and removed: nunet_seg_begin answers NUNET_EINVAL.)                    */
+enum { NUNET_SEG_DRY = 1, NUNET_SEG_FLAGS = 2 };
 typedef struct nunet_seg nunet_seg;
 int nunet_seg_begin(nunet_stream_t stream, int32_t mode);
 int nunet_seg_end(nunet_stream_t stream, nunet_seg** out);
-/* replay, ordered after what the caller queued on `stream`; `stream` continues after the program's last segment */
+/* replay, ordered after what the caller queued on `stream`; `stream` continues after the caller's lane of the program */
 int nunet_seg_launch(nunet_seg* prog, nunet_stream_t stream);
+/* graph launches per replay (one per lane used), cross-lane signals and waits recorded as flags, kernel nodes of all lanes */
 int nunet_seg_info(const nunet_seg* prog, int32_t* graph_launches, int32_t* event_records, int32_t* event_waits, int32_t* kernel_nodes);
 void nunet_seg_destroy(nunet_seg* prog);
 

@@ -22,7 +22,7 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 #define WAVE 64
-#define CONV_GROUP_MAX 4      // independent 3x3 convolutions one launch may carry (conv3x3.hip ConvGroup, plan.hip Sched::run_wave)
+#define CONV_GROUP_MAX 4      // problem slots of the 3x3 convolution's kernel argument (conv3x3.hip ConvGroup: the host fills one)
 
 // ---------------------------------------------------------------------------
 // error plumbing
@@ -81,8 +81,8 @@ int nunet_zero_async(void* p, size_t bytes, hipStream_t st);
 // Segmented recording of a multi-lane step (graph.hip). ROCm 7.2 replays a hipGraph with parallel branches by enqueueing
 // node after node with a synchronisation of its own (2.6-5 us per node, tools/graph_gap_probe.py), while a single-stream
 // graph replays as one batch of pre-built packets (0.7 us per node). So the plan's lanes are NOT captured as branches of one
-// graph: every lane keeps a real stream, its ops are captured into single-stream graph SEGMENTS, and the cross-lane
-// dependencies become event records / waits between the graph launches. The lane scheduler (plan.hip, Sched) routes its
+// graph: every lane keeps a real stream, its ops are captured into ONE single-stream graph, and the cross-lane
+// dependencies become device-side flags inside those graphs. The lane scheduler (plan.hip, Sched) routes its
 // stream waits, event records and "about to launch on this stream" through these hooks; they return false when no
 // recording is active (the caller then does the real HIP call).
 // ---------------------------------------------------------------------------

@@ -205,11 +205,13 @@ static inline int conv_coef_floats(int lt, int cin, bool bnr, int cout) { return
 // Staging is branch-free: C0 and C1 are multiples of the chunk width, so the address of every staging unit is
 // fixed for an item up to the chunk's (uniform) channel offset: pointers are set up once per item, a pixel
 // outside the image points at a page of zeros, and a chunk's staging is 12 plain 16-byte loads.
-// A launch carries up to CONV_GROUP_MAX independent problems of one kernel variant (same tile configuration, same fused
-// BatchNorm work): the plan's single-stream schedule groups ready convolutions of different blocks of the x_{i,j} grid, whose
-// workgroups then overlap each other's load / compute / store phases (two such launches side by side cost 1.3-1.4 x one,
-// tools/conv_concurrency_probe.py). Workgroups are dealt to the problems round-robin (problem k owns `grid[k]` of them, sorted
-// ascending), so all problems start together instead of one after the other.
+// The kernel argument can carry up to CONV_GROUP_MAX independent problems of one kernel variant, their workgroups dealt
+// round-robin (problem k owns `grid[k]` of them, sorted ascending). The host fills in ONE (n = 1, grid[0], p[0]): grouped
+// launches were built for a single-stream schedule, measured slower than the lanes and removed (profiles/r03_summary.md, 2).
+// The struct and conv_group_decode stay because the device code depends on their shape: the dynamic index grp.p[gk] is what
+// keeps the compiler from loading the ~60 fields of a problem into SGPRs up front. With one ConvP passed by value the 108
+// instantiations spill 5338 SGPRs in total instead of 894 and use 11260 instead of 9628 bytes of scratch per lane (compiled, not
+// yet timed): taking them out is a kernel change that needs a GPU comparison of its own.
 struct ConvGroup { int n; int grid[CONV_GROUP_MAX]; ConvP p[CONV_GROUP_MAX]; };
 
 // XCD-aware placement (for speed only, any placement is correct): workgroups are dealt round-robin over the 8 XCDs, each with its
@@ -657,7 +659,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3x3_kernel(ConvGroup grp)
       }
     }
   };
-  // (a group's problems interleave their workgroups, so block -> XCD is no longer vbid % 8: no remap there)
+  // (were a launch to carry several problems, they would interleave their workgroups and block -> XCD would no longer be vbid % 8:
+  //  no remap there)
   int item = grp.n == 1 ? xcd_remap(vbid, vgrid) : vbid;
   if (item >= p.nItems) return;
   Item cur = decode(item);
@@ -978,17 +981,15 @@ static void conv_setup(const nunet_conv_desc* d, ConvSetup& S) {
 }
 
 template <typename T, int WM, int WN, int SM, int SN>
-static int launch_conv_cfg(const nunet_conv_desc* const* ds, int n, hipStream_t st) {
+static int launch_conv_cfg(const nunet_conv_desc* d, hipStream_t st) {
   typedef ConvCfg<T, WM, WN, SM, SN> C;
-  ConvSetup S[CONV_GROUP_MAX];
-  for (int k = 0; k < n; ++k) conv_setup<T, WM, WN, SM, SN>(ds[k], S[k]);
+  ConvSetup s0;
+  conv_setup<T, WM, WN, SM, SN>(d, s0);
+  const ConvP& p = s0.p;
   const int cls = C::BN == 64 ? PC_CONV_M128N64 : C::BM == 256 ? PC_CONV_M256N32 : PC_CONV_M128N32;
-  if (n == 1 && S[0].p.S > 1) {
-    const ConvSetup& s0 = S[0];
-    const ConvP& p = s0.p;
-    const nunet_conv_desc* d = ds[0];
-    ProfScope ps(cls, s0.flops, s0.bytes, st);
-    ConvGroup g; g.n = 1; g.grid[0] = (int)s0.grid; g.p[0] = p;
+  ProfScope ps(cls, s0.flops, s0.bytes, st);
+  ConvGroup g; g.n = 1; g.grid[0] = (int)s0.grid; g.p[0] = p;
+  if (p.S > 1) {
     launch_conv_lt<T, WM, WN, SM, SN, true, false>(s0.lt, (unsigned)s0.grid, s0.dyn, st, g);
     SplitFinP f;
     f.slabs = p.slabs; f.slab_stride = p.slab_stride; f.S = p.S; f.bias = p.bias;
@@ -1004,21 +1005,9 @@ static int launch_conv_cfg(const nunet_conv_desc* const* ds, int n, hipStream_t 
     else NUNET_LAUNCH((splitk_finalize_kernel<T, false>), dim3((unsigned)fg), dim3(blk), 0, st, f);
     return nunet_check_launch("conv3x3 (K-split)");
   }
-  // one launch for the n problems (the caller grouped only problems of one variant, none of them K-split): sorted by grid size
-  // for the round-robin workgroup map, coefficient tables sized for the largest
-  int order[CONV_GROUP_MAX];
-  for (int k = 0; k < n; ++k) order[k] = k;
-  for (int a = 0; a < n; ++a) for (int b = a + 1; b < n; ++b) if (S[order[b]].grid < S[order[a]].grid) { const int t = order[a]; order[a] = order[b]; order[b] = t; }
-  ConvGroup g; g.n = n;
-  long total = 0; size_t dyn = 0; double fl = 0, by = 0;
-  for (int k = 0; k < n; ++k) {
-    const ConvSetup& s = S[order[k]];
-    g.grid[k] = (int)s.grid; g.p[k] = s.p; total += s.grid; if (s.dyn > dyn) dyn = s.dyn; fl += s.flops; by += s.bytes;
-  }
-  ProfScope ps(cls, fl, by, st);
-  if (S[0].bnr) launch_conv_lt<T, WM, WN, SM, SN, false, true>(S[0].lt, (unsigned)total, dyn, st, g);
-  else launch_conv_lt<T, WM, WN, SM, SN, false, false>(S[0].lt, (unsigned)total, dyn, st, g);
-  return nunet_check_launch(n > 1 ? "conv3x3 (group)" : "conv3x3");
+  if (s0.bnr) launch_conv_lt<T, WM, WN, SM, SN, false, true>(s0.lt, (unsigned)s0.grid, s0.dyn, st, g);
+  else launch_conv_lt<T, WM, WN, SM, SN, false, false>(s0.lt, (unsigned)s0.grid, s0.dyn, st, g);
+  return nunet_check_launch("conv3x3");
 }
 
 // Tile choice (measured per layer on MI355X, tools/conv_layers.py): the standard tiles are 128 pixels x 64 channels
@@ -1063,41 +1052,16 @@ static int conv_cfg_of(const nunet_conv_desc* d) {
   if (small) return 0;
   return cout % 64 == 0 ? 1 : 2;
 }
-template <typename T> static int launch_conv_n(const nunet_conv_desc* const* ds, int n, hipStream_t st) {
-  const int cfg = conv_cfg_of(ds[0]);
-  if (cfg == 0) return launch_conv_cfg<T, 4, 1, 1, 1>(ds, n, st);                            // 128 pixels x 32 channels
-  if (cfg == 1) return launch_conv_cfg<T, 2, 2, 2, 1>(ds, n, st);
-  if (cfg == 3) return launch_conv_cfg<T, 4, 1, 2, 2>(ds, n, st);                            // 256 x 64: 64 x 64 per wave, every fragment feeds two MFMAs
-  return launch_conv_cfg<T, 4, 1, 2, 1>(ds, n, st);
-}
-template <typename T> static int launch_conv(const nunet_conv_desc* d, hipStream_t st) { return launch_conv_n<T>(&d, 1, st); }
-
-// would this problem be K-split (then it is launched alone: its finalize launch follows it)?
-template <typename T> static int conv_is_split(const nunet_conv_desc* d) {
-  ConvSetup S;
+template <typename T> static int launch_conv(const nunet_conv_desc* d, hipStream_t st) {
   const int cfg = conv_cfg_of(d);
-  if (cfg == 0) conv_setup<T, 4, 1, 1, 1>(d, S); else if (cfg == 1) conv_setup<T, 2, 2, 2, 1>(d, S); else if (cfg == 3) conv_setup<T, 4, 1, 2, 2>(d, S); else conv_setup<T, 4, 1, 2, 1>(d, S);
-  return S.p.S > 1 ? 1 : 0;
-}
-
-static int conv_check(const nunet_conv_desc* d, bool ptrs = true);
-// Grouping key of a problem: problems with equal keys (>= 0) may share a launch. -1: launch it alone.
-int nunet_conv_group_key(const nunet_conv_desc* d) {
-  if (!d || conv_check(d) != NUNET_OK) return -1;
-  if (NUNET_DISPATCH(d->dtype, conv_is_split, d)) return -1;
-  return ((d->dtype * 4 + conv_cfg_of(d)) * 2 + (d->bn_y ? 1 : 0)) * 3 + d->in_tf;
-}
-// n problems of one key in one launch (internal: the plan's single-stream schedule)
-int nunet_conv3x3_group(const nunet_conv_desc* const* ds, int n, hipStream_t st) {
-  NUNET_REQUIRE(ds && n >= 1 && n <= CONV_GROUP_MAX, "conv3x3 group: 1..%d problems", CONV_GROUP_MAX);
-  const int key = nunet_conv_group_key(ds[0]);
-  for (int k = 0; k < n; ++k) { const int rc = conv_check(ds[k]); if (rc) return rc; }
-  if (n > 1) for (int k = 0; k < n; ++k) NUNET_REQUIRE(key >= 0 && nunet_conv_group_key(ds[k]) == key, "conv3x3 group: problems of different kernel variants");
-  return NUNET_DISPATCH(ds[0]->dtype, launch_conv_n, ds, n, st);
+  if (cfg == 0) return launch_conv_cfg<T, 4, 1, 1, 1>(d, st);                            // 128 pixels x 32 channels
+  if (cfg == 1) return launch_conv_cfg<T, 2, 2, 2, 1>(d, st);
+  if (cfg == 3) return launch_conv_cfg<T, 4, 1, 2, 2>(d, st);                            // 256 x 64: 64 x 64 per wave, every fragment feeds two MFMAs
+  return launch_conv_cfg<T, 4, 1, 2, 1>(d, st);
 }
 
 // ptrs == false (nunet_conv3x3_launch_info): the shape rules only, no pointer is required
-static int conv_check(const nunet_conv_desc* d, bool ptrs) {
+static int conv_check(const nunet_conv_desc* d, bool ptrs = true) {
   NUNET_REQUIRE(d && (!ptrs || (d->src0 && d->wpack && d->dst0)), "conv3x3: null pointer");
   const int cin = d->C0 + d->C1, cout = d->D0 + d->D1;
   NUNET_REQUIRE(d->dtype >= 0 && d->dtype <= 2, "conv3x3: bad dtype %d", d->dtype);
@@ -1144,7 +1108,7 @@ extern "C" int nunet_conv3x3_fwd(const nunet_conv_desc* d, nunet_stream_t s) {
   return NUNET_DISPATCH(d->dtype, launch_conv, d, (hipStream_t)s);
 }
 
-// Diagnostic (include/nunet_diag.h): what launch_conv_n would launch for this descriptor, from the same policy and setup code
+// Diagnostic (include/nunet_diag.h): what launch_conv would launch for this descriptor, from the same policy and setup code
 template <typename T, int WM, int WN, int SM, int SN>
 static int conv_info_cfg(const nunet_conv_desc* d, int cfg, nunet_conv_launch_info* o) {
   typedef ConvCfg<T, WM, WN, SM, SN> C;

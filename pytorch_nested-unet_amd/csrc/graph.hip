@@ -21,8 +21,6 @@
 
 namespace {
 
-constexpr int Q = 4;   // ROCm's graph stream pool (DEBUG_HIP_FORCE_GRAPH_QUEUES default)
-
 struct Capture {
   hipStream_t origin = nullptr;
   std::vector<int> lane;          // by node creation index; -1 = not tagged (caller's stream -> lane 0)
@@ -37,9 +35,7 @@ struct nunet_graph {
   hipGraphExec_t exec;
   hipStream_t launch_stream;      // see nunet_graph_end: own stream -> own hardware queue
   hipEvent_t ev_in, ev_out;
-  std::vector<hipGraphNode_t> node;          // creation order
-  std::vector<std::pair<int, int>> elist;    // edges in insertion order (the order matters to ROCm's stream assignment)
-  int nodes, edges_before, edges_after, padded, lanes_used;
+  int nodes, edges, lanes_used;
 };
 
 // Called by the plan's scheduler after every op it issues on `st` while a nunet_graph capture is
@@ -110,42 +106,14 @@ extern "C" int nunet_graph_end(nunet_stream_t s, nunet_graph** out) {
     return NUNET_ELAUNCH;
   }
   size_t n = 0, ne = 0;
-  std::vector<hipGraphNode_t> nodes, from, to;
-  bool ok = hipGraphGetNodes(g, nullptr, &n) == hipSuccess;
-  if (ok) { nodes.resize(n); ok = hipGraphGetNodes(g, nodes.data(), &n) == hipSuccess; }
-  if (ok) ok = hipGraphGetEdges(g, nullptr, nullptr, &ne) == hipSuccess;
-  if (ok) { from.resize(ne); to.resize(ne); ok = ne == 0 || hipGraphGetEdges(g, from.data(), to.data(), &ne) == hipSuccess; }
-  if (!ok) { (void)hipGetLastError(); (void)hipGraphDestroy(g); nunet_set_error("graph_end: cannot read the captured graph"); return NUNET_ELAUNCH; }
-
+  if (hipGraphGetNodes(g, nullptr, &n) != hipSuccess || hipGraphGetEdges(g, nullptr, nullptr, &ne) != hipSuccess) {
+    (void)hipGetLastError(); (void)hipGraphDestroy(g); nunet_set_error("graph_end: cannot read the captured graph"); return NUNET_ELAUNCH;
+  }
   nunet_graph* G = new nunet_graph();
-  G->graph = g; G->exec = nullptr; G->launch_stream = nullptr; G->ev_in = G->ev_out = nullptr; G->nodes = (int)n; G->edges_before = (int)ne; G->edges_after = (int)ne; G->padded = 0; G->lanes_used = 1;
-
-  {
-    int mx = 0;
-    for (size_t k = 0; k < g_cap.lane.size() && k < n; ++k) if (g_cap.lane[k] > mx) mx = g_cap.lane[k];
-    G->lanes_used = mx + 1;
-  }
-  // remember the edge lists as captured
-  G->node = nodes;
-  G->elist.clear();
-  {
-    size_t ne2 = 0;
-    std::vector<hipGraphNode_t> f2, t2;
-    if (hipGraphGetEdges(g, nullptr, nullptr, &ne2) == hipSuccess && ne2) {
-      f2.resize(ne2); t2.resize(ne2);
-      if (hipGraphGetEdges(g, f2.data(), t2.data(), &ne2) == hipSuccess) {
-        std::vector<std::pair<hipGraphNode_t, int>> idx(n);
-        for (size_t k = 0; k < n; ++k) idx[k] = {nodes[k], (int)k};
-        std::sort(idx.begin(), idx.end());
-        auto find = [&](hipGraphNode_t h) {
-          auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(h, -1));
-          return (it != idx.end() && it->first == h) ? it->second : -1;
-        };
-        for (size_t k = 0; k < ne2; ++k) { const int a = find(f2[k]), b = find(t2[k]); if (a >= 0 && b >= 0) G->elist.push_back({a, b}); }
-      }
-    }
-    (void)hipGetLastError();
-  }
+  G->graph = g; G->exec = nullptr; G->launch_stream = nullptr; G->ev_in = G->ev_out = nullptr; G->nodes = (int)n; G->edges = (int)ne;
+  int mx = 0;
+  for (size_t k = 0; k < g_cap.lane.size() && k < n; ++k) if (g_cap.lane[k] > mx) mx = g_cap.lane[k];
+  G->lanes_used = mx + 1;
   // ROCm maps a new stream to the least-used of its 4 hardware queues, and instantiation creates the
   // graph's 3 extra streams. Creating the launch stream right before makes these four consecutive
   // picks, i.e. four DISTINCT hardware queues (launching on the caller's stream instead let two graph
@@ -187,9 +155,9 @@ extern "C" int nunet_graph_launch(nunet_graph* G, nunet_stream_t s) {
   return NUNET_OK;
 }
 
-extern "C" int nunet_graph_info(const nunet_graph* G, int32_t* nodes, int32_t* edges_captured, int32_t* edges_final, int32_t* padding, int32_t* lanes) {
-  NUNET_REQUIRE(G && nodes && edges_captured && edges_final && padding && lanes, "graph_info: null pointer");
-  *nodes = G->nodes; *edges_captured = G->edges_before; *edges_final = G->edges_after; *padding = G->padded; *lanes = G->lanes_used;
+extern "C" int nunet_graph_info(const nunet_graph* G, int32_t* nodes, int32_t* edges, int32_t* lanes) {
+  NUNET_REQUIRE(G && nodes && edges && lanes, "graph_info: null pointer");
+  *nodes = G->nodes; *edges = G->edges; *lanes = G->lanes_used;
   return NUNET_OK;
 }
 
@@ -205,17 +173,19 @@ extern "C" void nunet_graph_destroy(nunet_graph* G) {
 
 
 // ---------------------------------------------------------------------------------------------------------
-// Segmented step (see common.h): a recorded program of {launch single-stream graph, record event, wait event} over real
-// streams. Recording takes two passes of the same step body:
-//   dry  - nothing is launched (g_dry_run); every cross-stream wait the lane scheduler asks for marks its event as NEEDED;
-//   real - streams capture lazily (the first launch after a cut begins a capture on that stream); a cross-stream wait or the
-//          record of a NEEDED event cuts the stream's open segment (end capture, instantiate, emit its launch) and is emitted
-//          as an instruction; records of events nobody waits on across streams are dropped (same-stream order is implicit).
+// Segmented step (see common.h): a recorded program of single-stream graph launches over real streams. Recording takes two
+// passes of the same step body:
+//   dry   - nothing is launched (g_dry_run); every cross-stream wait the lane scheduler asks for marks its event as NEEDED;
+//   flags - every lane stream captures lazily (its first launch begins the capture) and is cut once, at the end of the recording
+//           (end capture, instantiate, emit its launch); the cross-stream waits and the records of NEEDED events become
+//           device-side flags (below); records of events nobody waits on across streams are dropped (same-stream order is implicit).
+// (Cutting a lane at every cross-stream wait / needed record, with event records and waits between the graph launches, was built
+//  first and measured slower than both forms that are kept: profiles/r03_summary.md, 2.)
 // ---------------------------------------------------------------------------------------------------------
 thread_local bool g_dry_run = false;
 
 // ---------------------------------------------------------------------------------------------------------
-// Flag-synchronised lanes (recording mode 2). Every lane stream captures ONE single-stream graph for the whole step - the form
+// Flag-synchronised lanes (NUNET_SEG_FLAGS). Every lane stream captures ONE single-stream graph for the whole step - the form
 // ROCm replays as a batch of pre-built packets - and the cross-lane dependencies become device-side flags instead of graph edges
 // or events between graph launches:
 //   record of an event some other lane waits for  ->  flags[f] = step       (one thread, release, agent scope)
@@ -226,8 +196,8 @@ thread_local bool g_dry_run = false;
 // kernel starts after its lane's producer kernel has completed (release at the end of a kernel), the consumer kernel starts after
 // the wait kernel has exited (acquire at the start of a kernel); only the flag itself is accessed with agent-scope atomics.
 // The lanes must sit on different hardware queues (a wait kernel ahead of the signal it waits for in the SAME queue would never
-// end): the plan picks them by measured overlap (seg_pick_lanes) and the recording is refused when fewer than the lanes it
-// uses are distinct. A wait that is not satisfied within LANE_WAIT_TIMEOUT_S sets the program's error word (host-pinned) and
+// end): the plan picks them by measured overlap (seg_pick_lanes), and lanes it cannot tell apart share one STREAM, whose order
+// keeps a signal ahead of its wait. A wait that is not satisfied within LANE_WAIT_TIMEOUT_S sets the program's error word (host-pinned) and
 // exits, so a broken schedule fails loudly at the next launch instead of hanging the GPU.
 // ---------------------------------------------------------------------------------------------------------
 constexpr unsigned long long LANE_WAIT_TIMEOUT_TICKS = 400000000ull;   // s_memrealtime runs at 100 MHz: 4 s
@@ -259,12 +229,10 @@ __global__ __launch_bounds__(64) void lane_sync_kernel(LaneSyncP p) {
 }
 
 namespace {
-struct SegInstr { int op; hipStream_t st; hipEvent_t ev; hipGraphExec_t exec; };   // op 0 launch, 1 record, 2 wait
+struct SegLaunch { hipStream_t st; hipGraphExec_t exec; };   // one lane's graph, launched on its stream
 struct FlagOf { int f; hipStream_t st; };
 struct SegRec {
-  bool dry = false;
-  // mode 2 (flag-synchronised lanes)
-  bool flags_mode = false;
+  bool dry = false;                          // NUNET_SEG_DRY; else NUNET_SEG_FLAGS:
   unsigned* dflags = nullptr;                // [MAXF] flags, then [MAXL] lane counters (device memory, zeroed)
   unsigned* herr = nullptr;                  // host-pinned error word
   int nflags = 0, nwaits = 0, nsignals = 0;
@@ -308,8 +276,8 @@ struct SegRec {
   unsigned* ctr_of(hipStream_t st) { return dflags + MAXF + lane_of(st); }
   hipStream_t main = nullptr;
   std::vector<hipEvent_t> needed;            // sorted after the dry pass
-  std::vector<hipStream_t> capturing;        // streams with an open segment
-  std::vector<SegInstr> prog;
+  std::vector<hipStream_t> capturing;        // streams with an open capture
+  std::vector<SegLaunch> prog;
   std::vector<hipGraph_t> graphs;
   std::vector<hipGraphExec_t> execs;
   bool failed = false;
@@ -317,6 +285,7 @@ struct SegRec {
   bool is_cap(hipStream_t st) const { return std::find(capturing.begin(), capturing.end(), st) != capturing.end(); }
   bool is_needed(hipEvent_t e) const { return std::binary_search(needed.begin(), needed.end(), e); }
   void fail(const char* what, hipError_t e) { if (!failed) { failed = true; snprintf(err, sizeof(err), "%s: %s", what, hipGetErrorString(e)); } (void)hipGetLastError(); }
+  // close the lane's capture: its graph becomes one launch of the program
   void cut(hipStream_t st) {
     auto it = std::find(capturing.begin(), capturing.end(), st);
     if (it == capturing.end()) return;
@@ -326,19 +295,18 @@ struct SegRec {
     if (e != hipSuccess || !g) { fail("segment end capture", e); return; }
     size_t n = 0;
     (void)hipGraphGetNodes(g, nullptr, &n);
-    if (n == 0) { (void)hipGraphDestroy(g); return; }          // nothing was launched since the cut
+    if (n == 0) { (void)hipGraphDestroy(g); return; }          // nothing was launched on it
     hipGraphExec_t x = nullptr;
     e = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
     if (e != hipSuccess) { fail("segment instantiate", e); (void)hipGraphDestroy(g); return; }
     graphs.push_back(g); execs.push_back(x);
-    prog.push_back(SegInstr{0, st, nullptr, x});
+    prog.push_back(SegLaunch{st, x});
   }
   void touch(hipStream_t st) {
     if (dry) return;
-    if (flags_mode) { flush(st); begin_capture(st); return; }
-    begin_capture(st);
+    flush(st); begin_capture(st);
   }
-  // mode 2: the record of a needed event / a cross-lane wait, collected for the lane's next sync kernel
+  // the record of a needed event / a cross-lane wait, collected for the lane's next sync kernel
   void flag_signal(hipEvent_t ev, hipStream_t st) {
     if (nflags >= MAXF) { fail("too many cross-lane events", hipErrorInvalidValue); return; }
     const int f = nflags++;
@@ -367,54 +335,37 @@ thread_local std::vector<hipEvent_t> g_seg_needed;      // result of the last dr
 }  // namespace
 
 struct nunet_seg {
-  std::vector<SegInstr> prog;
+  std::vector<SegLaunch> prog;
   std::vector<hipGraph_t> graphs;
   std::vector<hipGraphExec_t> execs;
   hipStream_t main;
   hipEvent_t ev_in, ev_out;
-  int n_launch, n_record, n_wait, n_nodes;
-  unsigned* dflags; unsigned* herr;          // mode 2: flags + lane counters (device), error word (host-pinned)
+  int n_record, n_wait, n_nodes;
+  unsigned* dflags; unsigned* herr;          // flags + lane counters (device), error word (host-pinned)
 };
 
 bool seg_active() { return g_seg != nullptr; }
 bool seg_wait(hipStream_t st, hipEvent_t ev) {
   SegRec* r = g_seg;
   if (!r) return false;
-  if (r->dry) { r->needed.push_back(ev); return true; }
-  if (r->flags_mode) { r->flag_wait(st, ev); return true; }
-  hipEvent_t e = ev;
-  // one wait per (stream, event) between two cuts of the stream is enough
-  for (size_t k = r->prog.size(); k-- > 0;) {
-    const SegInstr& i = r->prog[k];
-    if (i.st != st) continue;
-    if (i.op == 2 && i.ev == e) return true;
-    if (i.op == 0) break;
-  }
-  r->cut(st);
-  r->prog.push_back(SegInstr{2, st, e, nullptr});
+  if (r->dry) r->needed.push_back(ev); else r->flag_wait(st, ev);
   return true;
 }
 bool seg_record(hipEvent_t ev, hipStream_t st) {
   SegRec* r = g_seg;
   if (!r) return false;
-  if (r->dry || !r->is_needed(ev)) return true;
-  if (r->flags_mode) { r->flag_signal(ev, st); return true; }
-  // (merging the records lazily - a lane cut only when another lane asks for one of its events - gives 33 instead of 55 segments
-  //  per step but 2.64 instead of 2.33 ms: consumers then wait for the producer lane's whole tail; measured, not kept)
-  r->cut(st);
-  r->prog.push_back(SegInstr{1, st, ev, nullptr});
+  if (!r->dry && r->is_needed(ev)) r->flag_signal(ev, st);
   return true;
 }
 void seg_touch(hipStream_t st) { if (g_seg) g_seg->touch(st); }
 
 extern "C" int nunet_seg_begin(nunet_stream_t s, int32_t mode) {
+  NUNET_REQUIRE(mode == NUNET_SEG_DRY || mode == NUNET_SEG_FLAGS, "seg_begin: mode %d is neither NUNET_SEG_DRY (1) nor NUNET_SEG_FLAGS (2)", mode);
   NUNET_REQUIRE(s, "seg_begin: recording needs an explicit (non-default) stream");
   NUNET_REQUIRE(!g_seg && !g_cap.active, "seg_begin: a recording / capture is already active on this thread");
-  NUNET_REQUIRE(mode >= 0 && mode <= 2, "seg_begin: mode %d", mode);
   SegRec* r = new SegRec();
   r->dry = mode == NUNET_SEG_DRY; r->main = (hipStream_t)s;
-  if (mode == NUNET_SEG_FLAGS) {
-    r->flags_mode = true;
+  if (!r->dry) {
     const size_t bytes = sizeof(unsigned) * (SegRec::MAXF + SegRec::MAXL + 1);      // flags | lane counters | device copy of the error word
     if (hipMalloc((void**)&r->dflags, bytes) != hipSuccess || hipMemset(r->dflags, 0, bytes) != hipSuccess ||
         hipHostMalloc((void**)&r->herr, sizeof(unsigned), hipHostMallocDefault) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
@@ -444,18 +395,14 @@ extern "C" int nunet_seg_end(nunet_stream_t s, nunet_seg** out) {
     if (out) *out = nullptr;
     return NUNET_OK;
   }
-  if (r->flags_mode) { for (size_t k = 0; k < r->pend.size(); ++k) r->flush(r->pend[k].st); }
+  for (size_t k = 0; k < r->pend.size(); ++k) r->flush(r->pend[k].st);
   while (!r->capturing.empty()) r->cut(r->capturing.back());
   nunet_seg* G = new nunet_seg();
   G->prog = r->prog; G->graphs = r->graphs; G->execs = r->execs; G->main = r->main; G->ev_in = G->ev_out = nullptr;
   G->dflags = r->dflags; G->herr = r->herr;
-  G->n_launch = G->n_record = G->n_wait = G->n_nodes = 0;
-  for (const SegInstr& i : G->prog) { if (i.op == 0) ++G->n_launch; else if (i.op == 1) ++G->n_record; else ++G->n_wait; }
-  if (r->flags_mode) {
-    G->n_record = r->nsignals; G->n_wait = r->nwaits;
-    // the caller's lane is launched first: it heads the dependency order, the others start with a wait for one of its flags
-    for (size_t k = 0; k < G->prog.size(); ++k) if (G->prog[k].st == G->main) { std::swap(G->prog[0], G->prog[k]); break; }
-  }
+  G->n_record = r->nsignals; G->n_wait = r->nwaits; G->n_nodes = 0;
+  // the caller's lane is launched first: it heads the dependency order, the others start with a wait for one of its flags
+  for (size_t k = 0; k < G->prog.size(); ++k) if (G->prog[k].st == G->main) { std::swap(G->prog[0], G->prog[k]); break; }
   for (hipGraph_t g : G->graphs) { size_t n = 0; (void)hipGraphGetNodes(g, nullptr, &n); G->n_nodes += (int)n; }
   const bool failed = r->failed;
   if (failed) nunet_set_error("seg_end: %s", r->err);
@@ -479,15 +426,13 @@ extern "C" int nunet_seg_launch(nunet_seg* G, nunet_stream_t s) {
     nunet_set_error("seg_launch: a cross-lane wait of an earlier replay timed out (flag %u): two lanes share a hardware queue, or a lane died", *G->herr - 1u);
     return NUNET_ELAUNCH;
   }
-  if (cs != G->main || G->dflags) { e = hipEventRecord(G->ev_in, cs); if (e == hipSuccess && cs != G->main) e = hipStreamWaitEvent(G->main, G->ev_in, 0); }
+  e = hipEventRecord(G->ev_in, cs);
+  if (e == hipSuccess && cs != G->main) e = hipStreamWaitEvent(G->main, G->ev_in, 0);
   for (size_t k = 0; k < G->prog.size() && e == hipSuccess; ++k) {
-    const SegInstr& i = G->prog[k];
-    // (flag mode: a side lane does not start polling before the caller's earlier work is done)
-    if (i.op == 0 && G->dflags && i.st != G->main) e = hipStreamWaitEvent(i.st, G->ev_in, 0);
-    if (e != hipSuccess) break;
-    if (i.op == 0) e = hipGraphLaunch(i.exec, i.st);
-    else if (i.op == 1) e = hipEventRecord(i.ev, i.st);
-    else e = hipStreamWaitEvent(i.st, i.ev, 0);
+    const SegLaunch& i = G->prog[k];
+    // (a side lane does not start polling before the caller's earlier work is done)
+    if (i.st != G->main) e = hipStreamWaitEvent(i.st, G->ev_in, 0);
+    if (e == hipSuccess) e = hipGraphLaunch(i.exec, i.st);
   }
   if (e == hipSuccess && cs != G->main) { e = hipEventRecord(G->ev_out, G->main); if (e == hipSuccess) e = hipStreamWaitEvent(cs, G->ev_out, 0); }
   if (e != hipSuccess) { nunet_set_error("seg_launch: %s", hipGetErrorString(e)); (void)hipGetLastError(); return NUNET_ELAUNCH; }
@@ -496,7 +441,7 @@ extern "C" int nunet_seg_launch(nunet_seg* G, nunet_stream_t s) {
 
 extern "C" int nunet_seg_info(const nunet_seg* G, int32_t* launches, int32_t* records, int32_t* waits, int32_t* kernel_nodes) {
   NUNET_REQUIRE(G && launches && records && waits && kernel_nodes, "seg_info: null pointer");
-  *launches = G->n_launch; *records = G->n_record; *waits = G->n_wait; *kernel_nodes = G->n_nodes;
+  *launches = (int32_t)G->prog.size(); *records = G->n_record; *waits = G->n_wait; *kernel_nodes = G->n_nodes;
   return NUNET_OK;
 }
 

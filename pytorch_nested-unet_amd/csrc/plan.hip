@@ -447,7 +447,7 @@ struct PlanRt {  // runtime objects owned by the plan (host side only)
   std::vector<hipEvent_t> events[2];   // [0] forward, [1] backward: an event is never re-recorded within one capture
   size_t events_used[2];
   int multistream;
-  int wave;                                // 1: single-stream schedule with grouped launches (Sched::run_wave) instead of lanes
+  int schedule;                            // NUNET_SCHEDULE_LANES: an op runs on its block's lane; NUNET_SCHEDULE_LIST: Sched::run_list picks
   bool lanes_external;
   std::vector<hipStream_t> cap_streams;   // never-reused streams for capture-time lane continuation
   size_t cap_next;
@@ -462,7 +462,6 @@ struct PlanRt {  // runtime objects owned by the plan (host side only)
   std::map<std::string, float> op_cost[2]; // measured cost (us) by op name, per pass; empty: the built-in estimates
   hipEvent_t b0_event;                     // recorded when the first gradient bucket (phase-1 nodes + heads) is complete
   bool b0_enabled;
-  int seg_lanes_distinct;                  // how many of them were measured to run beside the caller's stream and each other
   hipStream_t seg_lanes[3];                // side-lane streams of the segmented recording (created together: distinct hardware queues)
   std::vector<hipStream_t> seg_owned;      // every stream seg_pick_lanes created and kept (destroyed with the plan)
   struct Sched* open_sched;                // backward pass left open after phase 1 (nunet_plan_backward_phase bit 3): lanes, dependency state
@@ -692,7 +691,7 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
   rt->seg_lanes[0] = rt->seg_lanes[1] = rt->seg_lanes[2] = nullptr;
   rt->events_used[0] = rt->events_used[1] = 0;
   { const char* e = getenv("NUNET_MULTISTREAM"); rt->multistream = e ? atoi(e) : 1; }
-  rt->wave = 0;
+  rt->schedule = NUNET_SCHEDULE_LANES;
   for (int l = 0; l < NLANES; ++l) {
     rt->lanes[l] = nullptr;
     if (hipStreamCreateWithFlags(&rt->lanes[l], hipStreamNonBlocking) != hipSuccess) { rt->lanes_ok = false; (void)hipGetLastError(); }
@@ -812,17 +811,11 @@ struct Sched {
     if (rt->cap_next >= rt->cap_streams.size()) { failed = true; return nullptr; }
     return rt->cap_streams[rt->cap_next++];
   }
-  // begin an op on `lane` reading `rd` and writing `wr` resources; returns the stream to launch on
-  hipStream_t begin(int lane, std::initializer_list<int> rd, std::initializer_list<int> wr) {
-    int r[16], w[16], nr = 0, nw = 0;
-    for (int x : rd) if (x >= 0) { if (nr < 16) r[nr++] = x; else failed = true; }
-    for (int x : wr) if (x >= 0) { if (nw < 16) w[nw++] = x; else failed = true; }
-    return begin_v(lane_map[lane], r, nr, w, nw);
-  }
   // stream waits / event records: real HIP calls, or instructions of the segmented program being recorded (graph.hip)
   static void wait_on(hipStream_t st, hipEvent_t ev) { if (!seg_wait(st, ev)) (void)hipStreamWaitEvent(st, ev, 0); }
   static void record_on(hipEvent_t ev, hipStream_t st) { if (!seg_record(ev, st)) (void)hipEventRecord(ev, st); }
-  hipStream_t begin_v(int lane, const int* rd, int nrd, const int* wr, int nwr) {   // `lane` already mapped
+  // begin an op on `lane` (already mapped) reading `rd` and writing `wr` resources; returns the stream to launch on
+  hipStream_t begin_v(int lane, const int* rd, int nrd, const int* wr, int nwr) {
     if (!multi) return main_s;
     cur_lane = lane; nreads = 0; nwrites = 0; npend = 0;
     hipStream_t st = lane_s[lane];      // may be null while capturing (lane not started yet)
@@ -857,22 +850,21 @@ struct Sched {
   }
 
   // ---- deferred ops: the backward pass collects its ops first (descriptors captured by value), then issues them
-  // kind: what the single-stream schedule (run_wave) may group into one launch; the lane schedule runs every op through fn
-  enum { K_GEN = 0, K_CONV = 1 };
-  struct Op { int lane, leaf; float cost; int nrd, nwr; int rd[12], wr[8]; char name[32]; std::function<int(hipStream_t)> fn;
-              int kind; nunet_conv_desc cd; int alg_cin; };
+  struct Op { int lane, leaf; float cost; int nrd, nwr; int rd[12], wr[8]; char name[32]; std::function<int(hipStream_t)> fn; };
   std::vector<Op> ops;
-  // a 3x3 convolution (forward or input gradient): grouped with other ready convolutions of the same kernel variant by run_wave
+  // a 3x3 convolution (forward or input gradient)
   void add_conv(int lane, std::initializer_list<int> rd, std::initializer_list<int> wr, const nunet_conv_desc& d, int alg_cin = 0) {
     const double px = (double)d.N * d.H * d.W;
     add(lane, 0, 6.f + (float)(2.0 * 9 * (d.C0 + d.C1) * (d.D0 + d.D1) * px / 4e8), rd, wr, [d, alg_cin](hipStream_t ls) {
       g_prof_alg_cin = alg_cin; const int r = nunet_conv3x3_fwd(&d, ls); g_prof_alg_cin = 0; return r; });
-    ops.back().kind = K_CONV; ops.back().cd = d; ops.back().alg_cin = alg_cin;
   }
   void add(int lane, int leaf, float cost, std::initializer_list<int> rd, std::initializer_list<int> wr, std::function<int(hipStream_t)> fn) {
-    Op o; o.lane = lane_map[lane]; o.leaf = leaf; o.cost = cost; o.nrd = o.nwr = 0; o.kind = K_GEN; o.alg_cin = 0;
-    for (int x : rd) if (x >= 0) { if (o.nrd < 12) o.rd[o.nrd++] = x; else failed = true; }
-    for (int x : wr) if (x >= 0) { if (o.nwr < 8) o.wr[o.nwr++] = x; else failed = true; }
+    add_v(lane, leaf, cost, rd.begin(), (int)rd.size(), wr.begin(), (int)wr.size(), std::move(fn));
+  }
+  void add_v(int lane, int leaf, float cost, const int* rd, int nrd, const int* wr, int nwr, std::function<int(hipStream_t)> fn) {
+    Op o; o.lane = lane_map[lane]; o.leaf = leaf; o.cost = cost; o.nrd = o.nwr = 0;
+    for (int q = 0; q < nrd; ++q) if (rd[q] >= 0) { if (o.nrd < 12) o.rd[o.nrd++] = rd[q]; else failed = true; }
+    for (int q = 0; q < nwr; ++q) if (wr[q] >= 0) { if (o.nwr < 8) o.wr[o.nwr++] = wr[q]; else failed = true; }
     memcpy(o.name, cur_name, sizeof(o.name)); cur_name[0] = 0;
     measured_cost(o);
     o.fn = std::move(fn);
@@ -885,20 +877,11 @@ struct Sched {
     const auto it = m.find(o.name);
     if (it != m.end()) o.cost = it->second;
   }
-  void add_v(int lane, int leaf, float cost, const int* rd, int nrd, std::function<int(hipStream_t)> fn) {
-    Op o; o.lane = lane_map[lane]; o.leaf = leaf; o.cost = cost; o.nrd = o.nwr = 0; o.kind = K_GEN; o.alg_cin = 0;
-    for (int q = 0; q < nrd; ++q) if (rd[q] >= 0) { if (o.nrd < 12) o.rd[o.nrd++] = rd[q]; else failed = true; }
-    memcpy(o.name, cur_name, sizeof(o.name)); cur_name[0] = 0;
-    measured_cost(o);
-    o.fn = std::move(fn);
-    ops.push_back(std::move(o));
-  }
+  int issue(const int* order, const int* lane, int n);
   int run_ops();
-  int run_wave();
   int run_list();
-  bool wave;                           // single-stream schedule: no lanes, no events; run() picks
   bool list;                           // lanes assigned by a list scheduler over the dependency graph (run_list) instead of by block
-  int run() { return wave ? run_wave() : (list && multi) ? run_list() : run_ops(); }
+  int run() { return (list && multi) ? run_list() : run_ops(); }
   void end() {
     if (!multi) { stamp(main_s, 0); cur_name[0] = 0; return; }
     hipStream_t st = lane_s[cur_lane];
@@ -938,9 +921,8 @@ static void seg_pick_lanes(PlanRt* rt, hipStream_t main_s) {
   // the side lanes get the LOWEST stream priority: the chain lane's workgroups are dispatched ahead of theirs (+1.4 % on the
   // flag-synchronised step) - unless the caller says otherwise (nunet_plan_set_lane_priority): with RCCL's high-priority stream in
   // the process, lowest-priority lanes are served in time slices (every kernel on one of them took 100-190 us in the
-  // data-parallel rehearsal: 3.4-4.4 ms per step against 1.82 at default priority). NUNET_SIDE_PRIO overrides both.
-  int side_prio = rt->lane_low_priority;
-  { const char* e = getenv("NUNET_SIDE_PRIO"); if (e) side_prio = atoi(e); }
+  // data-parallel rehearsal: 3.4-4.4 ms per step against 1.82 at default priority).
+  const int side_prio = rt->lane_low_priority;
   int pr_least = 0, pr_greatest = 0;
   (void)hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest);
   // (measured and not kept: side lanes on CU-masked streams - hipExtStreamCreateWithCUMask, 16 to 96 CUs kept free for the chain -
@@ -992,7 +974,6 @@ static void seg_pick_lanes(PlanRt* rt, hipStream_t main_s) {
   // (fewer than three distinct queues found: lanes share a STREAM - never two streams of one queue, which the flag-synchronised
   //  program could not survive: a polling kernel ahead of its signal in the same queue)
   for (int q = 0; q < 3; ++q) rt->seg_lanes[q] = q < np ? pick[q] : (np > 0 ? pick[q % np] : main_s);
-  rt->seg_lanes_distinct = np;
   if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); if (eb) (void)hipEventDestroy(eb);
 }
 
@@ -1014,9 +995,7 @@ void Sched::init(nunet_plan* P, hipStream_t s, int pass_) {
     if (rt->stamps) { snprintf(cur_name, sizeof(cur_name), "start"); stamp(s, 0); cur_name[0] = 0; }
   }
   multi = rt->multistream != 0 && rt->lanes_ok && !rt->calibrating;
-  wave = rt->wave == 1 && !rt->calibrating;
-  list = rt->wave == 2 && !rt->calibrating;
-  if (wave) multi = false;             // one stream: no lanes to fork, no events
+  list = rt->schedule == NUNET_SCHEDULE_LIST && !rt->calibrating;
   failed = false;
   capturing = false;
   pool = &rt->events[pass]; pool_used = &rt->events_used[pass];
@@ -1068,19 +1047,27 @@ void Sched::init(nunet_plan* P, hipStream_t s, int pass_) {
   }
 }
 
-int Sched::run_ops() {
-  // ops are issued in program order (a simulated list schedule and a rewrite of the captured graph's edge order were
-  // both measured slower than the plain capture order on ROCm 7.2, see DESIGN.md, and are not kept)
+// Issue the collected ops: op order[q] on lane lane[order[q]], for q = 0 .. n-1; stops at the first launch that fails.
+int Sched::issue(const int* order, const int* lane, int n) {
   int rc = NUNET_OK;
-  for (size_t q = 0; q < ops.size() && rc == NUNET_OK; ++q) {
-    Op& o = ops[q];
-    hipStream_t st = begin_v(o.lane, o.rd, o.nrd, o.wr, o.nwr);
+  for (int q = 0; q < n && rc == NUNET_OK; ++q) {
+    Op& o = ops[order[q]];
+    hipStream_t st = begin_v(lane[order[q]], o.rd, o.nrd, o.wr, o.nwr);
     rc = o.fn(st);
     memcpy(cur_name, o.name, sizeof(cur_name));
     end();
   }
   ops.clear();
   return rc;
+}
+
+int Sched::run_ops() {
+  // ops are issued in program order, each on its block's lane (a simulated list schedule and a rewrite of the captured graph's
+  // edge order were both measured slower than the plain capture order on ROCm 7.2, see DESIGN.md, and are not kept)
+  const int n = (int)ops.size();
+  std::vector<int> order(n), lane(n);
+  for (int i = 0; i < n; ++i) { order[i] = i; lane[i] = ops[i].lane; }
+  return issue(order.data(), lane.data(), n);
 }
 
 // List schedule: the lane of every op is CHOSEN here instead of following its block. The hazards of the program order (read after
@@ -1093,18 +1080,11 @@ int Sched::run_ops() {
 // block-lane order put leaf work (weight gradients) in front of critical ops of the same lane.
 int Sched::run_list() {
   const int n = (int)ops.size();
-  constexpr int NLMAX = 4;
   // three lanes: measured on MI355X (96x96 bs16, flag-synchronised lanes) 2 / 3 / 4 lanes = 8640 / 9270 / 8950 images/s - the fourth
   // concurrent stream costs the critical chain more than its overlap buys; limiting the summed chip share of the concurrent ops
   // instead (a capacity model over the launch grids) only lost: 1.5 / 2.0 / 2.5 / 3.0 full-chip ops at once = 6610 / 8480 / 8720 /
   // 9260. A crossing dependency costs one sync kernel on each side (XSYNC; 0 / 3 / 10 us in the model: no difference).
-  static int NLs[2] = {0, 0}; static float XSYNC = 3.f;
-  if (!NLs[0]) {
-    const char* e = getenv("NUNET_LIST_LANES"); NLs[0] = NLs[1] = e ? atoi(e) : 3;
-    const char* f = getenv("NUNET_LIST_LANES_FWD"); if (f) NLs[0] = atoi(f);
-    for (int q = 0; q < 2; ++q) if (NLs[q] < 1 || NLs[q] > NLMAX) NLs[q] = 3;
-  }
-  const int NL = NLs[pass & 1];
+  constexpr int NL = 3; constexpr float XSYNC = 3.f;
   std::vector<std::vector<int>> succ(n), pred(n);
   std::vector<int> indeg(n, 0);
   {
@@ -1125,7 +1105,7 @@ int Sched::run_list() {
   //  grid-starved levels 2-4 scaled by 1.5 / 2 / 3 as a model of their in-step inflation (-0.5 / -2 / -2 %): the isolated costs
   //  schedule best)
   std::vector<int> ready, lane(n, 0), order;
-  float lane_free[NLMAX] = {0.f, 0.f, 0.f, 0.f};
+  float lane_free[NL] = {0.f, 0.f, 0.f};
   for (int i = 0; i < n; ++i) if (indeg[i] == 0) ready.push_back(i);
   // event-driven: the lane that falls idle first takes the most urgent op that could start on it by then; when nothing could, the
   // lane's clock moves on to the next moment something can (so leaf work fills the holes of a lane instead of queueing at its end)
@@ -1154,8 +1134,7 @@ int Sched::run_list() {
     order.push_back(p);
     for (int s2 : succ[p]) if (--indeg[s2] == 0) ready.push_back(s2);
   }
-  int rc = NUNET_OK;
-  if ((int)order.size() != n) { nunet_set_error("plan: list schedule placed %d of %d ops (dependency cycle)", (int)order.size(), n); rc = NUNET_EINVAL; }
+  if ((int)order.size() != n) { nunet_set_error("plan: list schedule placed %d of %d ops (dependency cycle)", (int)order.size(), n); ops.clear(); return NUNET_EINVAL; }
   // issue in simulated start order (stable: a topological order of the hazard DAG)
   std::vector<int> idx(order);
   std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return tend[a] - ops[a].cost < tend[b] - ops[b].cost; });
@@ -1169,82 +1148,7 @@ int Sched::run_list() {
       if (dbg > 1) for (int i : idx) fprintf(stderr, "  %8.1f %6.1f  L%d %s\n", tend[i] - ops[i].cost, ops[i].cost, lane[i], ops[i].name);
     }
   }
-  for (size_t q = 0; q < idx.size() && rc == NUNET_OK; ++q) {
-    Op& o = ops[idx[q]];
-    hipStream_t st = begin_v(lane[idx[q]], o.rd, o.nrd, o.wr, o.nwr);
-    rc = o.fn(st);
-    memcpy(cur_name, o.name, sizeof(cur_name));
-    end();
-  }
-  ops.clear();
-  return rc;
-}
-
-// Single-stream schedule ("wave" mode). ROCm 7.2 replays a hipGraph with parallel branches node by node from the host (3-6 us of
-// host time per node, 2-10 us of extra latency per dependent node around every fork / join, tools/graph_gap_probe*.py) but a
-// single-stream graph as one batch of pre-built packets (0.9 us per node, 0.3 us of host time). And two independent
-// convolutions running side by side cost 1.3-1.4 x one (tools/conv_concurrency_probe.py). So instead of forking lanes the pass is
-// emitted on ONE stream, in dependency order, with the concurrency INSIDE the launches: a list scheduler walks the ops by
-// critical-path priority and puts every ready convolution of the same kernel variant into the launch of the one it picked
-// (nunet_conv3x3_group: up to CONV_GROUP_MAX problems, workgroups dealt round-robin).
-int nunet_conv_group_key(const nunet_conv_desc* d);
-int nunet_conv3x3_group(const nunet_conv_desc* const* ds, int n, hipStream_t st);
-int Sched::run_wave() {
-  const int n = (int)ops.size();
-  std::vector<std::vector<int>> succ(n);
-  std::vector<int> indeg(n, 0), key(n, -1);
-  {
-    std::vector<int> lastw(NRES, -1);
-    std::vector<std::vector<int>> readers(NRES);
-    auto edge = [&](int a, int b) { if (a >= 0 && a != b && std::find(succ[a].begin(), succ[a].end(), b) == succ[a].end()) { succ[a].push_back(b); ++indeg[b]; } };
-    for (int i = 0; i < n; ++i) {
-      const Op& o = ops[i];
-      for (int q = 0; q < o.nrd; ++q) edge(lastw[o.rd[q]], i);
-      for (int q = 0; q < o.nwr; ++q) { edge(lastw[o.wr[q]], i); for (int r : readers[o.wr[q]]) edge(r, i); }
-      for (int q = 0; q < o.nrd; ++q) readers[o.rd[q]].push_back(i);
-      for (int q = 0; q < o.nwr; ++q) { lastw[o.wr[q]] = i; readers[o.wr[q]].clear(); }
-      if (o.kind == K_CONV) key[i] = nunet_conv_group_key(&o.cd);
-    }
-  }
-  std::vector<float> prio(n, 0.f);
-  for (int i = n - 1; i >= 0; --i) { float m = 0.f; for (int s : succ[i]) m = std::max(m, prio[s]); prio[i] = ops[i].cost + m; }
-  std::vector<int> ready;
-  std::vector<char> done(n, 0);
-  for (int i = 0; i < n; ++i) if (indeg[i] == 0) ready.push_back(i);
-  int rc = NUNET_OK, emitted = 0;
-  while (!ready.empty() && rc == NUNET_OK) {
-    int best = 0;
-    for (int q = 1; q < (int)ready.size(); ++q) if (prio[ready[q]] > prio[ready[best]] || (prio[ready[q]] == prio[ready[best]] && ready[q] < ready[best])) best = q;
-    const int p = ready[best];
-    int grp[CONV_GROUP_MAX]; int ng = 0;
-    grp[ng++] = p;
-    if (key[p] >= 0) {
-      // the other ready convolutions of the same variant, most urgent first
-      std::vector<int> cand;
-      for (int q : ready) if (q != p && key[q] == key[p]) cand.push_back(q);
-      std::sort(cand.begin(), cand.end(), [&](int a, int b) { return prio[a] > prio[b] || (prio[a] == prio[b] && a < b); });
-      for (int q : cand) if (ng < CONV_GROUP_MAX) grp[ng++] = q;
-    }
-    if (ng > 1) {
-      const nunet_conv_desc* ds[CONV_GROUP_MAX];
-      for (int k = 0; k < ng; ++k) ds[k] = &ops[grp[k]].cd;
-      rc = nunet_conv3x3_group(ds, ng, main_s);
-      snprintf(cur_name, sizeof(cur_name), "%.12s+%d", ops[p].name, ng - 1);
-    } else {
-      rc = ops[p].fn(main_s);
-      memcpy(cur_name, ops[p].name, sizeof(cur_name));
-    }
-    stamp(main_s, 0); cur_name[0] = 0;
-    for (int k = 0; k < ng; ++k) {
-      const int i = grp[k];
-      done[i] = 1; ++emitted;
-      ready.erase(std::find(ready.begin(), ready.end(), i));
-      for (int s : succ[i]) if (--indeg[s] == 0) ready.push_back(s);
-    }
-  }
-  if (rc == NUNET_OK && emitted != n) { nunet_set_error("plan: single-stream schedule emitted %d of %d ops (dependency cycle)", emitted, n); rc = NUNET_EINVAL; }
-  ops.clear();
-  return rc;
+  return issue(idx.data(), lane.data(), n);
 }
 
 // Lane of a block. Crossing hardware queues costs 5-10 us of dispatch latency per dependency edge, so the assignment
@@ -2012,7 +1916,7 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
       // back until the chain reaches the deep levels (B31 ..., grid-starved kernels that leave most CUs idle): they run
       // on lane 4 behind a dependency on the gradient that B22's upsample-backward hands to B31
       int wl = wlane, r_gate = -1;     // (measured +1.9 % on the step)
-      if (!P->cfg.unet && n.j > 0 && n.i + n.j == 4 && n.i <= 2 && (phases & 3) == 3 && !S.wave && !S.list) { wl = 4; r_gate = R_GX + 3 * 5 + 1; }
+      if (!P->cfg.unet && n.j > 0 && n.i + n.j == 4 && n.i <= 2 && (phases & 3) == 3 && !S.list) { wl = 4; r_gate = R_GX + 3 * 5 + 1; }
       const float wcost = 8.f + (float)(2.0 * 9 * ((double)L1.cinpad + L2.cinpad) * f * (double)c.N * H * W / 3.5e8);
       S.add(wl, 1, wcost, {rb + B_A1, r_dy2, r_dy1, r_in, rx[0], rx[1], rx[2], rx[3], r_up, r_gate}, {R_GSW + 2 * k, R_GSW + 2 * k + 1},
             [=](hipStream_t ls) {
@@ -2049,7 +1953,7 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
       for (size_t q = 0; q < rs.size(); q += 10) {
         const bool last = q + 10 >= rs.size();
         S.name("b0rdy");
-        S.add_v(4, 1, 0.f, rs.data() + q, (int)std::min<size_t>(10, rs.size() - q), [=](hipStream_t ls) {
+        S.add_v(4, 1, 0.f, rs.data() + q, (int)std::min<size_t>(10, rs.size() - q), nullptr, 0, [=](hipStream_t ls) {
           if (!last) return (int)NUNET_OK;
           hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
           (void)hipStreamIsCapturing(ls, &cs);
@@ -2067,7 +1971,7 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
     for (size_t h = 0; h < P->heads.size() && nr < 12; ++h) rs[nr++] = R_GSV + 30 + (int)h;
     const int nh = P->utab.n - P->ptab.n, nt = P->ptab.ntiles;
     S.name("heads.upd");
-    S.add_v(0, 1, 5.f, rs, nr, [=](hipStream_t ls) { return launch_update(P, arena, upd, nt, nh, ls); });
+    S.add_v(0, 1, 5.f, rs, nr, nullptr, 0, [=](hipStream_t ls) { return launch_update(P, arena, upd, nt, nh, ls); });
   }
   if (rc == NUNET_OK) rc = S.run();
   if (leave_open && rc == NUNET_OK && !S.failed) {
@@ -2155,7 +2059,6 @@ extern "C" int nunet_plan_reset_lanes(nunet_plan* P) {
   NUNET_REQUIRE(P, "plan_reset_lanes: null plan");
   PlanRt* rt = rt_of(P);
   rt->seg_lanes[0] = rt->seg_lanes[1] = rt->seg_lanes[2] = nullptr;
-  rt->seg_lanes_distinct = 0;
   return NUNET_OK;
 }
 
@@ -2218,8 +2121,10 @@ extern "C" int nunet_plan_set_lanes(nunet_plan* P, nunet_stream_t* lanes, int32_
 }
 
 extern "C" int nunet_plan_set_schedule(nunet_plan* P, int32_t schedule) {
-  NUNET_REQUIRE(P && (schedule == NUNET_SCHEDULE_LANES || schedule == NUNET_SCHEDULE_WAVE || schedule == NUNET_SCHEDULE_LIST), "plan_set_schedule: bad args");
-  rt_of(P)->wave = schedule;
+  NUNET_REQUIRE(P, "plan_set_schedule: null plan");
+  NUNET_REQUIRE(schedule == NUNET_SCHEDULE_LANES || schedule == NUNET_SCHEDULE_LIST,
+                "plan_set_schedule: schedule %d is neither NUNET_SCHEDULE_LANES (0) nor NUNET_SCHEDULE_LIST (2)", schedule);
+  rt_of(P)->schedule = schedule;
   return NUNET_OK;
 }
 

@@ -44,13 +44,12 @@ class TrainStep:
         (step_u8). Only uint8 crosses PCIe and the per-step NCHW->NHWC launch of the float path is gone.
         How the captured step is executed (all forms are bit-identical, tests/test_net_gpu.py):
           schedule  'lanes' - every op on its block's lane; 'list' - lanes chosen by a list scheduler over the hazard graph with
-                    measured per-op costs (nunet_plan_calibrate); 'wave' - one stream, grouped convolution launches
+                    measured per-op costs (nunet_plan_calibrate)
           segmented False - ONE hipGraph, the lanes as parallel branches (ROCm replays those node by node from the host);
-                    'flags' - one single-stream graph per lane, cross-lane dependencies as device-side flags (csrc/graph.hip);
-                    True - single-stream graph segments with events between graph launches
-        Both None (default): single-process training times (False, 'lanes') against ('flags', 'list') on the captured step and
-        keeps the faster (self.executor_choice); data-parallel training keeps (False, 'lanes'), whose graph can hold the RCCL
-        exchange. NUNET_SCHEDULE / NUNET_SEGMENTED force a form (tools).
+                    'flags' - one single-stream graph per lane, cross-lane dependencies as device-side flags (csrc/graph.hip)
+        Both None (default): single-process training times the two executors, (False, 'lanes') against ('flags', 'list'), on the
+        captured step and keeps the faster (self.executor_choice); data-parallel training keeps (False, 'lanes'), whose graph can
+        hold the RCCL exchange. NUNET_SCHEDULE (lanes | list) / NUNET_SEGMENTED (0 | flags) force a form (tools); any other value raises.
         optimizer: 'SGD' (momentum, weight_decay, nesterov; reference trains.py:229-231) or 'Adam' (betas, eps, weight_decay as
         L2 decay in the gradient, amsgrad off; trains.py:225-227). Either runs inside the step in every fused_update layout;
         Adam keeps flat exp_avg / exp_avg_sq, a device step counter and the step's two bias-correction scalars, refreshed by a
@@ -80,11 +79,12 @@ class TrainStep:
         self.executor_auto = schedule is None and segmented is None and env_sched is None and env_seg is None
         self.executor_choice = None          # {(segmented, schedule): ms per step} when the form was chosen by timing
         self.schedule = schedule or env_sched or "lanes"
-        if self.schedule not in ("lanes", "wave", "list"):
-            raise L.NunetError("TrainStep: schedule %r is not 'lanes', 'wave' or 'list'" % (self.schedule,))
-        self._set_schedule(self.schedule)
         if segmented is None:
-            segmented = {"0": False, "1": True, "2": "flags", "flags": "flags"}.get(env_seg or "0", False)
+            segmented = {"0": False, "2": "flags"}.get(env_seg or "0", env_seg)
+        if self.schedule not in ("lanes", "list") or (segmented is not False and segmented != "flags"):
+            raise L.NunetError("TrainStep: schedule %r, segmented %r: the executors are (segmented=False, schedule='lanes'), one multi-branch "
+                               "hipGraph, and (segmented='flags', schedule='list'), flag-synchronised lanes" % (self.schedule, segmented))
+        self._set_schedule(self.schedule)
         self.segmented = segmented
         self._calibrated = False
         self.dp_exec = (False, "lanes")      # executor of the data-parallel layout 1 pass (see _choose_layout)
@@ -460,10 +460,9 @@ class TrainStep:
         if self.dp and self.dp_mode == 3 and dist.get_backend(self.pg) == "gloo":
             self.dp_mode = 1                                # a host-side exchange cannot be a graph node
         if not self.dp:
-            # the whole step, recorded once on a side stream and replayed on the caller's: as ONE hipGraph (default), or
-            # - segmented=True - as a program of single-stream graph segments over the plan's lanes with the cross-lane
-            # dependencies as events between graph launches (csrc/graph.hip nunet_seg_*: explicit node -> queue placement on lanes
-            # chosen by measurement; 2.33 vs 1.91 ms per step on MI355X: every segment launch costs 10-13 us on its lane)
+            # the whole step, recorded once on a side stream and replayed on the caller's: as ONE hipGraph, or - segmented='flags' -
+            # as one single-stream graph per lane with the cross-lane dependencies as device-side flags (csrc/graph.hip nunet_seg_*:
+            # explicit node -> queue placement on lanes chosen by measurement)
             body = lambda: (self._fwd_bwd(), self._opt())
             if self.executor_auto:
                 self._choose_executor(s, body)
@@ -498,7 +497,7 @@ class TrainStep:
 
     def _set_schedule(self, schedule):
         self.schedule = schedule
-        L.check(L.lib().nunet_plan_set_schedule(self.pl.handle, {"lanes": 0, "wave": 1, "list": 2}[schedule]), "plan_set_schedule")
+        L.check(L.lib().nunet_plan_set_schedule(self.pl.handle, {"lanes": 0, "list": 2}[schedule]), "plan_set_schedule")
 
     def _build_executor(self, s, body, segmented, schedule):
         """The step body recorded in one of its executable forms (see __init__)."""
@@ -528,7 +527,7 @@ class TrainStep:
             # serialised). Such a program is thrown away and recorded again on newly picked lanes.
             prog = None
             for attempt in range(3):
-                prog = _SegProgram(s, body, flags=True)
+                prog = _SegProgram(s, body)
                 ms = self._time(self._as_step_runs(prog), 2, 8)
                 if ms < 0.9 * self._single_lane_ms:
                     break
@@ -538,7 +537,7 @@ class TrainStep:
                     prog = None
                     L.check(L.lib().nunet_plan_reset_lanes(self.pl.handle), "plan_reset_lanes")
         else:
-            prog = _SegProgram(s, body, flags=segmented == "flags") if segmented else _NativeGraph(s, body)
+            prog = _SegProgram(s, body) if segmented else _NativeGraph(s, body)
         self._calib_graph = None
         return prog
 
@@ -832,16 +831,15 @@ class TrainStep:
 
 class _SegProgram:
     """nunet_seg_* wrapper with the replay() surface of torch.cuda.CUDAGraph: the step body is run twice on `side_stream` - a dry
-    pass that launches nothing and finds the cross-lane events, then the recording pass."""
+    pass that launches nothing and finds the cross-lane events, then the pass that records the flag-synchronised lanes."""
 
-    def __init__(self, side_stream, body, flags=False):
+    def __init__(self, side_stream, body):
         import ctypes as C
         lib = L.lib()
         self.stream = side_stream            # the program replays on this stream: keep it alive
         self.handle = None
-        self.flags = bool(flags)
         with torch.cuda.stream(side_stream):
-            for mode in (1, 2 if flags else 0):      # NUNET_SEG_DRY, then NUNET_SEG_FLAGS / NUNET_SEG_RECORD
+            for mode in (1, 2):                      # NUNET_SEG_DRY, then NUNET_SEG_FLAGS
                 L.check(lib.nunet_seg_begin(L.stream(), mode), "seg_begin")
                 try:
                     body()
@@ -887,9 +885,9 @@ class _NativeGraph:
 
     def info(self):
         import ctypes as C
-        v = [C.c_int32() for _ in range(5)]
+        v = [C.c_int32() for _ in range(3)]
         L.check(L.lib().nunet_graph_info(self.handle, *[C.byref(x) for x in v]), "graph_info")
-        return dict(zip(("nodes", "edges_captured", "edges_final", "padding", "lanes"), (x.value for x in v)))
+        return dict(zip(("nodes", "edges", "lanes"), (x.value for x in v)))
 
     def replay(self):
         L.check(L.lib().nunet_graph_launch(self.handle, L.stream()), "graph_launch")

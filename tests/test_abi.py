@@ -10,6 +10,7 @@ import nunet_amd
 from nunet_amd import _lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NUNET_OK, NUNET_EINVAL = 0, -1      # include/nunet.h
 
 
 @pytest.fixture(scope="module")
@@ -96,3 +97,24 @@ def test_module_surface_matches_reference():
     with pytest.raises(L.NunetError):
         import torch
         m(torch.zeros(1, 3, 32, 32))     # CPU tensors: no silent fallback
+
+
+def test_only_the_two_kept_schedules_and_recording_modes_are_accepted(lib):
+    """Host-only: nunet_plan_set_schedule takes NUNET_SCHEDULE_LANES (0) and NUNET_SCHEDULE_LIST (2); the value of the removed
+    single-stream schedule (1) and anything else is NUNET_EINVAL with a message - never silently another schedule. The segment
+    recorder refuses the removed event mode (0) before it looks at the stream or at HIP."""
+    cfg = L.PlanCfg(2, 32, 32, 3, 1, 0, L.F32, 0)
+    p = lib.nunet_plan_create(C.byref(cfg))
+    assert p
+    try:
+        for ok in (0, 2, 0):
+            assert lib.nunet_plan_set_schedule(p, ok) == NUNET_OK
+        for bad in (1, 3):
+            assert lib.nunet_plan_set_schedule(p, bad) == NUNET_EINVAL
+            msg = lib.nunet_last_error()
+            assert msg and b"plan_set_schedule" in msg and str(bad).encode() in msg, msg
+    finally:
+        lib.nunet_plan_destroy(p)
+    assert lib.nunet_seg_begin(C.c_void_p(1), 0) == NUNET_EINVAL
+    msg = lib.nunet_last_error()
+    assert msg and b"seg_begin" in msg and b"mode 0" in msg, msg

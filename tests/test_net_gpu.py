@@ -732,10 +732,10 @@ def test_step_from_decoded_uint8_batches(dtype, synth):
 
 
 def test_segmented_step_program_equals_the_single_graph(synth):
-    """The step recorded as a program of single-stream graph segments over the plan's lanes (TrainStep(segmented=True): nunet_seg_*, cross-lane
-    dependencies as event records / waits between graph launches on streams chosen by measurement) computes exactly what the
-    one multi-branch hipGraph computes: bit-identical parameters, momentum and BatchNorm buffers after three steps. (A dropped
-    dependency would show as a race here: the program keeps only the event records some other lane waits on.)"""
+    """The step recorded as a program of single-stream graphs, one per lane (TrainStep(segmented='flags'): nunet_seg_*, cross-lane
+    dependencies as device-side flags, on streams chosen by measurement), and the list schedule compute exactly what the
+    one multi-branch hipGraph with block lanes computes: bit-identical parameters, momentum and BatchNorm buffers after three
+    steps. (A dropped dependency would show as a race here: the program keeps only the event records some other lane waits on.)"""
     import os
     from nunet_amd.trainer import TrainStep, _SegProgram
     n, hw = 16, 96
@@ -743,7 +743,7 @@ def test_segmented_step_program_equals_the_single_graph(synth):
     sd = {k: v.clone() for k, v in nunet_amd.archs.NestedUNet(1, 3, True).state_dict().items()}
     batches = [synth.synth_batch(n, hw, hw, 3, 1, seed=300 + k) for k in range(3)]
     outs = []
-    for seg, sched in ((False, "lanes"), (True, "lanes"), ("flags", "lanes"), ("flags", "list"), (False, "list")):
+    for seg, sched in ((False, "lanes"), ("flags", "lanes"), ("flags", "list"), (False, "list")):
         m = nunet_amd.archs.NestedUNet(1, 3, True, dtype="bf16")
         m.load_state_dict(sd)
         m = m.to(DEV).train()
@@ -754,8 +754,8 @@ def test_segmented_step_program_equals_the_single_graph(synth):
             info = ts.g_fb.info()
             print("segmented program (%s, %s):" % (seg, sched), info)
             assert info["event_waits"] >= info["event_records"] > 0 and info["kernel_nodes"] > 100
-            # flag-synchronised lanes: ONE single-stream graph per lane; event mode: a graph per segment between two cuts
-            assert (1 <= info["graph_launches"] <= 4) if seg == "flags" else info["graph_launches"] > 4
+            # flag-synchronised lanes: ONE single-stream graph per lane
+            assert 1 <= info["graph_launches"] <= 4
         for rep in range(8 if seg == "flags" else 1):       # (the flag program replays the same three batches: a race would not repeat)
             if rep:
                 ts.eng.flat_params.copy_(p0); ts.mom.copy_(m0); ts.eng.bnbuf.copy_(b0)
@@ -820,32 +820,14 @@ def test_flag_program_survives_a_lane_reset_and_the_capture_time_choice_is_recor
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("dtype", ["bf16", "fp32"])
-def test_single_stream_schedule_with_grouped_convs_equals_the_lane_schedule(dtype, synth):
-    """TrainStep(schedule='wave') / nunet_plan_set_schedule: the pass emitted on ONE stream in dependency order by a critical-path list scheduler, every ready 3x3
-    convolution of the same kernel variant riding in the launch of the one it picked (nunet_conv3x3_group: up to 4 problems per
-    launch, workgroups dealt round-robin). A grouped problem computes exactly what its own launch computes, so the step is
-    bit-identical to the multi-lane schedule's - parameters, momentum, BatchNorm buffers, losses - with deep supervision on."""
-    import os
+def test_removed_executor_forms_are_refused():
+    """schedule='wave' (one stream, grouped convolution launches) and segmented=True (graph segments with events between their
+    launches) were measured slower than both executors that are kept and removed: TrainStep refuses them by name instead of
+    running another form. The smallest legal plan, nothing captured."""
     from nunet_amd.trainer import TrainStep
-    n, hw = 16, 96
-    torch.manual_seed(13)
-    sd = {k: v.clone() for k, v in nunet_amd.archs.NestedUNet(1, 3, True).state_dict().items()}
-    batches = [synth.synth_batch(n, hw, hw, 3, 1, seed=400 + k) for k in range(3)]
-    outs = []
-    for sched in ("lanes", "wave"):
-        m = nunet_amd.archs.NestedUNet(1, 3, True, dtype=dtype)
-        m.load_state_dict(sd)
-        m = m.to(DEV).train()
-        ts = TrainStep(m, (n, 3, hw, hw), lr=1e-2, schedule=sched)
-        ts.capture(torch.from_numpy(batches[0][0]).to(DEV), torch.from_numpy(batches[0][1]).to(DEV))
-        if sched == "wave":
-            info = ts.g_fb.info()
-            assert info["lanes"] == 1, info                        # one stream: ROCm's batch-submit path, no parallel branches
-        for img, msk in batches:
-            ts.step(torch.from_numpy(img).to(DEV), torch.from_numpy(msk).to(DEV))
-        torch.cuda.synchronize()
-        outs.append([t.clone() for t in (ts.eng.flat_params, ts.mom, ts.eng.bnbuf, ts.loss_out)])
-        del ts, m
-    for a, b in zip(*outs):
-        assert torch.equal(a, b)
+    m = nunet_amd.archs.NestedUNet(1, 3, False, dtype="fp32").to(DEV).train()
+    for bad in (dict(schedule="wave"), dict(segmented=True)):
+        with pytest.raises(L.NunetError, match=r"segmented=False, schedule='lanes'.*segmented='flags', schedule='list'"):
+            TrainStep(m, (2, 3, 32, 32), lr=1e-2, **bad)
+    ts = TrainStep(m, (2, 3, 32, 32), lr=1e-2, segmented="flags", schedule="list")      # the kept names still construct
+    assert (ts.segmented, ts.schedule) == ("flags", "list")
