@@ -42,6 +42,20 @@ typedef struct {
 } nunet_conv_launch_info;
 int nunet_conv3x3_launch_info(const nunet_conv_desc* d, nunet_conv_launch_info* out);
 
+/* What the HIP runtime reports for the conv3x3 kernel instantiation the descriptor's launch would take (tile policy, K-split,
+ * fused BatchNorm-backward reduce, input transform as in nunet_conv3x3_launch_info). Needs a device, launches nothing, and
+ * like the query above requires no pointer of the descriptor. The tests hold it against the launch geometry: a kernel that
+ * spills (localSizeBytes) or of which fewer workgroups fit a CU than the grid was sized for (occupancy < per_cu) fails there. */
+typedef struct {
+  int32_t numRegs;                  /* hipFuncGetAttributes: vector registers per lane */
+  int32_t localSizeBytes;           /* ... scratch (spill) bytes per lane */
+  int32_t sharedSizeBytes;          /* ... static LDS bytes per workgroup */
+  int32_t blockSize, dynLdsBytes;   /* threads and dynamic LDS bytes of the launch */
+  int32_t occupancy;                /* hipOccupancyMaxActiveBlocksPerMultiprocessor at that block size and dynamic LDS */
+  int32_t wg_per_cu;                /* workgroups per CU the instantiation promises by registers (its __launch_bounds__) */
+} nunet_conv_kernel_attrs_t;
+int nunet_conv_kernel_attrs(const nunet_conv_desc* d, nunet_conv_kernel_attrs_t* out);
+
 typedef struct {
   int32_t A, B;                     /* a work item covers 32 A output x 32 B input channels */
   int32_t NI, TH, TW, SH;           /* pixel tile (at most 128 pixels, 192 with halo), as above */

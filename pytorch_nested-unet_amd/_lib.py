@@ -77,6 +77,12 @@ class ConvLaunchInfo(C.Structure):
                                     "nCoT", "S", "nch", "items", "grid", "per_cu")]
 
 
+class ConvKernelAttrs(C.Structure):
+    """nunet_conv_kernel_attrs_t (include/nunet_diag.h): the runtime's view of the kernel a ConvDesc would launch."""
+    _fields_ = [(k, _i32) for k in ("numRegs", "localSizeBytes", "sharedSizeBytes", "blockSize", "dynLdsBytes", "occupancy",
+                                    "wg_per_cu")]
+
+
 class WgradLaunchInfo(C.Structure):
     """nunet_wgrad_launch_info (include/nunet_diag.h): what a WgradDesc would launch."""
     _fields_ = [(k, _i32) for k in ("A", "B", "NI", "TH", "TW", "SH", "tilesX", "tilesY", "tilesG", "nMT", "nCoT", "nCiT",
@@ -208,6 +214,7 @@ _SIG = {
     "nunet_debug_stamp": (_i32, [_vp, _vp]),
     "nunet_conv3x3_launch_info": (_i32, [C.POINTER(ConvDesc), C.POINTER(ConvLaunchInfo)]),
     "nunet_conv3x3_wgrad_launch_info": (_i32, [C.POINTER(WgradDesc), C.POINTER(WgradLaunchInfo)]),
+    "nunet_conv_kernel_attrs": (_i32, [C.POINTER(ConvDesc), C.POINTER(ConvKernelAttrs)]),
     "nunet_graph_begin": (_i32, [_vp]),
     "nunet_graph_end": (_i32, [_vp, C.POINTER(_vp)]),
     "nunet_graph_launch": (_i32, [_vp, _vp]),

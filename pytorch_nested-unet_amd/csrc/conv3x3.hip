@@ -241,8 +241,22 @@ __device__ __forceinline__ void conv_group_decode(const ConvGroup& g, int b, int
   }
 }
 
+// Workgroups per CU an instantiation promises BY REGISTERS: the second argument of its __launch_bounds__ (the compiler then
+// keeps it within 512 / that many registers per lane, one wave of a workgroup per SIMD) and a cap on the persistent grid in
+// conv_setup, next to the LDS and thread limits - a grid sized for three resident workgroups queues its excess behind
+// workgroups that each run all their rounds when only two fit. Three (<= 168 registers) for the 128 x 32 tile, which is also what
+// its 41 KB of LDS allow; two (<= 256) for the larger tiles, whose LDS holds no more. DESIGN.md section 7 has the register table.
+// Today the value depends on the tile alone and equals the tile's LDS limit, so the cap in conv_setup binds for no launch: it is
+// a guard that keeps the grid and __launch_bounds__ in agreement should an instantiation ever have to promise less. The
+// other parameters are there for that case.
 template <typename T, int WM, int WN, int SM, int SN, bool SK, bool BNR, int LT>
-__global__ __launch_bounds__(64 * WM * WN, 2) void conv3x3_kernel(ConvGroup grp) {
+constexpr int conv_wg_per_cu() {
+  if (SM * SN > 1) return 2;
+  return 3;
+}
+
+template <typename T, int WM, int WN, int SM, int SN, bool SK, bool BNR, int LT>
+__global__ __launch_bounds__(64 * WM * WN, (conv_wg_per_cu<T, WM, WN, SM, SN, SK, BNR, LT>())) void conv3x3_kernel(ConvGroup grp) {
   typedef ConvCfg<T, WM, WN, SM, SN> C;
   int gk = 0, vbid = (int)blockIdx.x;
   if (grp.n > 1) conv_group_decode(grp, (int)blockIdx.x, gk, vbid);
@@ -251,6 +265,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3x3_kernel(ConvGroup grp)
   const int vgrid = grp.grid[gk];
   typedef Mma<T> M;
   constexpr int PS = C::PS, EPV = C::EPV, BN = C::BN, BM = C::BM, NT = C::NT, KS = C::KS, OS = C::OS;
+  // the LT2 prologue relies on it: bn_sum_replicas(C) * C <= 256 gives one (replica, channel) pair and at most one channel per thread
+  static_assert(NT == 256, "four waves per workgroup on every tile");
 
   // one LDS arena: [halo | weights] during the K loop, [BM][OS] output staging in the epilogue
   __shared__ __attribute__((aligned(16))) T s_buf[C::STAGE_ELEMS];
@@ -308,12 +324,13 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3x3_kernel(ConvGroup grp)
   __syncthreads();
   KSTAMP(1);
 
-  int abase[SM];
+  // fragment base of the thread's row(s) per tap ROW, at the left tap: the three taps of a row are PS, 2 * PS further on, which
+  // goes into the read's offset field (one address register per tap row instead of one per tap, held across the whole kernel)
+  int arow[SM][3];
 #pragma unroll
-  for (int a = 0; a < SM; ++a) abase[a] = s_hidx[(wm * SM + a) * 32 + r] * PS + 8 * h;
-  int toff[9];
+  for (int a = 0; a < SM; ++a)
 #pragma unroll
-  for (int tap = 0; tap < 9; ++tap) toff[tap] = ((tap / 3 - 1) * HW2 + (tap % 3 - 1)) * PS;
+    for (int ty = 0; ty < 3; ++ty) arow[a][ty] = (s_hidx[(wm * SM + a) * 32 + r] + (ty - 1) * HW2 - 1) * PS + 8 * h;
   const int bbase = ((wn * SN) * 32 + r) * PS + 8 * h;
   int hcode[C::UH];
   unsigned interior = 0u;            // LT: bit k = staging unit k is a pixel of the tile itself (not its halo ring)
@@ -327,6 +344,9 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3x3_kernel(ConvGroup grp)
     }
   }
   const int seg = tid & 3;           // 16-byte segment of a pixel's chunk row: the same for every unit of a thread (NT % 4 == 0)
+  // LDS element offset of the thread's staging unit 0 (halo pixel / weight row tid >> 2); unit k is k * (NT / 4) rows further on,
+  // a constant that goes into the write's offset field (written as ((tid + k * NT) >> 2) * PS every unit holds an address register)
+  const int srow = (tid >> 2) * PS + seg * EPV;
 
   struct Item { int co0, n0, y0, x0, ks; };
   auto decode = [&](int item) {
@@ -363,15 +383,11 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3x3_kernel(ConvGroup grp)
   // pixel * pitch + its 16-byte segment + the chunk's (uniform) channel offset - two VALU per unit and chunk and no
   // 64-bit pointer per unit held across the MFMA sweep. A pixel outside the image reads pixel 0 and is zeroed on the
   // way to LDS (write_lds), so a chunk's staging stays 12 plain 16-byte loads without branches.
-  unsigned woff[C::UW];              // tile-invariant: weight row (tap, co within the Cout tile) + segment
-#pragma unroll
-  for (int k = 0; k < C::UW; ++k) {
-    const int u = tid + k * NT;
-    const int row = u >> 2;
-    const int tap = row / BN, co = row - tap * BN;
-    // (a unit past the last weight row exists when 9*BN*4 is not a multiple of NT; it re-reads row 0 and is never written to LDS)
-    woff[k] = row < 9 * BN ? (unsigned)(((tap * p.Cout + co) * p.Cin + seg * EPV) * (int)sizeof(T)) : (unsigned)(seg * 16);
-  }
+  // tile-invariant: weight row (tap, co within the Cout tile) + segment of the thread's weight unit 0. Unit k is NT / 4 rows, a
+  // whole number of taps, further on: a UNIFORM step of NT / 4 / BN taps, so one offset register serves all UW units
+  static_assert((NT / 4) % BN == 0, "weight staging units of a thread differ by whole taps");
+  const unsigned woff0 = (unsigned)(((((tid >> 2) / BN) * p.Cout + (tid >> 2) % BN) * p.Cin + seg * EPV) * (int)sizeof(T));
+  const unsigned wstep = (unsigned)((NT / 4 / BN) * p.Cout * p.Cin * (int)sizeof(T));
   unsigned wco = 0u;                 // the loaded item's Cout tile: co0 * Cin elements, in bytes (uniform)
   auto set_ptrs = [&](const Item& it) { wco = (unsigned)(it.co0 * p.Cin * (int)sizeof(T)); };
   // The staging loads of a chunk: uniform part (source, pitch, channel offset) once, then one 16-byte load per unit.
@@ -397,7 +413,11 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3x3_kernel(ConvGroup grp)
       hreg[u].raw = *reinterpret_cast<const u32x4*>(c.base + (gp * c.pb + c.cb));
       if constexpr (LT == 2) yreg[u].raw = *reinterpret_cast<const u32x4*>((const char*)p.tf_y + (gp * c.yb + c.ycb));
     } else {
-      wreg[u - C::UH].raw = *reinterpret_cast<const u32x4*>((const char*)p.w + (woff[u - C::UH] + c.wb));
+      const int k = u - C::UH;
+      unsigned wo = woff0 + (unsigned)k * wstep;
+      // (a unit past the last weight row exists when 9*BN*4 is not a multiple of NT; it re-reads row 0 and is never written to LDS)
+      if ((k + 1) * NT > 9 * BN * 4 && (tid >> 2) + k * (NT / 4) >= 9 * BN) wo = (unsigned)(seg * 16);
+      wreg[k].raw = *reinterpret_cast<const u32x4*>((const char*)p.w + (wo + c.wb));
     }
   };
   auto load_regs = [&](int kb) {
@@ -413,7 +433,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3x3_kernel(ConvGroup grp)
       for (int k = 0; k < C::UH; ++k) {
         const int u = tid + k * NT;
         // (the bound check folds away for every k whose whole NT-unit run exists: no branch per unit)
-        if ((k + 1) * NT <= C::HPMAX * 4 || (u >> 2) < C::HPMAX) st16(&s_halo[(u >> 2) * PS + seg * EPV], hgp[k] >= 0 ? hreg[k] : zero16<T>());
+        if ((k + 1) * NT <= C::HPMAX * 4 || (u >> 2) < C::HPMAX) st16(&s_halo[srow + k * (NT / 4) * PS], hgp[k] >= 0 ? hreg[k] : zero16<T>());
       }
     } else {
       typedef typename FV<T>::type V;
@@ -431,7 +451,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3x3_kernel(ConvGroup grp)
           else v = bn_relu_bwd_apply<V>(vec_to_f<T>(hreg[k]), vec_to_f<T>(yreg[k]), sc, sh, cA, cB);
           Vec16<T> o = vec_from_f<T>(v);
           if (!ok) o = zero16<T>();
-          st16(&s_halo[(u >> 2) * PS + seg * EPV], o);
+          st16(&s_halo[srow + k * (NT / 4) * PS], o);
           if (store && ok && ((interior >> k) & 1u)) st16((T*)p.tf_store + (size_t)hgp[k] * p.tf_ps + c0, o);
         }
       }
@@ -439,7 +459,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3x3_kernel(ConvGroup grp)
 #pragma unroll
     for (int k = 0; k < C::UW; ++k) {
       const int u = tid + k * NT;
-      if ((k + 1) * NT <= 9 * BN * 4 || (u >> 2) < 9 * BN) st16(&s_w[(u >> 2) * PS + seg * EPV], wreg[k]);
+      if ((k + 1) * NT <= 9 * BN * 4 || (u >> 2) < 9 * BN) st16(&s_w[srow + k * (NT / 4) * PS], wreg[k]);
     }
   };
 
@@ -466,10 +486,16 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3x3_kernel(ConvGroup grp)
     constexpr int PD = 1;
     constexpr int NB = PD + 1;
     typename M::Frag fa[NB][SM], fb[NB][SN];
+    // (opaque to the optimiser from here on: it otherwise hoists `arow + PS` and `arow + 2 * PS` out of the chunk loop as address
+    //  registers of their own - six more held across the whole kernel - instead of folding them into the reads' offset fields)
+#pragma unroll
+    for (int a = 0; a < SM; ++a)
+#pragma unroll
+      for (int ty = 0; ty < 3; ++ty) asm volatile("" : "+v"(arow[a][ty]));
     auto read_step = [&](int j) {                 // j: compile-time after unrolling
       const int tap = j / KS, ks = j % KS, bu = j % NB;
 #pragma unroll
-      for (int a = 0; a < SM; ++a) fa[bu][a] = M::load(&s_halo[abase[a] + toff[tap] + ks * 16]);
+      for (int a = 0; a < SM; ++a) fa[bu][a] = M::load(&s_halo[arow[a][tap / 3] + (tap % 3) * PS + ks * 16]);
 #pragma unroll
       for (int b = 0; b < SN; ++b) fb[bu][b] = M::load(&s_w[bbase + (tap * BN + b * 32) * PS + ks * 16]);
     };
@@ -512,7 +538,6 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3x3_kernel(ConvGroup grp)
       }
     }
   };
-  static_assert(SM * 16 <= 64, "row-validity mask of the epilogue is one 64-bit word");
   // BNR: the y1 vectors of this thread's store units. They are requested BEFORE the last chunk's sweep, i.e. before the
   // next item's staging loads: loads return in order, so the epilogue's wait for them leaves those staging loads in
   // flight (requested in the epilogue, behind them, the wait drained all twelve and cost a memory latency per item).
@@ -520,7 +545,9 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3x3_kernel(ConvGroup grp)
   auto issue_byv = [&](const Item& cur) {
     if constexpr (BNR) {
       constexpr int SEGS = BN / EPV;
-      const int sg = tid % SEGS, m0 = tid / SEGS;
+      int tid_e = threadIdx.x;       // (opaque, as in epi_plain: the UO table addresses below are otherwise held across the chunk loop)
+      asm volatile("" : "+v"(tid_e));
+      const int sg = tid_e % SEGS, m0 = tid_e / SEGS;
 #pragma unroll
       for (int k = 0; k < C::UO; ++k) {
         const int m = m0 + k * (NT / SEGS);
@@ -534,6 +561,14 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3x3_kernel(ConvGroup grp)
     // Nothing in here waits on a global LOAD unless a destination accumulates (the bias sits in an LDS table since the
     // prologue): a wait would also drain the next item's staging loads already in flight (the counter is in-order).
     constexpr int SEGS = BN / EPV;
+    // The thread's coordinates are derived afresh from an opaque copy of its index: everything the epilogue computes from them
+    // (LDS addresses of the transposition, of the row masks, of the store units) is loop-invariant, and the optimiser otherwise
+    // keeps it in ~10 registers across the chunk loop, where the loaders' register peak is.
+    int tid_e = threadIdx.x;
+    asm volatile("" : "+v"(tid_e));
+    const int tid = tid_e, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave / WN, wn = wave % WN;
+    const int r = lane & 31, h = lane >> 5;
     const int sg = tid % SEGS, m0 = tid / SEGS;       // NT % SEGS == 0: every store unit of a thread has the same channel segment
     int gpu[C::UO];
 #pragma unroll
@@ -542,12 +577,16 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3x3_kernel(ConvGroup grp)
       gpu[k] = m < BM ? s_gpix[m] : -1;
     }
     // which of this thread's accumulator rows are pixels of the image (all 16*SM reads in flight at once)
-    unsigned long long rowmask = 0ull;
+    // (one 16-bit word per 32-row block, shifted in from the top: written as `bit << i` the 16 * SM single-bit constants end up
+    //  in registers of their own, hoisted out of the chunk loop - 24 of them on the 256-pixel tiles)
+    unsigned rowmask[SM];
+#pragma unroll
+    for (int a = 0; a < SM; ++a) rowmask[a] = 0u;
     if (p.stats) {
 #pragma unroll
       for (int a = 0; a < SM; ++a)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) rowmask |= (s_gpix[(wm * SM + a) * 32 + acc_row(i, h)] >= 0 ? 1ull : 0ull) << (a * 16 + i);
+        for (int i = 15; i >= 0; --i) rowmask[a] = (rowmask[a] << 1) | (s_gpix[(wm * SM + a) * 32 + acc_row(i, h)] >= 0 ? 1u : 0u);
     }
     KSTAMP(kst); ++kst;       // g: row masks / unit pixels read
     __syncthreads();  // every wave finished reading halo/weights: the arena becomes staging
@@ -564,7 +603,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3x3_kernel(ConvGroup grp)
           const int m = (wm * SM + a) * 32 + acc_row(i, h);
           const T tv = from_f32<T>(acc[a][b][i] + bias);
           if (!(NUNET_ABLATE & 1024)) s_out[m * OS + cl] = tv;
-          const float d = ((rowmask >> (a * 16 + i)) & 1ull) ? to_f32(tv) - bias : 0.f;
+          const float d = ((rowmask[a] >> i) & 1u) ? to_f32(tv) - bias : 0.f;
           s1 += d; s2 += d * d;
           acc[a][b][i] = 0.f;
         }
@@ -703,20 +742,46 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3x3_kernel(ConvGroup grp)
     if (vbid == 0 && p.tf_training && tid == 0 && p.tf_nbt) *p.tf_nbt += 1;
   }
   if constexpr (LT == 2) {
+    // Several replicas of the sums (Cin <= 128): they are fetched by nrep * Cin (<= 256 = NT) threads, one replica of one channel
+    // each, and meet in the LDS arena (idle until the first write_lds; the barrier at the top of the loop orders the reads below
+    // before it): two 16-byte loads per thread, requested together with the channel's mean / invstd / gamma / beta - still ONE
+    // memory round trip. fx_totals' sixteen loads per channel thread are 64 registers next to the first tile's staging loads in
+    // flight, which was the register peak of these kernels. (Integer sums: exact in any order.)
     const int nrep = bn_sum_replicas(p.Cin);
-    for (int c = tid; c < p.Cin; c += NT) {
-      const float mean = p.tf_save[c], istd = p.tf_save[p.Cin + c];
-      const float sc = p.tf_gamma[c] * istd;
-      double t1, t2;
-      fx_totals(p.tf_fx, p.Cin, nrep, c, t1, t2);
+    auto finish = [&](int c, float mean, float istd, float gam, float bet, const fx2_t& q0, const fx2_t& q1) {
+      const float sc = gam * istd;
+      const double t1 = fx_value(q0[0], q0[1]), t2 = fx_value(q1[0], q1[1]);
       float A, B;
       bn_bwd_AB(mean, istd, sc, (float)(t1 / (double)p.M), (float)(t2 / (double)p.M), A, B);
-      s_coef[c] = sc; s_coef[p.Cin + c] = __builtin_fmaf(-mean, sc, p.tf_beta[c]); s_coef[2 * p.Cin + c] = A; s_coef[3 * p.Cin + c] = B;
+      s_coef[c] = sc; s_coef[p.Cin + c] = __builtin_fmaf(-mean, sc, bet); s_coef[2 * p.Cin + c] = A; s_coef[3 * p.Cin + c] = B;
       if (vbid == 0) {
         // d beta = sum dz, d gamma = sum dz * xhat; the conv bias in front of a BatchNorm has gradient sum(dy) == 0
         if (p.tf_dbeta) p.tf_dbeta[c] = (float)t1;
         if (p.tf_dgamma) p.tf_dgamma[c] = (float)t2;
         if (p.tf_dbias) p.tf_dbias[c] = 0.f;
+      }
+    };
+    if (nrep > 1) {
+      fx2_t* const s_fx = reinterpret_cast<fx2_t*>(s_buf);   // [nrep][Cin][2]
+      const bool own = tid < p.Cin;                          // this thread finishes channel tid
+      float mean = 0.f, istd = 0.f, gam = 0.f, bet = 0.f;
+      if (own) { mean = p.tf_save[tid]; istd = p.tf_save[p.Cin + tid]; gam = p.tf_gamma[tid]; bet = p.tf_beta[tid]; }
+      if (tid < nrep * p.Cin) {
+        const int rr = tid / p.Cin, c = tid - rr * p.Cin;
+#pragma unroll
+        for (int v = 0; v < 2; ++v) s_fx[tid * 2 + v] = *reinterpret_cast<const fx2_t*>(p.tf_fx + ((size_t)(rr * 2 + v) * p.Cin + c) * NUNET_FX_WORDS);
+      }
+      __syncthreads();
+      if (own) {
+        fx2_t q0 = s_fx[tid * 2], q1 = s_fx[tid * 2 + 1];
+        for (int rr = 1; rr < nrep; ++rr) { q0 += s_fx[(rr * p.Cin + tid) * 2]; q1 += s_fx[(rr * p.Cin + tid) * 2 + 1]; }
+        finish(tid, mean, istd, gam, bet, q0, q1);
+      }
+    } else {
+      for (int c = tid; c < p.Cin; c += NT) {
+        const fx2_t q0 = *reinterpret_cast<const fx2_t*>(p.tf_fx + (size_t)c * NUNET_FX_WORDS);
+        const fx2_t q1 = *reinterpret_cast<const fx2_t*>(p.tf_fx + (size_t)(p.Cin + c) * NUNET_FX_WORDS);
+        finish(c, p.tf_save[c], p.tf_save[p.Cin + c], p.tf_gamma[c], p.tf_beta[c], q0, q1);
       }
     }
   }
@@ -916,6 +981,22 @@ static void launch_conv_lt(int lt, unsigned grid, size_t dyn, hipStream_t st, co
   else NUNET_LAUNCH((conv3x3_kernel<T, WM, WN, SM, SN, SK, BNR, 0>), dim3(grid), dim3(C::NT), dyn, st, g);
 }
 
+// The instantiation a launch takes - K-split (its kernel never carries the BNR epilogue: the finalize kernel does), BNR, LT -
+// as seen by the host: its residency promise (conv_wg_per_cu) and its entry point (nunet_conv_kernel_attrs)
+struct ConvKernelRef { int wg_per_cu; const void* fn; };
+template <typename T, int WM, int WN, int SM, int SN, bool SK, bool BNR>
+static ConvKernelRef conv_kernel_ref_lt(int lt) {
+  if (lt == 1) return {conv_wg_per_cu<T, WM, WN, SM, SN, SK, BNR, 1>(), (const void*)conv3x3_kernel<T, WM, WN, SM, SN, SK, BNR, 1>};
+  if (lt == 2) return {conv_wg_per_cu<T, WM, WN, SM, SN, SK, BNR, 2>(), (const void*)conv3x3_kernel<T, WM, WN, SM, SN, SK, BNR, 2>};
+  return {conv_wg_per_cu<T, WM, WN, SM, SN, SK, BNR, 0>(), (const void*)conv3x3_kernel<T, WM, WN, SM, SN, SK, BNR, 0>};
+}
+template <typename T, int WM, int WN, int SM, int SN>
+static ConvKernelRef conv_kernel_ref(bool sk, bool bnr, int lt) {
+  if (sk) return conv_kernel_ref_lt<T, WM, WN, SM, SN, true, false>(lt);
+  if (bnr) return conv_kernel_ref_lt<T, WM, WN, SM, SN, false, true>(lt);
+  return conv_kernel_ref_lt<T, WM, WN, SM, SN, false, false>(lt);
+}
+
 // everything a launch of one problem needs, for one tile configuration
 struct ConvSetup { ConvP p; long grid; long per_cu; size_t dyn; bool bnr; int lt; double flops, bytes; };
 template <typename T, int WM, int WN, int SM, int SN>
@@ -970,6 +1051,9 @@ static void conv_setup(const nunet_conv_desc* d, ConvSetup& S) {
   long per_cu = (long)(160 * 1024 / lds_bytes);
   if (per_cu < 1) per_cu = 1;
   if (per_cu > 2048 / C::NT) per_cu = 2048 / C::NT;
+  // ... and no more than the instantiation's registers admit (conv_wg_per_cu, the kernel's own __launch_bounds__)
+  const long by_regs = conv_kernel_ref<T, WM, WN, SM, SN>(p.S > 1, bnr, lt).wg_per_cu;
+  if (per_cu > by_regs) per_cu = by_regs;
   S.per_cu = per_cu;
   const long resident = 256 * per_cu;
   const long rounds = (items + resident - 1) / resident;
@@ -1047,6 +1131,10 @@ static int conv_cfg_of(const nunet_conv_desc* d) {
   //  level-0 conv1 -13 %, conv2 -3 %)
   //  (re-measured after the XCD remap, 96x96 bs16: the plain / BN-forward Cout = 64 convs of level 1 - 36864 pixels - are 8 % faster
   //   on the small tile as well: conv1 21.5 -> 19.7, conv2 14.1 -> 12.8 us; their input-gradient convs are not: 20.7 -> 32.6)
+  //  (round 4, 96x96 bs16, after the BN-backward kernels' register diet: level-0 dgrad2 - 32 -> 32, ONE Cout tile, so no transform is
+  //   repeated - is 20.8 us on the 128 x 32 tile against 24.9 on 256 x 32 in isolation, but the step is not faster with it: 9476
+  //   against 9516 img/s, four alternating runs each, every run of it below its neighbour (profiles/r04_summary.md, 3). It would
+  //   also regroup the fp32 partial sums of the fused BatchNorm reduce, i.e. change the step's results in the last bits. Not taken.)
   const bool small = items_std < 256 || (cout == 32 && d->in_tf != NUNET_TF_BN_RELU_BWD && px < (1L << 20)) ||
                      (cout == 64 && d->in_tf != NUNET_TF_BN_RELU_BWD && px < (1L << 16));
   if (small) return 0;
@@ -1133,6 +1221,37 @@ extern "C" int nunet_conv3x3_launch_info(const nunet_conv_desc* d, nunet_conv_la
   const int rc = conv_check(d, false);
   if (rc) return rc;
   return NUNET_DISPATCH(d->dtype, conv_info, d, out);
+}
+
+// Diagnostic (include/nunet_diag.h): what the runtime says about the kernel instantiation launch_conv would pick. No launch.
+template <typename T, int WM, int WN, int SM, int SN>
+static int conv_attrs_cfg(const nunet_conv_desc* d, nunet_conv_kernel_attrs_t* o) {
+  typedef ConvCfg<T, WM, WN, SM, SN> C;
+  ConvSetup S;
+  conv_setup<T, WM, WN, SM, SN>(d, S);
+  const ConvKernelRef k = conv_kernel_ref<T, WM, WN, SM, SN>(S.p.S > 1, S.bnr, S.lt);
+  hipFuncAttributes a;
+  hipError_t e = hipFuncGetAttributes(&a, k.fn);
+  NUNET_REQUIRE(e == hipSuccess, "conv3x3 kernel attrs: hipFuncGetAttributes: %s", hipGetErrorString(e));
+  int occ = 0;
+  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k.fn, C::NT, S.dyn);
+  NUNET_REQUIRE(e == hipSuccess, "conv3x3 kernel attrs: hipOccupancyMaxActiveBlocksPerMultiprocessor: %s", hipGetErrorString(e));
+  o->numRegs = a.numRegs; o->localSizeBytes = (int32_t)a.localSizeBytes; o->sharedSizeBytes = (int32_t)a.sharedSizeBytes;
+  o->blockSize = C::NT; o->dynLdsBytes = (int32_t)S.dyn; o->occupancy = occ; o->wg_per_cu = k.wg_per_cu;
+  return NUNET_OK;
+}
+template <typename T> static int conv_attrs(const nunet_conv_desc* d, nunet_conv_kernel_attrs_t* o) {
+  const int cfg = conv_cfg_of(d);
+  if (cfg == 0) return conv_attrs_cfg<T, 4, 1, 1, 1>(d, o);
+  if (cfg == 1) return conv_attrs_cfg<T, 2, 2, 2, 1>(d, o);
+  if (cfg == 3) return conv_attrs_cfg<T, 4, 1, 2, 2>(d, o);
+  return conv_attrs_cfg<T, 4, 1, 2, 1>(d, o);
+}
+extern "C" int nunet_conv_kernel_attrs(const nunet_conv_desc* d, nunet_conv_kernel_attrs_t* out) {
+  NUNET_REQUIRE(out, "conv3x3 kernel attrs: null output");
+  const int rc = conv_check(d, false);
+  if (rc) return rc;
+  return NUNET_DISPATCH(d->dtype, conv_attrs, d, out);
 }
 
 // ---------------------------------------------------------------------------
