@@ -16,7 +16,6 @@
 #include <map>
 #include <string>
 #include <vector>
-#include <string>
 #include <stdarg.h>
 
 #include "common.h"
@@ -28,60 +27,129 @@ static const int NBF[5] = {32, 64, 128, 256, 512};  // archs1.py:78
 // ---------------------------------------------------------------------------
 #define MAXENT 40
 #define HEAD_SLABS 256
-struct PackEnt { long long src, wf, wd; int cout, cin, cinpad, pad_; };
+struct PackEnt { long long src, wf, wd; int cout, cin, cinpad; };
 struct PackTab { int n; int ntiles; PackEnt e[MAXENT]; int tile0[MAXENT + 1]; };
-struct UnpackEnt { long long src, dst; int cout, cin, cinpad, taps, nvec, nslab; unsigned inv_taps, inv_cin; int fast; };   // inv_*: dec_inv(), fast: 32-bit decode is exact   // nslab > 1: sum of partial slabs (heads)
+struct UnpackEnt { long long src, dst; int cout, cin, cinpad, taps, nvec, nslab; };   // nslab > 1: sum of partial slabs (heads)
 struct UnpackTab { int n; int accumulate; UnpackEnt e[MAXENT]; };
 
-// One block per (layer, 32 Cout x 32 Cin tile): the OIHW rows of a tile are contiguous runs of
-// 32*9 floats (coalesced loads into LDS); both packed layouts are then written as contiguous
-// 32-element rows. PackTab carries a prefix sum of tiles per entry for the block -> tile map.
-template <typename T>
-__global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ params, T* __restrict__ arena, PackTab tab) {
-  __shared__ float s_t[32][32 * 9 + 1];
-  int e = 0;
-  while (e + 1 < tab.n && (int)blockIdx.x >= tab.tile0[e + 1]) ++e;
-  const PackEnt en = tab.e[e];
-  const int t = blockIdx.x - tab.tile0[e];
-  const int nci = (en.cinpad + 31) / 32;
-  const int co0 = (t / nci) * 32, ci0 = (t % nci) * 32;
-  const float* w = params + en.src;
-  const int cw = min(32, en.cin - ci0);            // real input channels in this tile (<= 0: pure padding)
-  const int rw = min(32, en.cout - co0);
-  // full tiles (all but the first layer's): 16-byte loads and 16-byte stores (8 packed elements); the scalar
-  // form below keeps the ragged ones
-  constexpr int EPV = Tr<T>::EPV;
-  const float* wrow = w + ((long long)co0 * en.cin + ci0) * 9;
-  const bool vload = rw == 32 && cw == 32 && en.cin % 4 == 0 && ((uintptr_t)wrow & 15) == 0;
-  if (vload) {
+// ---------------------------------------------------------------------------------------------------------
+// The walk every weight-layout kernel below shares. One block per (layer, 32 Cout x 32 Cin tile); PackTab carries a
+// prefix sum of tiles per entry for the block -> tile map. A tile lives in LDS as s[co_local][ci_local * 9 + tap]:
+// its OIHW rows (parameters, flat gradients) are contiguous runs of 32 * 9 floats, the native gradient scratch
+// [tap][co][cinpad] and both packed layouts are contiguous along ci (wf) or co (wd). The unpack kernels' blocks past
+// the last tile own one UnpackTab entry each (tail_entry); update_kernel numbers its head blocks there instead.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int TILE_LD = 32 * 9 + 1;
+struct Tile { int e, co0, ci0, cw, rw; };   // table entry, tile origin; cw / rw: real input channels / output rows in the tile (cw <= 0: pure padding)
+
+__device__ __forceinline__ Tile tile_of(const PackTab& tab, int bid) {
+  Tile t;
+  t.e = 0;
+  while (t.e + 1 < tab.n && bid >= tab.tile0[t.e + 1]) ++t.e;
+  const int i = bid - tab.tile0[t.e];
+  const int cout = tab.e[t.e].cout, cin = tab.e[t.e].cin, nci = (tab.e[t.e].cinpad + 31) / 32;
+  t.co0 = (i / nci) * 32; t.ci0 = (i % nci) * 32;
+  t.cw = min(32, cin - t.ci0); t.rw = min(32, cout - t.co0);
+  return t;
+}
+
+// 1x1 head: [nslab][tot] partial slabs (already OIHW order, tot <= 8 classes * 33 = 264), summed by one block of B threads in a
+// fixed order: B / ne threads share an element's slabs (a single thread walking all 256 slabs is a chain of 256
+// dependent-latency loads: that loop alone made the earlier fused kernels 100 us long), thread (part, e) adds slabs part,
+// part + parts, ... in order, the parts meet in LDS (B floats) and are added in order q = 0 .. parts - 1. The owning thread
+// calls f(element, sum). The order depends on B: 256 and 512 give different bits.
+template <int B, typename F>
+__device__ __forceinline__ void head_slab_sum(const float* __restrict__ dw, int tot, int nslab, float* lds, F f) {
+  for (int e0 = 0; e0 < tot; e0 += B) {
+    const int ne = min(B, tot - e0);
+    const int parts = B / ne;                     // threads per element
+    const int e = threadIdx.x % ne, part = threadIdx.x / ne;
+    float v = 0.f;
+    if (part < parts) {
+#pragma unroll 8
+      for (int sl = part; sl < nslab; sl += parts) v += dw[(long long)sl * tot + e0 + e];
+    }
+    lds[threadIdx.x] = part < parts ? v : 0.f;
+    __syncthreads();
+    if ((int)threadIdx.x < ne) {
+      float t = 0.f;
+      for (int q = 0; q < parts; ++q) t += lds[q * ne + threadIdx.x];
+      f(e0 + (int)threadIdx.x, t);
+    }
+    __syncthreads();
+  }
+}
+
+// A 256-thread block past the last tile: the slab sum of a 1x1 head, or a conv layer's bias / BatchNorm vectors (they follow the
+// weights in the scratch entry and in the flat arenas). f(index relative to the entry's dst, value).
+template <typename F>
+__device__ __forceinline__ void tail_entry(const UnpackEnt& en, const float* __restrict__ scratch, float* lds, F f) {
+  const float* dw = scratch + en.src;
+  const int nw = en.cout * en.cin * en.taps;
+  if (en.nslab > 1) {
+    head_slab_sum<256>(dw, nw + en.nvec * en.cout, en.nslab, lds, f);
+    return;
+  }
+  const float* vsrc = dw + (long long)en.taps * en.cout * en.cinpad;
+  for (int i = threadIdx.x; i < en.nvec * en.cout; i += blockDim.x) f(nw + i, vsrc[i]);
+}
+
+// scratch dw[tap][co][cinpad] -> LDS tile: 16-byte loads along ci for a full tile (an element-wise gather touches nine
+// 128-byte lines per wave load); a ragged tile element-wise, entries outside rw x cw left unwritten
+__device__ __forceinline__ void gather_scratch_tile(float (*s)[TILE_LD], const float* __restrict__ dw, const PackEnt& en, const Tile& t) {
+  if (t.rw == 32 && t.cw == 32 && en.cinpad % 4 == 0 && ((uintptr_t)dw & 15) == 0) {
+    for (int i = threadIdx.x; i < 9 * 32 * 8; i += blockDim.x) {
+      const int c4 = i & 7, ro = (i >> 3) & 31, tap = i >> 8;
+      const f32x4 v = *reinterpret_cast<const f32x4*>(dw + ((long long)tap * en.cout + t.co0 + ro) * en.cinpad + t.ci0 + c4 * 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[ro][(c4 * 4 + j) * 9 + tap] = v[j];
+    }
+  } else {
+    for (int i = threadIdx.x; i < 9 * 32 * 32; i += blockDim.x) {
+      const int ci = i & 31, ro = (i >> 5) & 31, tap = i >> 10;
+      if (ro < t.rw && ci < t.cw) s[ro][ci * 9 + tap] = dw[((long long)tap * en.cout + t.co0 + ro) * en.cinpad + t.ci0 + ci];
+    }
+  }
+}
+
+// OIHW rows w[co][cin][9] -> LDS tile: 16-byte loads for a full tile; a ragged one (the first layer's) element-wise, zero
+// outside rw x cw (the ci >= cin columns are written to wf as zeros)
+__device__ __forceinline__ void load_oihw_tile(float (*s)[TILE_LD], const float* __restrict__ w, const PackEnt& en, const Tile& t) {
+  const float* wrow = w + ((long long)t.co0 * en.cin + t.ci0) * 9;
+  if (t.rw == 32 && t.cw == 32 && en.cin % 4 == 0 && ((uintptr_t)wrow & 15) == 0) {
     for (int i = threadIdx.x; i < 32 * 72; i += blockDim.x) {
       const int ro = i / 72, k4 = i - ro * 72;
       const f32x4 v = *reinterpret_cast<const f32x4*>(wrow + (long long)ro * en.cin * 9 + k4 * 4);
-      float* d = &s_t[ro][k4 * 4];
+      float* d = &s[ro][k4 * 4];
       d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
     }
   } else {
     for (int i = threadIdx.x; i < 32 * 288; i += blockDim.x) {
       const int ro = i / 288, k = i - ro * 288;      // k = ci_local*9 + tap
       float v = 0.f;
-      if (ro < rw && k < cw * 9) v = w[((long long)(co0 + ro) * en.cin + ci0) * 9 + k];
-      s_t[ro][k] = v;
+      if (ro < t.rw && k < t.cw * 9) v = wrow[(long long)ro * en.cin * 9 + k];
+      s[ro][k] = v;
     }
   }
-  __syncthreads();
+}
+
+// LDS tile -> both packed layouts of T, wf[tap][co][cinpad] and (en.wd >= 0) the flipped / transposed wd[8 - tap][ci][co]:
+// 16-byte stores (8 packed elements per thread) where rows and alignment allow, element-wise otherwise
+template <typename T>
+__device__ __forceinline__ void store_packed_tile(const float (*s)[TILE_LD], T* __restrict__ arena, const PackEnt& en, const Tile& t) {
+  constexpr int EPV = Tr<T>::EPV;
   T* wf = arena + en.wf;
   T* wd = en.wd >= 0 ? arena + en.wd : nullptr;
-  const bool vst = rw == 32 && en.cinpad % 8 == 0 && en.cout % 8 == 0 && ((uintptr_t)wf & 15) == 0 && ((uintptr_t)wd & 15) == 0;
-  if (vst) {
+  if (t.rw == 32 && en.cinpad % 8 == 0 && en.cout % 8 == 0 && ((uintptr_t)wf & 15) == 0 && ((uintptr_t)wd & 15) == 0) {
     for (int i = threadIdx.x; i < 9 * 32 * 4; i += blockDim.x) {    // wf[tap][co][ci], ci fastest: 8 ci per thread
       const int g = i & 3, ro = (i >> 2) & 31, tap = i >> 7;
-      if (ci0 + g * 8 < en.cinpad) {
-        T* q = wf + ((long long)tap * en.cout + co0 + ro) * en.cinpad + ci0 + g * 8;
+      if (t.ci0 + g * 8 < en.cinpad) {
+        T* q = wf + ((long long)tap * en.cout + t.co0 + ro) * en.cinpad + t.ci0 + g * 8;
 #pragma unroll
         for (int h = 0; h < 8 / EPV; ++h) {
           Vec16<T> o;
 #pragma unroll
-          for (int e = 0; e < EPV; ++e) o.set(e, s_t[ro][(g * 8 + h * EPV + e) * 9 + tap]);
+          for (int e = 0; e < EPV; ++e) o.set(e, s[ro][(g * 8 + h * EPV + e) * 9 + tap]);
           st16(q + h * EPV, o);
         }
       }
@@ -89,13 +157,13 @@ __global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ par
     if (wd) {
       for (int i = threadIdx.x; i < 9 * 32 * 4; i += blockDim.x) {  // wd[8-tap][ci][co], co fastest: 8 co per thread
         const int g = i & 3, ci = (i >> 2) & 31, tap = i >> 7;
-        if (ci < cw) {
-          T* q = wd + ((long long)(8 - tap) * en.cin + ci0 + ci) * en.cout + co0 + g * 8;
+        if (ci < t.cw) {
+          T* q = wd + ((long long)(8 - tap) * en.cin + t.ci0 + ci) * en.cout + t.co0 + g * 8;
 #pragma unroll
           for (int h = 0; h < 8 / EPV; ++h) {
             Vec16<T> o;
 #pragma unroll
-            for (int e = 0; e < EPV; ++e) o.set(e, s_t[g * 8 + h * EPV + e][ci * 9 + tap]);
+            for (int e = 0; e < EPV; ++e) o.set(e, s[g * 8 + h * EPV + e][ci * 9 + tap]);
             st16(q + h * EPV, o);
           }
         }
@@ -105,134 +173,46 @@ __global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ par
   }
   for (int i = threadIdx.x; i < 9 * 32 * 32; i += blockDim.x) {   // wf[tap][co][ci], ci fastest
     const int ci = i & 31, ro = (i >> 5) & 31, tap = i >> 10;
-    if (ro < rw && ci0 + ci < en.cinpad)
-      wf[((long long)tap * en.cout + co0 + ro) * en.cinpad + ci0 + ci] = from_f32<T>(s_t[ro][ci * 9 + tap]);
+    if (ro < t.rw && t.ci0 + ci < en.cinpad)
+      wf[((long long)tap * en.cout + t.co0 + ro) * en.cinpad + t.ci0 + ci] = from_f32<T>(s[ro][ci * 9 + tap]);
   }
   if (wd) {
     for (int i = threadIdx.x; i < 9 * 32 * 32; i += blockDim.x) { // wd[8-tap][ci][co], co fastest
       const int ro = i & 31, ci = (i >> 5) & 31, tap = i >> 10;
-      if (ro < rw && ci < cw)
-        wd[((long long)(8 - tap) * en.cin + ci0 + ci) * en.cout + co0 + ro] = from_f32<T>(s_t[ro][ci * 9 + tap]);
+      if (ro < t.rw && ci < t.cw)
+        wd[((long long)(8 - tap) * en.cin + t.ci0 + ci) * en.cout + t.co0 + ro] = from_f32<T>(s[ro][ci * 9 + tap]);
     }
   }
 }
 
-__global__ __launch_bounds__(256) void unpack_kernel(const float* __restrict__ scratch, float* __restrict__ grads, UnpackTab tab) {
-  const UnpackEnt en = tab.e[blockIdx.y];
-  const float* dw = scratch + en.src;
-  float* g = grads + en.dst;
-  const long long nw = (long long)en.cout * en.cin * en.taps;
-  const long long total = nw + (long long)en.nvec * en.cout;
-  if (en.nslab > 1) {
-    // 1x1 head: [nslab][cout*cin + cout] partial slabs (already OIHW order), summed by one block:
-    // thread = slab, wave shuffles + LDS across the 4 waves, a handful of elements in total
-    if (blockIdx.x != 0) return;
-    __shared__ float s_p[256];
-    const int tot = (int)total;                       // <= HEAD classes * 33 = 264
-    for (int e0 = 0; e0 < tot; e0 += 256) {
-      const int ne = min(256, tot - e0);
-      const int parts = 256 / ne;                     // threads per element
-      const int e = threadIdx.x % ne, part = threadIdx.x / ne;
-      float v = 0.f;
-      if (part < parts) {
-#pragma unroll 8
-        for (int sl = part; sl < en.nslab; sl += parts) v += dw[(long long)sl * total + e0 + e];
-      }
-      s_p[threadIdx.x] = part < parts ? v : 0.f;
-      __syncthreads();
-      if ((int)threadIdx.x < ne) {
-        float t = 0.f;
-        for (int q = 0; q < parts; ++q) t += s_p[q * ne + threadIdx.x];
-        g[e0 + threadIdx.x] = tab.accumulate ? g[e0 + threadIdx.x] + t : t;
-      }
-      __syncthreads();
-    }
-    return;
-  }
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    float v;
-    if (i < nw) {
-      int tap, ci, co;
-      if (en.fast) {   // (two 64-bit divisions per element were most of this kernel's instructions)
-        const int ii = (int)i, t = dec_div(ii, en.inv_taps);
-        tap = ii - t * en.taps; co = dec_div(t, en.inv_cin); ci = t - co * en.cin;
-      } else {
-        tap = (int)(i % en.taps);
-        const long long t = i / en.taps;
-        ci = (int)(t % en.cin); co = (int)(t / en.cin);
-      }
-      v = dw[((long long)tap * en.cout + co) * en.cinpad + ci];
-    } else {
-      v = dw[(long long)en.taps * en.cout * en.cinpad + (i - nw)];
-    }
-    g[i] = tab.accumulate ? g[i] + v : v;
-  }
+// fp32 parameters -> both packed layouts
+template <typename T>
+__global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ params, T* __restrict__ arena, PackTab tab) {
+  __shared__ float s_t[32][TILE_LD];
+  const Tile t = tile_of(tab, blockIdx.x);
+  const PackEnt en = tab.e[t.e];
+  load_oihw_tile(s_t, params + en.src, en, t);
+  __syncthreads();
+  store_packed_tile(s_t, arena, en, t);
 }
 
-// The same gather as unpack_kernel, tiled like pack_kernel: one block per (layer, 32 Cout x 32 Cin tile) moves the
-// tile's [tap][co][ci] gradients through LDS with 16-byte loads along ci and writes the OIHW rows as 16-byte runs
-// (unpack_kernel's element-wise gather touches nine 128-byte lines per wave load). Blocks past the last tile own one
-// table entry each: its bias / BatchNorm vectors, or the slab sum of a 1x1 head.
+// Gradient scratch -> flat OIHW gradient arena (overwritten or accumulated into), the OIHW rows written as 16-byte runs
 __global__ __launch_bounds__(256) void unpack_tiled_kernel(const float* __restrict__ scratch, float* __restrict__ grads, PackTab tab, UnpackTab ut) {
-  __shared__ float s_t[32][32 * 9 + 1];
+  __shared__ float s_t[32][TILE_LD];
   if ((int)blockIdx.x >= tab.ntiles) {
     const UnpackEnt en = ut.e[(int)blockIdx.x - tab.ntiles];
-    const float* dw = scratch + en.src;
     float* g = grads + en.dst;
-    const int nw = en.cout * en.cin * en.taps;
-    if (en.nslab > 1) {                                  // 1x1 head: <= 264 elements, slabs summed in fixed order
-      const int tot = nw + en.nvec * en.cout;
-      for (int e0 = 0; e0 < tot; e0 += 256) {
-        const int ne = min(256, tot - e0);
-        const int parts = 256 / ne;
-        const int e = threadIdx.x % ne, part = threadIdx.x / ne;
-        float v = 0.f;
-        if (part < parts) {
-#pragma unroll 8
-          for (int sl = part; sl < en.nslab; sl += parts) v += dw[(long long)sl * tot + e0 + e];
-        }
-        s_t[0][threadIdx.x] = part < parts ? v : 0.f;
-        __syncthreads();
-        if ((int)threadIdx.x < ne) {
-          float t = 0.f;
-          for (int q = 0; q < parts; ++q) t += s_t[0][q * ne + threadIdx.x];
-          g[e0 + threadIdx.x] = ut.accumulate ? g[e0 + threadIdx.x] + t : t;
-        }
-        __syncthreads();
-      }
-      return;
-    }
-    const float* vsrc = dw + (long long)en.taps * en.cout * en.cinpad;
-    for (int i = threadIdx.x; i < en.nvec * en.cout; i += blockDim.x) g[nw + i] = ut.accumulate ? g[nw + i] + vsrc[i] : vsrc[i];
+    tail_entry(en, scratch, &s_t[0][0], [&](int i, float v) { g[i] = ut.accumulate ? g[i] + v : v; });
     return;
   }
-  int e = 0;
-  while (e + 1 < tab.n && (int)blockIdx.x >= tab.tile0[e + 1]) ++e;
-  const PackEnt en = tab.e[e];
-  const UnpackEnt ue = ut.e[e];
-  const int t = blockIdx.x - tab.tile0[e];
-  const int nci = (en.cinpad + 31) / 32;
-  const int co0 = (t / nci) * 32, ci0 = (t % nci) * 32;
-  const int cw = min(32, en.cin - ci0), rw = min(32, en.cout - co0);
-  if (cw <= 0) return;                                   // pure padding tile
-  const float* dw = scratch + ue.src;
-  float* grow = grads + ue.dst + ((long long)co0 * en.cin + ci0) * 9;
-  const bool full = rw == 32 && cw == 32;
-  if (full && en.cinpad % 4 == 0 && ((uintptr_t)dw & 15) == 0) {
-    for (int i = threadIdx.x; i < 9 * 32 * 8; i += blockDim.x) {
-      const int c4 = i & 7, ro = (i >> 3) & 31, tap = i >> 8;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(dw + ((long long)tap * en.cout + co0 + ro) * en.cinpad + ci0 + c4 * 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s_t[ro][(c4 * 4 + j) * 9 + tap] = v[j];
-    }
-  } else {
-    for (int i = threadIdx.x; i < 9 * 32 * 32; i += blockDim.x) {
-      const int ci = i & 31, ro = (i >> 5) & 31, tap = i >> 10;
-      if (ro < rw && ci < cw) s_t[ro][ci * 9 + tap] = dw[((long long)tap * en.cout + co0 + ro) * en.cinpad + ci0 + ci];
-    }
-  }
+  const Tile t = tile_of(tab, blockIdx.x);
+  if (t.cw <= 0) return;                                 // pure padding tile
+  const PackEnt en = tab.e[t.e];
+  const UnpackEnt ue = ut.e[t.e];
+  float* grow = grads + ue.dst + ((long long)t.co0 * en.cin + t.ci0) * 9;
+  gather_scratch_tile(s_t, scratch + ue.src, en, t);
   __syncthreads();
-  if (full && en.cin % 4 == 0 && ((uintptr_t)grow & 15) == 0) {
+  if (t.rw == 32 && t.cw == 32 && en.cin % 4 == 0 && ((uintptr_t)grow & 15) == 0) {
     for (int i = threadIdx.x; i < 32 * 72; i += blockDim.x) {
       const int ro = i / 72, k4 = i - ro * 72;
       f32x4* q = reinterpret_cast<f32x4*>(grow + (long long)ro * en.cin * 9 + k4 * 4);
@@ -244,7 +224,7 @@ __global__ __launch_bounds__(256) void unpack_tiled_kernel(const float* __restri
   } else {
     for (int i = threadIdx.x; i < 32 * 288; i += blockDim.x) {
       const int ro = i / 288, k = i - ro * 288;
-      if (ro < rw && k < cw * 9) {
+      if (ro < t.rw && k < t.cw * 9) {
         float* q = grow + (long long)ro * en.cin * 9 + k;
         *q = ut.accumulate ? *q + s_t[ro][k] : s_t[ro][k];
       }
@@ -252,87 +232,52 @@ __global__ __launch_bounds__(256) void unpack_tiled_kernel(const float* __restri
   }
 }
 
-
 // ---------------------------------------------------------------------------------------------------------
-// Fused optimiser step: native-layout gradient scratch -> SGD(momentum, weight decay, nesterov) on the fp32 master
-// parameters -> both packed 16-bit weight layouts of the NEXT forward/backward, one launch (replaces
-// unpack_kernel + sgd_kernel + pack_kernel, which ran one after the other with nothing to overlap them).
-// Same block -> (layer, 32 Cout x 32 Cin tile) map as pack_kernel; the tile's gradients arrive [tap][co][ci]
-// (coalesced along ci) and meet the OIHW parameters / momentum through LDS. The block of input-channel tile 0
-// also steps the layer's conv bias and BatchNorm gamma / beta; blocks past the last tile own the 1x1 heads
-// (sum of their gradient slabs, then the same step). torch.optim.SGD semantics (reference trains.py:229-231).
+// Fused optimiser step: native-layout gradient scratch -> optimiser step on the fp32 master parameters -> both packed
+// 16-bit weight layouts of the NEXT forward/backward, one launch (separate unpack, step and pack launches ran one after
+// the other with nothing to overlap them). The tile's gradients and its OIHW parameters meet in two LDS tiles; the
+// optimiser state is streamed from HBM. The block of input-channel tile 0 also steps the layer's conv bias and BatchNorm
+// gamma / beta; blocks past the last tile own the 1x1 heads (sum of their gradient slabs over 512 threads, then the same
+// step). torch.optim.SGD semantics (reference trains.py:229-231).
 // ---------------------------------------------------------------------------------------------------------
 struct UpdP { float* params; const float* scratch; float* grads; float gscale; int nconv;
               int bid_off; };   // first block's index in the whole-model block numbering (a launch may cover one VGGBlock's tiles, or the heads)
 
+// one element of the fused kernels outside the LDS tiles, at flat index idx: the scaled gradient to the flat arena when the
+// caller wants it, then the step unless loss scaling skipped it (live false)
+template <typename O>
+__device__ __forceinline__ void step_elem(const UpdP& u, const O& o, bool live, float gs, long long idx, float g) {
+  g *= gs;
+  if (u.grads) u.grads[idx] = g;
+  if (live) u.params[idx] = opt_elem(o, u.params[idx], g, idx);
+}
+
 template <typename T, typename O>
 __global__ __launch_bounds__(512) void update_kernel(UpdP u, O o, T* __restrict__ arena, PackTab tab, UnpackTab ut) {
-  __shared__ float s_t[32][32 * 9 + 1];
-  __shared__ float s_g[32][32 * 9 + 1];
+  __shared__ float s_t[32][TILE_LD];
+  __shared__ float s_g[32][TILE_LD];
   float gs = u.gscale;
   const bool live = o.begin(gs);   // false: a step skipped by loss scaling, which stores the unscaled gradients only
   if (!live && !u.grads) return;
   const int bid = (int)blockIdx.x + u.bid_off;
   if (bid >= tab.ntiles) {
-    // ---- 1x1 head: sum the gradient slabs (fixed order), then the step; <= 264 elements
     const UnpackEnt en = ut.e[u.nconv + bid - tab.ntiles];
-    const float* dw = u.scratch + en.src;
-    const int tot = en.cout * en.cin * en.taps + en.nvec * en.cout;
-    const int B = blockDim.x;     // B/ne threads share an element's slabs (see unpack_sgd_tiled_kernel), fixed order
-    for (int e0 = 0; e0 < tot; e0 += B) {
-      const int ne = min(B, tot - e0);
-      const int parts = B / ne;
-      const int el = threadIdx.x % ne, part = threadIdx.x / ne;
-      float v = 0.f;
-      if (part < parts) {
-#pragma unroll 8
-        for (int sl = part; sl < en.nslab; sl += parts) v += dw[(long long)sl * tot + e0 + el];
-      }
-      (&s_t[0][0])[threadIdx.x] = part < parts ? v : 0.f;
-      __syncthreads();
-      if ((int)threadIdx.x < ne) {
-        float g = 0.f;
-        for (int q = 0; q < parts; ++q) g += (&s_t[0][0])[q * ne + threadIdx.x];
-        g *= gs;
-        const long long idx = en.dst + e0 + threadIdx.x;
-        if (u.grads) u.grads[idx] = g;
-        if (live) u.params[idx] = opt_elem(o, u.params[idx], g, idx);
-      }
-      __syncthreads();
-    }
+    head_slab_sum<512>(u.scratch + en.src, en.cout * en.cin * en.taps + en.nvec * en.cout, en.nslab, &s_t[0][0],
+                       [&](int i, float g) { step_elem(u, o, live, gs, en.dst + i, g); });
     return;
   }
-  int e = 0;
-  while (e + 1 < tab.n && bid >= tab.tile0[e + 1]) ++e;
-  const PackEnt en = tab.e[e];
-  const UnpackEnt ue = ut.e[e];
-  const int t = bid - tab.tile0[e];
-  const int nci = (en.cinpad + 31) / 32;
-  const int co0 = (t / nci) * 32, ci0 = (t % nci) * 32;
-  const float* w = u.params + en.src;
+  const Tile t = tile_of(tab, bid);
+  const PackEnt en = tab.e[t.e];
+  const UnpackEnt ue = ut.e[t.e];
   const float* dw = u.scratch + ue.src;
-  const int cw = min(32, en.cin - ci0);            // real input channels in this tile (<= 0: pure padding)
-  const int rw = min(32, en.cout - co0);
-#pragma unroll 6
-  for (int i = threadIdx.x; i < 32 * 288; i += blockDim.x) {
-    const int ro = i / 288, k = i - ro * 288;      // k = ci_local*9 + tap
-    float v = 0.f;
-    if (ro < rw && k < cw * 9) v = w[((long long)(co0 + ro) * en.cin + ci0) * 9 + k];
-    s_t[ro][k] = v;
-  }
-#pragma unroll 6
-  for (int i = threadIdx.x; i < 9 * 32 * 32; i += blockDim.x) {   // scratch dw[tap][co][cinpad], ci fastest
-    const int ci = i & 31, ro = (i >> 5) & 31, tap = i >> 10;
-    float v = 0.f;
-    if (ro < rw && ci < cw) v = dw[((long long)tap * en.cout + co0 + ro) * en.cinpad + ci0 + ci];
-    s_g[ro][ci * 9 + tap] = v;
-  }
+  load_oihw_tile(s_t, u.params + en.src, en, t);
+  gather_scratch_tile(s_g, dw, en, t);
   __syncthreads();
 #pragma unroll 6
   for (int i = threadIdx.x; i < 32 * 288; i += blockDim.x) {
     const int ro = i / 288, k = i - ro * 288;
-    if (ro < rw && k < cw * 9) {
-      const long long idx = en.src + ((long long)(co0 + ro) * en.cin + ci0) * 9 + k;
+    if (ro < t.rw && k < t.cw * 9) {
+      const long long idx = en.src + ((long long)(t.co0 + ro) * en.cin + t.ci0) * 9 + k;
       const float g = s_g[ro][k] * gs;
       if (u.grads) u.grads[idx] = g;
       if (live) {
@@ -342,35 +287,18 @@ __global__ __launch_bounds__(512) void update_kernel(UpdP u, O o, T* __restrict_
       }
     }
   }
-  if (ci0 == 0) {
+  if (t.ci0 == 0) {
     // conv bias, BN gamma, BN beta of the output channels of this tile (they follow the weights in both arenas)
     const long long nw = (long long)en.cout * en.cin * 9;
-    for (int i = threadIdx.x; i < ue.nvec * rw; i += blockDim.x) {
-      const int v = i / rw, c = co0 + (i - v * rw);
+    for (int i = threadIdx.x; i < ue.nvec * t.rw; i += blockDim.x) {
+      const int v = i / t.rw, c = t.co0 + (i - v * t.rw);
       const long long idx = ue.dst + nw + (long long)v * en.cout + c;
-      const float g = dw[9LL * en.cout * en.cinpad + (long long)v * en.cout + c] * gs;
-      if (u.grads) u.grads[idx] = g;
-      if (live) u.params[idx] = opt_elem(o, u.params[idx], g, idx);
+      step_elem(u, o, live, gs, idx, dw[9LL * en.cout * en.cinpad + (long long)v * en.cout + c]);
     }
   }
   __syncthreads();
   if (!live) return;               // (uniform) the packed weights keep matching the unchanged parameters
-  T* wf = arena + en.wf;
-#pragma unroll 6
-  for (int i = threadIdx.x; i < 9 * 32 * 32; i += blockDim.x) {   // wf[tap][co][ci], ci fastest
-    const int ci = i & 31, ro = (i >> 5) & 31, tap = i >> 10;
-    if (ro < rw && ci0 + ci < en.cinpad)
-      wf[((long long)tap * en.cout + co0 + ro) * en.cinpad + ci0 + ci] = from_f32<T>(s_t[ro][ci * 9 + tap]);
-  }
-  if (en.wd >= 0) {
-    T* wd = arena + en.wd;
-#pragma unroll 6
-    for (int i = threadIdx.x; i < 9 * 32 * 32; i += blockDim.x) { // wd[8-tap][ci][co], co fastest
-      const int ro = i & 31, ci = (i >> 5) & 31, tap = i >> 10;
-      if (ro < rw && ci < cw)
-        wd[((long long)(8 - tap) * en.cin + ci0 + ci) * en.cout + co0 + ro] = from_f32<T>(s_t[ro][ci * 9 + tap]);
-    }
-  }
+  store_packed_tile(s_t, arena, en, t);
 }
 
 // block -> tile prefix table of a PackTab: entry i owns blocks [tile0[i], tile0[i + 1]) of the tile kernels, one per 32 x 32
@@ -407,14 +335,13 @@ extern "C" int nunet_pack_weights(const float* w, int32_t cout, int32_t cin, int
 
 extern "C" int nunet_unpack_wgrad(const float* dw, int32_t cout, int32_t cin, int32_t cin_pad, float* g, int32_t accumulate, nunet_stream_t s) {
   NUNET_REQUIRE(dw && g && cout > 0 && cin > 0 && cin_pad >= cin, "unpack_wgrad: bad args");
-  UnpackTab tab; memset(&tab, 0, sizeof(tab));
-  tab.n = 1; tab.accumulate = accumulate;
-  tab.e[0].src = 0; tab.e[0].dst = 0; tab.e[0].cout = cout; tab.e[0].cin = cin; tab.e[0].cinpad = cin_pad; tab.e[0].taps = 9; tab.e[0].nvec = 0; tab.e[0].nslab = 1;
-  tab.e[0].inv_taps = dec_inv(9); tab.e[0].inv_cin = dec_inv(cin); tab.e[0].fast = 9LL * cout * cin * (cin > 9 ? cin : 9) < (1ll << 32);
-  int gx = (int)ceil_div64(9LL * cout * cin, 256 * 4);
-  if (gx > 512) gx = 512;
-  if (gx < 1) gx = 1;
-  NUNET_LAUNCH(unpack_kernel, dim3(gx, 1), dim3(256), 0, (hipStream_t)s, dw, g, tab);
+  PackTab tab; memset(&tab, 0, sizeof(tab));
+  UnpackTab ut; memset(&ut, 0, sizeof(ut));
+  tab.n = ut.n = 1; ut.accumulate = accumulate;
+  tab.e[0].wd = -1; tab.e[0].cout = cout; tab.e[0].cin = cin; tab.e[0].cinpad = cin_pad;
+  ut.e[0].cout = cout; ut.e[0].cin = cin; ut.e[0].cinpad = cin_pad; ut.e[0].taps = 9; ut.e[0].nvec = 0; ut.e[0].nslab = 1;
+  pack_tiles(tab);
+  NUNET_LAUNCH(unpack_tiled_kernel, dim3(tab.ntiles), dim3(256), 0, (hipStream_t)s, dw, g, tab, ut);   // no vectors: no tail block
   return nunet_check_launch("unpack_wgrad");
 }
 
@@ -493,7 +420,7 @@ struct nunet_plan {
   size_t off_img;
   size_t X[5], GX[5];
   size_t off_dy[16][2], off_da1[16], off_gup[16], off_gpin[16];   // per-BLOCK backward scratch (dY ping-pong), so blocks of one level can run on different lanes
-  size_t off_sk[16]; long long sk_floats[16];   // per-BLOCK fp32 K-split slabs (blocks of the grid-starved levels; 0: none)   // per-level backward scratch (dY ping-pong)
+  size_t off_sk[16]; long long sk_floats[16];   // per-BLOCK fp32 K-split slabs (blocks of the grid-starved levels; 0: none)
   struct PlanRt* rt;
   size_t total;
   PackTab ptab;
@@ -671,13 +598,12 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
     pe.src = c.w_off; pe.wf = c.wf; pe.wd = c.wd; pe.cout = c.cout; pe.cin = c.cin; pe.cinpad = c.cinpad;
     UnpackEnt& ue = P->utab.e[P->utab.n++];
     ue.src = c.gs; ue.dst = c.w_off; ue.cout = c.cout; ue.cin = c.cin; ue.cinpad = c.cinpad; ue.taps = 9; ue.nvec = 3; ue.nslab = 1;
-    ue.inv_taps = dec_inv(9); ue.inv_cin = dec_inv(c.cin); ue.fast = 9LL * c.cout * c.cin * (c.cin > 9 ? c.cin : 9) < (1ll << 32);
   };
   for (size_t r = 0; r < P->reg.size(); ++r) { add_conv(P->exec[P->reg[r]].c1); add_conv(P->exec[P->reg[r]].c2); }
   pack_tiles(P->ptab);
   for (size_t k = 0; k < P->heads.size(); ++k) {
     UnpackEnt& ue = P->utab.e[P->utab.n++];
-    ue.src = P->heads[k].gs; ue.dst = P->heads[k].w_off; ue.cout = cfg->num_classes; ue.cin = NBF[0]; ue.cinpad = NBF[0]; ue.taps = 1; ue.nvec = 1; ue.nslab = HEAD_SLABS; ue.inv_taps = 0; ue.inv_cin = dec_inv(NBF[0]); ue.fast = 1;
+    ue.src = P->heads[k].gs; ue.dst = P->heads[k].w_off; ue.cout = cfg->num_classes; ue.cin = NBF[0]; ue.cinpad = NBF[0]; ue.taps = 1; ue.nvec = 1; ue.nslab = HEAD_SLABS;
   }
   PlanRt* rt = new PlanRt();
   rt->lanes_ok = true;
@@ -1368,24 +1294,20 @@ extern "C" int nunet_plan_grad_scratch(const nunet_plan* P, int64_t* byte_offset
 
 // blocks [bid0, bid0 + nblocks) of update_kernel's whole-model numbering: all of it (nunet_plan_opt_step, repack 1), one VGGBlock's
 // tiles or the heads (the in-pass step)
-template <typename O> static int launch_update_kernel(nunet_plan* P, void* arena, float* params, const O& o, float grad_scale, float* grads,
+template <typename T, typename O> static int launch_update_kernel(nunet_plan* P, void* arena, float* params, const O& o, float grad_scale, float* grads,
                                                       int bid0, int nblocks, double bytes, hipStream_t st) {
   if (nblocks <= 0) return NUNET_OK;
   UpdP u;
   u.params = params; u.scratch = (const float*)AB(arena, P->off_gs); u.grads = grads;
   u.gscale = grad_scale; u.nconv = P->ptab.n; u.bid_off = bid0;
-  void* wp = AB(arena, P->off_wpack);
-  const dim3 grid(nblocks), blk(512);
   ProfScope ps(PC_SGD, 0, bytes, st);
-  if (P->cfg.dtype == NUNET_F32) NUNET_LAUNCH((update_kernel<float, O>), grid, blk, 0, st, u, o, (float*)wp, P->ptab, P->utab);
-  else if (P->cfg.dtype == NUNET_BF16) NUNET_LAUNCH((update_kernel<bf16_t, O>), grid, blk, 0, st, u, o, (bf16_t*)wp, P->ptab, P->utab);
-  else NUNET_LAUNCH((update_kernel<f16_t, O>), grid, blk, 0, st, u, o, (f16_t*)wp, P->ptab, P->utab);
+  NUNET_LAUNCH((update_kernel<T, O>), dim3(nblocks), dim3(512), 0, st, u, o, (T*)AB(arena, P->off_wpack), P->ptab, P->utab);
   return nunet_check_launch(bid0 == 0 && nblocks == P->ptab.ntiles + P->utab.n - P->ptab.n ? "plan_opt_step" : "plan_opt_step (in pass)");
 }
 
 // In-pass step of blocks [bid0, bid0 + nblocks) with the optimiser nunet_plan_set_inpass_opt left in the plan
 template <typename U> static int launch_update(nunet_plan* P, void* arena, const U& s, int bid0, int nblocks, hipStream_t st) {
-  return opt_dispatch(&s.opt, [&](const auto& o) { return launch_update_kernel(P, arena, s.params, o, s.gscale, s.grads, bid0, nblocks, 0.0, st); });
+  return opt_dispatch(&s.opt, [&](const auto& o) { return NUNET_DISPATCH(P->cfg.dtype, launch_update_kernel, P, arena, s.params, o, s.gscale, s.grads, bid0, nblocks, 0.0, st); });
 }
 
 // The optimiser step as part of the backward pass: with parameters set here, every whole pass (nunet_plan_backward, or
@@ -1413,77 +1335,26 @@ extern "C" int nunet_plan_set_inpass_opt(nunet_plan* P, float* params, const nun
 // parameters and the optimiser state as 16-byte runs, the flat gradient arena is written only when the caller wants it.
 template <typename O>
 __global__ __launch_bounds__(256) void unpack_sgd_tiled_kernel(UpdP u, O o, PackTab tab, UnpackTab ut) {
-  __shared__ float s_t[32][32 * 9 + 1];
+  __shared__ float s_t[32][TILE_LD];
   float gs = u.gscale;
   const bool live = o.begin(gs);   // false: a step skipped by loss scaling, which stores the unscaled gradients only
   if (!live && !u.grads) return;
-  auto step1 = [&](long long idx, float g) {
-    g *= gs;
-    if (u.grads) u.grads[idx] = g;
-    if (live) u.params[idx] = opt_elem(o, u.params[idx], g, idx);
-  };
   if ((int)blockIdx.x >= tab.ntiles) {
     const UnpackEnt en = ut.e[(int)blockIdx.x - tab.ntiles];
-    const float* dw = u.scratch + en.src;
-    const int nw = en.cout * en.cin * en.taps;
-    if (en.nslab > 1) {
-      // 1x1 head: 256/ne threads share an element's slabs (a single thread walking all 256 slabs is a chain of 256
-      // dependent-latency loads: that loop alone made the earlier fused kernels 100 us long), fixed summation order
-      const int tot = nw + en.nvec * en.cout;
-      for (int e0 = 0; e0 < tot; e0 += 256) {
-        const int ne = min(256, tot - e0);
-        const int parts = 256 / ne;
-        const int e = threadIdx.x % ne, part = threadIdx.x / ne;
-        float v = 0.f;
-        if (part < parts) {
-#pragma unroll 8
-          for (int sl = part; sl < en.nslab; sl += parts) v += dw[(long long)sl * tot + e0 + e];
-        }
-        s_t[0][threadIdx.x] = part < parts ? v : 0.f;
-        __syncthreads();
-        if ((int)threadIdx.x < ne) {
-          float g = 0.f;
-          for (int q = 0; q < parts; ++q) g += s_t[0][q * ne + threadIdx.x];
-          step1(en.dst + e0 + threadIdx.x, g);
-        }
-        __syncthreads();
-      }
-      return;
-    }
-    const float* vsrc = dw + (long long)en.taps * en.cout * en.cinpad;
-    for (int i = threadIdx.x; i < en.nvec * en.cout; i += blockDim.x) step1(en.dst + nw + i, vsrc[i]);
+    tail_entry(en, u.scratch, &s_t[0][0], [&](int i, float g) { step_elem(u, o, live, gs, en.dst + i, g); });
     return;
   }
-  int e = 0;
-  while (e + 1 < tab.n && (int)blockIdx.x >= tab.tile0[e + 1]) ++e;
-  const PackEnt en = tab.e[e];
-  const UnpackEnt ue = ut.e[e];
-  const int t = blockIdx.x - tab.tile0[e];
-  const int nci = (en.cinpad + 31) / 32;
-  const int co0 = (t / nci) * 32, ci0 = (t % nci) * 32;
-  const int cw = min(32, en.cin - ci0), rw = min(32, en.cout - co0);
-  if (cw <= 0) return;
-  const float* dw = u.scratch + ue.src;
-  const long long row0 = ue.dst + ((long long)co0 * en.cin + ci0) * 9;
-  const bool full = rw == 32 && cw == 32;
-  if (full && en.cinpad % 4 == 0 && ((uintptr_t)dw & 15) == 0) {
-    for (int i = threadIdx.x; i < 9 * 32 * 8; i += blockDim.x) {
-      const int c4 = i & 7, ro = (i >> 3) & 31, tap = i >> 8;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(dw + ((long long)tap * en.cout + co0 + ro) * en.cinpad + ci0 + c4 * 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s_t[ro][(c4 * 4 + j) * 9 + tap] = v[j];
-    }
-  } else {
-    for (int i = threadIdx.x; i < 9 * 32 * 32; i += blockDim.x) {
-      const int ci = i & 31, ro = (i >> 5) & 31, tap = i >> 10;
-      if (ro < rw && ci < cw) s_t[ro][ci * 9 + tap] = dw[((long long)tap * en.cout + co0 + ro) * en.cinpad + ci0 + ci];
-    }
-  }
+  const Tile t = tile_of(tab, blockIdx.x);
+  if (t.cw <= 0) return;
+  const PackEnt en = tab.e[t.e];
+  const UnpackEnt ue = ut.e[t.e];
+  const long long row0 = ue.dst + ((long long)t.co0 * en.cin + t.ci0) * 9;
+  gather_scratch_tile(s_t, u.scratch + ue.src, en, t);
   __syncthreads();
   bool al = ((uintptr_t)(u.params + row0) & 15) == 0 && (!u.grads || ((uintptr_t)(u.grads + row0) & 15) == 0);
 #pragma unroll
   for (int q = 0; q < O::NS; ++q) al = al && ((uintptr_t)(o.st[q] + row0) & 15) == 0;
-  if (full && en.cin % 4 == 0 && al) {
+  if (t.rw == 32 && t.cw == 32 && en.cin % 4 == 0 && al) {
     for (int i = threadIdx.x; i < 32 * 72; i += blockDim.x) {
       const int ro = i / 72, k4 = i - ro * 72;
       const long long idx = row0 + (long long)ro * en.cin * 9 + k4 * 4;
@@ -1514,7 +1385,7 @@ __global__ __launch_bounds__(256) void unpack_sgd_tiled_kernel(UpdP u, O o, Pack
   } else {
     for (int i = threadIdx.x; i < 32 * 288; i += blockDim.x) {
       const int ro = i / 288, k = i - ro * 288;
-      if (ro < rw && k < cw * 9) step1(row0 + (long long)ro * en.cin * 9 + k, s_t[ro][k]);
+      if (ro < t.rw && k < t.cw * 9) step_elem(u, o, live, gs, row0 + (long long)ro * en.cin * 9 + k, s_t[ro][k]);
     }
   }
 }
@@ -1540,15 +1411,15 @@ extern "C" int nunet_plan_opt_step(nunet_plan* P, float* params, const nunet_opt
   ARENA_CHECK("plan_opt_step");
   return opt_dispatch(opt, [&](const auto& o) {
     const double bytes = (double)P->nparams * ((repack ? 24.0 : 20.0) + (grads ? 4.0 : 0.0) + 8.0 * (o.NS - 1));
-    if (repack) return launch_update_kernel(P, arena, params, o, grad_scale, grads, 0, P->ptab.ntiles + P->utab.n - P->ptab.n, bytes, (hipStream_t)s);
+    if (repack) return NUNET_DISPATCH(P->cfg.dtype, launch_update_kernel, P, arena, params, o, grad_scale, grads, 0, P->ptab.ntiles + P->utab.n - P->ptab.n, bytes, (hipStream_t)s);
     return launch_unpack_step(P, arena, params, o, grad_scale, grads, bytes, (hipStream_t)s);
   });
 }
 
-// Square norm of the gradient scratch for gradient clipping (include/nunet.h nunet_clip): unpack_sgd_tiled_kernel's
+// Square norm of the gradient scratch for gradient clipping (include/nunet.h nunet_clip): the unpack kernels'
 // block -> (layer, 32 x 32 tile | vector tail | head) map, read-only. A conv tile sums the squares of its real [tap][co][ci]
 // entries (ci < cin: the padding up to cinpad does not count) straight from the scratch, 16-byte loads along ci; a tail block
-// takes the layer's conv bias, gamma and beta; a head block sums the slabs first, in unpack_sgd_tiled_kernel's order, and
+// takes the layer's conv bias, gamma and beta; a head block sums the slabs first (head_slab_sum<256>, so in unpack_sgd_tiled_kernel's order) and
 // squares the sum. Products exact in double, a thread's elements in index order, then block256_sum_f64: one partial per
 // workgroup, plain store (a pure-padding tile stores 0).
 __global__ __launch_bounds__(256) void plan_sqnorm_kernel(const float* __restrict__ scratch, PackTab tab, UnpackTab ut, double* __restrict__ ws) {
@@ -1556,56 +1427,25 @@ __global__ __launch_bounds__(256) void plan_sqnorm_kernel(const float* __restric
   __shared__ double s_w[4];
   double acc = 0.0;
   if ((int)blockIdx.x >= tab.ntiles) {
-    const UnpackEnt en = ut.e[(int)blockIdx.x - tab.ntiles];
-    const float* dw = scratch + en.src;
-    const int nw = en.cout * en.cin * en.taps;
-    if (en.nslab > 1) {
-      const int tot = nw + en.nvec * en.cout;
-      for (int e0 = 0; e0 < tot; e0 += 256) {
-        const int ne = min(256, tot - e0);
-        const int parts = 256 / ne;
-        const int e = threadIdx.x % ne, part = threadIdx.x / ne;
-        float v = 0.f;
-        if (part < parts) {
-#pragma unroll 8
-          for (int sl = part; sl < en.nslab; sl += parts) v += dw[(long long)sl * tot + e0 + e];
-        }
-        s_p[threadIdx.x] = part < parts ? v : 0.f;
-        __syncthreads();
-        if ((int)threadIdx.x < ne) {
-          float g = 0.f;
-          for (int q = 0; q < parts; ++q) g += s_p[q * ne + threadIdx.x];
-          acc += (double)g * (double)g;
-        }
-        __syncthreads();
-      }
-    } else {
-      const float* vsrc = dw + (long long)en.taps * en.cout * en.cinpad;
-      for (int i = threadIdx.x; i < en.nvec * en.cout; i += blockDim.x) acc += (double)vsrc[i] * (double)vsrc[i];
-    }
+    tail_entry(ut.e[(int)blockIdx.x - tab.ntiles], scratch, s_p, [&](int, float g) { acc += (double)g * (double)g; });
   } else {
-    int e = 0;
-    while (e + 1 < tab.n && (int)blockIdx.x >= tab.tile0[e + 1]) ++e;
-    const PackEnt en = tab.e[e];
-    const int t = blockIdx.x - tab.tile0[e];
-    const int nci = (en.cinpad + 31) / 32;
-    const int co0 = (t / nci) * 32, ci0 = (t % nci) * 32;
-    const int cw = min(32, en.cin - ci0), rw = min(32, en.cout - co0);
-    const float* dw = scratch + ut.e[e].src;
-    if (cw > 0 && en.cinpad % 4 == 0 && ((uintptr_t)dw & 15) == 0) {
+    const Tile t = tile_of(tab, blockIdx.x);
+    const PackEnt en = tab.e[t.e];
+    const float* dw = scratch + ut.e[t.e].src;
+    if (t.cw > 0 && en.cinpad % 4 == 0 && ((uintptr_t)dw & 15) == 0) {
       for (int i = threadIdx.x; i < 9 * 32 * 8; i += blockDim.x) {
         const int c4 = i & 7, ro = (i >> 3) & 31, tap = i >> 8;
-        if (ro >= rw || c4 * 4 >= cw) continue;      // (ci0 + c4 * 4 < cin <= cinpad, a multiple of 4: the run is inside the row)
-        const f32x4 v = *reinterpret_cast<const f32x4*>(dw + ((long long)tap * en.cout + co0 + ro) * en.cinpad + ci0 + c4 * 4);
+        if (ro >= t.rw || c4 * 4 >= t.cw) continue;      // (t.ci0 + c4 * 4 < cin <= cinpad, a multiple of 4: the run is inside the row)
+        const f32x4 v = *reinterpret_cast<const f32x4*>(dw + ((long long)tap * en.cout + t.co0 + ro) * en.cinpad + t.ci0 + c4 * 4);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          if (c4 * 4 + j < cw) acc += (double)v[j] * (double)v[j];
+          if (c4 * 4 + j < t.cw) acc += (double)v[j] * (double)v[j];
       }
-    } else if (cw > 0) {
+    } else if (t.cw > 0) {
       for (int i = threadIdx.x; i < 9 * 32 * 32; i += blockDim.x) {
         const int ci = i & 31, ro = (i >> 5) & 31, tap = i >> 10;
-        if (ro < rw && ci < cw) {
-          const float v = dw[((long long)tap * en.cout + co0 + ro) * en.cinpad + ci0 + ci];
+        if (ro < t.rw && ci < t.cw) {
+          const float v = dw[((long long)tap * en.cout + t.co0 + ro) * en.cinpad + t.ci0 + ci];
           acc += (double)v * (double)v;
         }
       }

@@ -557,6 +557,62 @@ def test_fused_update_equals_unpack_sgd_pack(dtype, mode, synth):
         assert torch.equal(l1, ts.logits)          # same packed weights, deterministic reductions: bit-identical
 
 
+def _head_slab_sum_host(slabs, B):
+    """The documented order of the 1x1 head's slab sum for a block of B threads (plan.hip head_slab_sum), in float32 with
+    sequential adds: elements in chunks of B; in a chunk of ne elements parts = B // ne threads share an element, thread
+    (part, e) adds slabs part, part + parts, ... in order from 0, and the parts are added in order 0 .. parts - 1 from 0."""
+    nslab, tot = slabs.shape
+    out = np.zeros(tot, dtype=np.float32)
+    for e0 in range(0, tot, B):
+        ne = min(B, tot - e0)
+        parts = B // ne
+        total = np.zeros(ne, dtype=np.float32)
+        for part in range(parts):
+            v = np.zeros(ne, dtype=np.float32)
+            for sl in range(part, nslab, parts):
+                v = v + slabs[sl, e0:e0 + ne]
+            total = total + v
+        out[e0:e0 + ne] = total
+    return out
+
+
+@pytest.mark.parametrize("ncls", [1, 4, 8])
+def test_head_slab_sum_order_in_every_layout(ncls, synth):
+    """The head gradient is the sum of 256 slabs in a fixed order that depends on the block size of the kernel that forms it:
+    256 threads in layout 0 (unpack_tiled_kernel) and layout 2 (unpack_sgd_tiled_kernel), 512 in layout 1 (update_kernel).
+    ncls 1, 4, 8 give 33, 132 and 264 elements: many parts per element; one part; two chunks (256 + 8) for 256 threads and
+    one chunk for 512. The flat head gradients equal a host emulation of that order bit for bit, and every other entry
+    (conv weights, bias, gamma, beta: copies of the scratch) is bit-identical across the three layouts."""
+    from nunet_amd.trainer import TrainStep
+    m, st, x, t = build((2, 16, 16, 3, ncls, False, True, True), synth)
+    m.train()
+    ts = TrainStep(m, tuple(x.shape), lr=5e-2, momentum=0.9, weight_decay=1e-3, nesterov=True, use_graph=False, fused_update=0, keep_grads=True)
+    ts.x.copy_(x.to(DEV)); ts.t.copy_(t.to(DEV))
+    ts._fwd_loss(); ts._bwd(3)                     # gradient scratch complete, not yet unpacked
+    eng = ts.eng
+    tot = ncls * 32 + ncls
+    nh = eng.flat_params.numel() - tot             # the head is the last parameter pair, and the first scratch entry
+    slabs = ts._grad_scratch()[0][:256 * tot].view(256, tot).cpu().numpy()
+    e256 = torch.from_numpy(_head_slab_sum_host(slabs, 256))
+    e512 = torch.from_numpy(_head_slab_sum_host(slabs, 512))
+    assert float(e256.abs().max()) > 0
+    p0, m0 = eng.flat_params.clone(), ts.mom.clone()
+    grads = {}
+    ts._bwd(4)                                     # layout 0: unpack into the flat arena
+    torch.cuda.synchronize()
+    grads[0] = eng.flat_grads.cpu()
+    for mode in (2, 1):
+        eng.flat_params.copy_(p0); ts.mom.copy_(m0); eng.flat_grads.zero_()
+        ts.fused_update = mode
+        ts._opt()                                  # nunet_plan_opt_step (repack 0 / 1) on the same scratch, grad_scale 1
+        torch.cuda.synchronize()
+        grads[mode] = eng.flat_grads.cpu()
+    assert torch.equal(grads[0][nh:], e256)
+    assert torch.equal(grads[2][nh:], e256)
+    assert torch.equal(grads[1][nh:], e512)
+    assert torch.equal(grads[0][:nh], grads[2][:nh]) and torch.equal(grads[0][:nh], grads[1][:nh])
+
+
 @pytest.mark.parametrize("dtype", ["bf16", "fp32"])
 @pytest.mark.parametrize("ds", [False, True])
 def test_optimiser_step_inside_the_backward_pass(dtype, ds, synth):

@@ -243,24 +243,62 @@ def test_conv3x3_wgrad_pair(dt):
         assert torch.equal(dw, ref)      # same slices, same summation order: bit-identical
 
 
-@pytest.mark.parametrize("dt", [L.F32, L.BF16])
+# (cout, cin, cin_pad) of the weight-layout kernels' 32 Cout x 32 Cin tile walk
+LAYOUT_SHAPES = [
+    (32, 3, 32),     # ragged first layer, padding columns
+    (32, 32, 32),    # one full vector tile
+    (64, 96, 96),    # 2 x 3 full tiles
+    (32, 48, 48),    # partial last Cin tile on the vector-store path
+    (40, 36, 36),    # ragged rows, cinpad % 8 != 0: scalar stores
+]
+
+
+@pytest.mark.parametrize("dt", [L.F32, L.BF16, L.F16])
 def test_pack_unpack_roundtrip(dt):
+    """nunet_pack_weights is pure data movement: wf is the rounded weight permuted to [tap][co][cinpad] with the padding
+    columns written as zeros, wd the flipped / transposed [8 - tap][ci][co] pack, both bit for bit; so is the unpack."""
     g = torch.Generator().manual_seed(5)
-    w = torch.randn(64, 3, 3, 3, generator=g)
-    wf, _ = pack(w, dt, cin_pad=32, want_wd=False)
-    wf = wf.float().view(9, 64, 32).cpu()
-    ref = q(w, dt).permute(2, 3, 0, 1).reshape(9, 64, 3)
-    assert torch.equal(wf[:, :, :3], ref) and float(wf[:, :, 3:].abs().max()) == 0
-    w2 = torch.randn(32, 48, 3, 3, generator=g)
-    _, wd = pack(w2, dt)
-    wd = wd.float().view(9, 48, 32).cpu()
-    assert torch.equal(wd, q(w2, dt).flip(2, 3).permute(2, 3, 1, 0).reshape(9, 48, 32))
+    for cout, cin, cin_pad in LAYOUT_SHAPES:
+        w = torch.randn(cout, cin, 3, 3, generator=g)
+        wg = w.to(DEV)
+        wf = torch.full((9 * cout * cin_pad,), 7.0, dtype=tdt(dt), device=DEV)     # (the padding columns must be WRITTEN as zeros)
+        wd = torch.full((9 * cout * cin,), 7.0, dtype=tdt(dt), device=DEV)
+        L.check(L.lib().nunet_pack_weights(L.ptr(wg), cout, cin, cin_pad, dt, L.ptr(wf), L.ptr(wd), L.stream()), "pack")
+        wf = wf.view(9, cout, cin_pad).cpu()
+        ref = w.to(tdt(dt))
+        assert torch.equal(wf[:, :, :cin], ref.permute(2, 3, 0, 1).reshape(9, cout, cin)), (DT[dt], cout, cin, cin_pad)
+        assert bool((wf[:, :, cin:] == 0).all()), (DT[dt], cout, cin, cin_pad)
+        assert torch.equal(wd.view(9, cin, cout).cpu(), ref.flip(2, 3).permute(2, 3, 1, 0).reshape(9, cin, cout)), (DT[dt], cout, cin, cin_pad)
     dw = torch.randn(9, 64, 32, generator=g)
     gg = torch.ones(64 * 3 * 9, dtype=torch.float32, device=DEV)
     dw_g = dw.to(DEV)
     L.check(L.lib().nunet_unpack_wgrad(L.ptr(dw_g), 64, 3, 32, L.ptr(gg), 1, L.stream()), "unpack")
     exp = dw[:, :, :3].permute(1, 2, 0).reshape(64, 3, 3, 3) + 1.0
-    np.testing.assert_allclose(gg.view(64, 3, 3, 3).cpu().numpy(), exp.numpy(), rtol=1e-6)
+    assert torch.equal(gg.view(64, 3, 3, 3).cpu(), exp)      # one add per element
+
+
+@pytest.mark.parametrize("accumulate", [0, 1])
+@pytest.mark.parametrize("shape,offset", [(sh, 0) for sh in LAYOUT_SHAPES] + [((64, 96, 96), 1)])
+def test_unpack_wgrad_is_exact(shape, offset, accumulate):
+    """nunet_unpack_wgrad runs the plan's own unpack_tiled_kernel on a one-layer table: scratch [tap][co][cinpad] -> OIHW is one
+    copy per element (accumulate 0) or one fp32 add (accumulate 1), so the result equals the host permutation bit for bit.
+    offset 1: the destination starts one float into its buffer, so the 16-byte store path falls back to the scalar one."""
+    cout, cin, cin_pad = shape
+    g = torch.Generator().manual_seed(17)
+    dw = torch.randn(9, cout, cin_pad, generator=g)
+    g0 = torch.randn(offset + cout * cin * 9, generator=g)
+    buf = torch.empty(offset + cout * cin * 9, dtype=torch.float32, device=DEV)
+    buf.copy_(g0)
+    dw_g = torch.empty(9, cout, cin_pad, dtype=torch.float32, device=DEV)
+    dw_g.copy_(dw)
+    dst = buf[offset:]
+    L.check(L.lib().nunet_unpack_wgrad(L.ptr(dw_g), cout, cin, cin_pad, L.ptr(dst), accumulate, L.stream()), "unpack")
+    exp = dw[:, :, :cin].permute(1, 2, 0).reshape(-1)
+    if accumulate:
+        exp = g0[offset:] + exp
+    got = buf.cpu()
+    assert torch.equal(got[offset:], exp), (shape, offset, accumulate)
+    assert torch.equal(got[:offset], g0[:offset])
 
 
 @pytest.mark.parametrize("dt", [L.F32, L.BF16, L.F16])
