@@ -880,7 +880,8 @@ def test_lovasz_hinge_large_images_match_oracle(shape):
     ref = O.lovasz_hinge(xo.squeeze(1), t.double().squeeze(1))
     ref.backward()
     assert abs(float(loss.detach()) - float(ref)) < 2e-5 * max(1.0, float(ref))
-    np.testing.assert_allclose(xd.grad.cpu().numpy(), xo.grad.numpy(), atol=3e-7, rtol=2e-3)
+    np.testing.assert_allclose(xd.grad.cpu().numpy(), xo.grad.numpy(), atol=1e-8, rtol=2e-3)    # these inputs have fp32 ties; measured: 7e-9 at most
+    # (the tie-free, per-pixel criterion is tests/test_lovasz_gpu.py)
     with pytest.raises(L.NunetError):
         big = torch.zeros(1, 1, 2048, 4096, device=DEV)                                         # 2^23 px: refused loudly
         nunet_amd.losses.LovaszHingeLoss()(big, big)
