@@ -67,6 +67,22 @@ typedef struct {
 } nunet_wgrad_launch_info;
 int nunet_conv3x3_wgrad_launch_info(const nunet_wgrad_desc* d, nunet_wgrad_launch_info* out);
 
+/* Launch geometry of the BCE-Dice loss, the fused loss step (NUNET_LOSS_BCE_DICE), the IoU counts and the mask export, from
+ * the very expressions their launches use. A pure host function: no GPU call, no pointer but `out`. N and heads are read where
+ * the entry has them (the two losses; heads by the loss step alone), per_or_n is the elements per image of a loss and the
+ * element count of the other two. It refuses what the entry itself refuses by size (N, heads, the loss step's 2^24 per image).
+ * Every kernel walks its items with one grid-stride loop per (y, z) plane of the grid; the BCE-Dice forward also runs a
+ * one-wave final kernel over the grid.x partial slabs of each image. */
+enum { NUNET_LOSS_ENTRY_BCE_DICE_FWD = 0, NUNET_LOSS_ENTRY_BCE_DICE_BWD = 1, NUNET_LOSS_ENTRY_LOSS_STEP = 2,
+       NUNET_LOSS_ENTRY_IOU_COUNTS = 3, NUNET_LOSS_ENTRY_SIGMOID_U8 = 4 };
+typedef struct {
+  int32_t grid_x, grid_y, grid_z;   /* workgroups: blocks per image (or over all elements) x images x heads */
+  int32_t block;                    /* threads of a workgroup */
+  int64_t items;                    /* loop items of one (y, z) plane: elements, 4-element vectors for the mask export (its n % 4 tail is apart) */
+  int64_t trips_max, trips_min;     /* most and fewest grid-stride trips a thread takes (0: a thread without an item) */
+} nunet_loss_launch_info_t;
+int nunet_loss_launch_info(int32_t entry, int32_t N, int64_t per_or_n, int32_t heads, nunet_loss_launch_info_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,14 @@ class WgradLaunchInfo(C.Structure):
                                     "ksplit", "grid")]
 
 
+LOSS_ENTRY_BCE_DICE_FWD, LOSS_ENTRY_BCE_DICE_BWD, LOSS_ENTRY_LOSS_STEP, LOSS_ENTRY_IOU_COUNTS, LOSS_ENTRY_SIGMOID_U8 = range(5)
+
+
+class LossLaunchInfo(C.Structure):
+    """nunet_loss_launch_info_t (include/nunet_diag.h): what a loss / IoU / mask-export entry would launch."""
+    _fields_ = [(k, _i32) for k in ("grid_x", "grid_y", "grid_z", "block")] + [(k, _i64) for k in ("items", "trips_max", "trips_min")]
+
+
 class BnFwdDesc(C.Structure):
     _fields_ = [("dtype", _i32), ("N", _i32), ("H", _i32), ("W", _i32), ("C", _i32),
                 ("y", _vp), ("PY", _i32),
@@ -215,6 +223,7 @@ _SIG = {
     "nunet_conv3x3_launch_info": (_i32, [C.POINTER(ConvDesc), C.POINTER(ConvLaunchInfo)]),
     "nunet_conv3x3_wgrad_launch_info": (_i32, [C.POINTER(WgradDesc), C.POINTER(WgradLaunchInfo)]),
     "nunet_conv_kernel_attrs": (_i32, [C.POINTER(ConvDesc), C.POINTER(ConvKernelAttrs)]),
+    "nunet_loss_launch_info": (_i32, [_i32, _i32, _i64, _i32, C.POINTER(LossLaunchInfo)]),
     "nunet_graph_begin": (_i32, [_vp]),
     "nunet_graph_end": (_i32, [_vp, C.POINTER(_vp)]),
     "nunet_graph_launch": (_i32, [_vp, _vp]),

@@ -968,6 +968,10 @@ extern "C" int nunet_head_bwd(int32_t dtype, int32_t N, int32_t H, int32_t W, in
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 constexpr int BCE_GX = 64;      // most blocks per image
+// The grids of the loss, metric and export launches, one helper per entry: the launch and nunet_loss_launch_info
+// (include/nunet_diag.h) both call it.
+static int bce_dice_fwd_gx(int64_t per) { return grid_for(per, 256 * 4, BCE_GX); }
+static int bce_dice_bwd_gx(int64_t per) { return grid_for(per, 256 * 4, 64); }
 __global__ __launch_bounds__(256) void bce_dice_partial_kernel(const float* __restrict__ x, const float* __restrict__ t, int64_t per, float* __restrict__ ws, int N) {
   const int n = blockIdx.y;
   const float* xs = x + (int64_t)n * per;
@@ -1028,7 +1032,7 @@ extern "C" int nunet_bce_dice_fwd(const float* logits, const float* target, int3
   NUNET_REQUIRE(logits && target && ws && loss && N > 0 && per > 0, "bce_dice_fwd: bad args");
   NUNET_REQUIRE(ws_bytes >= nunet_bce_dice_ws_bytes(N), "bce_dice_fwd: workspace of %zu bytes, nunet_bce_dice_ws_bytes(%d) = %zu", ws_bytes, (int)N, nunet_bce_dice_ws_bytes(N));
   hipStream_t st = (hipStream_t)s;
-  const int gx = grid_for(per, 256 * 4, BCE_GX);
+  const int gx = bce_dice_fwd_gx(per);
   ProfScope ps(PC_LOSS, 0, (double)N * per * 8, st);
   NUNET_LAUNCH(bce_dice_partial_kernel, dim3(gx, N), dim3(256), 0, st, logits, target, per, ws, N);
   NUNET_LAUNCH(bce_dice_final_kernel, dim3(1), dim3(64), 0, st, ws, N, gx, per, loss);
@@ -1037,7 +1041,7 @@ extern "C" int nunet_bce_dice_fwd(const float* logits, const float* target, int3
 extern "C" int nunet_bce_dice_bwd(const float* logits, const float* target, int32_t N, int64_t per, const float* ws, size_t ws_bytes, const float* gscale, float* dlogits, nunet_stream_t s) {
   NUNET_REQUIRE(logits && target && ws && dlogits && N > 0 && per > 0, "bce_dice_bwd: bad args");
   NUNET_REQUIRE(ws_bytes >= nunet_bce_dice_ws_bytes(N), "bce_dice_bwd: workspace of %zu bytes, nunet_bce_dice_ws_bytes(%d) = %zu", ws_bytes, (int)N, nunet_bce_dice_ws_bytes(N));
-  const int gx = grid_for(per, 256 * 4, 64);
+  const int gx = bce_dice_bwd_gx(per);
   ProfScope ps(PC_LOSS, 0, (double)N * per * 12, (hipStream_t)s);
   NUNET_LAUNCH(bce_dice_bwd_kernel, dim3(gx, N), dim3(256), 0, (hipStream_t)s, logits, target, per, ws, gscale, dlogits, N);
   return nunet_check_launch("bce_dice_bwd");
@@ -1052,6 +1056,7 @@ extern "C" int nunet_bce_dice_bwd(const float* logits, const float* target, int3
 // zero launch ahead, no same-address atomics, and bit-reproducible run to run); the second kernel adds the <= 64 slabs
 // of its image with one wave.
 constexpr int LOSS_GX = 64;     // most blocks per (image, head)
+static int loss_step_gx(int64_t per) { return grid_for(per, 256, LOSS_GX); }    // one element per thread up to 128x128 images: the step waits on this pair of launches
 __global__ __launch_bounds__(256) void loss_step_partial_kernel(const float* __restrict__ x, const float* __restrict__ t, int64_t per, float* __restrict__ ws, int N, int heads, float iou_thr) {
   const int n = blockIdx.y, hd = blockIdx.z;
   const float* xs = x + ((int64_t)hd * N + n) * per;
@@ -1172,7 +1177,7 @@ static int loss_step(const float* logits, const float* target, int32_t N, int64_
   hipStream_t st = (hipStream_t)s;
   if (loss_kind == NUNET_LOSS_LOVASZ_HINGE)
     return lovasz_loss_step(logits, target, N, per, heads, ws, dlogits, loss_out, meters, iou_logit_threshold, seed_scale, st);
-  const int gx = grid_for(per, 256, LOSS_GX);     // one element per thread up to 128x128 images: the step waits on this pair of launches
+  const int gx = loss_step_gx(per);
   ProfScope ps(PC_LOSS, 0, (double)N * per * heads * 16, st);
   NUNET_LAUNCH(loss_step_partial_kernel, dim3(gx, N, heads), dim3(256), 0, st, logits, target, per, ws, N, heads, iou_logit_threshold);
   NUNET_LAUNCH(loss_step_bwd_kernel, dim3(gx, N, heads), dim3(256), 0, st, logits, target, per, ws, gx, N, heads, dlogits, loss_out, meters, seed_scale);
@@ -1208,10 +1213,11 @@ __global__ __launch_bounds__(256) void iou_counts_kernel(const float* __restrict
     atomicAdd(&counts[1], (unsigned long long)cu);
   }
 }
+static int iou_counts_gx(int64_t n) { return grid_for(n, 256 * 4, 256); }
 extern "C" int nunet_iou_counts(const float* logits, const float* target, int64_t n, float logit_threshold, unsigned long long* counts, nunet_stream_t s) {
   NUNET_REQUIRE(logits && target && counts && n > 0, "iou_counts: bad args");
   ProfScope ps(PC_LOSS, 0, (double)n * 8, (hipStream_t)s);
-  NUNET_LAUNCH(iou_counts_kernel, dim3(grid_for(n, 256 * 4, 256)), dim3(256), 0, (hipStream_t)s, logits, target, n, logit_threshold, counts);
+  NUNET_LAUNCH(iou_counts_kernel, dim3(iou_counts_gx(n)), dim3(256), 0, (hipStream_t)s, logits, target, n, logit_threshold, counts);
   return nunet_check_launch("iou_counts");
 }
 
@@ -1249,11 +1255,43 @@ __global__ __launch_bounds__(256) void sigmoid_u8_kernel(const float* __restrict
     out[i] = (uint8_t)sigmoid_byte(s_thr, logits[i]);
   }
 }
+static int sigmoid_u8_gx(int64_t n) { return grid_for(n / 4 + 1, 256, 2048); }
 extern "C" int nunet_sigmoid_u8(const float* logits, const float* thresholds, uint8_t* out, int64_t n, nunet_stream_t s) {
   NUNET_REQUIRE(logits && thresholds && out && n > 0, "sigmoid_u8: bad args");
   NUNET_REQUIRE(((uintptr_t)logits & 15) == 0 && ((uintptr_t)out & 3) == 0, "sigmoid_u8: logits must be 16-byte and out 4-byte aligned");
-  NUNET_LAUNCH(sigmoid_u8_kernel, dim3(grid_for(n / 4 + 1, 256, 2048)), dim3(256), 0, (hipStream_t)s, logits, thresholds, out, n);
+  NUNET_LAUNCH(sigmoid_u8_kernel, dim3(sigmoid_u8_gx(n)), dim3(256), 0, (hipStream_t)s, logits, thresholds, out, n);
   return nunet_check_launch("sigmoid_u8");
+}
+
+// Launch geometry of the entries above (include/nunet_diag.h): the grids come from the helpers the launches call, the trip
+// counts from the loops' own form, `for (i = block * 256 + thread; i < items; i += grid.x * 256)`: thread 0 of block 0 takes the
+// most trips, the last thread of the last block the fewest.
+extern "C" int nunet_loss_launch_info(int32_t entry, int32_t N, int64_t per_or_n, int32_t heads, nunet_loss_launch_info_t* out) {
+  NUNET_REQUIRE(out, "loss launch info: null output");
+  NUNET_REQUIRE(per_or_n > 0, "loss launch info: %lld elements", (long long)per_or_n);
+  int gx = 0, gy = 1, gz = 1;
+  int64_t items = per_or_n;
+  switch (entry) {
+    case NUNET_LOSS_ENTRY_BCE_DICE_FWD:
+    case NUNET_LOSS_ENTRY_BCE_DICE_BWD:
+      NUNET_REQUIRE(N > 0, "loss launch info: N = %d", (int)N);
+      gx = entry == NUNET_LOSS_ENTRY_BCE_DICE_FWD ? bce_dice_fwd_gx(per_or_n) : bce_dice_bwd_gx(per_or_n); gy = N;
+      break;
+    case NUNET_LOSS_ENTRY_LOSS_STEP:
+      NUNET_REQUIRE(N > 0 && heads >= 1 && heads <= 8, "loss launch info: N = %d, heads = %d", (int)N, (int)heads);
+      NUNET_REQUIRE(per_or_n <= (1ll << 24), "loss_step: image too large");
+      gx = loss_step_gx(per_or_n); gy = N; gz = heads;
+      break;
+    case NUNET_LOSS_ENTRY_IOU_COUNTS: gx = iou_counts_gx(per_or_n); break;
+    case NUNET_LOSS_ENTRY_SIGMOID_U8: gx = sigmoid_u8_gx(per_or_n); items = per_or_n / 4; break;
+    default: NUNET_REQUIRE(false, "loss launch info: entry %d", (int)entry);
+  }
+  const int64_t threads = (int64_t)gx * 256;
+  out->grid_x = gx; out->grid_y = gy; out->grid_z = gz; out->block = 256;
+  out->items = items;
+  out->trips_max = ceil_div64(items, threads);
+  out->trips_min = items / threads;
+  return NUNET_OK;
 }
 
 // ---------------------------------------------------------------------------
