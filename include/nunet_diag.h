@@ -67,6 +67,38 @@ typedef struct {
 } nunet_wgrad_launch_info;
 int nunet_conv3x3_wgrad_launch_info(const nunet_wgrad_desc* d, nunet_wgrad_launch_info* out);
 
+/* Read-only accessor of the block-output GRADIENT slots, the counterpart of nunet_plan_feature: arena byte offset, pitch and
+ * channel count of dL/dx_{i,j} (NHWC, in the plan's STORAGE dtype - fp32, bf16 or fp16 as the plan was created). The gradient
+ * level buffers are bump-allocated on their own, beside the feature buffers and apart from every per-block scratch: no
+ * kernel of the backward pass writes a slot after its last consumer has accumulated into it, so after nunet_plan_backward
+ * every slot still holds the complete gradient its block's backward started from. Returns -1 when the plan has no block (i, j). */
+int64_t nunet_plan_feature_grad(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels);
+/* ... and of a1 = relu(bn1(conv1(input))) of block (i, j), the activation between its two convolutions, which a training forward
+ * stores (dense: pitch == channels) for the weight gradient of conv2 and no later kernel writes. With x_{i,j} > 0 it gives a test
+ * the ReLU decisions the pass actually took. */
+int64_t nunet_plan_block_act1(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels);
+
+/* Launch census of the last forward (pass 0) and the last backward (pass 1) the plan issued: one entry per 3x3 convolution
+ * (forward conv or input gradient) and one per weight-gradient pair, in the order the plan handed them to its scheduler, with
+ * the op label the scheduler gives them ("B<i><j>.conv1", ".conv2", ".dgrad2", ".dgrad1", ".wgrad") and the launch geometry
+ * nunet_conv3x3_launch_info / nunet_conv3x3_wgrad_launch_info report for the descriptor the plan actually built (its real
+ * K-split workspace, fused BatchNorm-backward reduce, input transform and destination split). Host bookkeeping only: no device
+ * work, no synchronisation; a pass replayed from a graph leaves the census of its capture. */
+enum { NUNET_CENSUS_CONV = 0, NUNET_CENSUS_WGRAD_PAIR = 1 };
+typedef struct {
+  char label[32];
+  int32_t kind;                     /* NUNET_CENSUS_CONV: `conv` and the descriptor facts below; NUNET_CENSUS_WGRAD_PAIR: `wgrad[0..1]` (conv1, conv2) */
+  int32_t N, H, W;
+  int32_t C0, C1, D0, D1;           /* conv: source and destination split of the descriptor */
+  int32_t in_tf, has_bn_y;          /* conv: input transform (NUNET_TF_*), fused BatchNorm-backward reduce */
+  uint32_t acc0_mask;               /* conv: accumulating dst0 slots */
+  int64_t splitk_ws_floats;         /* conv: K-split workspace offered (0: none) */
+  nunet_conv_launch_info conv;
+  nunet_wgrad_launch_info wgrad[2];
+} nunet_plan_census_entry;
+int32_t nunet_plan_census_count(const nunet_plan* p, int32_t pass);
+int nunet_plan_census_get(const nunet_plan* p, int32_t pass, int32_t index, nunet_plan_census_entry* out);
+
 /* Launch geometry of the BCE-Dice loss, the fused loss step (NUNET_LOSS_BCE_DICE), the IoU counts and the mask export, from
  * the very expressions their launches use. A pure host function: no GPU call, no pointer but `out`. N and heads are read where
  * the entry has them (the two losses; heads by the loss step alone), per_or_n is the elements per image of a loss and the

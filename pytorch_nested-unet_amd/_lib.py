@@ -89,6 +89,16 @@ class WgradLaunchInfo(C.Structure):
                                     "ksplit", "grid")]
 
 
+CENSUS_CONV, CENSUS_WGRAD_PAIR = 0, 1
+
+
+class PlanCensusEntry(C.Structure):
+    """nunet_plan_census_entry (include/nunet_diag.h): one convolution or weight-gradient pair the plan issued."""
+    _fields_ = [("label", C.c_char * 32), ("kind", _i32), ("N", _i32), ("H", _i32), ("W", _i32),
+                ("C0", _i32), ("C1", _i32), ("D0", _i32), ("D1", _i32), ("in_tf", _i32), ("has_bn_y", _i32),
+                ("acc0_mask", _u32), ("splitk_ws_floats", _i64), ("conv", ConvLaunchInfo), ("wgrad", WgradLaunchInfo * 2)]
+
+
 LOSS_ENTRY_BCE_DICE_FWD, LOSS_ENTRY_BCE_DICE_BWD, LOSS_ENTRY_LOSS_STEP, LOSS_ENTRY_IOU_COUNTS, LOSS_ENTRY_SIGMOID_U8 = range(5)
 
 
@@ -210,6 +220,10 @@ _SIG = {
     "nunet_plan_grad_sqnorm": (_i32, [_vp, _vp, _sz, _vp, _sz, _vp]),
     "nunet_plan_repack": (_i32, [_vp, _vp, _vp, _sz, _vp]),
     "nunet_plan_feature": (_i64, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "nunet_plan_feature_grad": (_i64, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "nunet_plan_block_act1": (_i64, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "nunet_plan_census_count": (_i32, [_vp, _i32]),
+    "nunet_plan_census_get": (_i32, [_vp, _i32, _i32, C.POINTER(PlanCensusEntry)]),
     "nunet_plan_set_multistream": (_i32, [_vp, _i32]),
     "nunet_plan_set_schedule": (_i32, [_vp, _i32]),
     "nunet_plan_calibrate": (_i32, [_vp, _i32]),

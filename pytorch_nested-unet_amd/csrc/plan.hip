@@ -394,6 +394,7 @@ struct PlanRt {  // runtime objects owned by the plan (host side only)
   struct Sched* open_sched;                // backward pass left open after phase 1 (nunet_plan_backward_phase bit 3): lanes, dependency state
   std::vector<hipEvent_t> b0_events;       // ... and the last-writer events of the first bucket's gradients, for nunet_plan_bucket0_wait
   std::vector<std::string> stamp_labels[2];
+  std::vector<nunet_plan_census_entry> census[2];   // nunet_plan_census_*: the convolutions / weight-gradient pairs of the last forward [0] / backward [1]
 };
 void graph_tag_tail(hipStream_t st, int lane);   // graph.hip: lane bookkeeping of an active nunet_graph capture
 int graph_record_external(hipStream_t st, hipEvent_t ev);   // graph.hip: event record node at the tail of a capturing stream
@@ -661,6 +662,36 @@ extern "C" int64_t nunet_plan_feature(const nunet_plan* p, int32_t i, int32_t j,
   return -1;
 }
 
+extern "C" int64_t nunet_plan_feature_grad(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels) {
+  if (!p || i < 0 || i > 4) return -1;
+  for (size_t k = 0; k < p->exec.size(); ++k)
+    if (p->exec[k].i == i && p->exec[k].j == j) {
+      if (pitch) *pitch = p->PX[i];
+      if (channels) *channels = NBF[i];
+      return (int64_t)(p->GX[i] + (size_t)p->exec[k].out_slot * NBF[i] * p->es);
+    }
+  return -1;
+}
+extern "C" int64_t nunet_plan_block_act1(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels) {
+  if (!p || i < 0 || i > 4) return -1;
+  for (size_t k = 0; k < p->exec.size(); ++k)
+    if (p->exec[k].i == i && p->exec[k].j == j) {
+      if (pitch) *pitch = NBF[i];
+      if (channels) *channels = NBF[i];
+      return (int64_t)p->exec[k].a1;
+    }
+  return -1;
+}
+extern "C" int32_t nunet_plan_census_count(const nunet_plan* p, int32_t pass) {
+  return (p && p->rt && (pass == 0 || pass == 1)) ? (int32_t)p->rt->census[pass].size() : 0;
+}
+extern "C" int nunet_plan_census_get(const nunet_plan* p, int32_t pass, int32_t index, nunet_plan_census_entry* out) {
+  NUNET_REQUIRE(p && p->rt && out && (pass == 0 || pass == 1), "plan_census_get: bad args");
+  NUNET_REQUIRE(index >= 0 && (size_t)index < p->rt->census[pass].size(), "plan_census_get: index out of range");
+  *out = p->rt->census[pass][index];
+  return NUNET_OK;
+}
+
 #define CK(expr)                \
   do {                          \
     int rc_ = (expr);           \
@@ -778,8 +809,25 @@ struct Sched {
   // ---- deferred ops: the backward pass collects its ops first (descriptors captured by value), then issues them
   struct Op { int lane, leaf; float cost; int nrd, nwr; int rd[12], wr[8]; char name[32]; std::function<int(hipStream_t)> fn; };
   std::vector<Op> ops;
+  // launch census (nunet_diag.h): the geometry the launch's own host queries report for the descriptor handed to the scheduler
+  void census_conv(const nunet_conv_desc& d) {
+    nunet_plan_census_entry e; memset(&e, 0, sizeof(e));
+    memcpy(e.label, cur_name, sizeof(e.label)); e.label[sizeof(e.label) - 1] = 0;
+    e.kind = NUNET_CENSUS_CONV; e.N = d.N; e.H = d.H; e.W = d.W;
+    e.C0 = d.C0; e.C1 = d.C1; e.D0 = d.D0; e.D1 = d.D1; e.in_tf = d.in_tf; e.has_bn_y = d.bn_y != nullptr; e.acc0_mask = d.acc0_mask;
+    e.splitk_ws_floats = d.splitk_ws ? d.splitk_ws_floats : 0;
+    if (nunet_conv3x3_launch_info(&d, &e.conv) == NUNET_OK) rt->census[pass & 1].push_back(e);
+  }
+  void census_wgrad(const nunet_wgrad_desc& a, const nunet_wgrad_desc& b) {
+    nunet_plan_census_entry e; memset(&e, 0, sizeof(e));
+    memcpy(e.label, cur_name, sizeof(e.label)); e.label[sizeof(e.label) - 1] = 0;
+    e.kind = NUNET_CENSUS_WGRAD_PAIR; e.N = a.N; e.H = a.H; e.W = a.W;
+    if (nunet_conv3x3_wgrad_launch_info(&a, &e.wgrad[0]) == NUNET_OK && nunet_conv3x3_wgrad_launch_info(&b, &e.wgrad[1]) == NUNET_OK)
+      rt->census[pass & 1].push_back(e);
+  }
   // a 3x3 convolution (forward or input gradient)
   void add_conv(int lane, std::initializer_list<int> rd, std::initializer_list<int> wr, const nunet_conv_desc& d, int alg_cin = 0) {
+    census_conv(d);
     const double px = (double)d.N * d.H * d.W;
     add(lane, 0, 6.f + (float)(2.0 * 9 * (d.C0 + d.C1) * (d.D0 + d.D1) * px / 4e8), rd, wr, [d, alg_cin](hipStream_t ls) {
       g_prof_alg_cin = alg_cin; const int r = nunet_conv3x3_fwd(&d, ls); g_prof_alg_cin = 0; return r; });
@@ -918,6 +966,7 @@ void Sched::init(nunet_plan* P, hipStream_t s, int pass_) {
       if (hipMalloc((void**)&rt->stamps, 2 * STAMP_CAP * sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); rt->stamps = nullptr; }
     }
     rt->stamp_labels[pass].clear();
+    rt->census[pass].clear();
     if (rt->stamps) { snprintf(cur_name, sizeof(cur_name), "start"); stamp(s, 0); cur_name[0] = 0; }
   }
   multi = rt->multistream != 0 && rt->lanes_ok && !rt->calibrating;
@@ -1749,6 +1798,7 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
       w1.dw_floats = (int64_t)L1.ks * w1.slab_stride; w2.dw_floats = (int64_t)L2.ks * w2.slab_stride;
       const int alg_cin = (i == 0 && n.in_prefix == 0) ? c.input_channels : 0;
       S.name("B%d%d.wgrad", n.i, n.j);
+      S.census_wgrad(w1, w2);
       int rx[4] = {-1, -1, -1, -1}, r_in = -1, r_up = -1;
       if (n.in_prefix == 0) r_in = (i == 0 ? R_IMG : rb + B_PIN);
       else { for (int q = 0; q < n.in_prefix && q < 4; ++q) rx[q] = R_X + i * 5 + q; r_up = rb + B_UP; }

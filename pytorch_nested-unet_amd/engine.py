@@ -40,8 +40,28 @@ class Plan:
 
     def feature(self, i, j):
         """Block output x_{i,j} as an [N,H_i,W_i,C] NHWC view (tests/debug)."""
+        return self._slot(L.lib().nunet_plan_feature, i, j)
+
+    def feature_grad(self, i, j):
+        """dL/dx_{i,j} as an [N,H_i,W_i,C] NHWC view in the storage dtype, intact after backward (tests/debug)."""
+        return self._slot(L.lib().nunet_plan_feature_grad, i, j)
+
+    def block_act1(self, i, j):
+        """relu(bn1(conv1(.))) of block (i, j) as the training forward stored it, [N,H_i,W_i,C] NHWC (tests/debug)."""
+        return self._slot(L.lib().nunet_plan_block_act1, i, j)
+
+    def census(self, backward):
+        """The convolutions / weight-gradient pairs of the last forward (False) / backward (True): [PlanCensusEntry] (tests/debug)."""
+        lib, out = L.lib(), []
+        for k in range(lib.nunet_plan_census_count(self.handle, int(backward))):
+            e = L.PlanCensusEntry()
+            L.check(lib.nunet_plan_census_get(self.handle, int(backward), k, C.byref(e)), "nunet_plan_census_get")
+            out.append(e)
+        return out
+
+    def _slot(self, query, i, j):
         pitch, ch = C.c_int32(), C.c_int32()
-        off = L.lib().nunet_plan_feature(self.handle, i, j, C.byref(pitch), C.byref(ch))
+        off = query(self.handle, i, j, C.byref(pitch), C.byref(ch))
         if off < 0:
             raise L.NunetError("no feature x%d_%d" % (i, j))
         es = 4 if self.dtype == L.F32 else 2
