@@ -387,17 +387,14 @@ struct PlanRt {  // runtime objects owned by the plan (host side only)
   int lane_low_priority;                   // side lanes of the flag-synchronised program at the lowest stream priority (default 1)
   int calibrating;                         // nunet_plan_calibrate: single lane + stamps, to measure every op's isolated cost
   std::map<std::string, float> op_cost[2]; // measured cost (us) by op name, per pass; empty: the built-in estimates
-  hipEvent_t b0_event;                     // recorded when the first gradient bucket (phase-1 nodes + heads) is complete
-  bool b0_enabled;
   hipStream_t seg_lanes[3];                // side-lane streams of the segmented recording (created together: distinct hardware queues)
   std::vector<hipStream_t> seg_owned;      // every stream seg_pick_lanes created and kept (destroyed with the plan)
-  struct Sched* open_sched;                // backward pass left open after phase 1 (nunet_plan_backward_phase bit 3): lanes, dependency state
+  struct Sched* open_sched;                // backward pass left open after phase 1 (nunet_plan_backward_phase 1|8): lanes, dependency state
   std::vector<hipEvent_t> b0_events;       // ... and the last-writer events of the first bucket's gradients, for nunet_plan_bucket0_wait
   std::vector<std::string> stamp_labels[2];
   std::vector<nunet_plan_census_entry> census[2];   // nunet_plan_census_*: the convolutions / weight-gradient pairs of the last forward [0] / backward [1]
 };
 void graph_tag_tail(hipStream_t st, int lane);   // graph.hip: lane bookkeeping of an active nunet_graph capture
-int graph_record_external(hipStream_t st, hipEvent_t ev);   // graph.hip: event record node at the tail of a capturing stream
 #define STAMP_CAP 512
 __global__ void stamp_kernel(unsigned long long* p) { *p = wall_clock64(); }
 struct nunet_plan;
@@ -614,7 +611,7 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
   rt->calibrating = 0;
   rt->lane_low_priority = 1;
   memset(&rt->upd, 0, sizeof(rt->upd));
-  rt->b0_event = nullptr; rt->b0_enabled = false; rt->open_sched = nullptr;
+  rt->open_sched = nullptr;
   rt->seg_lanes[0] = rt->seg_lanes[1] = rt->seg_lanes[2] = nullptr;
   rt->events_used[0] = rt->events_used[1] = 0;
   { const char* e = getenv("NUNET_MULTISTREAM"); rt->multistream = e ? atoi(e) : 1; }
@@ -1601,9 +1598,14 @@ static int block_of_slot(const nunet_plan* P, int l, int s) {
   return -1;
 }
 
-// phases: 1 = heads and the last anti-diagonal's blocks (75 % of the gradient bytes);
-//         2 = the remaining blocks; 4 = unpack into the flat OIHW gradient arena. 7 = everything.
+// phases (bit 0 = heads and the last anti-diagonal's blocks, 75 % of the gradient bytes; bit 1 = the remaining blocks; bit 2 = unpack
+// into the flat OIHW gradient arena; bit 3 = leave the pass open; bit 4 = continue the open pass) - five values, any other is refused:
+//   3     whole pass                    7      whole pass + unpack (nunet_plan_backward)        4   unpack only
+//   1|8   phase 1, pass left open       2|16   continue the open pass with phase 2 and join
 extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, const float* dlogits, void* arena, size_t arena_bytes, float* grads, int32_t accumulate, int32_t phases, nunet_stream_t s) {
+  if (phases != 3 && phases != 7 && phases != 4 && phases != (1 | 8) && phases != (2 | 16)) {
+    nunet_set_error("plan_backward: phases %d is not one of 3, 7, 4, 1|8 = 9, 2|16 = 18", (int)phases); return NUNET_EINVAL;
+  }
   NUNET_REQUIRE(P && params && dlogits && arena && grads, "plan_backward: null pointer");
   ARENA_CHECK("plan_backward");
   hipStream_t st = (hipStream_t)s;
@@ -1619,11 +1621,11 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
   const int k_split = nnodes - P->first_phase_nodes;      // phase 1: nodes [k_split, nnodes); phase 2: [0, k_split)
   const int k_hi = (phases & 1) ? nnodes - 1 : k_split - 1;
   const int k_lo = (phases & 2) ? 0 : k_split;
-  // bit 3: leave the pass OPEN after this call - no join: the lanes, their tails and the dependency tracker stay alive in the plan,
+  // 1|8: leave the pass OPEN after this call - no join: the lanes, their tails and the dependency tracker stay alive in the plan,
   // the caller's stream is not made to wait for anything, and nunet_plan_bucket0_wait(P, s2) orders another stream behind exactly
-  // the gradients of the first bucket; bit 4: CONTINUE that open pass (its lanes, its tracker) instead of forking anew, and join at
+  // the gradients of the first bucket; 2|16: CONTINUE that open pass (its lanes, its tracker) instead of forking anew, and join at
   // the end. Together they let a data-parallel caller put the first bucket's exchange BESIDE phase 2 inside one captured graph
-  // without the fork / join barrier that cutting the pass into two calls used to cost.
+  // without a fork / join barrier between the phases.
   const bool leave_open = (phases & 8) != 0, cont = (phases & 16) != 0;
   PlanRt* const rt = rt_of(P);
   NUNET_REQUIRE(!cont || rt->open_sched, "plan_backward: phase bit 4 (continue) without an open pass");
@@ -1664,7 +1666,6 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
     });
     written[0][h.slot] = true;
   }
-  const bool b0_inside = (phases & 3) == 3 && rt_of(P)->b0_enabled && !P->cfg.unet;   // bucket 0 signalled from inside the pass
   // in-pass optimiser step: only a WHOLE pass may carry it (a data-parallel caller exchanges the gradients between the phases)
   const auto upd = rt_of(P)->upd;
   const bool inpass = upd.params != nullptr && (phases & 3) == 3;
@@ -1832,28 +1833,6 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
         });
       }
     }
-    // "bucket 0 complete" (data-parallel exchange beside the rest of the backward pass, nunet_plan_bucket0_*): on the otherwise
-    // unused lane 4, ops that read every gradient resource of the phase-1 nodes and the heads; the last one sums the phase's
-    // weight-gradient slabs and records the plan's event - as an external event record node when the pass is being captured
-    if (k == k_split && b0_inside && S.multi) {
-      std::vector<int> rs;
-      for (int kk = k_split; kk < nnodes; ++kk) { rs.push_back(R_GSW + 2 * kk); rs.push_back(R_GSW + 2 * kk + 1); rs.push_back(R_GSV + 2 * kk); rs.push_back(R_GSV + 2 * kk + 1); }
-      for (size_t h = 0; h < P->heads.size(); ++h) rs.push_back(R_GSV + 30 + (int)h);
-      hipEvent_t ev = rt_of(P)->b0_event;
-      for (size_t q = 0; q < rs.size(); q += 10) {
-        const bool last = q + 10 >= rs.size();
-        S.name("b0rdy");
-        S.add_v(4, 1, 0.f, rs.data() + q, (int)std::min<size_t>(10, rs.size() - q), nullptr, 0, [=](hipStream_t ls) {
-          if (!last) return (int)NUNET_OK;
-          hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-          (void)hipStreamIsCapturing(ls, &cs);
-          if (cs == hipStreamCaptureStatusActive) return graph_record_external(ls, ev);
-          const hipError_t e = hipEventRecord(ev, ls);
-          if (e != hipSuccess) { nunet_set_error("plan_backward: bucket-0 event record: %s", hipGetErrorString(e)); return (int)NUNET_ELAUNCH; }
-          return (int)NUNET_OK;
-        });
-      }
-    }
   }
   if (inpass && (phases & 1) && !P->heads.empty()) {
     // the 1x1 heads: blocks past the last tile of the update kernel's numbering
@@ -1890,29 +1869,14 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
   return nunet_check_launch("unpack_grads");
 }
 
-// Data-parallel exchange beside the backward pass. After nunet_plan_bucket0_enable(P, 1), a backward call that runs phases 1 and 2
-// together records the plan's event once every gradient of the first bucket (nunet_plan_grad_scratch) is complete;
-// nunet_plan_bucket0_wait makes `s` wait for the most recent such record (call it after launching the pass or the graph holding it).
-extern "C" int nunet_plan_bucket0_enable(nunet_plan* P, int32_t on) {
-  NUNET_REQUIRE(P, "plan_bucket0_enable: null plan");
-  PlanRt* rt = rt_of(P);
-  if (on && !rt->b0_event && hipEventCreateWithFlags(&rt->b0_event, hipEventDisableTiming) != hipSuccess) {
-    nunet_set_error("plan_bucket0_enable: %s", hipGetErrorString(hipGetLastError())); return NUNET_ELAUNCH;
-  }
-  rt->b0_enabled = on != 0 && !P->cfg.unet;
-  return rt->b0_enabled ? 1 : 0;     // 1: armed; 0: not available for this plan (callers exchange after the pass)
-}
+// Data-parallel exchange beside the backward pass: with the pass left open (phases 1|8), `s` waits for the kernels that complete
+// the first bucket (nunet_plan_grad_scratch), nothing else. While the pass is being captured `s` must be a stream the capture has
+// not used (it joins the capture here, as a lane continuation does).
 extern "C" int nunet_plan_bucket0_wait(nunet_plan* P, nunet_stream_t s) {
   NUNET_REQUIRE(P, "plan_bucket0_wait: null plan");
-  if (rt_of(P)->open_sched) {
-    // an open pass (backward phase bit 3): `s` waits for the kernels that complete the first bucket, nothing else. While the pass is
-    // being captured `s` must be a stream the capture has not used (it joins the capture here, as a lane continuation does).
-    for (hipEvent_t e : rt_of(P)->b0_events)
-      if (hipStreamWaitEvent((hipStream_t)s, e, 0) != hipSuccess) { nunet_set_error("plan_bucket0_wait: %s", hipGetErrorString(hipGetLastError())); return NUNET_ELAUNCH; }
-    return NUNET_OK;
-  }
-  NUNET_REQUIRE(rt_of(P)->b0_event && rt_of(P)->b0_enabled, "plan_bucket0_wait: neither an open pass nor the bucket-0 event is armed");
-  if (hipStreamWaitEvent((hipStream_t)s, rt_of(P)->b0_event, 0) != hipSuccess) { nunet_set_error("plan_bucket0_wait: %s", hipGetErrorString(hipGetLastError())); return NUNET_ELAUNCH; }
+  NUNET_REQUIRE(rt_of(P)->open_sched, "plan_bucket0_wait: no open pass (nunet_plan_backward_phase 1|8 comes first)");
+  for (hipEvent_t e : rt_of(P)->b0_events)
+    if (hipStreamWaitEvent((hipStream_t)s, e, 0) != hipSuccess) { nunet_set_error("plan_bucket0_wait: %s", hipGetErrorString(hipGetLastError())); return NUNET_ELAUNCH; }
   return NUNET_OK;
 }
 

@@ -30,6 +30,16 @@ from .optim_state import flat_to_torch_state, torch_state_to_flat
 from .parallel import allreduce_flat_, broadcast_flat_
 
 
+def dp_layout_from_env(environ):
+    """(layout, auto) of the data-parallel step from NUNET_DP_MODE: unset / 'auto' -> (1, True), '1' -> (1, False),
+    '3' -> (3, False); any other value raises. No GPU use."""
+    mode = environ.get("NUNET_DP_MODE", "auto")
+    if mode not in ("auto", "1", "3"):
+        raise L.NunetError("TrainStep: NUNET_DP_MODE %r: the data-parallel step layouts are 1, one exchange of the whole gradient "
+                           "scratch behind the backward pass, and 3, both bucket exchanges inside the step's graph (or auto)" % (mode,))
+    return (1, True) if mode == "auto" else (int(mode), False)
+
+
 class TrainStep:
     def __init__(self, model, batch_shape, lr=1e-3, momentum=0.9, weight_decay=1e-4, nesterov=False,
                  use_graph=True, process_group=None, keep_grads=True, fused_update=None, loss="BCEDiceLoss", input_u8=False,
@@ -156,27 +166,23 @@ class TrainStep:
         self.steps = 0
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (process_group is not None or dist.is_initialized()) else 1
-        # NUNET_FORCE_DP=1: take the data-parallel code path (bucketed exchange, three graphs) with any world size, so that a
+        # NUNET_FORCE_DP=1: take the data-parallel code path (the gradient exchange of layout 1 or 3) with any world size, so that a
         # one-GPU box can rehearse it over RCCL with a single rank (bench.py initialises the process group)
         self.dp = self.world > 1 or (os.environ.get("NUNET_FORCE_DP") == "1" and dist.is_initialized())
         if self.dp:
             # RCCL's high-priority stream lives in this process: beside it lowest-priority lanes are served in time slices
             L.check(L.lib().nunet_plan_set_lane_priority(self.pl.handle, 0), "plan_set_lane_priority")
-        # Data-parallel step layout (NUNET_DP_MODE). 1 (default): one lane-faithful graph for forward + loss + the whole
-        # backward, ONE exchange of the complete gradient scratch, one graph for unpack + SGD. 0: backward cut in two phases
-        # so that bucket 0's exchange runs beside phase 2. Measured on one MI355X (single-rank RCCL group,
-        # NUNET_FORCE_DP=1 python bench.py): the cut costs 350-500 us per step (phase 1 is the anti-diagonal's dependency chain with nothing
-        # beside it, 2.71 ms vs 2.18 ms) - more than the 36.7 MB exchange it hides is expected to take on >= 4 GPUs.
+        # Data-parallel step layout (NUNET_DP_MODE), two of them. 1 (default): one lane-faithful graph for forward + loss + the
+        # whole backward, ONE exchange of the complete gradient scratch, one graph for unpack + the optimiser step.
         # 3: the whole step is ONE graph that contains both exchanges as nodes: the backward pass is issued as phase 1 left open
-        # (nunet_plan_backward_phase bit 3: no join), the first bucket's all-reduce goes to a side stream that waits for exactly
-        # the kernels producing it, phase 2 continues on the open lanes beside it, the second bucket and the optimiser step
-        # follow the join. Overlap without a fork / join barrier inside the pass and without any host call during the step
+        # (nunet_plan_backward_phase 1|8: no join), the first bucket's all-reduce goes to a side stream that waits for exactly
+        # the kernels producing it, phase 2 continues on the open lanes beside it (2|16), the second bucket and the optimiser
+        # step follow the join. Overlap without a fork / join barrier inside the pass and without any host call during the step
         # (RCCL only: a gloo exchange is a host round trip and cannot be captured).
         # NUNET_DP_MODE unset / "auto": with more than one rank, capture() times layouts 1 and 3 on the real exchange and
         # keeps the faster (the decision is all-reduced, so every rank takes the same one); one rank: layout 1.
-        mode = os.environ.get("NUNET_DP_MODE", "auto")
-        self.dp_auto = mode == "auto" and self.dp
-        self.dp_mode = 1 if mode == "auto" else int(mode)
+        self.dp_mode, auto = dp_layout_from_env(os.environ)
+        self.dp_auto = auto and self.dp
         if self.dp and self.dp_mode == 3 and dist.get_backend(process_group) == "gloo":
             self.dp_mode = 1             # a gloo exchange is a host round trip: it cannot sit inside the step's graph
         self.dp_choice = None        # {layout: ms per step} when the layout was chosen by measurement
@@ -200,22 +206,14 @@ class TrainStep:
         self._inpass_set = False
         self._packed = False          # the arena's packed weights match the fp32 parameters
         self.g_fb = None
-        self.g_b2 = None
         self.g_opt = None
         self._buckets = self._grad_scratch() if self.dp else None
         if self.scaler_cfg is not None and not self.dp:
             self._grad_scratch()             # (self._scratch: what the overflow check reads)
-        self._b0_armed = False
-        self._comm = torch.cuda.Stream() if self.dp else None
-        if self.dp and self.dp_mode == 2:
-            self._arm_bucket0(True)
         for p, off in zip(self.eng.module_params, self.eng.param_off):
             p.grad = self.eng.flat_grads[off:off + p.numel()].view(p.shape)
         if self.world > 1:
             self.broadcast_state()
-
-    def _arm_bucket0(self, on):
-        self._b0_armed = L.lib().nunet_plan_bucket0_enable(self.pl.handle, 1 if on else 0) == 1
 
     def broadcast_state(self, src=0):
         """Rank `src`'s parameters, optimiser state (momentum; Adam's moments and step), loss-scaler state, clip state (max_norm
@@ -339,7 +337,6 @@ class TrainStep:
 
     def _grad_scratch(self):
         """The plan's native-layout gradient scratch as two fp32 views in gradient-ready order."""
-        import ctypes as C
         off, b0, tot = C.c_int64(), C.c_int64(), C.c_int64()
         L.check(L.lib().nunet_plan_grad_scratch(self.pl.handle, C.byref(off), C.byref(b0), C.byref(tot)), "plan_grad_scratch")
         flat = self.pl.arena[off.value:off.value + 4 * tot.value].view(torch.float32)
@@ -353,42 +350,14 @@ class TrainStep:
             return None
         return dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
 
-    def _dp_step(self, run1, run2, run3):
-        """Data-parallel step: bucket 0 (heads + the last anti-diagonal = 75 % of the gradient bytes,
-        complete after backward phase 1) is all-reduced while phase 2 runs; bucket 1 follows; unpack +
-        SGD (grad_scale 1/world) run on the reduced scratch."""
-        if self.dp_mode in (1, 2):
-            run1()
-            if run2 is not None:
-                run2()
-            if self.dp_mode == 2 and self._b0_armed and dist.get_backend(self.pg) != "gloo":
-                # bucket 0 starts on the side stream as soon as the pass (still running) has recorded "bucket 0
-                # complete"; bucket 1 follows the pass on the caller's stream
-                b0, b1 = self._buckets
-                cur = torch.cuda.current_stream()
-                L.check(L.lib().nunet_plan_bucket0_wait(self.pl.handle, self._comm.cuda_stream), "plan_bucket0_wait")
-                with torch.cuda.stream(self._comm):
-                    h0 = dist.all_reduce(b0, op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
-                h1 = dist.all_reduce(b1, op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
-                with torch.cuda.stream(self._comm):
-                    h0.wait()
-                cur.wait_stream(self._comm)
-                h1.wait()
-            else:
-                h = self._exchange(self._scratch)
-                if h is not None:
-                    h.wait()
-            run3()
-            return
-        b0, b1 = self._buckets
-        run1()
-        h0 = self._exchange(b0)
-        run2()
-        h1 = self._exchange(b1)
-        for h in (h0, h1):
-            if h is not None:
-                h.wait()
-        run3()
+    def _exchange_after_pass_step(self, run_pass, run_opt):
+        """Layout 1: forward + loss + the whole backward pass, ONE all-reduce of the complete gradient scratch, then unpack + the
+        optimiser step (grad_scale 1/world) on the reduced scratch."""
+        run_pass()
+        h = self._exchange(self._scratch)
+        if h is not None:
+            h.wait()
+        run_opt()
 
     def _in_graph_exchange_step(self):
         """Layout 3: forward, loss, the backward pass with both gradient exchanges and the optimiser step as one stream of
@@ -419,17 +388,11 @@ class TrainStep:
         if self.dp and self.dp_mode == 3:
             return self._in_graph_exchange_step()
         if self.dp:
-            one_pass = self.dp_mode in (1, 2)     # the bucket-0 event is recorded by a pass that runs both phases together
-            self._dp_step((lambda: (self._fwd_loss(), self._bwd(3))) if one_pass else (lambda: (self._fwd_loss(), self._bwd(1))),
-                          None if one_pass else (lambda: self._bwd(2)),
-                          lambda: (None if self.fused_update else self._bwd(4), self._opt()))
+            self._exchange_after_pass_step(lambda: (self._fwd_loss(), self._bwd(3)),
+                                           lambda: (None if self.fused_update else self._bwd(4), self._opt()))
         else:
             self._fwd_bwd()
             self._opt()
-
-    def _allreduce(self):
-        if self.world > 1:
-            allreduce_flat_(self.eng.flat_grads, self.pg)
 
     def capture(self, inp, target):
         """Capture forward+loss+backward(+SGD) into hipGraphs. Needs one REAL batch for the
@@ -471,23 +434,10 @@ class TrainStep:
         else:
             if self.dp_auto:
                 self._choose_layout(s)
-            if self.dp_mode in (1, 2):
+            if self.dp_mode == 1:
                 self._capture_one_pass(s)
-            elif self.dp_mode == 3:
+            else:
                 self._capture_in_graph_exchange(s)
-        if self.dp and self.dp_mode not in (1, 2, 3):
-            self.g_fb = torch.cuda.CUDAGraph()          # forward + loss + backward phase 1
-            with torch.cuda.graph(self.g_fb, capture_error_mode="thread_local"):   # (the RCCL watchdog thread polls events meanwhile)
-                self._fwd_loss()
-                self._bwd(1)
-            self.g_b2 = torch.cuda.CUDAGraph()          # backward phase 2
-            with torch.cuda.graph(self.g_b2, capture_error_mode="thread_local"):   # (the RCCL watchdog thread polls events meanwhile)
-                self._bwd(2)
-            self.g_opt = torch.cuda.CUDAGraph()         # unpack + SGD
-            with torch.cuda.graph(self.g_opt, capture_error_mode="thread_local"):   # (the RCCL watchdog thread polls events meanwhile)
-                if not self.fused_update:
-                    self._bwd(4)
-                self._opt()
         torch.cuda.synchronize()
         with torch.no_grad():
             for dst, src in zip(state, snap):
@@ -594,27 +544,21 @@ class TrainStep:
         self.segmented = best[0]
 
     def _capture_one_pass(self, s):
-        """Layouts 1 and 2: forward + loss + the whole backward as one graph (layout 2: with the bucket-0 event recorded
-        inside it), the exchange between, unpack + SGD as a second graph."""
-        self._arm_bucket0(self.dp_mode == 2)
+        """Layout 1: forward + loss + the whole backward as one graph, the exchange between, unpack + the optimiser step as a
+        second graph. The pass may run as flag-synchronised list-scheduled lanes (self.dp_exec, chosen by _choose_layout)."""
         body = lambda: (self._fwd_loss(), self._bwd(3))
-        # layout 1 may run its pass as flag-synchronised list-scheduled lanes (self.dp_exec, chosen by _choose_layout); layout 2
-        # records an event inside the pass's graph and keeps the single hipGraph
-        ex = self.dp_exec if self.dp_mode == 1 else (False, "lanes")
-        self.g_fb = self._build_executor(s, body, *ex)
-        self.g_b2 = None
+        self.g_fb = self._build_executor(s, body, *self.dp_exec)
         self.g_opt = _NativeGraph(s, lambda: (None if self.fused_update else self._bwd(4), self._opt()))
 
     def _capture_in_graph_exchange(self, s):
         """Layout 3: the whole data-parallel step, exchanges included, as one graph."""
         self.g_fb = _NativeGraph(s, self._in_graph_exchange_step)
-        self.g_b2 = self.g_opt = None
+        self.g_opt = None
 
     def _choose_layout(self, s, reps=8):
         """Time layout 1 (one exchange after the pass) against layout 3 (both exchanges inside the step's graph, bucket 0
         beside phase 2 of the backward pass) on the real process group and keep the faster. The caller restores the
-        training state. (Layout 2 - an event recorded inside the graph - stays selectable but is not a candidate: ROCm 7.2
-        releases a waiter on such an event only when the graph ends, tests/test_dist_gpu.py.)"""
+        training state."""
         times = []
         modes = [(1, (False, "lanes"))]
         if dist.get_backend(self.pg) != "gloo":
@@ -646,7 +590,7 @@ class TrainStep:
                     run = self.g_fb.replay
                 else:
                     self._capture_one_pass(s)
-                    run = lambda: self._dp_step(self.g_fb.replay, None, self.g_opt.replay)
+                    run = lambda: self._exchange_after_pass_step(self.g_fb.replay, self.g_opt.replay)
             except Exception as e:       # e.g. a runtime that cannot capture the collectives, no two streams on distinct queues
                 err = e
             if not all_agree(err is None):
@@ -664,7 +608,7 @@ class TrainStep:
         else:
             dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.pg)     # the slowest rank decides, identically everywhere
         t = t.tolist()
-        label = lambda m, ex: {1: "exchange_after_pass", 2: "bucket0_event_in_graph", 3: "exchange_inside_graph"}[m] + ("" if ex[0] is False else "/flags+list")
+        label = lambda m, ex: {1: "exchange_after_pass", 3: "exchange_inside_graph"}[m] + ("" if ex[0] is False else "/flags+list")
         self.dp_choice = {label(m, ex): v for (m, ex), v in zip(modes, t)}
         best = min(range(len(t)), key=lambda q: t[q])
         self.dp_mode, self.dp_exec = modes[best]
@@ -701,7 +645,7 @@ class TrainStep:
                                "after this TrainStep was built: its graphs would update orphaned memory. Build a new TrainStep.")
         if self.g_fb is not None:
             if self.dp and self.dp_mode != 3:
-                self._dp_step(self.g_fb.replay, self.g_b2.replay if self.g_b2 is not None else None, self.g_opt.replay)
+                self._exchange_after_pass_step(self.g_fb.replay, self.g_opt.replay)
             else:
                 self.g_fb.replay()
         else:

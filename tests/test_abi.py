@@ -118,3 +118,34 @@ def test_only_the_two_kept_schedules_and_recording_modes_are_accepted(lib):
     assert lib.nunet_seg_begin(C.c_void_p(1), 0) == NUNET_EINVAL
     msg = lib.nunet_last_error()
     assert msg and b"seg_begin" in msg and b"mode 0" in msg, msg
+
+
+def test_backward_phase_takes_the_five_issued_values_only(lib):
+    """Host-only: nunet_plan_backward_phase refuses every `phases` value but 3, 7, 4, 1|8, 2|16 before it looks at a pointer - a
+    joined phase 1 or a stand-alone phase 2 is not a state of the pass. An accepted value goes on to the pointer check."""
+    cfg = L.PlanCfg(2, 32, 32, 3, 1, 0, L.F32, 0)
+    p = lib.nunet_plan_create(C.byref(cfg))
+    assert p
+    try:
+        for bad in (0, 1, 2, 5, 6, 8, 11, 16, 19, 32):
+            assert lib.nunet_plan_backward_phase(p, None, None, None, 0, None, 0, bad, None) == NUNET_EINVAL
+            msg = lib.nunet_last_error()
+            assert msg and b"plan_backward" in msg and b"phases %d " % bad in msg, msg
+        assert lib.nunet_plan_backward_phase(p, None, None, None, 0, None, 0, 3, None) == NUNET_EINVAL
+        msg = lib.nunet_last_error()
+        assert msg and b"null pointer" in msg and b"phases" not in msg, msg
+    finally:
+        lib.nunet_plan_destroy(p)
+
+
+def test_bucket0_wait_needs_an_open_pass(lib):
+    """Host-only: on a plan whose backward pass was not left open (phases 1|8) there is nothing to wait for."""
+    cfg = L.PlanCfg(2, 32, 32, 3, 1, 0, L.F32, 0)
+    p = lib.nunet_plan_create(C.byref(cfg))
+    assert p
+    try:
+        assert lib.nunet_plan_bucket0_wait(p, None) == NUNET_EINVAL
+        msg = lib.nunet_last_error()
+        assert msg and b"plan_bucket0_wait" in msg and b"open pass" in msg, msg
+    finally:
+        lib.nunet_plan_destroy(p)

@@ -2,22 +2,14 @@
 replicas stay identical (rank 1 starts from other parameters and BatchNorm buffers, replaced by rank 0's at construction), the
 update is Adam on the rank-mean gradient, and broadcast_state carries the Adam state and step."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
+
+from dist_cases import run_ranks
 
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, use_graph, dp_mode, q):
@@ -54,30 +46,10 @@ def _worker(rank, world, port, use_graph, dp_mode, q):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("use_graph,dp_mode", [(False, 1), (True, 1), (True, 0), (True, "auto")])
+@pytest.mark.parametrize("use_graph,dp_mode", [(False, 1), (True, 1), (True, "auto")])
 def test_two_rank_data_parallel_adam_step(use_graph, dp_mode, synth):
     import nunet_amd
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, use_graph, dp_mode, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    import queue
-    res = {}
-    for _ in range(150):
-        try:
-            r = q.get(timeout=2)
-            res[r[0]] = r[1:]
-            if len(res) == 2:
-                break
-        except queue.Empty:
-            if any(p.exitcode not in (None, 0) for p in procs):
-                break
-    assert len(res) == 2, "a rank failed: exit codes %s" % [p.exitcode for p in procs]
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    res = run_ranks(_worker, 2, use_graph, dp_mode)
     # rank 0's optimiser state (zeros, t = 0) replaced rank 1's
     assert res[0][5] == (0.0, 0.0, 0.0) and res[1][5] == (0.0, 0.0, 0.0)
     # replicas identical after one and after two steps; two steps counted

@@ -3,22 +3,14 @@ the GPU over gloo): the norm is taken after the exchange, so both ranks report t
 rank-mean p.grad / coef - from different batches, apply the same factor without any extra collective and stay identical; rank
 0's max_norm replaces rank 1's at construction."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
+
+from dist_cases import run_ranks
 
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, q):
@@ -61,27 +53,7 @@ def _worker(rank, world, port, q):
 
 
 def test_two_ranks_clip_by_the_same_norm():
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    import queue
-    res = {}
-    for _ in range(150):
-        try:
-            r = q.get(timeout=2)
-            res[r[0]] = r[1:]
-            if len(res) == 2:
-                break
-        except queue.Empty:
-            if any(p.exitcode not in (None, 0) for p in procs):
-                break
-    assert len(res) == 2, "a rank failed: exit codes %s" % [p.exitcode for p in procs]
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    res = run_ranks(_worker, 2)
     n0 = res[0][0]
     assert res[1][0] == n0                                   # the probe already saw the exchanged gradient on both ranks
     want = float(torch.tensor(0.25 * n0, dtype=torch.float32))

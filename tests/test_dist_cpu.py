@@ -1,22 +1,17 @@
 """N>1 host logic on CPU: world_size-2 gloo process group (127.0.0.1 rendezvous)."""
 import os
-import socket
 
 import numpy as np
+import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
 import nunet_amd
+from dist_cases import free_port
+from nunet_amd import _lib as L
 from nunet_amd import parallel
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
+from nunet_amd.trainer import dp_layout_from_env
 
 
 def _worker(rank, world, port, q):
@@ -44,7 +39,7 @@ def _worker(rank, world, port, q):
 def test_gloo_world2_allreduce_and_sgd():
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -103,7 +98,7 @@ def test_bench_under_a_launcher_keeps_its_environment():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--dist-dry-run"],
+                        "--master-port", str(free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--dist-dry-run"],
                        capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -113,3 +108,15 @@ def test_bench_under_a_launcher_keeps_its_environment():
 def test_bench_rejects_a_world_size_that_contradicts_gpus():
     rc, lines, err = _run_bench(["--gpus", "2", "--dist-dry-run"], {"WORLD_SIZE": "3", "RANK": "0"})
     assert rc != 0 and not lines and "does not match" in err
+
+
+def test_dp_layout_from_env_takes_the_two_layouts_that_exist():
+    """NUNET_DP_MODE: unset / auto -> layout 1, to be timed against 3 at capture; 1 and 3 as given; the removed layouts (0: backward
+    cut in two graphs; 2: event recorded inside the graph) and anything else raise, naming the value."""
+    assert dp_layout_from_env({}) == (1, True)
+    assert dp_layout_from_env({"NUNET_DP_MODE": "auto"}) == (1, True)
+    assert dp_layout_from_env({"NUNET_DP_MODE": "1"}) == (1, False)
+    assert dp_layout_from_env({"NUNET_DP_MODE": "3"}) == (3, False)
+    for bad in ("0", "2", "4", "fast"):
+        with pytest.raises(L.NunetError, match="NUNET_DP_MODE %r" % bad):
+            dp_layout_from_env({"NUNET_DP_MODE": bad})

@@ -2,22 +2,14 @@
 gloo (RCCL cannot put two ranks on one device). Checks the DP step (trainer.TrainStep, world=2):
 replicas stay identical and the update equals SGD on the rank-averaged gradient."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
+
+from dist_cases import run_ranks
 
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, use_graph, dp_mode, q):
@@ -58,30 +50,10 @@ def _worker(rank, world, port, use_graph, dp_mode, q):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("use_graph,dp_mode", [(False, 1), (True, 1), (True, 0), (True, "auto")])
+@pytest.mark.parametrize("use_graph,dp_mode", [(False, 1), (True, 1), (True, "auto")])
 def test_two_rank_data_parallel_step(use_graph, dp_mode, synth):
     import nunet_amd
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, use_graph, dp_mode, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    import queue
-    res = {}
-    for _ in range(150):
-        try:
-            r = q.get(timeout=2)
-            res[r[0]] = r[1:]
-            if len(res) == 2:
-                break
-        except queue.Empty:
-            if any(p.exitcode not in (None, 0) for p in procs):
-                break
-    assert len(res) == 2, "a rank failed: exit codes %s" % [p.exitcode for p in procs]
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    res = run_ranks(_worker, 2, use_graph, dp_mode)
     # replicas identical after one and after two steps
     assert np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][2], res[1][2])
     assert np.array_equal(res[0][1], res[1][1])
@@ -107,91 +79,9 @@ def test_two_rank_data_parallel_step(use_graph, dp_mode, synth):
     assert np.array_equal(res[0][5], res[0][4]) and np.array_equal(res[1][5], res[0][4])
 
 
-def _bucket0_worker(port, q):
-    os.environ.update(NUNET_DP_MODE="2", NUNET_FORCE_DP="1", NUNET_DEBUG_SPIN_US="2000", RANK="0", WORLD_SIZE="1",
-                      MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    import torch.distributed as dist
-    import nunet_amd
-    from nunet_amd import _lib as L
-    from nunet_amd.trainer import TrainStep
-    torch.cuda.set_device(0)
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-    synth = nunet_amd.synth
-    torch.manual_seed(0)
-    m = nunet_amd.archs.NestedUNet(1, 3, False, dtype="bf16").cuda().train()
-    ts = TrainStep(m, (16, 3, 96, 96), lr=1e-3)
-    assert ts.dp and ts._b0_armed
-    batches = []
-    for k in range(4):
-        img, msk = synth.synth_batch(16, 96, 96, 3, 1, seed=900 + k)
-        batches.append((torch.from_numpy(img).cuda(), torch.from_numpy(msk).cuda()))
-    ts.capture(*batches[0])
-    b0, _ = ts._buckets
-    side = torch.cuda.Stream()
-    snap = torch.empty_like(b0)                           # allocated up front: a device malloc would synchronise
-    ok_wait, lead_ms, pass_ms = [], [], []
-    for x, t in batches[1:]:
-        ts.x.copy_(x); ts.t.copy_(t)
-        b0.zero_()                                         # stale on purpose: only this pass can make the snapshot right
-        torch.cuda.synchronize()
-        e_snap, e_end, e_beg = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e_beg.record()
-        ts.g_fb.replay()                                   # forward + loss + whole backward, one graph, still running
-        e_end.record()                                     # end of the pass (caller's stream)
-        L.check(L.lib().nunet_plan_bucket0_wait(ts.pl.handle, side.cuda_stream), "bucket0_wait")
-        with torch.cuda.stream(side):
-            snap.copy_(b0, non_blocking=True)              # ordered after "bucket 0 complete" only
-            e_snap.record()
-        torch.cuda.synchronize()
-        ok_wait.append(bool(torch.equal(snap, b0)) and float(b0.abs().sum()) > 0)
-        lead_ms.append(e_snap.elapsed_time(e_end))         # > 0: the snapshot was complete before the pass ended
-        pass_ms.append(e_beg.elapsed_time(e_end))
-        ts.g_opt.replay()
-    # and the full step in this layout still trains
-    for x, t in batches:
-        ts.step(x, t)
-    torch.cuda.synchronize()
-    loss, iou = ts.epoch_stats()
-    q.put((ok_wait, lead_ms, pass_ms, loss))
-    dist.destroy_process_group()
-
-
-def test_bucket0_event_orders_the_exchange_inside_the_graph():
-    """NUNET_DP_MODE=2: a stream that waits on the plan's bucket-0 event after the graph launch sees the first bucket's
-    FINAL gradients (bitwise), and the full step in this layout trains."""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p = ctx.Process(target=_bucket0_worker, args=(_free_port(), q))
-    p.start()
-    import queue
-    res = None
-    for _ in range(150):                      # a worker that died must not hold the GPU box for the full timeout
-        try:
-            res = q.get(timeout=2)
-            break
-        except queue.Empty:
-            if p.exitcode not in (None, 0):
-                break
-    p.join(60)
-    assert res is not None and p.exitcode == 0, "worker failed (exit code %s)" % p.exitcode
-    ok_wait, lead_ms, pass_ms, loss = res
-    assert all(ok_wait), ok_wait            # ordering: the waiting stream read the FINAL first bucket, bit for bit
-    assert np.isfinite(loss)
-    # control: phase 2 is headed by a 2 ms spin kernel (NUNET_DEBUG_SPIN_US), so the pass lasts > 3.5 ms and a stream that
-    # is released by the bucket-0 event - not by the end of the graph - finishes its copy of the 27 MB bucket at least
-    # 1 ms before the pass ends; a copy that merely queued behind the whole graph gives a lead near zero.
-    print("pass (ms):", pass_ms, "bucket-0 lead over the end of the pass (ms):", lead_ms)
-    assert min(pass_ms) > 3.5, pass_ms
-    if min(lead_ms) <= 1.0:
-        pytest.xfail("ROCm 7.2 on this box releases a stream waiting on an event-record node of a running hipGraph only when "
-                     "the graph is (almost) done: lead %.3f ms with 2 ms of phase 2 still to run. Layout 2 therefore buys no "
-                     "overlap here; TrainStep's NUNET_DP_MODE=auto times layouts 1 and 2 and keeps the faster (DESIGN.md §6)."
-                     % min(lead_ms))
-
-
 def _rccl_worker(rank, world, port, q):
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    os.environ.pop("NUNET_DP_MODE", None)                 # auto: layouts 1 and 2 are timed, the faster is kept
+    os.environ.pop("NUNET_DP_MODE", None)                 # auto: layouts 1 and 3 are timed, the faster is kept
     import torch.distributed as dist
     import nunet_amd
     from nunet_amd.trainer import TrainStep
@@ -218,33 +108,14 @@ def _rccl_worker(rank, world, port, q):
 def test_rccl_two_gpus_replicas_stay_identical():
     """The real exchange: two ranks on two GPUs over RCCL, step layout chosen by measurement (NUNET_DP_MODE auto).
     Replicas that were initialised differently are identical after construction and stay identical through training."""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_rccl_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    import queue
-    res = {}
-    for _ in range(150):
-        try:
-            r = q.get(timeout=2)
-            res[r[0]] = r[1:]
-            if len(res) == 2:
-                break
-        except queue.Empty:
-            if any(p.exitcode not in (None, 0) for p in procs):
-                break
-    for p in procs:
-        p.join(60)
-    assert len(res) == 2 and all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
+    res = run_ranks(_rccl_worker, 2)
     assert np.array_equal(res[0][0], res[1][0])
     assert np.isfinite(res[0][1]) and np.isfinite(res[1][1])
     assert res[0][2] == res[1][2] and res[0][2] in (1, 3)          # the same measured layout on both ranks
     print("layout chosen:", res[0][2], "ms per layout:", res[0][3])
 
 
-def _in_graph_worker(port, q):
+def _in_graph_worker(rank, world, port, q):
     os.environ.update(NUNET_FORCE_DP="1", NUNET_DEBUG_SPIN_US="2000", RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     import ctypes as C
     import torch.distributed as dist
@@ -299,7 +170,7 @@ def _in_graph_worker(port, q):
         torch.cuda.synchronize()
         out[mode] = (ts.eng.flat_params.clone().cpu(), ts.mom.clone().cpu(), ts.epoch_stats(), leads)
         del ts, m
-    q.put((bool(torch.equal(out[1][0], out[3][0]) and torch.equal(out[1][1], out[3][1])), out[1][2], out[3][2], out[3][3]))
+    q.put((rank, bool(torch.equal(out[1][0], out[3][0]) and torch.equal(out[1][1], out[3][1])), out[1][2], out[3][2], out[3][3]))
     dist.destroy_process_group()
 
 
@@ -310,22 +181,7 @@ def test_exchange_inside_the_step_graph_overlaps_phase_two():
       * the first bucket's exchange sits on a side branch that is released by its producing kernels, not by the end of the pass:
         with a 2 ms spin kernel heading phase 2 (NUNET_DEBUG_SPIN_US) the bucket is ready - and bitwise final - more than 1 ms
         before the step ends, while the second bucket is ready only at the end of the pass."""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p = ctx.Process(target=_in_graph_worker, args=(_free_port(), q))
-    p.start()
-    import queue
-    res = None
-    for _ in range(200):
-        try:
-            res = q.get(timeout=2)
-            break
-        except queue.Empty:
-            if p.exitcode not in (None, 0):
-                break
-    p.join(60)
-    assert res is not None and p.exitcode == 0, "worker failed (exit code %s)" % p.exitcode
-    same, s1, s3, leads = res
+    same, s1, s3, leads = run_ranks(_in_graph_worker, 1, polls=200)[0]
     assert same, "layout 3 must compute what layout 1 computes"
     assert s1 == s3 and np.isfinite(s1[0])
     print("ms from bucket-ready to the end of the step (bucket 0, bucket 1):", leads)

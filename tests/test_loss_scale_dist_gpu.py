@@ -2,22 +2,14 @@
 over gloo): rank 0's scaler state replaces rank 1's at construction, and an inf that only rank 1's gradient holds before the
 exchange makes BOTH ranks skip the step (the exchange carries it; no extra collective) and back off identically."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
+
+from dist_cases import run_ranks
 
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, q):
@@ -61,27 +53,7 @@ def _worker(rank, world, port, q):
 
 
 def test_two_rank_skip_is_collective():
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    import queue
-    res = {}
-    for _ in range(150):
-        try:
-            r = q.get(timeout=2)
-            res[r[0]] = r[1:]
-            if len(res) == 2:
-                break
-        except queue.Empty:
-            if any(p.exitcode not in (None, 0) for p in procs):
-                break
-    assert len(res) == 2, "a rank failed: exit codes %s" % [p.exitcode for p in procs]
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    res = run_ranks(_worker, 2)
     assert res[0][0] == res[1][0] == (1024.0, 0)            # rank 0's scaler state won at construction
     for k, want in enumerate([(1024.0, 0), (512.0, 1), (512.0, 1)]):
         assert res[0][1][k][0] == res[1][1][k][0] == want, (k, res[0][1][k][0], res[1][1][k][0])
