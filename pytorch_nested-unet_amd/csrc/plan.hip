@@ -364,8 +364,17 @@ struct Node {
   int up_slot;     // slot of X_{i+1} that is upsampled into the concat, -1: none
   ConvL c1, c2;
   size_t y1, a1, y2, up, pin;  // arena byte offsets
+  size_t dy[2], da1, gup, gpin;   // ... backward scratch (dY of conv2 / conv1) of the BLOCK, so blocks of one level can run on different lanes
+  size_t sk; long long sk_floats; // ... fp32 K-split slabs of the BLOCK (blocks of the grid-starved levels; 0 floats: none)
+  // backward pass, decided at creation (plan_backward_facts): destinations that an earlier op of the pass wrote first are accumulated into
+  unsigned acc0_mask;             // dgrad1: bit q = slot q of the concat prefix's gradient
+  int acc_pool, acc_up;           // pool-backward / upsample-backward
+  bool bn2_in_head;               // the reduce pass of BatchNorm2's backward rides in a head's backward (Head::bnr_block)
 };
-struct Head { long long w_off, b_off, gs; int slot; };
+struct Head { long long w_off, b_off, gs; int slot; int acc, bnr_block; };   // backward: accumulate flag, block whose BN2 reduce it carries (-1: none)
+// what the resource ids of the lane scheduler are laid out for (NestedUNet has 15 blocks, UNet 9)
+#define NUNET_MAX_BLOCKS 15
+#define NUNET_MAX_HEADS 4
 
 #define NLANES 10
 struct PlanRt {  // runtime objects owned by the plan (host side only)
@@ -378,7 +387,6 @@ struct PlanRt {  // runtime objects owned by the plan (host side only)
   bool lanes_external;
   std::vector<hipStream_t> cap_streams;   // never-reused streams for capture-time lane continuation
   size_t cap_next;
-  bool bwd_written[5][5]; int bwd_pp[5];   // state carried between backward phases
   // NUNET_STAMPS=1 diagnostic: a 1-thread kernel after every scheduled op writes the 100 MHz wall clock,
   // so the real timeline of an (unprofiled) hipGraph replay can be read back (tools/stamp_timeline.py)
   unsigned long long* stamps;              // device, [2][STAMP_CAP]
@@ -417,8 +425,6 @@ struct nunet_plan {
   size_t off_wpack; long long wpack_elems;
   size_t off_img;
   size_t X[5], GX[5];
-  size_t off_dy[16][2], off_da1[16], off_gup[16], off_gpin[16];   // per-BLOCK backward scratch (dY ping-pong), so blocks of one level can run on different lanes
-  size_t off_sk[16]; long long sk_floats[16];   // per-BLOCK fp32 K-split slabs (blocks of the grid-starved levels; 0: none)
   struct PlanRt* rt;
   size_t total;
   PackTab ptab;
@@ -433,6 +439,30 @@ static size_t bump(size_t& cur, size_t bytes) {
   size_t o = align_up(cur, 256);
   cur = o + bytes;
   return o;
+}
+
+// The static facts of the backward pass. A gradient destination is assigned by its first writer and accumulated into by the later
+// ones; the lane scheduler serialises the writers of one slot in issue order - heads by index, then blocks for k descending -, so
+// a walk in that order decides every accumulate flag from cfg alone. Writers of the gradient of x_{l,s} (slot s of GX_l): a head
+// (level 0), the dgrad of conv1 of a level-l block whose concat holds slot s, the upsample-backward of the level l-1 block that
+// upsampled it, the pool-backward of the level l+1 encoder block (slot 0). A head that no block writes after COMPLETES its slot
+// and takes the output block's BatchNorm-backward reduce in its epilogue (nunet_head_bwd_bnr); every other block runs the
+// stand-alone reduce (the same fusion in upsample- / pool-backward was measured slower, see elementwise.hip).
+static bool plan_backward_facts(nunet_plan* P) {
+  bool written[5][5] = {}, by_block[5][5] = {};
+  auto write = [&](int l, int sl, bool block) { const int acc = written[l][sl]; written[l][sl] = true; by_block[l][sl] |= block; return acc; };
+  for (Head& h : P->heads) { h.acc = write(0, h.slot, false); h.bnr_block = -1; }
+  for (int k = (int)P->exec.size() - 1; k >= 0; --k) {
+    Node& n = P->exec[k];
+    if (!written[n.i][n.out_slot]) { nunet_set_error("plan_backward: internal: grad of x%d_%d never produced", n.i, n.j); return false; }
+    if (n.in_prefix == 0 && n.i > 0) n.acc_pool = write(n.i - 1, 0, true);        // through MaxPool2d(2,2) into x_{i-1,0}
+    for (int q = 0; q < n.in_prefix; ++q) n.acc0_mask |= (unsigned)write(n.i, q, true) << q;
+    if (n.in_prefix > 0) n.acc_up = write(n.i + 1, n.up_slot, true);              // through the bilinear upsample into x_{i+1,up_slot}
+  }
+  for (Head& h : P->heads)
+    for (size_t k = 0; k < P->exec.size() && !by_block[0][h.slot]; ++k)
+      if (P->exec[k].i == 0 && P->exec[k].out_slot == h.slot) { h.bnr_block = (int)k; P->exec[k].bn2_in_head = true; }
+  return true;
 }
 
 extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
@@ -509,6 +539,11 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
     h.slot = unet ? 1 : (nheads == 4 ? k + 1 : 4);
     P->heads.push_back(h);
   }
+  if (P->exec.size() > NUNET_MAX_BLOCKS || P->heads.size() > NUNET_MAX_HEADS) {
+    nunet_set_error("plan_create: %zu blocks / %zu heads, the lane scheduler's resource ids cover %d / %d", P->exec.size(), P->heads.size(), NUNET_MAX_BLOCKS, NUNET_MAX_HEADS);
+    delete P; return nullptr;
+  }
+  if (!plan_backward_facts(P)) { delete P; return nullptr; }
   // Gradient scratch in the order gradients COMPLETE during backward (heads, then blocks in reverse
   // execution order): the first bucket = heads + the last anti-diagonal (75 % of the bytes,
   // SURVEY.md §3.4) is a contiguous prefix, ready for an early all-reduce.
@@ -518,7 +553,6 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
   P->first_phase_nodes = unet ? 4 : 5;
   P->gs_bucket0 = 0;
   long long slab = 0;
-  const int ks_max = 0;
   for (int k = (int)P->exec.size() - 1; k >= 0; --k) {
     Node& n = P->exec[k];
     for (int cv = 1; cv >= 0; --cv) {
@@ -535,7 +569,7 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
       const bool big = (long long)cfg->N * cfg->H * cfg->W >= (1LL << 20);
       c.wg_target = big ? (c.cinpad < o.cinpad ? 256 : 512) : (c.cinpad < o.cinpad ? 96 : 192);
       nunet_wgrad_desc wd; memset(&wd, 0, sizeof(wd));
-      wd.N = cfg->N; wd.H = P->hl[n.i]; wd.W = P->wl[n.i]; wd.C0 = c.cinpad; wd.Cout = c.cout; wd.target_wgs = c.wg_target; wd.max_slabs = ks_max;
+      wd.N = cfg->N; wd.H = P->hl[n.i]; wd.W = P->wl[n.i]; wd.C0 = c.cinpad; wd.Cout = c.cout; wd.target_wgs = c.wg_target;
       c.ks = nunet_conv3x3_wgrad_slabs(&wd);
       c.slab = slab; slab += (long long)c.ks * 9LL * c.cout * c.cinpad;
     }
@@ -568,12 +602,13 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
     if (n.in_prefix == 0 && n.i > 0) n.pin = bump(cur, (size_t)P->px[n.i] * NBF[n.i - 1] * P->es);
   }
   for (size_t k = 0; k < P->exec.size(); ++k) {
-    const int i = P->exec[k].i;
+    Node& n = P->exec[k];
+    const int i = n.i;
     const size_t plane = (size_t)P->px[i] * NBF[i] * P->es;
-    P->off_dy[k][0] = bump(cur, plane); P->off_dy[k][1] = bump(cur, plane);
-    P->off_da1[k] = bump(cur, plane);
-    P->off_gup[k] = bump(cur, i < 4 ? (size_t)P->px[i] * NBF[i + 1] * P->es : 256);
-    P->off_gpin[k] = bump(cur, i > 0 ? (size_t)P->px[i] * NBF[i - 1] * P->es : 256);
+    n.dy[0] = bump(cur, plane); n.dy[1] = bump(cur, plane);
+    n.da1 = bump(cur, plane);
+    n.gup = bump(cur, i < 4 ? (size_t)P->px[i] * NBF[i + 1] * P->es : 256);
+    n.gpin = bump(cur, i > 0 ? (size_t)P->px[i] * NBF[i - 1] * P->es : 256);
   }
   // K-split slabs for the blocks of the grid-starved levels (up to 8 slices of the block's widest conv output, the input
   // gradient of conv1); deterministic (fixed summation order). One buffer per BLOCK: the four convs of a block follow each
@@ -581,11 +616,11 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
 #ifndef NUNET_SK_MINLEV
 #define NUNET_SK_MINLEV 3
 #endif
-  for (size_t k = 0; k < P->exec.size() && k < 16; ++k) {
-    const Node& n = P->exec[k];
+  for (size_t k = 0; k < P->exec.size(); ++k) {
+    Node& n = P->exec[k];
     const int maxc = n.i < NUNET_SK_MINLEV ? 0 : (n.c1.cinpad > n.c1.cout ? n.c1.cinpad : n.c1.cout);
-    P->sk_floats[k] = 8LL * P->px[n.i] * maxc;   // up to 8 slabs
-    P->off_sk[k] = bump(cur, (size_t)P->sk_floats[k] * 4 + 16);
+    n.sk_floats = 8LL * P->px[n.i] * maxc;   // up to 8 slabs
+    n.sk = bump(cur, (size_t)n.sk_floats * 4 + 16);
   }
   P->total = align_up(cur, 256);
 
@@ -648,36 +683,25 @@ extern "C" int64_t nunet_plan_param_count(const nunet_plan* p) { return p ? p->n
 extern "C" int64_t nunet_plan_bnbuf_count(const nunet_plan* p) { return p ? p->nbnbuf : 0; }
 extern "C" int32_t nunet_plan_bn_layers(const nunet_plan* p) { return p ? p->nbn : 0; }
 extern "C" int32_t nunet_plan_num_heads(const nunet_plan* p) { return p ? (int32_t)p->heads.size() : 0; }
-extern "C" int64_t nunet_plan_feature(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels) {
-  if (!p || i < 0 || i > 4) return -1;
-  for (size_t k = 0; k < p->exec.size(); ++k)
-    if (p->exec[k].i == i && p->exec[k].j == j) {
-      if (pitch) *pitch = p->PX[i];
-      if (channels) *channels = NBF[i];
-      return (int64_t)(p->X[i] + (size_t)p->exec[k].out_slot * NBF[i] * p->es);
-    }
+static int block_at(const nunet_plan* p, int i, int j) {   // index into exec of x_{i,j}, -1: none
+  for (size_t k = 0; p && k < p->exec.size(); ++k) if (p->exec[k].i == i && p->exec[k].j == j) return (int)k;
   return -1;
 }
-
-extern "C" int64_t nunet_plan_feature_grad(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels) {
-  if (!p || i < 0 || i > 4) return -1;
-  for (size_t k = 0; k < p->exec.size(); ++k)
-    if (p->exec[k].i == i && p->exec[k].j == j) {
-      if (pitch) *pitch = p->PX[i];
-      if (channels) *channels = NBF[i];
-      return (int64_t)(p->GX[i] + (size_t)p->exec[k].out_slot * NBF[i] * p->es);
-    }
-  return -1;
+static int64_t slot_offset(const nunet_plan* p, const size_t* level, int32_t i, int32_t j, int32_t* pitch, int32_t* channels) {
+  const int k = block_at(p, i, j);
+  if (k < 0) return -1;
+  if (pitch) *pitch = p->PX[i];
+  if (channels) *channels = NBF[i];
+  return (int64_t)(level[i] + (size_t)p->exec[k].out_slot * NBF[i] * p->es);
 }
+extern "C" int64_t nunet_plan_feature(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels) { return slot_offset(p, p ? p->X : nullptr, i, j, pitch, channels); }
+extern "C" int64_t nunet_plan_feature_grad(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels) { return slot_offset(p, p ? p->GX : nullptr, i, j, pitch, channels); }
 extern "C" int64_t nunet_plan_block_act1(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels) {
-  if (!p || i < 0 || i > 4) return -1;
-  for (size_t k = 0; k < p->exec.size(); ++k)
-    if (p->exec[k].i == i && p->exec[k].j == j) {
-      if (pitch) *pitch = NBF[i];
-      if (channels) *channels = NBF[i];
-      return (int64_t)p->exec[k].a1;
-    }
-  return -1;
+  const int k = block_at(p, i, j);
+  if (k < 0) return -1;
+  if (pitch) *pitch = NBF[i];
+  if (channels) *channels = NBF[i];
+  return (int64_t)p->exec[k].a1;
 }
 extern "C" int32_t nunet_plan_census_count(const nunet_plan* p, int32_t pass) {
   return (p && p->rt && (pass == 0 || pass == 1)) ? (int32_t)p->rt->census[pass].size() : 0;
@@ -701,15 +725,31 @@ static inline char* AB(void* arena, size_t off) { return (char*)arena + off; }
 // Lane scheduler. The x_{i,j} grid has natural concurrency: blocks of level i depend only
 // on levels i and i+-1, and weight gradients depend on nothing downstream. Every kernel
 // here is latency-bound on its own (short contractions, grid-starved deep levels), so the
-// plan issues level i on stream "lane i" (wgrad of level i on lane 5+i), forked from and
-// joined to the caller's stream with events. Exact RAW / WAW / WAR dependencies come from a
-// per-buffer tracker (last-writer event, last-reader event per lane). Captured by the
-// caller, the lanes become parallel branches of ONE hipGraph.
+// plan issues every op on a stream of its own choosing - a block's ops on the block's lane
+// (lane_of: the critical chain on lane 0, the side blocks on lanes 1-3 by anti-diagonal; a
+// block's weight gradients on that same lane), or wherever the list scheduler (Sched::run_list)
+// places them -, forked from and joined to the caller's stream with events. Exact RAW / WAW /
+// WAR dependencies come from a per-buffer tracker (last-writer event, last-reader event per
+// lane). Captured by the caller, the lanes become parallel branches of ONE hipGraph.
 // ---------------------------------------------------------------------------
+// Resource ids of the tracker in numeric order, with what each range spans (B = NUNET_MAX_BLOCKS blocks)
 #define NRES 512
-enum { R_X = 0, R_GX = 25, R_BLK = 50, R_LVL = 330, R_IMG = 230, R_LOGITS = 231, R_DLOGITS = 232, R_WP = 233, R_GS = 238, R_SK = 470, R_GSW = 240, R_GSV = 280, R_PRM = 485 };
+enum {
+  R_X = 0, R_GX = 25,                            // 5 levels x 5 slots each: block outputs (slot s of X_l: R_X + 5 l + s); their gradients
+  R_BLK = 50,                                    // B x B_STRIDE: the forward buffers of a block (B_*)
+  R_IMG = 230, R_LOGITS = 231, R_DLOGITS = 232,  // 1 each
+  R_WP = 233,                                    // 5 levels: packed weights
+  R_GSW = 240, R_GSV = 280,                      // B x 2 each (conv1, conv2): weight gradients; BatchNorm-backward sums + small-vector gradients
+  R_GSH = 310,                                   // NUNET_MAX_HEADS: the gradients of a head
+  R_LVL = 330,                                   // B x L_STRIDE: the backward scratch of a block (L_*)
+  R_SK = 470, R_PRM = 485                        // B each: split-K workspace; parameters stepped inside the pass
+};
 enum { B_Y1 = 0, B_A1, B_Y2, B_UP, B_PIN, B_ST1, B_ST2, B_STRIDE = 8 };
 enum { L_DY0 = 0, L_DY1, L_DA1, L_GUP, L_GPIN, L_STRIDE = 8 };
+static_assert(B_ST2 < B_STRIDE && L_GPIN < L_STRIDE && R_X + 5 * 5 <= R_GX && R_GX + 5 * 5 <= R_BLK && R_BLK + NUNET_MAX_BLOCKS * B_STRIDE <= R_IMG &&
+              R_IMG < R_LOGITS && R_LOGITS < R_DLOGITS && R_DLOGITS < R_WP && R_WP + 5 <= R_GSW && R_GSW + 2 * NUNET_MAX_BLOCKS <= R_GSV &&
+              R_GSV + 2 * NUNET_MAX_BLOCKS <= R_GSH && R_GSH + NUNET_MAX_HEADS <= R_LVL && R_LVL + NUNET_MAX_BLOCKS * L_STRIDE <= R_SK &&
+              R_SK + NUNET_MAX_BLOCKS <= R_PRM && R_PRM + NUNET_MAX_BLOCKS <= NRES, "resource-id ranges overlap at this capacity");
 
 struct Sched {
   hipStream_t main_s;
@@ -1133,10 +1173,54 @@ static int lane_of(const nunet_plan* P, const Node& n) {
   return n.i + n.j;           // side blocks: diagonals 1..3 -> lanes 1..3
 }
 
-static int blk_index(const nunet_plan* P, int i, int in_prefix_zero_only) {
-  for (size_t q = 0; q < P->exec.size(); ++q)
-    if (P->exec[q].i == i && (!in_prefix_zero_only || P->exec[q].in_prefix == 0)) return (int)q;
-  return -1;
+// ---- views: what a launch is handed together with the resource ids the tracker orders it by, each spelled once ---------------
+struct Buf { char* p; int r; };
+static Buf slot_of(const nunet_plan* P, void* arena, bool grad, int l, int s) {   // slot s of level l's block outputs (grad: of their gradients)
+  return {AB(arena, (grad ? P->GX : P->X)[l] + (size_t)s * NBF[l] * P->es), (grad ? R_GX : R_X) + l * 5 + s};
+}
+// Input of block k as conv1 and its weight gradient read it: one source (the image, or the pooled output of the encoder block
+// above), or the first in_prefix slots of the level with the upsampled output of the level below behind them. grad: the mirror
+// that conv1's input gradient writes (the image has none). r: the ids of prefix slots 0..3 (or of the one source), then of the second.
+struct Cat { char* p[2]; int c[2], pitch[2]; int r[5]; };
+static Cat block_in(const nunet_plan* P, void* arena, int k, bool grad) {
+  const Node& n = P->exec[k];
+  const int i = n.i, rb = R_BLK + k * B_STRIDE, rl = R_LVL + k * L_STRIDE;
+  Cat v = {{nullptr, nullptr}, {0, 0}, {0, 0}, {-1, -1, -1, -1, -1}};
+  if (n.in_prefix > 0) {
+    v.p[0] = slot_of(P, arena, grad, i, 0).p; v.c[0] = n.in_prefix * NBF[i]; v.pitch[0] = P->PX[i];
+    for (int q = 0; q < n.in_prefix && q < 4; ++q) v.r[q] = slot_of(P, arena, grad, i, q).r;
+    v.p[1] = AB(arena, grad ? n.gup : n.up); v.c[1] = v.pitch[1] = NBF[i + 1]; v.r[4] = grad ? rl + L_GUP : rb + B_UP;
+  } else if (i > 0) { v.p[0] = AB(arena, grad ? n.gpin : n.pin); v.c[0] = v.pitch[0] = NBF[i - 1]; v.r[0] = grad ? rl + L_GPIN : rb + B_PIN; }
+  else { v.p[0] = AB(arena, P->off_img); v.c[0] = v.pitch[0] = 32; v.r[0] = R_IMG; }
+  return v;
+}
+template <typename D> static void set_src(D& d, const Cat& v) {   // nunet_conv_desc / nunet_wgrad_desc
+  d.src0 = v.p[0]; d.C0 = v.c[0]; d.P0 = v.pitch[0]; d.src1 = v.p[1]; d.C1 = v.c[1]; d.P1 = v.pitch[1];
+}
+// BatchNorm layer cv + 1 of block k as a pass sees it: the raw conv output y it normalises, its affine parameters and saved
+// statistics, and the fixed-point sums of the pass (0: the forward statistics; 1: the BatchNorm-backward sums, whose id also
+// covers the layer's small-vector gradients gv = [dbias | dgamma | dbeta] in the scratch)
+struct BnView { char* y; int r_y, C; const float *gamma, *beta; float* mean_invstd; int64_t* fx; int r_fx; float* gv; };
+static BnView bn_view(const nunet_plan* P, void* arena, const float* params, int k, int cv, int pass) {
+  const Node& n = P->exec[k];
+  const ConvL& L = cv ? n.c2 : n.c1;
+  const int rb = R_BLK + k * B_STRIDE;
+  return {AB(arena, cv ? n.y2 : n.y1), rb + (cv ? B_Y2 : B_Y1), L.cout, params + L.g_off, params + L.be_off, (float*)AB(arena, P->off_save) + L.save,
+          (int64_t*)fx_of(arena, P, pass, pass ? L.bsum : L.stats), pass ? R_GSV + 2 * k + cv : rb + (cv ? B_ST2 : B_ST1),
+          pass ? (float*)AB(arena, P->off_gs) + L.gs + 9LL * L.cout * L.cinpad : nullptr};
+}
+template <typename D> static void set_bn(D& b, const BnView& v) {   // nunet_bnr_desc / nunet_bn_bwd_desc: the reduce pass's view
+  b.y = v.y; b.PY = v.C; b.mean_invstd = v.mean_invstd; b.gamma = v.gamma; b.beta = v.beta; b.sums = v.fx;
+}
+static void set_tf_bn_bwd(nunet_conv_desc& d, const BnView& v) {     // the apply pass on a dgrad's way into LDS
+  d.in_tf = NUNET_TF_BN_RELU_BWD; d.tf_y = v.y; d.tf_py = v.C; d.tf_fx = v.fx;
+  d.tf_gamma = v.gamma; d.tf_beta = v.beta; d.tf_mean_invstd = v.mean_invstd;
+  d.tf_dbias = v.gv; d.tf_dgamma = v.gv + v.C; d.tf_dbeta = v.gv + 2 * v.C;
+}
+static int set_splitk(nunet_conv_desc& d, const nunet_plan* P, void* arena, int k) {   // block k's split-K workspace; returns its id (-1: none)
+  const Node& n = P->exec[k];
+  if (n.sk_floats > 0) { d.splitk_ws = (float*)AB(arena, n.sk); d.splitk_ws_floats = n.sk_floats; }
+  return n.sk_floats > 0 ? R_SK + k : -1;
 }
 
 // every plan entry that touches the arena checks what the caller says it owns against the plan's own layout
@@ -1153,7 +1237,6 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
   hipStream_t st = (hipStream_t)s;
   const nunet_plan_cfg& c = P->cfg;
   const int dt = c.dtype, es = P->es;
-  float* save = (float*)AB(arena, P->off_save);
   char* wpack = AB(arena, P->off_wpack);
   // prerequisites of everything on the caller's stream, before the fork: both fixed-point sum regions (the
   // BatchNorm statistics of this pass and the BatchNorm-backward sums of the pass that may follow) in one launch
@@ -1161,7 +1244,6 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
   if (!staged) CK(nunet_nchw_to_nhwc(input, c.N, c.input_channels, c.H, c.W, dt, AB(arena, P->off_img), 32, (nunet_stream_t)st));
 
   Sched S; S.init(P, st, 0);
-  int rc = NUNET_OK;
   const bool skip_pack = (training_flags & 2) != 0;   // the caller vouches that nunet_plan_opt_step(repack 1) / _repack left the packed weights current
   if (!skip_pack) {
     S.name("pack");
@@ -1172,39 +1254,32 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
   // (The x2 upsample of a block output can ride in the producer's BatchNorm launch as a second block role - nunet_bn_fwd_desc.up,
   // bit-identical, ten launches fewer per forward. Measured on MI355X, same box: single-lane step unchanged (2.557 vs 2.554 ms),
   // multi-lane graph step SLOWER (8326 vs 8700 and 8041 vs 8232 img/s). The plan keeps the stand-alone launch.)
-  for (size_t k = 0; k < P->exec.size() && rc == NUNET_OK; ++k) {
+  for (int k = 0; k < (int)P->exec.size(); ++k) {
     const Node& n = P->exec[k];
     const int i = n.i, f = NBF[i], H = P->hl[i], W = P->wl[i];
-    const int lane = lane_of(P, n), rb = R_BLK + (int)k * B_STRIDE;
-    const int rskf = P->sk_floats[k] > 0 ? R_SK + (int)k : -1;
+    const int lane = lane_of(P, n), rb = R_BLK + k * B_STRIDE;
+    const Cat in = block_in(P, arena, k, false);
+    const BnView bn1 = bn_view(P, arena, params, k, 0, 0), bn2 = bn_view(P, arena, params, k, 1, 0);
     if (n.up_slot >= 0) {
+      const Buf x = slot_of(P, arena, false, i + 1, n.up_slot);
       S.name("B%d%d.upF", n.i, n.j);
-      S.add(lane, 0, 7.f, {R_X + (i + 1) * 5 + n.up_slot}, {rb + B_UP}, [=](hipStream_t ls) {
-        return nunet_upsample2x_fwd(dt, c.N, P->hl[i + 1], P->wl[i + 1], NBF[i + 1],
-                                    AB(arena, P->X[i + 1] + (size_t)n.up_slot * NBF[i + 1] * es), P->PX[i + 1], AB(arena, n.up), NBF[i + 1], ls);
+      S.add(lane, 0, 7.f, {x.r}, {in.r[4]}, [=](hipStream_t ls) {
+        return nunet_upsample2x_fwd(dt, c.N, P->hl[i + 1], P->wl[i + 1], NBF[i + 1], x.p, P->PX[i + 1], in.p[1], NBF[i + 1], ls);
       });
     }
     // ---- conv1: raw output y1 + its BatchNorm sums (fixed point) ---------------------------------------------
     {
-      const ConvL& L = n.c1;
       nunet_conv_desc d; memset(&d, 0, sizeof(d));
       d.dtype = dt; d.N = c.N; d.H = H; d.W = W;
-      d.wpack = wpack + (size_t)L.wf * es;
+      set_src(d, in);
+      d.wpack = wpack + (size_t)n.c1.wf * es;
       d.bias = nullptr;  // absorbed by the BatchNorm that follows (bn_stat_coeffs)
-      d.dst0 = AB(arena, n.y1); d.D0 = f; d.Q0 = f;
-      d.stats = training ? (int64_t*)fx_of(arena, P, 0, L.stats) : nullptr;
-      if (P->sk_floats[k] > 0) { d.splitk_ws = (float*)AB(arena, P->off_sk[k]); d.splitk_ws_floats = P->sk_floats[k]; }
+      d.dst0 = bn1.y; d.D0 = f; d.Q0 = f;
+      d.stats = training ? bn1.fx : nullptr;
+      const int rsk = set_splitk(d, P, arena, k);
       const int alg_cin = (i == 0 && n.in_prefix == 0) ? c.input_channels : 0;
       S.name("B%d%d.conv1", n.i, n.j);
-      if (n.in_prefix == 0) {
-        if (i == 0) { d.src0 = AB(arena, P->off_img); d.C0 = 32; d.P0 = 32; S.add_conv(lane, {R_IMG, R_WP + i}, {rb + B_Y1, rb + B_ST1, rskf}, d, alg_cin); }
-        else { d.src0 = AB(arena, n.pin); d.C0 = NBF[i - 1]; d.P0 = NBF[i - 1]; S.add_conv(lane, {rb + B_PIN, R_WP + i}, {rb + B_Y1, rb + B_ST1, rskf}, d, alg_cin); }
-      } else {
-        d.src0 = AB(arena, P->X[i]); d.C0 = n.in_prefix * f; d.P0 = P->PX[i];
-        d.src1 = AB(arena, n.up); d.C1 = NBF[i + 1]; d.P1 = NBF[i + 1];
-        S.add_conv(lane, {R_X + i * 5 + 0, n.in_prefix > 1 ? R_X + i * 5 + 1 : -1, n.in_prefix > 2 ? R_X + i * 5 + 2 : -1,
-                          n.in_prefix > 3 ? R_X + i * 5 + 3 : -1, rb + B_UP, R_WP + i}, {rb + B_Y1, rb + B_ST1, rskf}, d, alg_cin);
-      }
+      S.add_conv(lane, {in.r[0], in.r[1], in.r[2], in.r[3], in.r[4], R_WP + i}, {bn1.r_y, bn1.r_fx, rsk}, d, alg_cin);
     }
     // ---- conv2: BatchNorm1 + ReLU applied to y1 on the way into LDS (archs1.py:23-28); the activation a1 is
     // stored on the side for the weight gradient when a backward pass may follow -----------------------------------
@@ -1212,53 +1287,52 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
       const ConvL& L = n.c2; const ConvL& L1 = n.c1;
       nunet_conv_desc d; memset(&d, 0, sizeof(d));
       d.dtype = dt; d.N = c.N; d.H = H; d.W = W;
-      d.src0 = AB(arena, n.y1); d.C0 = f; d.P0 = f;
+      d.src0 = bn1.y; d.C0 = f; d.P0 = f;
       d.in_tf = NUNET_TF_BN_RELU; d.tf_training = training;
-      d.tf_fx = training ? (const int64_t*)fx_of(arena, P, 0, L1.stats) : nullptr;
-      d.tf_gamma = params + L1.g_off; d.tf_beta = params + L1.be_off; d.tf_conv_bias = params + L1.b_off;
+      d.tf_fx = training ? bn1.fx : nullptr;
+      d.tf_gamma = bn1.gamma; d.tf_beta = bn1.beta; d.tf_conv_bias = params + L1.b_off;
       d.tf_running_mean = bnbuf + L1.rm_off; d.tf_running_var = bnbuf + L1.rv_off; d.tf_nbt = nbt ? nbt + L1.bn_index : nullptr;
-      d.tf_mean_invstd = save + L1.save; d.tf_momentum = 0.1f; d.tf_eps = 1e-5f;
+      d.tf_mean_invstd = bn1.mean_invstd; d.tf_momentum = 0.1f; d.tf_eps = 1e-5f;
       d.tf_store = training ? AB(arena, n.a1) : nullptr; d.tf_ps = f;
       d.wpack = wpack + (size_t)L.wf * es;
-      d.dst0 = AB(arena, n.y2); d.D0 = f; d.Q0 = f;
-      d.stats = training ? (int64_t*)fx_of(arena, P, 0, L.stats) : nullptr;
-      if (P->sk_floats[k] > 0) { d.splitk_ws = (float*)AB(arena, P->off_sk[k]); d.splitk_ws_floats = P->sk_floats[k]; }
+      d.dst0 = bn2.y; d.D0 = f; d.Q0 = f;
+      d.stats = training ? bn2.fx : nullptr;
+      const int rsk = set_splitk(d, P, arena, k);
       S.name("B%d%d.conv2", n.i, n.j);
-      S.add_conv(lane, {rb + B_Y1, rb + B_ST1, R_WP + i}, {rb + B_Y2, rb + B_ST2, rb + B_A1, rskf}, d);
+      S.add_conv(lane, {bn1.r_y, bn1.r_fx, R_WP + i}, {bn2.r_y, bn2.r_fx, rb + B_A1, rsk}, d);
     }
     // ---- BatchNorm2 + ReLU (+ 2x2 max-pool for the encoder column): the block output has many consumers
     // (convs of the same level, the upsample, the pool, a head) and is materialised once in its level-buffer slot ------
     {
       const ConvL& L = n.c2;
+      const Buf out = slot_of(P, arena, false, i, n.out_slot);
       nunet_bn_fwd_desc b; memset(&b, 0, sizeof(b));
       b.dtype = dt; b.N = c.N; b.H = H; b.W = W; b.C = f;
-      b.y = AB(arena, n.y2); b.PY = f; b.conv_bias = params + L.b_off; b.stats = (const int64_t*)fx_of(arena, P, 0, L.stats);
-      b.gamma = params + L.g_off; b.beta = params + L.be_off;
+      b.y = bn2.y; b.PY = f; b.conv_bias = params + L.b_off; b.stats = bn2.fx;
+      b.gamma = bn2.gamma; b.beta = bn2.beta;
       b.running_mean = bnbuf + L.rm_off; b.running_var = bnbuf + L.rv_off;
       b.num_batches_tracked = nbt ? nbt + L.bn_index : nullptr;
-      b.save_mean_invstd = save + L.save; b.training = training; b.momentum = 0.1f; b.eps = 1e-5f;
-      b.a = AB(arena, P->X[i] + (size_t)n.out_slot * f * es); b.PA = P->PX[i];
+      b.save_mean_invstd = bn2.mean_invstd; b.training = training; b.momentum = 0.1f; b.eps = 1e-5f;
+      b.a = out.p; b.PA = P->PX[i];
       int rpin = -1;
       if (n.in_prefix == 0 && i < 4) {  // encoder column: feed the next level (archs1.py:115,118,122,127)
-        const int q = blk_index(P, i + 1, 1);
-        if (q >= 0) { b.pooled = AB(arena, P->exec[q].pin); b.PP = f; rpin = R_BLK + q * B_STRIDE + B_PIN; }
+        const int q = block_at(P, i + 1, 0);
+        if (q >= 0) { const Cat nx = block_in(P, arena, q, false); b.pooled = nx.p[0]; b.PP = f; rpin = nx.r[0]; }
       }
       S.name("B%d%d.bnF2", n.i, n.j);
-      S.add(lane, 0, 6.f, {rb + B_Y2, rb + B_ST2}, {R_X + i * 5 + n.out_slot, rpin}, [=](hipStream_t ls) { return nunet_bn_relu_fwd(&b, ls); });
+      S.add(lane, 0, 6.f, {bn2.r_y, bn2.r_fx}, {out.r, rpin}, [=](hipStream_t ls) { return nunet_bn_relu_fwd(&b, ls); });
     }
   }
-  if (rc == NUNET_OK) {
-    const long long plane = (long long)c.N * c.num_classes * c.H * c.W;
-    for (size_t k = 0; k < P->heads.size() && rc == NUNET_OK; ++k) {
-      const Head hd = P->heads[k];
-      S.name("head%d.F", (int)k);
-      S.add(0, 0, 10.f, {R_X + hd.slot}, {R_LOGITS + 0}, [=](hipStream_t ls) {
-        return nunet_head_fwd(dt, c.N, c.H, c.W, NBF[0], c.num_classes, AB(arena, P->X[0] + (size_t)hd.slot * NBF[0] * es), P->PX[0],
-                              params + hd.w_off, params + hd.b_off, logits + plane * k, ls);
-      });
-    }
+  const long long plane = (long long)c.N * c.num_classes * c.H * c.W;
+  for (size_t k = 0; k < P->heads.size(); ++k) {
+    const Head hd = P->heads[k];
+    const Buf x = slot_of(P, arena, false, 0, hd.slot);
+    S.name("head%d.F", (int)k);
+    S.add(0, 0, 10.f, {x.r}, {R_LOGITS + 0}, [=](hipStream_t ls) {
+      return nunet_head_fwd(dt, c.N, c.H, c.W, NBF[0], c.num_classes, x.p, P->PX[0], params + hd.w_off, params + hd.b_off, logits + plane * k, ls);
+    });
   }
-  if (rc == NUNET_OK) rc = S.run();
+  int rc = S.run();
   S.join();  // always rejoin the caller's stream (also on error: a capture must not be left forked)
   if (rc == NUNET_OK && S.failed) { nunet_set_error("plan_forward: lane scheduler overflow (capture stream pool / dependency lists)"); rc = NUNET_EINVAL; }
   return rc;
@@ -1573,31 +1647,6 @@ static int launch_reduce(nunet_plan* P, void* arena, int k_lo, int k_hi, hipStre
   return nunet_check_launch("wgrad slab reduce");
 }
 
-// Which op COMPLETES the gradient of block output x_{l,s} (slot s of GX_l)? Writers: a head (level 0), the dgrad of conv1
-// of a block of level l whose concat holds slot s, the upsample-backward of the level l-1 block that upsampled it, the
-// pool-backward of the level l+1 encoder block (slot 0). Ops are issued heads first, then blocks for k descending, and
-// writers of one slot are serialised in that order by the lane scheduler - so the last writer is the block writer with
-// the smallest k (or the head when no block writes the slot). A head that completes its slot (the output block's) takes
-// that block's BatchNorm-backward reduce in its epilogue (nunet_head_bwd_bnr); every other block runs the stand-alone
-// reduce (the same fusion in upsample- / pool-backward was measured slower, see elementwise.hip).
-enum { LW_NONE = 0, LW_HEAD, LW_DGRAD, LW_UPB, LW_POOLB };
-static void last_writer(const nunet_plan* P, int l, int s, int& kind, int& kk) {
-  kind = LW_NONE; kk = 1 << 30;
-  for (size_t h = 0; h < P->heads.size(); ++h) if (l == 0 && P->heads[h].slot == s) { kind = LW_HEAD; kk = 1 << 29; }
-  for (int k = (int)P->exec.size() - 1; k >= 0; --k) {
-    const Node& n = P->exec[k];
-    int w = LW_NONE;
-    if (n.i == l && n.in_prefix > s && !(n.i == 0 && n.in_prefix == 0)) w = LW_DGRAD;
-    if (n.i + 1 == l && n.in_prefix > 0 && n.up_slot == s) w = LW_UPB;
-    if (n.i - 1 == l && n.in_prefix == 0 && n.i > 0 && s == 0) w = LW_POOLB;
-    if (w != LW_NONE && k < kk) { kind = w; kk = k; }
-  }
-}
-static int block_of_slot(const nunet_plan* P, int l, int s) {
-  for (size_t k = 0; k < P->exec.size(); ++k) if (P->exec[k].i == l && P->exec[k].out_slot == s) return (int)k;
-  return -1;
-}
-
 // phases (bit 0 = heads and the last anti-diagonal's blocks, 75 % of the gradient bytes; bit 1 = the remaining blocks; bit 2 = unpack
 // into the flat OIHW gradient arena; bit 3 = leave the pass open; bit 4 = continue the open pass) - five values, any other is refused:
 //   3     whole pass                    7      whole pass + unpack (nunet_plan_backward)        4   unpack only
@@ -1613,10 +1662,7 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
   const int dt = c.dtype, es = P->es;
   float* gsr = (float*)AB(arena, P->off_gs);
   float* slabs = (float*)AB(arena, P->off_slab);
-  float* save = (float*)AB(arena, P->off_save);
   char* wpack = AB(arena, P->off_wpack);
-  bool (&written)[5][5] = rt_of(P)->bwd_written;
-  if (phases & 1) memset(written, 0, sizeof(written));
   const int nnodes = (int)P->exec.size();
   const int k_split = nnodes - P->first_phase_nodes;      // phase 1: nodes [k_split, nnodes); phase 2: [0, k_split)
   const int k_hi = (phases & 1) ? nnodes - 1 : k_split - 1;
@@ -1637,34 +1683,19 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
   else NUNET_REQUIRE(S.main_s == st, "plan_backward: continue on the stream the open pass was started on");
   rt->open_sched = nullptr;
   struct Owner { Sched* s; PlanRt* rt; bool keep; ~Owner() { if (keep) rt->open_sched = s; else sched_free(s); } } owner{Sp, rt, false};
-  int rc = NUNET_OK;
   const long long plane = (long long)c.N * c.num_classes * c.H * c.W;
-  // reduce pass of block kt's second BatchNorm, for the kernel that completes its output gradient
-  auto bnr_of = [&](int kt) {
-    const Node& t = P->exec[kt];
-    nunet_bnr_desc b; memset(&b, 0, sizeof(b));
-    b.y = AB(arena, t.y2); b.PY = NBF[t.i]; b.mean_invstd = save + t.c2.save;
-    b.gamma = params + t.c2.g_off; b.beta = params + t.c2.be_off; b.sums = (int64_t*)fx_of(arena, P, 1, t.c2.bsum);
-    return b;
-  };
-  auto completes = [&](int l, int sl, int kind, int k) {      // does op (kind, block k) complete x_{l,sl}'s gradient?
-    int lk, lkk; last_writer(P, l, sl, lk, lkk);
-    if (lk != kind || (kind != LW_HEAD && lkk != k)) return -1;
-    return block_of_slot(P, l, sl);
-  };
-  for (size_t k = 0; k < P->heads.size() && rc == NUNET_OK && (phases & 1); ++k) {
-    const Head& h = P->heads[k];
-    const int acc = written[0][h.slot] ? 1 : 0;
-    const int kt = completes(0, h.slot, LW_HEAD, -1);
+  for (size_t k = 0; k < P->heads.size() && (phases & 1); ++k) {
+    const Head h = P->heads[k];
+    const int kt = h.bnr_block;    // the block whose output gradient this head completes: its BatchNorm2 reduce rides in the epilogue
+    const Buf x = slot_of(P, arena, false, 0, h.slot), gx = slot_of(P, arena, true, 0, h.slot);
     nunet_bnr_desc bd; memset(&bd, 0, sizeof(bd));
-    if (kt >= 0) bd = bnr_of(kt);
+    int r_y = -1, r_sums = -1;
+    if (kt >= 0) { const BnView v = bn_view(P, arena, params, kt, 1, 1); set_bn(bd, v); r_y = v.r_y; r_sums = v.r_fx; }
     S.name("head%d.B", (int)k);
-    S.add(0, 0, 15.f, {R_X + h.slot, R_DLOGITS, kt >= 0 ? R_BLK + kt * B_STRIDE + B_Y2 : -1}, {R_GX + h.slot, R_GSV + 30 + (int)k, kt >= 0 ? R_GSV + 2 * kt + 1 : -1}, [=](hipStream_t ls) {
-      return nunet_head_bwd_bnr(dt, c.N, c.H, c.W, NBF[0], c.num_classes, AB(arena, P->X[0] + (size_t)h.slot * NBF[0] * es), P->PX[0],
-                                params + h.w_off, dlogits + plane * k, AB(arena, P->GX[0] + (size_t)h.slot * NBF[0] * es), P->PX[0],
-                                acc, gsr + h.gs, HEAD_SLABS, kt >= 0 ? &bd : nullptr, ls);
+    S.add(0, 0, 15.f, {x.r, R_DLOGITS, r_y}, {gx.r, R_GSH + (int)k, r_sums}, [=](hipStream_t ls) {
+      return nunet_head_bwd_bnr(dt, c.N, c.H, c.W, NBF[0], c.num_classes, x.p, P->PX[0], params + h.w_off, dlogits + plane * k, gx.p, P->PX[0],
+                                h.acc, gsr + h.gs, HEAD_SLABS, kt >= 0 ? &bd : nullptr, ls);
     });
-    written[0][h.slot] = true;
   }
   // in-pass optimiser step: only a WHOLE pass may carry it (a data-parallel caller exchanges the gradients between the phases)
   const auto upd = rt_of(P)->upd;
@@ -1674,41 +1705,29 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
   static int spin_us = -1;
   if (spin_us < 0) { const char* e = getenv("NUNET_DEBUG_SPIN_US"); spin_us = e ? atoi(e) : 0; }
 
-  for (int k = k_hi; k >= k_lo && rc == NUNET_OK; --k) {
+  for (int k = k_hi; k >= k_lo; --k) {
     const Node& n = P->exec[k];
     const int i = n.i, f = NBF[i], H = P->hl[i], W = P->wl[i];
     const int lane = lane_of(P, n), wlane = 5 + lane, rb = R_BLK + k * B_STRIDE, rl = R_LVL + k * L_STRIDE;
-    const int rsk = P->sk_floats[k] > 0 ? R_SK + k : -1;
-    if (!written[i][n.out_slot]) { nunet_set_error("plan_backward: internal: grad of x%d_%d never produced", n.i, n.j); rc = NUNET_EINVAL; break; }
+    const Buf gxo = slot_of(P, arena, true, i, n.out_slot);           // the block-output gradient its consumers accumulated
     if (spin_us > 0 && k == k_split - 1 && (phases & 2)) {
       const int us = spin_us;
       S.name("spin");
-      S.add(lane, 0, 0.f, {R_GX + i * 5 + n.out_slot}, {R_GX + i * 5 + n.out_slot}, [=](hipStream_t ls) { return nunet_debug_spin(us, 1, (nunet_stream_t)ls); });
+      S.add(lane, 0, 0.f, {gxo.r}, {gxo.r}, [=](hipStream_t ls) { return nunet_debug_spin(us, 1, (nunet_stream_t)ls); });
     }
     const ConvL& L1 = n.c1; const ConvL& L2 = n.c2;
-    char* const dy2 = AB(arena, P->off_dy[k][0]); char* const dy1 = AB(arena, P->off_dy[k][1]);
-    char* const da1 = AB(arena, P->off_da1[k]);
-    const int r_dy2 = rl + L_DY0, r_dy1 = rl + L_DY1, r_da1 = rl + L_DA1;
-    const int r_v2 = R_GSV + 2 * k + 1, r_v1 = R_GSV + 2 * k;       // per-conv sums + small-vector gradients
-    const int r_gxo = R_GX + i * 5 + n.out_slot;
-    float* const gv2 = gsr + L2.gs + 9LL * L2.cout * L2.cinpad;     // [dbias | dgamma | dbeta]
-    float* const gv1 = gsr + L1.gs + 9LL * L1.cout * L1.cinpad;
+    const BnView bn1 = bn_view(P, arena, params, k, 0, 1), bn2 = bn_view(P, arena, params, k, 1, 1);
+    const Buf dy2 = {AB(arena, n.dy[0]), rl + L_DY0}, dy1 = {AB(arena, n.dy[1]), rl + L_DY1}, da1 = {AB(arena, n.da1), rl + L_DA1};
     const bool has_dgrad1 = !(i == 0 && n.in_prefix == 0);           // no gradient into the image
 
     // ---- BatchNorm2 + ReLU backward, REDUCE pass: sum dz, sum dz * xhat over the block-output gradient (which several
-    // consumers accumulated into its level-buffer slot) -> fixed-point sums
-    nunet_bn_bwd_desc b2; memset(&b2, 0, sizeof(b2));
-    b2.dtype = dt; b2.N = c.N; b2.H = H; b2.W = W; b2.C = f;
-    b2.da = AB(arena, P->GX[i] + (size_t)n.out_slot * f * es); b2.PDA = P->PX[i]; b2.y = AB(arena, n.y2); b2.PY = f;
-    b2.mean_invstd = save + L2.save; b2.gamma = params + L2.g_off; b2.beta = params + L2.be_off;
-    b2.sums = (int64_t*)fx_of(arena, P, 1, L2.bsum);
-    {
-      int lk, lkk; last_writer(P, i, n.out_slot, lk, lkk);
-      const bool fused = lk == LW_HEAD;   // taken by the head backward, which completed the gradient
-      if (!fused) {
-        S.name("B%d%d.bnR2", n.i, n.j);
-        S.add(lane, 0, 9.f, {r_gxo, rb + B_Y2}, {r_v2}, [=](hipStream_t ls) { return nunet_bn_relu_bwd_reduce(&b2, ls); });
-      }
+    // consumers accumulated into its level-buffer slot) -> fixed-point sums; not when a head backward took it
+    if (!n.bn2_in_head) {
+      nunet_bn_bwd_desc b2; memset(&b2, 0, sizeof(b2));
+      b2.dtype = dt; b2.N = c.N; b2.H = H; b2.W = W; b2.C = f;
+      b2.da = gxo.p; b2.PDA = P->PX[i]; set_bn(b2, bn2);
+      S.name("B%d%d.bnR2", n.i, n.j);
+      S.add(lane, 0, 9.f, {gxo.r, bn2.r_y}, {bn2.r_fx}, [=](hipStream_t ls) { return nunet_bn_relu_bwd_reduce(&b2, ls); });
     }
 
     // ---- dgrad of conv2: the APPLY pass of BatchNorm2's backward happens on the way into LDS (dy2 is stored on the
@@ -1716,100 +1735,79 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
     {
       nunet_conv_desc d; memset(&d, 0, sizeof(d));
       d.dtype = dt; d.N = c.N; d.H = H; d.W = W;
-      d.src0 = b2.da; d.C0 = f; d.P0 = P->PX[i];
-      d.in_tf = NUNET_TF_BN_RELU_BWD; d.tf_y = AB(arena, n.y2); d.tf_py = f; d.tf_fx = b2.sums;
-      d.tf_gamma = b2.gamma; d.tf_beta = b2.beta; d.tf_mean_invstd = save + L2.save;
-      d.tf_dbias = gv2; d.tf_dgamma = gv2 + L2.cout; d.tf_dbeta = gv2 + 2 * L2.cout;
-      d.tf_store = dy2; d.tf_ps = f;
+      d.src0 = gxo.p; d.C0 = f; d.P0 = P->PX[i];
+      set_tf_bn_bwd(d, bn2);
+      d.tf_store = dy2.p; d.tf_ps = f;
       d.wpack = wpack + (size_t)L2.wd * es;
-      d.dst0 = da1; d.D0 = f; d.Q0 = f;
-      d.bn_y = AB(arena, n.y1); d.bn_py = f; d.bn_mean_invstd = save + L1.save;
-      d.bn_gamma = params + L1.g_off; d.bn_beta = params + L1.be_off; d.bn_sums = (int64_t*)fx_of(arena, P, 1, L1.bsum);
-      if (P->sk_floats[k] > 0) { d.splitk_ws = (float*)AB(arena, P->off_sk[k]); d.splitk_ws_floats = P->sk_floats[k]; }
+      d.dst0 = da1.p; d.D0 = f; d.Q0 = f;
+      d.bn_y = bn1.y; d.bn_py = f; d.bn_mean_invstd = bn1.mean_invstd;
+      d.bn_gamma = bn1.gamma; d.bn_beta = bn1.beta; d.bn_sums = bn1.fx;
+      const int rsk = set_splitk(d, P, arena, k);
       S.name("B%d%d.dgrad2", n.i, n.j);
-      S.add_conv(lane, {r_gxo, rb + B_Y2, rb + B_Y1, R_WP + i}, {r_dy2, r_da1, r_v2, r_v1, rsk}, d);
+      S.add_conv(lane, {gxo.r, bn2.r_y, bn1.r_y, R_WP + i}, {dy2.r, da1.r, bn2.r_fx, bn1.r_fx, rsk}, d);
     }
     // ---- dgrad of conv1 with BatchNorm1's apply pass on the way in; the first block has no input gradient and
     // runs the stand-alone apply pass for its weight gradient instead
     if (has_dgrad1) {
+      const Cat g = block_in(P, arena, k, true);
       nunet_conv_desc d; memset(&d, 0, sizeof(d));
       d.dtype = dt; d.N = c.N; d.H = H; d.W = W;
-      d.src0 = da1; d.C0 = f; d.P0 = f;
-      d.in_tf = NUNET_TF_BN_RELU_BWD; d.tf_y = AB(arena, n.y1); d.tf_py = f; d.tf_fx = (const int64_t*)fx_of(arena, P, 1, L1.bsum);
-      d.tf_gamma = params + L1.g_off; d.tf_beta = params + L1.be_off; d.tf_mean_invstd = save + L1.save;
-      d.tf_dbias = gv1; d.tf_dgamma = gv1 + L1.cout; d.tf_dbeta = gv1 + 2 * L1.cout;
-      d.tf_store = dy1; d.tf_ps = f;
+      d.src0 = da1.p; d.C0 = f; d.P0 = f;
+      set_tf_bn_bwd(d, bn1);
+      d.tf_store = dy1.p; d.tf_ps = f;
       d.wpack = wpack + (size_t)L1.wd * es;
-      if (P->sk_floats[k] > 0) { d.splitk_ws = (float*)AB(arena, P->off_sk[k]); d.splitk_ws_floats = P->sk_floats[k]; }
+      d.dst0 = g.p[0]; d.D0 = g.c[0]; d.Q0 = g.pitch[0];
+      d.dst1 = g.p[1]; d.D1 = g.c[1]; d.Q1 = g.pitch[1];
+      if (n.in_prefix > 0) { d.acc_slot_w = f; d.acc0_mask = n.acc0_mask; }
+      const int rsk = set_splitk(d, P, arena, k);
       S.name("B%d%d.dgrad1", n.i, n.j);
+      S.add_conv(lane, {da1.r, bn1.r_y, bn1.r_fx, R_WP + i}, {dy1.r, g.r[0], g.r[1], g.r[2], g.r[3], g.r[4], rsk}, d);
       if (n.in_prefix == 0) {
-        d.dst0 = AB(arena, P->off_gpin[k]); d.D0 = NBF[i - 1]; d.Q0 = NBF[i - 1];
-        S.add_conv(lane, {r_da1, rb + B_Y1, r_v1, R_WP + i}, {r_dy1, rl + L_GPIN, rsk}, d);
         // through MaxPool2d(2,2) into x_{i-1,0}
-        const int acc = written[i - 1][0] ? 1 : 0;
+        const Buf x = slot_of(P, arena, false, i - 1, 0), gx = slot_of(P, arena, true, i - 1, 0);
         S.name("B%d%d.poolB", n.i, n.j);
-        S.add(lane, 0, 8.f, {rl + L_GPIN, R_X + (i - 1) * 5 + 0}, {R_GX + (i - 1) * 5 + 0}, [=](hipStream_t ls) {
-          return nunet_maxpool2x2_bwd(dt, c.N, P->hl[i - 1], P->wl[i - 1], NBF[i - 1], AB(arena, P->X[i - 1]), P->PX[i - 1],
-                                      AB(arena, P->off_gpin[k]), NBF[i - 1], AB(arena, P->GX[i - 1]), P->PX[i - 1], acc, ls);
+        S.add(lane, 0, 8.f, {g.r[0], x.r}, {gx.r}, [=](hipStream_t ls) {
+          return nunet_maxpool2x2_bwd(dt, c.N, P->hl[i - 1], P->wl[i - 1], NBF[i - 1], x.p, P->PX[i - 1], g.p[0], NBF[i - 1], gx.p, P->PX[i - 1], n.acc_pool, ls);
         });
-        written[i - 1][0] = true;
       } else {
-        d.dst0 = AB(arena, P->GX[i]); d.D0 = n.in_prefix * f; d.Q0 = P->PX[i]; d.acc_slot_w = f;
-        for (int q = 0; q < n.in_prefix; ++q) { if (written[i][q]) d.acc0_mask |= 1u << q; written[i][q] = true; }
-        d.dst1 = AB(arena, P->off_gup[k]); d.D1 = NBF[i + 1]; d.Q1 = NBF[i + 1];
-        S.add_conv(lane, {r_da1, rb + B_Y1, r_v1, R_WP + i},
-                   {r_dy1, R_GX + i * 5 + 0, n.in_prefix > 1 ? R_GX + i * 5 + 1 : -1, n.in_prefix > 2 ? R_GX + i * 5 + 2 : -1,
-                    n.in_prefix > 3 ? R_GX + i * 5 + 3 : -1, rl + L_GUP, rsk}, d);
         // through the bilinear upsample into x_{i+1,up_slot}
-        const int acc = written[i + 1][n.up_slot] ? 1 : 0;
+        const Buf gx = slot_of(P, arena, true, i + 1, n.up_slot);
         S.name("B%d%d.upB", n.i, n.j);
-        S.add(lane, 0, 11.f, {rl + L_GUP}, {R_GX + (i + 1) * 5 + n.up_slot}, [=](hipStream_t ls) {
-          return nunet_upsample2x_bwd(dt, c.N, P->hl[i + 1], P->wl[i + 1], NBF[i + 1], AB(arena, P->off_gup[k]), NBF[i + 1],
-                                      AB(arena, P->GX[i + 1] + (size_t)n.up_slot * NBF[i + 1] * es), P->PX[i + 1], acc, ls);
+        S.add(lane, 0, 11.f, {g.r[4]}, {gx.r}, [=](hipStream_t ls) {
+          return nunet_upsample2x_bwd(dt, c.N, P->hl[i + 1], P->wl[i + 1], NBF[i + 1], g.p[1], NBF[i + 1], gx.p, P->PX[i + 1], n.acc_up, ls);
         });
-        written[i + 1][n.up_slot] = true;
       }
     } else {
       nunet_bn_bwd_desc b1; memset(&b1, 0, sizeof(b1));
       b1.dtype = dt; b1.N = c.N; b1.H = H; b1.W = W; b1.C = f;
-      b1.da = da1; b1.PDA = f; b1.y = AB(arena, n.y1); b1.PY = f;
-      b1.mean_invstd = save + L1.save; b1.gamma = params + L1.g_off; b1.beta = params + L1.be_off;
-      b1.sums = (int64_t*)fx_of(arena, P, 1, L1.bsum);
-      b1.dbias = gv1; b1.dgamma = gv1 + L1.cout; b1.dbeta = gv1 + 2 * L1.cout;
-      b1.dy = dy1; b1.PDY = f;
+      b1.da = da1.p; b1.PDA = f; set_bn(b1, bn1);
+      b1.dbias = bn1.gv; b1.dgamma = bn1.gv + bn1.C; b1.dbeta = bn1.gv + 2 * bn1.C;
+      b1.dy = dy1.p; b1.PDY = f;
       S.name("B%d%d.bnA1", n.i, n.j);
-      S.add(lane, 0, 9.f, {r_da1, rb + B_Y1, r_v1}, {r_dy1}, [=](hipStream_t ls) { return nunet_bn_relu_bwd_apply(&b1, ls); });
+      S.add(lane, 0, 9.f, {da1.r, bn1.r_y, bn1.r_fx}, {dy1.r}, [=](hipStream_t ls) { return nunet_bn_relu_bwd_apply(&b1, ls); });
     }
     // ---- both weight gradients of the block in one launch (leaves of the dependency graph: only the slab reduce
     // reads them); conv1's problem first: it may carry the first layer's algorithmic Cin for the profiler
     {
+      const Cat in = block_in(P, arena, k, false);
       nunet_wgrad_desc w1, w2; memset(&w1, 0, sizeof(w1)); memset(&w2, 0, sizeof(w2));
       w1.dtype = w2.dtype = dt; w1.N = w2.N = c.N; w1.H = w2.H = H; w1.W = w2.W = W;
       w2.src0 = AB(arena, n.a1); w2.C0 = f; w2.P0 = f;
-      if (n.in_prefix == 0) {
-        if (i == 0) { w1.src0 = AB(arena, P->off_img); w1.C0 = 32; w1.P0 = 32; }
-        else { w1.src0 = AB(arena, n.pin); w1.C0 = NBF[i - 1]; w1.P0 = NBF[i - 1]; }
-      } else {
-        w1.src0 = AB(arena, P->X[i]); w1.C0 = n.in_prefix * f; w1.P0 = P->PX[i];
-        w1.src1 = AB(arena, n.up); w1.C1 = NBF[i + 1]; w1.P1 = NBF[i + 1];
-      }
-      w1.dy = dy1; w2.dy = dy2; w1.Cout = w2.Cout = f; w1.PY = w2.PY = f;
+      set_src(w1, in);
+      w1.dy = dy1.p; w2.dy = dy2.p; w1.Cout = w2.Cout = f; w1.PY = w2.PY = f;
       w1.dw = L1.ks > 1 ? slabs + L1.slab : gsr + L1.gs; w1.slab_stride = 9LL * L1.cout * L1.cinpad; w1.max_slabs = L1.ks; w1.target_wgs = L1.wg_target;
       w2.dw = L2.ks > 1 ? slabs + L2.slab : gsr + L2.gs; w2.slab_stride = 9LL * L2.cout * L2.cinpad; w2.max_slabs = L2.ks; w2.target_wgs = L2.wg_target;
       w1.dw_floats = (int64_t)L1.ks * w1.slab_stride; w2.dw_floats = (int64_t)L2.ks * w2.slab_stride;
       const int alg_cin = (i == 0 && n.in_prefix == 0) ? c.input_channels : 0;
       S.name("B%d%d.wgrad", n.i, n.j);
       S.census_wgrad(w1, w2);
-      int rx[4] = {-1, -1, -1, -1}, r_in = -1, r_up = -1;
-      if (n.in_prefix == 0) r_in = (i == 0 ? R_IMG : rb + B_PIN);
-      else { for (int q = 0; q < n.in_prefix && q < 4; ++q) rx[q] = R_X + i * 5 + q; r_up = rb + B_UP; }
       // The weight gradients of the shallow blocks of the critical chain (B04, B13, B22: full-chip launches) are held
       // back until the chain reaches the deep levels (B31 ..., grid-starved kernels that leave most CUs idle): they run
       // on lane 4 behind a dependency on the gradient that B22's upsample-backward hands to B31
       int wl = wlane, r_gate = -1;     // (measured +1.9 % on the step)
       if (!P->cfg.unet && n.j > 0 && n.i + n.j == 4 && n.i <= 2 && (phases & 3) == 3 && !S.list) { wl = 4; r_gate = R_GX + 3 * 5 + 1; }
       const float wcost = 8.f + (float)(2.0 * 9 * ((double)L1.cinpad + L2.cinpad) * f * (double)c.N * H * W / 3.5e8);
-      S.add(wl, 1, wcost, {rb + B_A1, r_dy2, r_dy1, r_in, rx[0], rx[1], rx[2], rx[3], r_up, r_gate}, {R_GSW + 2 * k, R_GSW + 2 * k + 1},
+      S.add(wl, 1, wcost, {rb + B_A1, dy2.r, dy1.r, in.r[0], in.r[1], in.r[2], in.r[3], in.r[4], r_gate}, {R_GSW + 2 * k, R_GSW + 2 * k + 1},
             [=](hipStream_t ls) {
               g_prof_alg_cin = alg_cin; int r = nunet_conv3x3_wgrad_pair(&w1, &w2, ls); g_prof_alg_cin = 0;
               // the block's K-split slabs are summed right behind it on the same lane: 15 small launches hidden beside the
@@ -1828,7 +1826,7 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
         const int t0 = tab.tile0[2 * r0], t1 = tab.tile0[2 * r0 + 2];
         const long long np = 9LL * (L1.cout * L1.cinpad + L2.cout * L2.cinpad);
         S.name("B%d%d.upd", n.i, n.j);
-        S.add(wlane, 1, 4.f + (float)(np * 28.0 / 3.0e6), {R_GSW + 2 * k, R_GSW + 2 * k + 1, R_GSV + 2 * k, R_GSV + 2 * k + 1}, {R_PRM + k}, [=](hipStream_t ls) {
+        S.add(wlane, 1, 4.f + (float)(np * 28.0 / 3.0e6), {R_GSW + 2 * k, R_GSW + 2 * k + 1, bn1.r_fx, bn2.r_fx}, {R_PRM + k}, [=](hipStream_t ls) {
           return launch_update(P, arena, upd, t0, t1 - t0, ls);
         });
       }
@@ -1837,12 +1835,12 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
   if (inpass && (phases & 1) && !P->heads.empty()) {
     // the 1x1 heads: blocks past the last tile of the update kernel's numbering
     int rs[12]; int nr = 0;
-    for (size_t h = 0; h < P->heads.size() && nr < 12; ++h) rs[nr++] = R_GSV + 30 + (int)h;
+    for (size_t h = 0; h < P->heads.size() && nr < 12; ++h) rs[nr++] = R_GSH + (int)h;
     const int nh = P->utab.n - P->ptab.n, nt = P->ptab.ntiles;
     S.name("heads.upd");
     S.add_v(0, 1, 5.f, rs, nr, nullptr, 0, [=](hipStream_t ls) { return launch_update(P, arena, upd, nt, nh, ls); });
   }
-  if (rc == NUNET_OK) rc = S.run();
+  int rc = S.run();
   if (leave_open && rc == NUNET_OK && !S.failed) {
     // the producers of the first bucket: last-writer events of every gradient resource of the phase-1 nodes and the heads
     // (single-lane issue: none - everything is in order on the caller's stream, which the caller makes its side stream wait for)
@@ -1855,7 +1853,7 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
       rt->b0_events.push_back(e);
     };
     for (int kk = k_split; kk < nnodes; ++kk) { take(R_GSW + 2 * kk); take(R_GSW + 2 * kk + 1); take(R_GSV + 2 * kk); take(R_GSV + 2 * kk + 1); }
-    for (size_t h = 0; h < P->heads.size(); ++h) take(R_GSV + 30 + (int)h);
+    for (size_t h = 0; h < P->heads.size(); ++h) take(R_GSH + (int)h);
     owner.keep = true;
     return NUNET_OK;
   }
