@@ -259,13 +259,27 @@ int nunet_bce_dice_bwd(const float* logits, const float* target, int32_t N, int6
  * dlogits of their mean, IoU counts of the last head. logits/dlogits: [heads][N][per].
  * loss_out: [heads+1] (per head, then the mean). meters (may be NULL): double[4]:
  * [0] += mean loss, [1] += IoU of this batch, [2],[3] = intersection / union counts.
- * loss_kind: NUNET_LOSS_BCE_DICE (losses.py:103-117) or NUNET_LOSS_LOVASZ_HINGE (losses.py:120-129, the loss behind the
- * reference's published table README.md:102-108; one class only: the reference squeezes dim 1). */
-enum { NUNET_LOSS_BCE_DICE = 0, NUNET_LOSS_LOVASZ_HINGE = 1 };
+ * loss_kind: NUNET_LOSS_BCE_DICE (losses.py:103-117), NUNET_LOSS_LOVASZ_HINGE (losses.py:120-129, the loss behind the
+ * reference's published table README.md:102-108; one class only: the reference squeezes dim 1) or NUNET_LOSS_BCE_LOGITS
+ * (torch.nn.BCEWithLogitsLoss(), trains.py:27-28,210-211; any class count). The BCE_LOGITS kind reads logits and targets once:
+ * its first launch, on the grid of the BCE_DICE kind, stores dlogits = (sigmoid(x) - t) / (N * per * heads) and per-block
+ * partial sums, a one-workgroup launch adds them in a fixed order. */
+enum { NUNET_LOSS_BCE_DICE = 0, NUNET_LOSS_LOVASZ_HINGE = 1, NUNET_LOSS_BCE_LOGITS = 2 };
 size_t nunet_loss_step_ws_bytes(int32_t N, int64_t per_sample, int32_t heads, int32_t loss_kind);
 int nunet_loss_step(const float* logits, const float* target, int32_t N, int64_t per_sample,
                     int32_t heads, int32_t loss_kind, float* ws, size_t ws_bytes, float* dlogits, float* loss_out,
                     double* meters, float iou_logit_threshold, nunet_stream_t s);
+/* BCEWithLogitsLoss (trains.py:27-28,210-211: torch.nn.BCEWithLogitsLoss() with its defaults - mean reduction, no weight, no
+ * pos_weight). logits/target: n elements of any shape, targets anywhere in [0, 1]:
+ *   loss = (1 / n) sum_i max(x_i, 0) - x_i t_i + log1p(exp(-|x_i|)),      dloss/dx_i = (sigmoid(x_i) - t_i) / n.
+ * The forward writes one partial per workgroup to ws (nunet_bce_logits_ws_bytes(n) bytes, 4-byte aligned) with plain stores and
+ * sums them in a fixed order: no atomics, bit-reproducible. The backward needs no workspace: dlogits = gscale[0] * dloss/dlogits
+ * (gscale == NULL: 1), the scale as the last multiply. Pointers need 4-byte alignment only. */
+size_t nunet_bce_logits_ws_bytes(int64_t n);
+int nunet_bce_logits_fwd(const float* logits, const float* target, int64_t n, float* ws, size_t ws_bytes, float* loss,
+                         nunet_stream_t s);
+int nunet_bce_logits_bwd(const float* logits, const float* target, int64_t n, const float* gscale, float* dlogits,
+                         nunet_stream_t s);
 /* LovaszHingeLoss (losses.py:49-96,120-129; per_image=True, mean over images). logits/target: [N][per_image]
  * (num_classes must be 1: the reference squeezes dim 1). Per-image sort: in LDS up to 16384 pixels, chunk sorts +
  * global bitonic merge passes above (up to 2^22); ws of nunet_lovasz_ws_bytes(N, per_image) bytes, 256-byte aligned.

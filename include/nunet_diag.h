@@ -99,14 +99,16 @@ typedef struct {
 int32_t nunet_plan_census_count(const nunet_plan* p, int32_t pass);
 int nunet_plan_census_get(const nunet_plan* p, int32_t pass, int32_t index, nunet_plan_census_entry* out);
 
-/* Launch geometry of the BCE-Dice loss, the fused loss step (NUNET_LOSS_BCE_DICE), the IoU counts and the mask export, from
+/* Launch geometry of the BCE-Dice loss, the fused loss step (NUNET_LOSS_BCE_DICE, and the first launch of NUNET_LOSS_BCE_LOGITS,
+ * which runs on the same grid), the IoU counts, the mask export and the stand-alone BCEWithLogitsLoss pair, from
  * the very expressions their launches use. A pure host function: no GPU call, no pointer but `out`. N and heads are read where
- * the entry has them (the two losses; heads by the loss step alone), per_or_n is the elements per image of a loss and the
- * element count of the other two. It refuses what the entry itself refuses by size (N, heads, the loss step's 2^24 per image).
+ * the entry has them (the BCE-Dice loss and the loss step; heads by the loss step alone), per_or_n is the elements per image of
+ * those and the element count of the others. It refuses what the entry itself refuses by size (N, heads, the loss step's 2^24 per image).
  * Every kernel walks its items with one grid-stride loop per (y, z) plane of the grid; the BCE-Dice forward also runs a
  * one-wave final kernel over the grid.x partial slabs of each image. */
 enum { NUNET_LOSS_ENTRY_BCE_DICE_FWD = 0, NUNET_LOSS_ENTRY_BCE_DICE_BWD = 1, NUNET_LOSS_ENTRY_LOSS_STEP = 2,
-       NUNET_LOSS_ENTRY_IOU_COUNTS = 3, NUNET_LOSS_ENTRY_SIGMOID_U8 = 4 };
+       NUNET_LOSS_ENTRY_IOU_COUNTS = 3, NUNET_LOSS_ENTRY_SIGMOID_U8 = 4, NUNET_LOSS_ENTRY_BCE_LOGITS_FWD = 5,
+       NUNET_LOSS_ENTRY_BCE_LOGITS_BWD = 6 };
 typedef struct {
   int32_t grid_x, grid_y, grid_z;   /* workgroups: blocks per image (or over all elements) x images x heads */
   int32_t block;                    /* threads of a workgroup */

@@ -99,7 +99,8 @@ class PlanCensusEntry(C.Structure):
                 ("acc0_mask", _u32), ("splitk_ws_floats", _i64), ("conv", ConvLaunchInfo), ("wgrad", WgradLaunchInfo * 2)]
 
 
-LOSS_ENTRY_BCE_DICE_FWD, LOSS_ENTRY_BCE_DICE_BWD, LOSS_ENTRY_LOSS_STEP, LOSS_ENTRY_IOU_COUNTS, LOSS_ENTRY_SIGMOID_U8 = range(5)
+(LOSS_ENTRY_BCE_DICE_FWD, LOSS_ENTRY_BCE_DICE_BWD, LOSS_ENTRY_LOSS_STEP, LOSS_ENTRY_IOU_COUNTS, LOSS_ENTRY_SIGMOID_U8,
+ LOSS_ENTRY_BCE_LOGITS_FWD, LOSS_ENTRY_BCE_LOGITS_BWD) = range(7)
 
 
 class LossLaunchInfo(C.Structure):
@@ -180,6 +181,9 @@ _SIG = {
     "nunet_bce_dice_ws_bytes": (C.c_size_t, [_i32]),
     "nunet_bce_dice_fwd": (_i32, [_vp, _vp, _i32, _i64, _vp, _sz, _vp, _vp]),
     "nunet_bce_dice_bwd": (_i32, [_vp, _vp, _i32, _i64, _vp, _sz, _vp, _vp, _vp]),
+    "nunet_bce_logits_ws_bytes": (C.c_size_t, [_i64]),
+    "nunet_bce_logits_fwd": (_i32, [_vp, _vp, _i64, _vp, _sz, _vp, _vp]),
+    "nunet_bce_logits_bwd": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "nunet_loss_step_ws_bytes": (C.c_size_t, [_i32, _i64, _i32, _i32]),
     "nunet_loss_step": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _sz, _vp, _vp, _vp, _f32, _vp]),
     "nunet_lovasz_ws_bytes": (C.c_size_t, [_i32, _i64]),
@@ -306,7 +310,7 @@ def stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-LOSS_BCE_DICE, LOSS_LOVASZ_HINGE = 0, 1
+LOSS_BCE_DICE, LOSS_LOVASZ_HINGE, LOSS_BCE_LOGITS = 0, 1, 2
 
 
 def nbytes(t):

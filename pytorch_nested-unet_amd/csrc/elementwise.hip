@@ -1,9 +1,9 @@
 // elementwise.hip — the HBM-bound kernels of the UNet++ path (NHWC, 16 B/lane):
 //   BatchNorm2d(+ReLU)(+MaxPool2d) forward, BatchNorm/ReLU backward,
 //   MaxPool2d(2,2) fwd/bwd, bilinear x2 align_corners upsample fwd/bwd,
-//   1x1 heads fwd/bwd, BCEDiceLoss fwd/bwd, IoU counts, SGD, layout helpers.
+//   1x1 heads fwd/bwd, BCEDiceLoss fwd/bwd, BCEWithLogitsLoss fwd/bwd, IoU counts, SGD, layout helpers.
 // Reference arithmetic: finished/archs1.py:17-21,82-83,105-111; losses.py:103-117;
-// metrics.py:6-18; trains.py:229-231.
+// metrics.py:6-18; trains.py:27-28,210-211,229-231.
 #include <cmath>
 #include <stdlib.h>
 #include <string.h>
@@ -36,7 +36,7 @@ int nunet_check_launch(const char* what) {
   return NUNET_OK;
 }
 extern "C" const char* nunet_last_error(void) { return g_err; }
-extern "C" int nunet_version(void) { return 102; }
+extern "C" int nunet_version(void) { return 103; }
 
 static inline int grid_for(int64_t items, int block, int cap = 256 * 16) {
   int64_t g = ceil_div64(items, block);
@@ -1159,24 +1159,154 @@ __global__ __launch_bounds__(256) void loss_step_bwd_kernel(const float* __restr
     ds[i] = g * (kb * (pv - tv) - invN * ddice) * sc;
   }
 }
+
+// ---------------------------------------------------------------------------
+// BCEWithLogitsLoss (trains.py:27-28,210-211: torch.nn.BCEWithLogitsLoss(), mean over all elements)
+// ---------------------------------------------------------------------------
+// l_i = max(x, 0) - x t + log1p(exp(-|x|)), the BCE term of the kernels above; d loss / dx_i = (sigmoid(x_i) - t_i) / count
+// depends on no sum, so the stand-alone backward needs no workspace and the loss step forms it in the pass that sums l_i.
+__device__ __forceinline__ float bce_logits_term(float xv, float tv) { return fmaxf(xv, 0.f) - xv * tv + log1pf(expf(-fabsf(xv))); }
+
+constexpr int BCEL_GX = 256;    // most blocks of the stand-alone pair: one element per thread up to 65536, a grid-stride loop above
+static int bce_logits_gx(int64_t n) { return grid_for(n, 256, BCEL_GX); }
+__global__ __launch_bounds__(256) void bce_logits_partial_kernel(const float* __restrict__ x, const float* __restrict__ t, int64_t n, float* __restrict__ ws) {
+  float a = 0.f;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) a += bce_logits_term(x[i], t[i]);
+  a = wave_sum(a);
+  __shared__ float s[4];
+  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) ws[blockIdx.x] = ((s[0] + s[1]) + s[2]) + s[3];    // one partial per block, a plain store
+}
+__global__ void bce_logits_final_kernel(const float* __restrict__ ws, int gx, int64_t n, float* __restrict__ loss) {
+  // single wave: lane l adds partials l, l + 64, ... in that order, then the butterfly (a fixed order: bit-reproducible)
+  const int l = threadIdx.x;
+  float v = 0.f;
+  for (int b = l; b < gx; b += 64) v += ws[b];
+  v = wave_sum(v);
+  if (l == 0) loss[0] = v / (float)n;
+}
+__global__ __launch_bounds__(256) void bce_logits_bwd_kernel(const float* __restrict__ x, const float* __restrict__ t, int64_t n, const float* __restrict__ gscale, float* __restrict__ dx) {
+  const float g = gscale ? gscale[0] : 1.f;
+  const float k = 1.f / (float)n;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    dx[i] = (sigmoidf_(x[i]) - t[i]) * k * g;    // the upstream scale is the last multiply: a power of two is exact
+}
+extern "C" size_t nunet_bce_logits_ws_bytes(int64_t n) { return n > 0 ? (size_t)bce_logits_gx(n) * sizeof(float) : 0; }
+extern "C" int nunet_bce_logits_fwd(const float* logits, const float* target, int64_t n, float* ws, size_t ws_bytes, float* loss, nunet_stream_t s) {
+  NUNET_REQUIRE(logits && target && ws && loss && n > 0, "bce_logits_fwd: bad args");
+  NUNET_REQUIRE(ws_bytes >= nunet_bce_logits_ws_bytes(n), "bce_logits_fwd: workspace of %zu bytes, nunet_bce_logits_ws_bytes(%lld) = %zu", ws_bytes,
+                (long long)n, nunet_bce_logits_ws_bytes(n));
+  hipStream_t st = (hipStream_t)s;
+  const int gx = bce_logits_gx(n);
+  ProfScope ps(PC_LOSS, 0, (double)n * 8, st);
+  NUNET_LAUNCH(bce_logits_partial_kernel, dim3(gx), dim3(256), 0, st, logits, target, n, ws);
+  NUNET_LAUNCH(bce_logits_final_kernel, dim3(1), dim3(64), 0, st, ws, gx, n, loss);
+  return nunet_check_launch("bce_logits_fwd");
+}
+extern "C" int nunet_bce_logits_bwd(const float* logits, const float* target, int64_t n, const float* gscale, float* dlogits, nunet_stream_t s) {
+  NUNET_REQUIRE(logits && target && dlogits && n > 0, "bce_logits_bwd: bad args");
+  ProfScope ps(PC_LOSS, 0, (double)n * 12, (hipStream_t)s);
+  NUNET_LAUNCH(bce_logits_bwd_kernel, dim3(bce_logits_gx(n)), dim3(256), 0, (hipStream_t)s, logits, target, n, gscale, dlogits);
+  return nunet_check_launch("bce_logits_bwd");
+}
+
+// Loss step, NUNET_LOSS_BCE_LOGITS: one pass over [heads][N][per] on the grid of the BCE-Dice kind reads logits and targets once,
+// stores d mean / d logits and leaves per-block slabs [heads][N][LOSS_GX] x {BCE sum, iou-inter, iou-union} with plain stores; one
+// workgroup then adds the slabs in a fixed order and writes the losses and the meters (the semantics of loss_step_bwd_kernel's).
+__global__ __launch_bounds__(256) void bce_logits_step_kernel(const float* __restrict__ x, const float* __restrict__ t, int64_t per, float* __restrict__ ws, int N, int heads, float iou_thr,
+                                                              float* __restrict__ dx, const float* __restrict__ seed_scale) {
+  const int n = blockIdx.y, hd = blockIdx.z;
+  const float* xs = x + ((int64_t)hd * N + n) * per;
+  const float* ts = t + (int64_t)n * per;
+  float* ds = dx + ((int64_t)hd * N + n) * per;
+  const float k = 1.f / ((float)N * (float)per * (float)heads);    // mean over all elements, then over the heads (trains.py:120-123)
+  const float sc = seed_scale ? seed_scale[0] : 1.f;                // loss scaling: the last multiply
+  float a = 0.f;
+  unsigned ci = 0, cu = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < per; i += (int64_t)gridDim.x * blockDim.x) {
+    const float xv = xs[i], tv = ts[i];
+    ds[i] = (sigmoidf_(xv) - tv) * k * sc;
+    a += bce_logits_term(xv, tv);
+    const bool p = xv >= iou_thr, b = tv > 0.5f; ci += (p && b) ? 1u : 0u; cu += (p || b) ? 1u : 0u;
+  }
+  a = wave_sum(a);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { ci += __shfl_xor(ci, o); cu += __shfl_xor(cu, o); }
+  __shared__ float s_f[4][3];
+  const int wv = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { s_f[wv][0] = a; s_f[wv][1] = (float)ci; s_f[wv][2] = (float)cu; }
+  __syncthreads();
+  if (threadIdx.x < 3)    // (counts <= 2^24 per image: exact in fp32)
+    ws[((((size_t)hd * N + n) * LOSS_GX) + blockIdx.x) * 3 + threadIdx.x] = ((s_f[0][threadIdx.x] + s_f[1][threadIdx.x]) + s_f[2][threadIdx.x]) + s_f[3][threadIdx.x];
+}
+__global__ __launch_bounds__(256) void bce_logits_step_final_kernel(const float* __restrict__ ws, int gx, int N, int heads, int64_t per, float* __restrict__ loss_out, double* __restrict__ meters) {
+  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
+  __shared__ float s_bce[4][8];
+  __shared__ double s_cnt[4][2];
+  const int64_t slabs = (int64_t)N * gx;     // thread j takes slabs j, j + 256, ... of every head, image-major: a fixed order
+  double ci = 0.0, cu = 0.0;
+  for (int k = 0; k < heads; ++k) {
+    float bce = 0.f;
+    for (int64_t j = threadIdx.x; j < slabs; j += 256) {
+      const int64_t q = j / gx;
+      const float* w = ws + ((((size_t)k * N + q) * LOSS_GX) + (j - q * gx)) * 3;
+      bce += w[0];
+      if (k == heads - 1) { ci += (double)w[1]; cu += (double)w[2]; }    // IoU of the last head (trains.py:124,128)
+    }
+    bce = wave_sum(bce);
+    if (l == 0) s_bce[wv][k] = bce;
+  }
+  ci = wave_sum_f64(ci); cu = wave_sum_f64(cu);
+  if (l == 0) { s_cnt[wv][0] = ci; s_cnt[wv][1] = cu; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float mean = 0.f;
+    for (int k = 0; k < heads; ++k) {
+      const float bce = ((s_bce[0][k] + s_bce[1][k]) + s_bce[2][k]) + s_bce[3][k];
+      const float lk = bce / ((float)N * (float)per);
+      loss_out[k] = lk;
+      mean += lk;
+    }
+    mean /= (float)heads;
+    loss_out[heads] = mean;
+    if (meters) {
+      const double inter = s_cnt[0][0] + s_cnt[1][0] + s_cnt[2][0] + s_cnt[3][0], uni = s_cnt[0][1] + s_cnt[1][1] + s_cnt[2][1] + s_cnt[3][1];
+      meters[0] += (double)mean;
+      meters[1] += (inter + 1e-5) / (uni + 1e-5);
+      meters[2] = inter; meters[3] = uni;
+    }
+  }
+}
+static int bce_logits_loss_step(const float* logits, const float* target, int32_t N, int64_t per, int32_t heads, float* ws, float* dlogits,
+                                float* loss_out, double* meters, float iou_thr, const float* seed_scale, hipStream_t st) {
+  const int gx = loss_step_gx(per);
+  ProfScope ps(PC_LOSS, 0, (double)N * per * heads * 12, st);
+  NUNET_LAUNCH(bce_logits_step_kernel, dim3(gx, N, heads), dim3(256), 0, st, logits, target, per, ws, N, heads, iou_thr, dlogits, seed_scale);
+  NUNET_LAUNCH(bce_logits_step_final_kernel, dim3(1), dim3(256), 0, st, ws, gx, N, heads, per, loss_out, meters);
+  return nunet_check_launch("loss_step");
+}
 size_t lovasz_step_ws_bytes(int32_t N, int64_t per, int32_t heads);    // lovasz.hip
 int lovasz_loss_step(const float* logits, const float* target, int32_t N, int64_t per, int32_t heads, float* ws, float* dlogits,
                      float* loss_out, double* meters, float iou_thr, const float* seed_scale, hipStream_t st);
 extern "C" size_t nunet_loss_step_ws_bytes(int32_t N, int64_t per, int32_t heads, int32_t loss_kind) {
   if (N <= 0 || per <= 0 || heads < 1) return 0;
   if (loss_kind == NUNET_LOSS_LOVASZ_HINGE) return lovasz_step_ws_bytes(N, per, heads);
+  if (loss_kind == NUNET_LOSS_BCE_LOGITS) return (size_t)heads * N * LOSS_GX * 3 * sizeof(float);
   return (size_t)heads * N * LOSS_GX * 6 * sizeof(float);
 }
 static int loss_step(const float* logits, const float* target, int32_t N, int64_t per, int32_t heads, int32_t loss_kind, float* ws, size_t ws_bytes,
                      float* dlogits, float* loss_out, double* meters, float iou_logit_threshold, const float* seed_scale, nunet_stream_t s) {
   NUNET_REQUIRE(logits && target && ws && dlogits && loss_out && N > 0 && per > 0 && heads >= 1 && heads <= 8, "loss_step: bad args");
-  NUNET_REQUIRE(loss_kind == NUNET_LOSS_BCE_DICE || loss_kind == NUNET_LOSS_LOVASZ_HINGE, "loss_step: loss_kind %d", (int)loss_kind);
+  NUNET_REQUIRE(loss_kind == NUNET_LOSS_BCE_DICE || loss_kind == NUNET_LOSS_LOVASZ_HINGE || loss_kind == NUNET_LOSS_BCE_LOGITS, "loss_step: loss_kind %d", (int)loss_kind);
   NUNET_REQUIRE(per <= (1ll << 24), "loss_step: image too large");    // per-image IoU counts stay exact in fp32
   NUNET_REQUIRE(ws_bytes >= nunet_loss_step_ws_bytes(N, per, heads, loss_kind), "loss_step: workspace of %zu bytes, nunet_loss_step_ws_bytes = %zu",
                 ws_bytes, nunet_loss_step_ws_bytes(N, per, heads, loss_kind));
   hipStream_t st = (hipStream_t)s;
   if (loss_kind == NUNET_LOSS_LOVASZ_HINGE)
     return lovasz_loss_step(logits, target, N, per, heads, ws, dlogits, loss_out, meters, iou_logit_threshold, seed_scale, st);
+  if (loss_kind == NUNET_LOSS_BCE_LOGITS)
+    return bce_logits_loss_step(logits, target, N, per, heads, ws, dlogits, loss_out, meters, iou_logit_threshold, seed_scale, st);
   const int gx = loss_step_gx(per);
   ProfScope ps(PC_LOSS, 0, (double)N * per * heads * 16, st);
   NUNET_LAUNCH(loss_step_partial_kernel, dim3(gx, N, heads), dim3(256), 0, st, logits, target, per, ws, N, heads, iou_logit_threshold);
@@ -1284,6 +1414,8 @@ extern "C" int nunet_loss_launch_info(int32_t entry, int32_t N, int64_t per_or_n
       break;
     case NUNET_LOSS_ENTRY_IOU_COUNTS: gx = iou_counts_gx(per_or_n); break;
     case NUNET_LOSS_ENTRY_SIGMOID_U8: gx = sigmoid_u8_gx(per_or_n); items = per_or_n / 4; break;
+    case NUNET_LOSS_ENTRY_BCE_LOGITS_FWD:
+    case NUNET_LOSS_ENTRY_BCE_LOGITS_BWD: gx = bce_logits_gx(per_or_n); break;
     default: NUNET_REQUIRE(false, "loss launch info: entry %d", (int)entry);
   }
   const int64_t threads = (int64_t)gx * 256;

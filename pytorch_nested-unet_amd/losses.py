@@ -1,5 +1,6 @@
 """Drop-in `losses` module (reference registry: `losses.__dict__[config['loss']]()`,
-trains.py:213). BCEDiceLoss follows reference losses.py:103-117."""
+trains.py:213). BCEDiceLoss follows reference losses.py:103-117. BCEWithLogitsLoss is the third `--loss` of the
+reference, which takes it from torch.nn (trains.py:27-28,210-211) and keeps it out of its `losses.__all__`, as this module does."""
 import torch
 from torch import nn
 
@@ -43,6 +44,43 @@ class BCEDiceLoss(nn.Module):
 
     def forward(self, input, target):
         return _BCEDiceFn.apply(input.contiguous(), target.contiguous())
+
+
+class _BCEWithLogitsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target):
+        L.require_gpu_tensor(logits, torch.float32, "logits")
+        L.require_gpu_tensor(target, torch.float32, "target")
+        if logits.shape != target.shape or logits.numel() == 0:
+            raise L.NunetError("BCEWithLogitsLoss: logits %s vs target %s" % (tuple(logits.shape), tuple(target.shape)))
+        n = logits.numel()
+        lib = L.lib()
+        ws = torch.empty((lib.nunet_bce_logits_ws_bytes(n) + 3) // 4, dtype=torch.float32, device=logits.device)
+        loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+        L.check(lib.nunet_bce_logits_fwd(L.ptr(logits), L.ptr(target), n, L.ptr(ws), L.nbytes(ws), L.ptr(loss), L.stream()),
+                "nunet_bce_logits_fwd")
+        ctx.save_for_backward(logits, target)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target = ctx.saved_tensors
+        g = g.contiguous().float()
+        dx = torch.empty_like(logits)
+        L.check(L.lib().nunet_bce_logits_bwd(L.ptr(logits), L.ptr(target), logits.numel(), L.ptr(g), L.ptr(dx), L.stream()),
+                "nunet_bce_logits_bwd")
+        return dx, None
+
+
+class BCEWithLogitsLoss(nn.Module):
+    """torch.nn.BCEWithLogitsLoss() with its defaults (reference trains.py:210-211): the mean over all elements of
+    max(x, 0) - x t + log1p(exp(-|x|)); any shape, targets anywhere in [0, 1]."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, input, target):
+        return _BCEWithLogitsFn.apply(input.contiguous(), target.contiguous())
 
 
 class _LovaszFn(torch.autograd.Function):

@@ -45,9 +45,11 @@ class TrainStep:
                  use_graph=True, process_group=None, keep_grads=True, fused_update=None, loss="BCEDiceLoss", input_u8=False,
                  schedule=None, segmented=None, optimizer="SGD", betas=(0.9, 0.999), eps=1e-8, loss_scale=None,
                  clip_grad_norm=None):
-        """loss: 'BCEDiceLoss' (reference losses.py:103-117, the default of trains.py:58) or 'LovaszHingeLoss'
-        (losses.py:120-129, the loss of the reference's published table README.md:102-108; one class only) - both run
-        inside the step's graph and under data parallel.
+        """loss: 'BCEDiceLoss' (reference losses.py:103-117, the default of trains.py:58), 'LovaszHingeLoss'
+        (losses.py:120-129, the loss of the reference's published table README.md:102-108; one class only) or
+        'BCEWithLogitsLoss' (torch.nn.BCEWithLogitsLoss(), trains.py:27-28,210-211; any num_classes: its gradient needs no
+        sum, so one pass over logits and targets forms it with the partial sums) - all run inside the step's graph and
+        under data parallel.
         input_u8: the step's inputs are the DECODED uint8 batch (images [N,H,W,C], masks [N,H,W,K] in {0,255}) plus optional
         per-sample augmentation codes; Normalize, /255, the mask scaling, rot90 / flips and the layout change of the
         reference's sample pipeline (dataset.py:66-74, trains.py:258-266) run as the first two launches of the step's graph
@@ -113,7 +115,7 @@ class TrainStep:
         self.logits = torch.empty((self.heads, n, self.ncls, h, w), dtype=torch.float32, device=dev)
         self.dlogits = torch.empty_like(self.logits)
         self.per = self.ncls * h * w
-        kinds = {"BCEDiceLoss": L.LOSS_BCE_DICE, "LovaszHingeLoss": L.LOSS_LOVASZ_HINGE}
+        kinds = {"BCEDiceLoss": L.LOSS_BCE_DICE, "LovaszHingeLoss": L.LOSS_LOVASZ_HINGE, "BCEWithLogitsLoss": L.LOSS_BCE_LOGITS}
         if loss not in kinds:
             raise L.NunetError("TrainStep: loss %r is not one of %s" % (loss, sorted(kinds)))
         if loss == "LovaszHingeLoss" and self.ncls != 1:

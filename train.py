@@ -35,7 +35,7 @@ from nunet_amd.trainer import TrainStep, cosine_lr
 from nunet_amd.utils import AverageMeter, str2bool
 
 ARCH_NAMES = archs.__all__
-LOSS_NAMES = losses.__all__
+LOSS_NAMES = losses.__all__ + ['BCEWithLogitsLoss']      # trains.py:27-28 (a new list: the module's stays the reference's)
 
 
 def parse_args():
@@ -49,7 +49,7 @@ def parse_args():
     p.add_argument('--num_classes', default=1, type=int)
     p.add_argument('--input_w', default=96, type=int)
     p.add_argument('--input_h', default=96, type=int)
-    p.add_argument('--loss', default='BCEDiceLoss', choices=LOSS_NAMES)   # both losses run inside the fused step (TrainStep)
+    p.add_argument('--loss', default='BCEDiceLoss', choices=LOSS_NAMES)   # every loss runs inside the fused step (TrainStep)
     p.add_argument('--dataset', default='synthetic_blobs')
     p.add_argument('--optimizer', default='SGD', choices=['Adam', 'SGD'])
     p.add_argument('--lr', '--learning_rate', default=1e-3, type=float)
@@ -155,7 +155,7 @@ def main():
         with open('models/%s/config.yml' % config['name'], 'w') as f:
             yaml.dump(config, f)
 
-    criterion = losses.__dict__[config['loss']]().cuda()
+    criterion = getattr(losses, config['loss'])().cuda()
     torch.manual_seed(config['seed'])
     model = archs.__dict__[config['arch']](config['num_classes'], config['input_channels'], config['deep_supervision'],
                                            dtype=config['dtype'])
@@ -166,7 +166,7 @@ def main():
     val = tuple(v.cuda() for v in make_split(config['val_size'], h, w, config['input_channels'], config['num_classes'], 2000))
     steps = config['train_size'] // (bs * world)          # drop_last=True (trains.py:296); global batch = world x bs
 
-    fused = not (config['loss'] == 'LovaszHingeLoss' and config['num_classes'] != 1)   # TrainStep: SGD or Adam, either loss
+    fused = not (config['loss'] == 'LovaszHingeLoss' and config['num_classes'] != 1)   # TrainStep: SGD or Adam, any loss
     if world > 1 and not fused:
         raise SystemExit('data parallel runs the fused step: multi-class LovaszHingeLoss is not fused')
     u8 = fused and config['device_pipeline'] and config['input_channels'] == 3 and config['num_classes'] == 1
