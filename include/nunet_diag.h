@@ -117,6 +117,27 @@ typedef struct {
 } nunet_loss_launch_info_t;
 int nunet_loss_launch_info(int32_t entry, int32_t N, int64_t per_or_n, int32_t heads, nunet_loss_launch_info_t* out);
 
+/* The x2 bilinear upsample's backward pass by its gather kernel (one thread per output, every tap a global load), whatever the
+ * shape: the arguments of nunet_upsample2x_bwd, which takes the LDS-tiled kernel when H >= 4 and W >= 4. The two leave the
+ * same bytes; the tests hold one against the other. */
+int nunet_upsample2x_bwd_gather(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C,
+                                const void* dy, int32_t PDY, void* dx, int32_t PDX, int32_t accumulate, nunet_stream_t stream);
+/* Launch geometry of the upsample forward (backward = 0) or backward (1) pass, from the very code the launch runs. A pure host
+ * function. Pass p (of `passes`) covers the g = min(workgroups, items - p * workgroups) items from p * workgroups on: workgroup
+ * b < g takes item p * workgroups + the XCD remap of (b, g) below. The forward kernel and the gather kernel (which does not
+ * remap) count blocks of 256 outputs as items. */
+typedef struct {
+  int32_t tiled;                    /* backward: 1 = LDS-tiled kernel, 0 = gather kernel; forward: 0 */
+  int32_t workgroups, passes;
+  int32_t TR, TC, SG;               /* tiled: low-res rows, columns and 16-byte channel groups of a work item (edge items hold fewer) */
+  int32_t lds_bytes;                /* tiled: static LDS of a workgroup */
+  int32_t reserved;
+  int64_t items;
+} nunet_upsample_launch_info_t;
+int nunet_upsample_launch_info(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t backward, nunet_upsample_launch_info_t* out);
+/* The work item that workgroup b of G takes first (common.h, xcd_remap: one contiguous item range per XCD), evaluated on the host. */
+int32_t nunet_xcd_remap_host(int32_t b, int32_t G);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,6 +108,11 @@ class LossLaunchInfo(C.Structure):
     _fields_ = [(k, _i32) for k in ("grid_x", "grid_y", "grid_z", "block")] + [(k, _i64) for k in ("items", "trips_max", "trips_min")]
 
 
+class UpsampleLaunchInfo(C.Structure):
+    """nunet_upsample_launch_info_t (include/nunet_diag.h): what an upsample forward / backward call would launch."""
+    _fields_ = [(k, _i32) for k in ("tiled", "workgroups", "passes", "TR", "TC", "SG", "lds_bytes", "reserved")] + [("items", _i64)]
+
+
 class BnFwdDesc(C.Structure):
     _fields_ = [("dtype", _i32), ("N", _i32), ("H", _i32), ("W", _i32), ("C", _i32),
                 ("y", _vp), ("PY", _i32),
@@ -175,6 +180,9 @@ _SIG = {
     "nunet_maxpool2x2_bwd": (_i32, [_i32] * 5 + [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp]),
     "nunet_upsample2x_fwd": (_i32, [_i32] * 5 + [_vp, _i32, _vp, _i32, _vp]),
     "nunet_upsample2x_bwd": (_i32, [_i32] * 5 + [_vp, _i32, _vp, _i32, _i32, _vp]),
+    "nunet_upsample2x_bwd_gather": (_i32, [_i32] * 5 + [_vp, _i32, _vp, _i32, _i32, _vp]),
+    "nunet_upsample_launch_info": (_i32, [_i32] * 6 + [C.POINTER(UpsampleLaunchInfo)]),
+    "nunet_xcd_remap_host": (_i32, [_i32, _i32]),
     "nunet_head_fwd": (_i32, [_i32] * 6 + [_vp, _i32, _vp, _vp, _vp, _vp]),
     "nunet_head_bwd": (_i32, [_i32] * 6 + [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp]),
     "nunet_head_bwd_bnr": (_i32, [_i32] * 6 + [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, C.POINTER(BnrDesc), _vp]),

@@ -152,6 +152,22 @@ __device__ __forceinline__ void dec4(const Dec4& d, long long i, int& cg, long l
   }
 }
 
+// XCD-aware placement (for speed only, any placement is correct): workgroups are dealt round-robin over the 8 XCDs, each with its
+// own 4 MB L2, so blocks b and b + 8 share an L2 and b, b + 1 never do. Work items that read the same data are CONSECUTIVE in item
+// order (the Cout tiles of one pixel tile of a conv; the Cout x Cin tiles of one pixel slice of a weight gradient; neighbouring
+// pixel tiles, whose halos overlap; neighbouring rows of an upsample, which interpolate from the same source rows): taking
+// item = block would send them to eight different L2s, each of which fetches the tile from memory again. The map below hands
+// every XCD one contiguous range of the items instead: block b (XCD b % 8, the (b / 8)-th block that XCD receives) takes item
+// base(b % 8) + b / 8. A bijection of [0, G) for every G >= 1 (tests/test_xcd_remap_cpu.py through nunet_xcd_remap_host).
+#ifndef NUNET_XCD_REMAP
+#define NUNET_XCD_REMAP 1
+#endif
+__host__ __device__ __forceinline__ int xcd_remap(int b, int G) {
+  if (!NUNET_XCD_REMAP) return b;
+  const int x = b & 7, l = b >> 3, q = G >> 3, rem = G & 7;
+  return (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + l;
+}
+
 // ---------------------------------------------------------------------------
 // Order-independent per-channel sums (BatchNorm statistics, BatchNorm-backward sums).
 // Hundreds of workgroups add one partial sum each to the same channel. fp32 atomics would make the

@@ -214,20 +214,7 @@ static inline int conv_coef_floats(int lt, int cin, bool bnr, int cout) { return
 // yet timed): taking them out is a kernel change that needs a GPU comparison of its own.
 struct ConvGroup { int n; int grid[CONV_GROUP_MAX]; ConvP p[CONV_GROUP_MAX]; };
 
-// XCD-aware placement (for speed only, any placement is correct): workgroups are dealt round-robin over the 8 XCDs, each with its
-// own 4 MB L2, so blocks b and b + 8 share an L2 and b, b + 1 never do. Work items that read the same data are CONSECUTIVE in item
-// order (the Cout tiles of one pixel tile of a conv; the Cout x Cin tiles of one pixel slice of a weight gradient; neighbouring
-// pixel tiles, whose halos overlap): taking item = block would send them to eight different L2s, each of which fetches the tile
-// from memory again. The map below hands every XCD one contiguous range of the items instead: block b (XCD b % 8, the (b / 8)-th
-// block that XCD receives) takes item base(b % 8) + b / 8.
-#ifndef NUNET_XCD_REMAP
-#define NUNET_XCD_REMAP 1
-#endif
-__device__ __forceinline__ int xcd_remap(int b, int G) {
-  if (!NUNET_XCD_REMAP) return b;
-  const int x = b & 7, l = b >> 3, q = G >> 3, rem = G & 7;
-  return (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + l;
-}
+// (XCD-aware placement of the work items: xcd_remap() in common.h)
 __device__ __forceinline__ void conv_group_decode(const ConvGroup& g, int b, int& k, int& v) {
   int base = 0, prevg = 0, live = g.n;
   k = 0; v = b;

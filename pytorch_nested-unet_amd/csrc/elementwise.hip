@@ -683,7 +683,16 @@ __global__ __launch_bounds__(256) void upsample_fwd_kernel(const T* __restrict__
   const float sy = HO > 1 ? (float)(H - 1) / (float)(HO - 1) : 0.f;
   const float sx = WO > 1 ? (float)(W - 1) / (float)(WO - 1) : 0.f;
   const int64_t total = (int64_t)N * HO * WO * G;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+  // block -> 256 consecutive outputs through xcd_remap: every XCD takes one contiguous range of each pass, so the output rows
+  // that interpolate from the same source rows meet in one L2 (dealt round-robin, every L2 fetched nearly the whole source).
+  // The map is taken over the blocks a pass really has: a short last pass remapped over the whole grid would land on the
+  // first XCD alone (items 0 .. rest - 1 of the map are XCD 0's), which then runs twice as long as the others.
+  const int64_t nblk = (total + 255) / 256;
+  for (int64_t base = 0; base < nblk; base += gridDim.x) {
+    const int gp = (int)(nblk - base < (int64_t)gridDim.x ? nblk - base : (int64_t)gridDim.x);
+    if ((int)blockIdx.x >= gp) break;
+    const int64_t i = (base + xcd_remap((int)blockIdx.x, gp)) * 256 + threadIdx.x;
+    if (i >= total) break;
     int cg, ox, oy, n; long long o;
     dec4(dc, i, cg, o, ox, oy, n);
     int y0, y1, x0, x1; float ly, lx;
@@ -698,9 +707,58 @@ __global__ __launch_bounds__(256) void upsample_fwd_kernel(const T* __restrict__
     st16(y + o * PY + cg * EPV, r);
   }
 }
-// gather form of the transposed interpolation: one thread per low-res pixel
+// One tap of the backward sum, acc[e] <- acc[e] + w * g[e], with the operation order written out (contraction off, as in up_lerp):
+// whether the multiply fuses with the add is otherwise the compiler's choice per call site, and it does not choose the same for
+// every tap. The thread-per-output kernel, compiled with `acc[e] += w * g` under the default contraction, came out with fused
+// multiply-adds except at a few (tap, element) sites that its vectoriser had split into a multiply and an add; the same statement
+// in the tiled kernel split at other sites (1 ulp of fp32: 1 fp32 output in 5, 1 fp16 output in 25000). Every result recorded so
+// far was computed with that build, so its sites are kept, in this one function that both backward kernels take every tap through:
+// they cannot differ from each other, and a later compiler cannot move a rounding. t = 5 j + k is the tap's index in the window.
+// How the table was obtained: from the ISA of the three instantiations of that kernel (hipcc -S --cuda-device-only), following
+// each element's accumulator through its 25 v_pk_fma_f32 / v_pk_add_f32(v_mul) steps; bf16 and fp16 have the same sites, fp32
+// only the second row. How it was checked: the same walk over the ISA of this file's gather kernel gives the same sites for all
+// three types, and bench.py --dump-outputs (which reaches the sites through the tiled kernel) is byte-identical to that build in
+// bf16, fp16 and fp32 (profiles/r05_summary.md, 1). t is a constant in the gather kernel. In the tiled kernel, whose row loop is
+// rolled, it is a run-time value: the two or four elements with sites compute both forms and select (a scalar branch around that
+// for the taps without a site measured slower, 9.9 against 9.1 us per launch, as did unrolling the rows, which spills).
+template <int EPV> __device__ __forceinline__ bool up_tap_split(int t, int e) {
+  return (e >= EPV - 2 && t >= 14 && t <= 21) || (EPV == 8 && e < 2 && (t == 3 || t == 14));
+}
+template <typename T> __device__ __forceinline__ void up_bwd_tap(float* acc, int t, float w, const Vec16<T>& g) {
+#pragma clang fp contract(off)
+  constexpr int EPV = Tr<T>::EPV;
+#pragma unroll
+  for (int e = 0; e < EPV; ++e) {
+    const float ge = g.get(e);
+    if (e >= EPV - 2 || (EPV == 8 && e < 2)) {     // the elements that have sites: both forms and a select where t is a run-time value
+      const float p = w * ge;
+      const float two = acc[e] + p, one = __builtin_fmaf(w, ge, acc[e]);
+      acc[e] = up_tap_split<EPV>(t, e) ? two : one;
+    } else acc[e] = __builtin_fmaf(w, ge, acc[e]);
+  }
+}
+// The high-res rows that interpolate from low-res row ic have source coordinate in (ic-1, ic+1): an open interval
+// of 2/sc = 4 + 2/(n_in-1) < 5 output rows, so it holds at most 5 of them, found among the 6 starting at
+// floor((ic-1)/sc). Weights come from the same up_taps() as the forward pass. n_in >= 4. One function for both
+// backward kernels: base and weights of a row / column are the same bits in either.
+__device__ __forceinline__ void up_window(int ic, float sc, int n_in, int n_out, int& base, float* w5) {
+  base = max(0, (int)floorf((float)(ic - 1) / sc));
+  float w6[6];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    int i0, i1; float l;
+    up_taps(min(base + j, n_out - 1), sc, n_in, i0, i1, l);
+    w6[j] = base + j < n_out ? (i0 == ic ? 1.f - l : 0.f) + (i1 == ic ? l : 0.f) : 0.f;
+  }
+  const bool shift = w6[0] == 0.f;
+#pragma unroll
+  for (int j = 0; j < 5; ++j) w5[j] = shift ? w6[j + 1] : w6[j];
+  base += shift ? 1 : 0;
+}
+// gather form of the transposed interpolation: one thread per low-res pixel and 16-byte channel group, every tap a global
+// load. Serves extents below 4 (the general loop) and is what the tiled form below is tested against, byte for byte.
 template <typename T>
-__global__ __launch_bounds__(256) void upsample_bwd_kernel(const T* __restrict__ dy, int PDY, T* __restrict__ dx, int PDX, int accumulate, int N, int H, int W, int C, Dec4 dc) {
+__global__ __launch_bounds__(256) void upsample_bwd_gather_kernel(const T* __restrict__ dy, int PDY, T* __restrict__ dx, int PDX, int accumulate, int N, int H, int W, int C, Dec4 dc) {
   constexpr int EPV = Tr<T>::EPV;
   const int G = C / EPV, HO = 2 * H, WO = 2 * W;
   const float sy = HO > 1 ? (float)(H - 1) / (float)(HO - 1) : 0.f;
@@ -714,28 +772,11 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const T* __restrict__
 #pragma unroll
     for (int e = 0; e < EPV; ++e) acc[e] = 0.f;
     if (H >= 4 && W >= 4) {
-      // The high-res rows that interpolate from low-res row iy have source coordinate in (iy-1, iy+1): an open interval
-      // of 2/sy = 4 + 2/(H-1) < 5 output rows, so it holds at most 5 of them, found among the 6 starting at
-      // floor((iy-1)/sy). Weights come from the same up_taps() as the forward pass; the 5x5 window is then read with
-      // unconditional (clamped, zero-weighted) loads that the compiler can keep in flight together, in the same
-      // (oy, ox) order as the general loop below.
+      // the 5x5 window (up_window) is read with unconditional (clamped, zero-weighted) loads that the compiler can keep in
+      // flight together, in the same (oy, ox) order as the general loop below
       int yb, xb; float wy[5], wx[5];
-      auto window = [&](int ic, float sc, int n_in, int n_out, int& base, float* w5) {
-        base = max(0, (int)floorf((float)(ic - 1) / sc));
-        float w6[6];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-          int i0, i1; float l;
-          up_taps(min(base + j, n_out - 1), sc, n_in, i0, i1, l);
-          w6[j] = base + j < n_out ? (i0 == ic ? 1.f - l : 0.f) + (i1 == ic ? l : 0.f) : 0.f;
-        }
-        const bool shift = w6[0] == 0.f;
-#pragma unroll
-        for (int j = 0; j < 5; ++j) w5[j] = shift ? w6[j + 1] : w6[j];
-        base += shift ? 1 : 0;
-      };
-      window(iy, sy, H, HO, yb, wy);
-      window(ix, sx, W, WO, xb, wx);
+      up_window(iy, sy, H, HO, yb, wy);
+      up_window(ix, sx, W, WO, xb, wx);
 #pragma unroll
       for (int j = 0; j < 5; ++j) {
         const int oy = min(yb + j, HO - 1);
@@ -744,8 +785,7 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const T* __restrict__
           const int ox = min(xb + k, WO - 1);
           const Vec16<T> g = ld16(b + ((int64_t)oy * WO + ox) * PDY);
           const float w = wy[j] * wx[k];
-#pragma unroll
-          for (int e = 0; e < EPV; ++e) acc[e] += w * g.get(e);
+          up_bwd_tap<T>(acc, 5 * j + k, w, g);
         }
       }
     } else {
@@ -776,16 +816,159 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const T* __restrict__
     st16(q, r);
   }
 }
+// Tiled form of the transposed interpolation, H >= 4 && W >= 4. A work item is (image, band of <= UPB_TILE low-res rows, band of
+// <= UPB_TILE low-res columns, slab of <= UPB_SLAB 16-byte channel groups), items in raster order [N][row band][column band][slab]
+// and dealt to the XCDs in contiguous ranges (xcd_remap): the two 64-byte halves of a 128-byte pixel and the halos of neighbouring
+// bands are read by workgroups that share an L2. The workgroup stages the high-res window of its item in LDS once, with coalesced
+// 16-byte loads that are all in flight together - rows from the first row's window base to min(last row's base + 4, HO - 1),
+// columns likewise - and every thread then forms one (low-res pixel, channel group) output from 25 LDS reads: the clamped
+// addresses, the weights (up_window, once per row and column of the item, through LDS), the (j, k) order, zero-weight taps
+// included (0 * inf must stay NaN: the fp16 overflow check relies on it) and the final read-add-round are those of the gather
+// kernel, which read each of those lines from memory up to 25 times from neighbouring threads and 2.7 times from HBM.
+// Window extent: the exact base of row ic is floor((ic - 1) (2 + 1 / (n - 1))) + 1 (0 for ic = 0), so over a band of t <= n rows
+// it grows by at most 2 (t - 1) + 1 and the window holds at most 2 t + 4 high-res rows; the fp32 coordinate can move a base by
+// one while n <= 2^20 (the launcher's condition): UPB_WIN = 2 t + 5 = 21 at t = 8.
+// LDS: 21 * 21 * 64 B = 27.6 KB + 0.4 KB of tables: five workgroups fit a CU's 160 KB.
+#define UPB_TILE 8
+#define UPB_SLAB 4
+#define UPB_WIN (2 * UPB_TILE + 5)
+#define UPB_STAGE ((UPB_WIN * UPB_WIN * UPB_SLAB + 255) / 256)     // staging loads per thread (7)
+#define UPB_GRID_CAP 4096
+struct UpbShape { int tiled, TR, TC, SG, nbr, nbc, nsl, grid, passes; long long items; };
+static inline UpbShape upb_shape(int N, int H, int W, int G, int PDY, int esize, bool backward, bool force_gather) {
+  UpbShape u; memset(&u, 0, sizeof(u));
+  // (tiled: 32-bit offsets within an image of dy; the gather kernel takes what is larger)
+  if (backward && !force_gather && H >= 4 && W >= 4 && H <= (1 << 20) && W <= (1 << 20) && 4ll * H * W * PDY * esize < (1ll << 31)) {
+    u.nbr = ceil_div(H, UPB_TILE); u.TR = ceil_div(H, u.nbr); u.nbr = ceil_div(H, u.TR);     // bands of equal height (the last may be shorter)
+    u.nbc = ceil_div(W, UPB_TILE); u.TC = ceil_div(W, u.nbc); u.nbc = ceil_div(W, u.TC);
+    u.SG = G < UPB_SLAB ? G : UPB_SLAB; u.nsl = ceil_div(G, u.SG);
+    u.items = (long long)N * u.nbr * u.nbc * u.nsl;
+    u.tiled = u.items < (1ll << 31) && make_dec4(u.items, u.nsl, u.nbc, u.nbr).fast ? 1 : 0;
+  }
+  if (!u.tiled) {     // thread per output, 256 outputs a block (the forward kernel and the gather kernel)
+    u.TR = u.TC = u.SG = u.nbr = u.nbc = u.nsl = 0;
+    u.items = ceil_div64((long long)N * H * W * G * (backward ? 1 : 4), 256);
+  }
+  u.grid = (int)(u.items > UPB_GRID_CAP ? UPB_GRID_CAP : (u.items < 1 ? 1 : u.items));
+  u.passes = (int)ceil_div64(u.items, u.grid);
+  return u;
+}
+template <typename T>
+__global__ __launch_bounds__(256, 5) void upsample_bwd_kernel(const T* __restrict__ dy, int PDY, T* __restrict__ dx, int PDX, int accumulate, int N, int H, int W, int C,
+                                                           int TR, int TC, int SG, long long items, Dec4 dc) {
+  constexpr int EPV = Tr<T>::EPV;
+  __shared__ u32x4 s_g[UPB_WIN * UPB_WIN * UPB_SLAB];       // [row][column][UPB_SLAB] of the item's window
+  __shared__ float s_w[2][UPB_TILE][5];                     // window weights of the item's rows [0] and columns [1]
+  __shared__ int s_b[2][UPB_TILE];                          // ... and their window bases
+  const int G = C / EPV, HO = 2 * H, WO = 2 * W;
+  const float sy = (float)(H - 1) / (float)(HO - 1);
+  const float sx = (float)(W - 1) / (float)(WO - 1);
+  const int tid = threadIdx.x;
+  const int gl = tid & (UPB_SLAB - 1);                      // channel group within the slab, staging and output alike
+  const int lr = tid >> 5, lc = (tid >> 2) & 7;             // output pixel of the thread within the item (8 x 8 x UPB_SLAB threads)
+  for (long long base = 0; base < items; base += gridDim.x) {
+    // (the map over the workgroups this pass has items for: a short last pass goes to all XCDs, as in upsample_fwd_kernel)
+    const int gp = (int)(items - base < (long long)gridDim.x ? items - base : (long long)gridDim.x);
+    if ((int)blockIdx.x >= gp) break;
+    const long long it = base + xcd_remap((int)blockIdx.x, gp);
+    // item -> (slab, column band, row band, image): the multiply form of dec4 alone (upb_shape takes the tiled kernel only
+    // where it is exact), the 64-bit divisions of the general form cost registers that a fifth workgroup per CU needs
+    const int ii = (int)it;
+    const int t0 = dec_div(ii, dc.iG), sl = ii - t0 * dc.G;
+    const int t1 = dec_div(t0, dc.iW), bc = t0 - t1 * dc.W;
+    const int n = dec_div(t1, dc.iH), br = t1 - n * dc.H;
+    const int r0 = br * TR, c0 = bc * TC, g0 = sl * SG;
+    const int nr = min(TR, H - r0), nc = min(TC, W - c0), ng = min(SG, G - g0);
+    if (tid < nr) {
+      int base; float w5[5];
+      up_window(r0 + tid, sy, H, HO, base, w5);
+      s_b[0][tid] = base;
+#pragma unroll
+      for (int j = 0; j < 5; ++j) s_w[0][tid][j] = w5[j];
+    } else if (tid >= 64 && tid - 64 < nc) {
+      int base; float w5[5];
+      up_window(c0 + tid - 64, sx, W, WO, base, w5);
+      s_b[1][tid - 64] = base;
+#pragma unroll
+      for (int j = 0; j < 5; ++j) s_w[1][tid - 64][j] = w5[j];
+    }
+    __syncthreads();
+    int y_lo = s_b[0][0], y_hi = y_lo, x_lo = s_b[1][0], x_hi = x_lo;
+    for (int j = 1; j < nr; ++j) { y_lo = min(y_lo, s_b[0][j]); y_hi = max(y_hi, s_b[0][j]); }
+    for (int j = 1; j < nc; ++j) { x_lo = min(x_lo, s_b[1][j]); x_hi = max(x_hi, s_b[1][j]); }
+    y_hi = min(y_hi + 4, HO - 1); x_hi = min(x_hi + 4, WO - 1);
+    const int wr = min(y_hi - y_lo + 1, UPB_WIN), wc = min(x_hi - x_lo + 1, UPB_WIN);     // (the min never binds, see above)
+    // stage: flat index t = (row * wc + column) * UPB_SLAB + group; row = t / (wc * UPB_SLAB) by a float reciprocal (t < 2048,
+    // divisor <= 84: (t + 0.5) / d stays >= 0.5 / 84 away from an integer, fp32 rounding moves it by < 2^-18)
+    const int per_row = wc * UPB_SLAB, nst = wr * per_row;
+    const float inv_row = 1.f / (float)per_row;
+    const T* b = dy + ((int64_t)n * HO * WO) * PDY + g0 * EPV;     // (uniform; an image's byte offsets fit 31 bits, upb_shape)
+    Vec16<T> v[UPB_STAGE];
+#pragma unroll
+    for (int k = 0; k < UPB_STAGE; ++k) {
+      const int t = tid + k * 256;
+      if (t < nst && gl < ng) {
+        const int r = (int)(((float)t + 0.5f) * inv_row);
+        const int c = (t - r * per_row) >> 2;
+        v[k] = ld16(b + (unsigned)(((y_lo + r) * WO + (x_lo + c)) * PDY + gl * EPV));
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < UPB_STAGE; ++k) {
+      const int t = tid + k * 256;
+      if (t < nst && gl < ng) s_g[t] = v[k].raw;
+    }
+    const bool live = lr < nr && lc < nc && gl < ng;
+    const long long o = ((long long)n * H + (r0 + lr)) * W + (c0 + lc);
+    T* q = dx + o * PDX + (g0 + gl) * EPV;
+    Vec16<T> r = (accumulate && live) ? ld16(q) : zero16<T>();     // (in flight while the taps are summed)
+    __syncthreads();
+    if (live) {
+      float acc[EPV];
+#pragma unroll
+      for (int e = 0; e < EPV; ++e) acc[e] = 0.f;
+      float wx[5];
+#pragma unroll
+      for (int k = 0; k < 5; ++k) wx[k] = s_w[1][lc][k];
+      const int yb = s_b[0][lr], xb = s_b[1][lc];
+      // (one window row at a time: unrolled over j the compiler hoists all 25 reads, 100 registers, and a fifth workgroup no
+      //  longer fits the CU)
+#pragma unroll 1
+      for (int j = 0; j < 5; ++j) {
+        const int oy = min(yb + j, HO - 1);
+        const float wyj = s_w[0][lr][j];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+          const int ox = min(xb + k, WO - 1);
+          Vec16<T> g;
+          g.raw = s_g[((oy - y_lo) * wc + (ox - x_lo)) * UPB_SLAB + gl];
+          const float w = wyj * wx[k];
+          up_bwd_tap<T>(acc, 5 * j + k, w, g);
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < EPV; ++e) r.set(e, (accumulate ? r.get(e) : 0.f) + acc[e]);
+      st16(q, r);
+    }
+    __syncthreads();     // the next item rewrites the tables and the window
+  }
+}
 template <typename T> static int launch_up_fwd(int N, int H, int W, int C, const void* x, int PX, void* y, int PY, hipStream_t st) {
   const int64_t total = (int64_t)N * 4 * H * W * (C / Tr<T>::EPV);
   ProfScope ps(PC_UP_FWD, 0, (double)N * H * W * C * sizeof(T) * 5.0, st);
-  NUNET_LAUNCH((upsample_fwd_kernel<T>), dim3(grid_for(total, 256)), dim3(256), 0, st, (const T*)x, PX, (T*)y, PY, N, H, W, C, make_dec4(total, C / Tr<T>::EPV, 2 * W, 2 * H));
+  const UpbShape u = upb_shape(N, H, W, C / Tr<T>::EPV, PX, (int)sizeof(T), false, false);
+  NUNET_LAUNCH((upsample_fwd_kernel<T>), dim3(u.grid), dim3(256), 0, st, (const T*)x, PX, (T*)y, PY, N, H, W, C, make_dec4(total, C / Tr<T>::EPV, 2 * W, 2 * H));
   return nunet_check_launch("upsample_fwd");
 }
-template <typename T> static int launch_up_bwd(int N, int H, int W, int C, const void* dy, int PDY, void* dx, int PDX, int acc, hipStream_t st) {
+template <typename T> static int launch_up_bwd(int N, int H, int W, int C, const void* dy, int PDY, void* dx, int PDX, int acc, bool force_gather, hipStream_t st) {
   const int64_t total = (int64_t)N * H * W * (C / Tr<T>::EPV);
   ProfScope ps(PC_UP_BWD, 0, (double)N * H * W * C * sizeof(T) * (acc ? 6.0 : 5.0), st);
-  NUNET_LAUNCH((upsample_bwd_kernel<T>), dim3(grid_for(total, 256)), dim3(256), 0, st, (const T*)dy, PDY, (T*)dx, PDX, acc, N, H, W, C, make_dec4(total, C / Tr<T>::EPV, W, H));
+  const UpbShape u = upb_shape(N, H, W, C / Tr<T>::EPV, PDY, (int)sizeof(T), true, force_gather);
+  if (u.tiled)
+    NUNET_LAUNCH((upsample_bwd_kernel<T>), dim3(u.grid), dim3(256), 0, st, (const T*)dy, PDY, (T*)dx, PDX, acc, N, H, W, C, u.TR, u.TC, u.SG, u.items,
+                 make_dec4(u.items, u.nsl, u.nbc, u.nbr));
+  else
+    NUNET_LAUNCH((upsample_bwd_gather_kernel<T>), dim3(u.grid), dim3(256), 0, st, (const T*)dy, PDY, (T*)dx, PDX, acc, N, H, W, C, make_dec4(total, C / Tr<T>::EPV, W, H));
   return nunet_check_launch("upsample_bwd");
 }
 extern "C" int nunet_upsample2x_fwd(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, const void* x, int32_t PX, void* y, int32_t PY, nunet_stream_t s) {
@@ -798,8 +981,24 @@ extern "C" int nunet_upsample2x_bwd(int32_t dtype, int32_t N, int32_t H, int32_t
   int rc = ew_check("upsample_bwd", dtype, N, H, W, C, PDY, PDX);
   if (rc) return rc;
   NUNET_REQUIRE(dy && dx, "upsample_bwd: null pointer");
-  return NUNET_DISPATCH(dtype, launch_up_bwd, N, H, W, C, dy, PDY, dx, PDX, accumulate, (hipStream_t)s);
+  return NUNET_DISPATCH(dtype, launch_up_bwd, N, H, W, C, dy, PDY, dx, PDX, accumulate, false, (hipStream_t)s);
 }
+extern "C" int nunet_upsample2x_bwd_gather(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, const void* dy, int32_t PDY, void* dx, int32_t PDX, int32_t accumulate, nunet_stream_t s) {
+  int rc = ew_check("upsample_bwd_gather", dtype, N, H, W, C, PDY, PDX);
+  if (rc) return rc;
+  NUNET_REQUIRE(dy && dx, "upsample_bwd_gather: null pointer");
+  return NUNET_DISPATCH(dtype, launch_up_bwd, N, H, W, C, dy, PDY, dx, PDX, accumulate, true, (hipStream_t)s);
+}
+extern "C" int nunet_upsample_launch_info(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t backward, nunet_upsample_launch_info_t* out) {
+  NUNET_REQUIRE(out, "upsample_launch_info: null pointer");
+  int rc = ew_check("upsample_launch_info", dtype, N, H, W, C, C, C);
+  if (rc) return rc;
+  const UpbShape u = upb_shape(N, H, W, C / (16 / dtype_size(dtype)), C, dtype_size(dtype), backward != 0, false);
+  out->tiled = u.tiled; out->workgroups = u.grid; out->passes = u.passes; out->items = u.items;
+  out->reserved = 0; out->TR = u.TR; out->TC = u.TC; out->SG = u.SG; out->lds_bytes = u.tiled ? (int32_t)(UPB_WIN * UPB_WIN * UPB_SLAB * 16 + 2 * UPB_TILE * 6 * 4) : 0;
+  return NUNET_OK;
+}
+extern "C" int32_t nunet_xcd_remap_host(int32_t b, int32_t G) { return xcd_remap(b, G); }
 
 // ---------------------------------------------------------------------------
 // 1x1 heads. Lane = channel: 32-lane half-waves walk pixels.
