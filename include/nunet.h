@@ -40,7 +40,7 @@ enum {
   NUNET_ENODEV = -3   /* no gfx950 device / code object */
 };
 
-int nunet_version(void);   /* 102: schedule 1 (single-stream) and recording mode 0 (event segments) of 101 are refused, nunet_graph_info reports nodes, edges, lanes */
+int nunet_version(void);   /* 103: BCEWithLogitsLoss in the loss step; nunet_seg_metrics and nunet_eval_step were added under the same number (additions only). 102: schedule 1 (single-stream) and recording mode 0 (event segments) of 101 are refused, nunet_graph_info reports nodes, edges, lanes */
 const char* nunet_last_error(void);
 
 /* ------------------------------------------------------------------------ */
@@ -243,7 +243,8 @@ int nunet_head_bwd_bnr(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C
                        float* dw_slabs, int32_t nslabs, const nunet_bnr_desc* bnr, nunet_stream_t s);
 
 /* ------------------------------------------------------------------------ */
-/* BCEDiceLoss (losses.py:103-117), iou_score (metrics.py:6-18)              */
+/* BCEDiceLoss (losses.py:103-117), iou_score (metrics.py:6-18), the other   */
+/* metrics of metrics.py (:21-53) and the validation step (trains.py:150-188) */
 /* ------------------------------------------------------------------------ */
 /* Every entry that takes a caller-provided workspace (or the plan arena) also takes its size in bytes and returns
  * NUNET_EINVAL when it is smaller than the matching *_bytes() query says: the library never writes past what the
@@ -295,6 +296,41 @@ int nunet_lovasz_hinge_bwd(const float* dlogits_unit, const float* gscale, int64
  * bit-exact against the reference. The caller finds it by bisection with the reference's sigmoid. */
 int nunet_iou_counts(const float* logits, const float* target, int64_t n, float logit_threshold,
                      unsigned long long* counts, nunet_stream_t s);
+/* Segmentation sums of one logits tensor, per class: the rest of the reference's metrics.py - numeric_score's FP / FN / TP / TN
+ * (:31-44), Acc (:47-53) and the three sums of dice_coef (:21-29). logits / target: NCHW fp32 [N][K][hw], K <= NUNET_EVAL_MAX_CLASSES,
+ * hw <= 2^24. Counts follow the rule of nunet_iou_counts (predicted foreground iff x >= iou_logit_threshold, NaN is not; labelled
+ * foreground iff t > 0.5): over the classes, sum tp is its intersection and sum (tp + fp + fn) its union, exactly. soft_i =
+ * sum sigmoid(x) t, soft_p = sum sigmoid(x), soft_t = sum t with the fp32 sigmoid of the loss kernels, added in double.
+ * One read of both tensors; every workgroup stores one partial to `ws` (the ws_bytes query, 8-byte aligned), a one-workgroup
+ * launch adds them in index order: no atomics, no pre-zeroing, bit-identical from run to run. accumulate: out += instead of
+ * out = (an assigning call zeroes the classes >= K). `out` is DEVICE memory. */
+#define NUNET_EVAL_MAX_CLASSES 8
+typedef struct nunet_seg_sums {
+  uint64_t tp[NUNET_EVAL_MAX_CLASSES], fp[NUNET_EVAL_MAX_CLASSES], fn[NUNET_EVAL_MAX_CLASSES], tn[NUNET_EVAL_MAX_CLASSES];
+  double soft_i[NUNET_EVAL_MAX_CLASSES], soft_p[NUNET_EVAL_MAX_CLASSES], soft_t[NUNET_EVAL_MAX_CLASSES];
+} nunet_seg_sums;
+size_t nunet_seg_metrics_ws_bytes(int32_t N, int32_t K, int64_t hw);
+int nunet_seg_metrics(const float* logits, const float* target, int32_t N, int32_t K, int64_t hw, float iou_logit_threshold,
+                      void* ws, size_t ws_bytes, nunet_seg_sums* out, int32_t accumulate, nunet_stream_t s);
+/* One validation batch, no gradient (trains.py:150-188). logits: [heads][N][K][hw], target: [N][K][hw].
+ * loss_out[k], k < heads: the loss of head k by the device code of the stand-alone forward of `loss_kind` (nunet_bce_dice_fwd
+ * over N images of K * hw, nunet_bce_logits_fwd over N * K * hw, nunet_lovasz_hinge_fwd over N images of hw - one class only),
+ * bit-equal to it; loss_out[heads]: their fp32 left-to-right sum divided once by heads (trains.py:165-168). Then the sums above
+ * of the LAST head (trains.py:170,174) and one launch that updates `meters`: 512 bytes of DEVICE memory, zeroed by the caller
+ * before the first batch, AverageMeter.update(value, N) (trains.py:176-177) of the batch values, all formed in double:
+ *   IoU = (sum tp + 1e-5) / (sum (tp + fp + fn) + 1e-5), dice = (2 sum soft_i + 1e-5) / (sum soft_p + sum soft_t + 1e-5),
+ *   acc = sum (tp + tn) / (N K hw), loss = loss_out[heads].
+ * ws: the ws_bytes query, 256-byte aligned. Every argument is checked before the first launch. */
+typedef struct nunet_eval_meters {
+  double loss_sum, iou_sum, dice_sum, acc_sum;    /* += batch value * N */
+  double samples;                                 /* += N */
+  double last_iou, last_dice, last_acc;           /* this batch */
+  uint64_t tp[NUNET_EVAL_MAX_CLASSES], fp[NUNET_EVAL_MAX_CLASSES], fn[NUNET_EVAL_MAX_CLASSES], tn[NUNET_EVAL_MAX_CLASSES];   /* += per class */
+  double soft_i[NUNET_EVAL_MAX_CLASSES], soft_p[NUNET_EVAL_MAX_CLASSES], soft_t[NUNET_EVAL_MAX_CLASSES];
+} nunet_eval_meters;
+size_t nunet_eval_step_ws_bytes(int32_t N, int32_t K, int64_t hw, int32_t heads, int32_t loss_kind);
+int nunet_eval_step(const float* logits, const float* target, int32_t N, int32_t K, int64_t hw, int32_t heads, int32_t loss_kind,
+                    void* ws, size_t ws_bytes, float* loss_out, nunet_eval_meters* meters, float iou_logit_threshold, nunet_stream_t s);
 /* Mask export of the evaluation driver (reference val.py:100-105): out[i] = uint8(sigmoid(logits[i]) * 255), bit-exact
  * against the reference's sigmoid: thresholds[k-1] (k = 1..255, fp32, device) = the smallest logit whose byte is >= k as
  * the REFERENCE computes it (the caller derives them once by bisection with the reference's sigmoid); NaN maps to 0. */

@@ -117,6 +117,11 @@ typedef struct {
 } nunet_loss_launch_info_t;
 int nunet_loss_launch_info(int32_t entry, int32_t N, int64_t per_or_n, int32_t heads, nunet_loss_launch_info_t* out);
 
+/* The counterpart for nunet_seg_metrics: its first launch runs grid_x blocks per plane x K classes (grid_y) x N images (grid_z),
+ * one grid-stride loop over the hw pixels of a plane; a one-workgroup launch of 256 threads follows, in which thread j adds
+ * the entries j, j + 256, ... of the N * grid_x partials of each class. A pure host function; refuses what the entry refuses by size. */
+int nunet_seg_metrics_launch_info(int32_t N, int32_t K, int64_t hw, nunet_loss_launch_info_t* out);
+
 /* The x2 bilinear upsample's backward pass by its gather kernel (one thread per output, every tap a global load), whatever the
  * shape: the arguments of nunet_upsample2x_bwd, which takes the LDS-tiled kernel when H >= 4 and W >= 4. The two leave the
  * same bytes; the tests hold one against the other. */

@@ -108,6 +108,26 @@ class LossLaunchInfo(C.Structure):
     _fields_ = [(k, _i32) for k in ("grid_x", "grid_y", "grid_z", "block")] + [(k, _i64) for k in ("items", "trips_max", "trips_min")]
 
 
+EVAL_MAX_CLASSES = 8       # NUNET_EVAL_MAX_CLASSES in include/nunet.h
+_u64x8, _f64x8 = C.c_uint64 * EVAL_MAX_CLASSES, C.c_double * EVAL_MAX_CLASSES
+_SEG_FIELDS = [(k, _u64x8) for k in ("tp", "fp", "fn", "tn")] + [(k, _f64x8) for k in ("soft_i", "soft_p", "soft_t")]
+
+
+class SegSums(C.Structure):
+    """nunet_seg_sums (include/nunet.h): per-class counts and soft sums of one logits tensor; 448 bytes of device memory."""
+    _fields_ = list(_SEG_FIELDS)
+
+
+class EvalMeters(C.Structure):
+    """nunet_eval_meters (include/nunet.h): the validation pass's AverageMeter sums and dataset counts; 512 bytes of device memory."""
+    _fields_ = [(k, C.c_double) for k in ("loss_sum", "iou_sum", "dice_sum", "acc_sum", "samples", "last_iou", "last_dice", "last_acc")] + list(_SEG_FIELDS)
+
+
+def read_struct(t, cls):
+    """A device byte tensor holding one `cls` -> the ctypes struct on the host (one synchronising copy)."""
+    return cls.from_buffer_copy(bytes(t.cpu().numpy().tobytes()[:C.sizeof(cls)]))
+
+
 class UpsampleLaunchInfo(C.Structure):
     """nunet_upsample_launch_info_t (include/nunet_diag.h): what an upsample forward / backward call would launch."""
     _fields_ = [(k, _i32) for k in ("tiled", "workgroups", "passes", "TR", "TC", "SG", "lds_bytes", "reserved")] + [("items", _i64)]
@@ -198,6 +218,11 @@ _SIG = {
     "nunet_lovasz_hinge_fwd": (_i32, [_vp, _vp, _i32, _i64, _vp, _sz, _vp, _vp, _vp]),
     "nunet_lovasz_hinge_bwd": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "nunet_iou_counts": (_i32, [_vp, _vp, _i64, _f32, _vp, _vp]),
+    "nunet_seg_metrics_ws_bytes": (C.c_size_t, [_i32, _i32, _i64]),
+    "nunet_seg_metrics": (_i32, [_vp, _vp, _i32, _i32, _i64, _f32, _vp, _sz, _vp, _i32, _vp]),
+    "nunet_seg_metrics_launch_info": (_i32, [_i32, _i32, _i64, C.POINTER(LossLaunchInfo)]),
+    "nunet_eval_step_ws_bytes": (C.c_size_t, [_i32, _i32, _i64, _i32, _i32]),
+    "nunet_eval_step": (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _i32, _vp, _sz, _vp, _vp, _f32, _vp]),
     "nunet_sigmoid_u8": (_i32, [_vp, _vp, _vp, _i64, _vp]),
     "nunet_sgd_step": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32, _f32, _i32, _i32, _f32, _vp]),
     "nunet_adam_prepare": (_i32, [_vp, C.c_double, C.c_double, _vp, _vp, _vp]),

@@ -1,9 +1,10 @@
 // elementwise.hip — the HBM-bound kernels of the UNet++ path (NHWC, 16 B/lane):
 //   BatchNorm2d(+ReLU)(+MaxPool2d) forward, BatchNorm/ReLU backward,
 //   MaxPool2d(2,2) fwd/bwd, bilinear x2 align_corners upsample fwd/bwd,
-//   1x1 heads fwd/bwd, BCEDiceLoss fwd/bwd, BCEWithLogitsLoss fwd/bwd, IoU counts, SGD, layout helpers.
+//   1x1 heads fwd/bwd, BCEDiceLoss fwd/bwd, BCEWithLogitsLoss fwd/bwd, IoU counts, per-class segmentation sums, the
+//   validation step, SGD, layout helpers.
 // Reference arithmetic: finished/archs1.py:17-21,82-83,105-111; losses.py:103-117;
-// metrics.py:6-18; trains.py:27-28,210-211,229-231.
+// metrics.py:6-53; trains.py:27-28,150-188,210-211,229-231.
 #include <cmath>
 #include <stdlib.h>
 #include <string.h>
@@ -1548,6 +1549,204 @@ extern "C" int nunet_iou_counts(const float* logits, const float* target, int64_
   ProfScope ps(PC_LOSS, 0, (double)n * 8, (hipStream_t)s);
   NUNET_LAUNCH(iou_counts_kernel, dim3(iou_counts_gx(n)), dim3(256), 0, (hipStream_t)s, logits, target, n, logit_threshold, counts);
   return nunet_check_launch("iou_counts");
+}
+
+// ---------------------------------------------------------------------------
+// Segmentation sums of one logits tensor (the rest of the reference's metrics.py: numeric_score's FP/FN/TP/TN :31-44, Acc :47-53,
+// dice_coef :21-29) per class, with the foreground rule of iou_counts_kernel: predicted iff x >= thr (NaN: not), labelled
+// iff t > 0.5 - so sum tp and sum (tp + fp + fn) over the classes ARE nunet_iou_counts' intersection and union.
+// One read of logits and targets on the grid (blocks per plane, class, image): every workgroup leaves one partial
+// {soft_i, soft_p, soft_t (double), tp, fp, fn, tn (uint32: a plane holds <= 2^24 pixels)} in its slab entry with plain stores;
+// one workgroup then adds the entries of a class in index order (image-major, thread j takes entries j, j + 256, ...; a fixed
+// tree over lanes and waves). No atomics, no pre-zero launch: the result is bit-identical from run to run.
+// ---------------------------------------------------------------------------
+constexpr int SEG_GX = 64;      // most blocks per (image, class) plane
+struct SegPart { double s[3]; unsigned c[4]; };    // 40 bytes
+static int seg_metrics_gx(int64_t hw) { return grid_for(hw, 256, SEG_GX); }
+__global__ __launch_bounds__(256) void seg_metrics_partial_kernel(const float* __restrict__ x, const float* __restrict__ t, int64_t hw, float thr, SegPart* __restrict__ ws) {
+  const int k = blockIdx.y, n = blockIdx.z, K = gridDim.y;
+  const int64_t plane = (int64_t)n * K + k;
+  const float* xs = x + plane * hw;
+  const float* ts = t + plane * hw;
+  double si = 0.0, sp = 0.0, st = 0.0;
+  unsigned tp = 0, fp = 0, fn = 0, tn = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < hw; i += (int64_t)gridDim.x * blockDim.x) {
+    const float xv = xs[i], tv = ts[i];
+    const double pv = (double)sigmoidf_(xv);
+    si += pv * (double)tv; sp += pv; st += (double)tv;
+    const bool a = xv >= thr, b = tv > 0.5f;
+    tp += (a && b) ? 1u : 0u; fp += (a && !b) ? 1u : 0u; fn += (!a && b) ? 1u : 0u; tn += (!a && !b) ? 1u : 0u;
+  }
+  si = wave_sum_f64(si); sp = wave_sum_f64(sp); st = wave_sum_f64(st);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { tp += __shfl_xor(tp, o); fp += __shfl_xor(fp, o); fn += __shfl_xor(fn, o); tn += __shfl_xor(tn, o); }
+  __shared__ double s_d[4][3];
+  __shared__ unsigned s_c[4][4];
+  const int wv = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { s_d[wv][0] = si; s_d[wv][1] = sp; s_d[wv][2] = st; s_c[wv][0] = tp; s_c[wv][1] = fp; s_c[wv][2] = fn; s_c[wv][3] = tn; }
+  __syncthreads();
+  SegPart* w = ws + plane * SEG_GX + blockIdx.x;
+  if (threadIdx.x < 3) w->s[threadIdx.x] = ((s_d[0][threadIdx.x] + s_d[1][threadIdx.x]) + s_d[2][threadIdx.x]) + s_d[3][threadIdx.x];
+  else if (threadIdx.x < 7) { const int q = threadIdx.x - 3; w->c[q] = ((s_c[0][q] + s_c[1][q]) + s_c[2][q]) + s_c[3][q]; }
+}
+__global__ __launch_bounds__(256) void seg_metrics_final_kernel(const SegPart* __restrict__ ws, int gx, int N, int K, nunet_seg_sums* __restrict__ out, int accumulate) {
+  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
+  __shared__ double s_d[4][NUNET_EVAL_MAX_CLASSES][3];
+  __shared__ unsigned long long s_c[4][NUNET_EVAL_MAX_CLASSES][4];
+  const int64_t entries = (int64_t)N * gx;     // of one class, image-major
+  for (int k = 0; k < K; ++k) {
+    double d[3] = {0.0, 0.0, 0.0};
+    unsigned long long c[4] = {0ull, 0ull, 0ull, 0ull};
+    for (int64_t j = threadIdx.x; j < entries; j += 256) {
+      const int64_t n = j / gx;
+      const SegPart* w = ws + (n * K + k) * SEG_GX + (j - n * gx);
+#pragma unroll
+      for (int q = 0; q < 3; ++q) d[q] += w->s[q];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) c[q] += (unsigned long long)w->c[q];
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) d[q] = wave_sum_f64(d[q]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      for (int o = 32; o > 0; o >>= 1) c[q] += __shfl_xor(c[q], o);
+    if (l == 0) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) s_d[wv][k][q] = d[q];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) s_c[wv][k][q] = c[q];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < NUNET_EVAL_MAX_CLASSES) {     // one thread per class; classes >= K hold zeros after an assigning call
+    const int k = threadIdx.x;
+    const bool on = k < K;
+    double d[3]; unsigned long long c[4];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) d[q] = on ? ((s_d[0][k][q] + s_d[1][k][q]) + s_d[2][k][q]) + s_d[3][k][q] : 0.0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) c[q] = on ? ((s_c[0][k][q] + s_c[1][k][q]) + s_c[2][k][q]) + s_c[3][k][q] : 0ull;
+    if (accumulate) {
+      if (on) {
+        out->tp[k] += c[0]; out->fp[k] += c[1]; out->fn[k] += c[2]; out->tn[k] += c[3];
+        out->soft_i[k] += d[0]; out->soft_p[k] += d[1]; out->soft_t[k] += d[2];
+      }
+    } else {
+      out->tp[k] = c[0]; out->fp[k] = c[1]; out->fn[k] = c[2]; out->tn[k] = c[3];
+      out->soft_i[k] = d[0]; out->soft_p[k] = d[1]; out->soft_t[k] = d[2];
+    }
+  }
+}
+extern "C" size_t nunet_seg_metrics_ws_bytes(int32_t N, int32_t K, int64_t hw) {
+  if (N <= 0 || K <= 0 || K > NUNET_EVAL_MAX_CLASSES || hw <= 0) return 0;
+  return (size_t)N * K * SEG_GX * sizeof(SegPart);
+}
+static int seg_metrics_check(const char* what, int32_t N, int32_t K, int64_t hw) {
+  NUNET_REQUIRE(N > 0 && N <= 65535, "%s: N = %d (1 .. 65535)", what, (int)N);
+  NUNET_REQUIRE(K >= 1 && K <= NUNET_EVAL_MAX_CLASSES, "%s: %d classes (1 .. %d)", what, (int)K, NUNET_EVAL_MAX_CLASSES);
+  NUNET_REQUIRE(hw > 0 && hw <= (1ll << 24), "%s: %lld pixels per plane (1 .. 2^24)", what, (long long)hw);
+  return NUNET_OK;
+}
+static void seg_metrics_launch(const float* logits, const float* target, int32_t N, int32_t K, int64_t hw, float thr, void* ws, nunet_seg_sums* out,
+                               int32_t accumulate, hipStream_t st) {
+  const int gx = seg_metrics_gx(hw);
+  ProfScope ps(PC_LOSS, 0, (double)N * K * hw * 8, st);
+  NUNET_LAUNCH(seg_metrics_partial_kernel, dim3(gx, K, N), dim3(256), 0, st, logits, target, hw, thr, (SegPart*)ws);
+  NUNET_LAUNCH(seg_metrics_final_kernel, dim3(1), dim3(256), 0, st, (const SegPart*)ws, gx, N, K, out, accumulate);
+}
+extern "C" int nunet_seg_metrics(const float* logits, const float* target, int32_t N, int32_t K, int64_t hw, float iou_logit_threshold,
+                                 void* ws, size_t ws_bytes, nunet_seg_sums* out, int32_t accumulate, nunet_stream_t s) {
+  if (int rc = seg_metrics_check("seg_metrics", N, K, hw)) return rc;
+  NUNET_REQUIRE(logits && target && ws && out, "seg_metrics: null pointer");
+  NUNET_REQUIRE(((uintptr_t)ws & 7) == 0 && ((uintptr_t)out & 7) == 0, "seg_metrics: workspace and sums must be 8-byte aligned");
+  NUNET_REQUIRE(ws_bytes >= nunet_seg_metrics_ws_bytes(N, K, hw), "seg_metrics: workspace of %zu bytes, nunet_seg_metrics_ws_bytes = %zu", ws_bytes,
+                nunet_seg_metrics_ws_bytes(N, K, hw));
+  seg_metrics_launch(logits, target, N, K, hw, iou_logit_threshold, ws, out, accumulate, (hipStream_t)s);
+  return nunet_check_launch("seg_metrics");
+}
+extern "C" int nunet_seg_metrics_launch_info(int32_t N, int32_t K, int64_t hw, nunet_loss_launch_info_t* out) {
+  NUNET_REQUIRE(out, "seg_metrics launch info: null output");
+  if (int rc = seg_metrics_check("seg_metrics launch info", N, K, hw)) return rc;
+  const int gx = seg_metrics_gx(hw);
+  const int64_t threads = (int64_t)gx * 256;
+  out->grid_x = gx; out->grid_y = K; out->grid_z = N; out->block = 256;
+  out->items = hw;
+  out->trips_max = ceil_div64(hw, threads);
+  out->trips_min = hw / threads;
+  return NUNET_OK;
+}
+
+// ---------------------------------------------------------------------------
+// One validation batch without a gradient (trains.py:150-188): the loss of every head BY THE STAND-ALONE FORWARDS (their
+// kernels on their grids: loss_out[k] is what the losses.* module returns for head k, bit for bit), the segmentation sums of
+// the last head (trains.py:170,174), and one thread that forms the head mean, the batch values and the AverageMeter sums.
+// Workspace: per head one 256-byte aligned region of the forward's own workspace, (Lovasz) the unit-gradient scratch the
+// forward writes and nobody reads, the slab of seg_metrics, the batch's nunet_seg_sums.
+// ---------------------------------------------------------------------------
+static size_t eval_head_ws(int32_t N, int32_t K, int64_t hw, int32_t loss_kind) {
+  const size_t b = loss_kind == NUNET_LOSS_LOVASZ_HINGE ? nunet_lovasz_ws_bytes(N, hw)
+                 : loss_kind == NUNET_LOSS_BCE_LOGITS ? nunet_bce_logits_ws_bytes((int64_t)N * K * hw) : nunet_bce_dice_ws_bytes(N);
+  return align_up(b, 256);
+}
+static size_t eval_unit_ws(int32_t N, int64_t hw, int32_t loss_kind) { return loss_kind == NUNET_LOSS_LOVASZ_HINGE ? align_up((size_t)N * hw * sizeof(float), 256) : 0; }
+extern "C" size_t nunet_eval_step_ws_bytes(int32_t N, int32_t K, int64_t hw, int32_t heads, int32_t loss_kind) {
+  if (N <= 0 || K <= 0 || K > NUNET_EVAL_MAX_CLASSES || hw <= 0 || heads < 1 || heads > 8) return 0;
+  return (size_t)heads * eval_head_ws(N, K, hw, loss_kind) + eval_unit_ws(N, hw, loss_kind) + align_up(nunet_seg_metrics_ws_bytes(N, K, hw), 256) +
+         align_up(sizeof(nunet_seg_sums), 256);
+}
+__global__ void eval_finalize_kernel(float* __restrict__ loss_out, int heads, const nunet_seg_sums* __restrict__ b, nunet_eval_meters* __restrict__ m, int N, int K, int64_t hw) {
+#pragma clang fp contract(off)      // sum += value * N as AverageMeter evaluates it: the product rounded, then the add
+  if (threadIdx.x != 0) return;
+  float mean = loss_out[0];                       // sum(criterion(o, t) for o in out) / len(out): left to right, one division
+  for (int k = 1; k < heads; ++k) mean += loss_out[k];
+  mean = mean / (float)heads;
+  loss_out[heads] = mean;
+  unsigned long long tp = 0, fp = 0, fn = 0, tn = 0;
+  double si = 0.0, sp = 0.0, st = 0.0;
+  for (int k = 0; k < K; ++k) {
+    tp += b->tp[k]; fp += b->fp[k]; fn += b->fn[k]; tn += b->tn[k];
+    si += b->soft_i[k]; sp += b->soft_p[k]; st += b->soft_t[k];
+    m->tp[k] += b->tp[k]; m->fp[k] += b->fp[k]; m->fn[k] += b->fn[k]; m->tn[k] += b->tn[k];
+    m->soft_i[k] += b->soft_i[k]; m->soft_p[k] += b->soft_p[k]; m->soft_t[k] += b->soft_t[k];
+  }
+  const double iou = ((double)tp + 1e-5) / ((double)(tp + fp + fn) + 1e-5);
+  const double dice = (2.0 * si + 1e-5) / (sp + st + 1e-5);
+  const double acc = (double)(tp + tn) / ((double)N * (double)K * (double)hw);
+  const double w = (double)N;                     // AverageMeter.update(value, N)
+  m->loss_sum += (double)mean * w; m->iou_sum += iou * w; m->dice_sum += dice * w; m->acc_sum += acc * w;
+  m->samples += w;
+  m->last_iou = iou; m->last_dice = dice; m->last_acc = acc;
+}
+extern "C" int nunet_eval_step(const float* logits, const float* target, int32_t N, int32_t K, int64_t hw, int32_t heads, int32_t loss_kind,
+                               void* ws, size_t ws_bytes, float* loss_out, nunet_eval_meters* meters, float iou_logit_threshold, nunet_stream_t s) {
+  if (int rc = seg_metrics_check("eval_step", N, K, hw)) return rc;
+  NUNET_REQUIRE(heads >= 1 && heads <= 8, "eval_step: %d heads (1 .. 8)", (int)heads);
+  NUNET_REQUIRE(loss_kind == NUNET_LOSS_BCE_DICE || loss_kind == NUNET_LOSS_LOVASZ_HINGE || loss_kind == NUNET_LOSS_BCE_LOGITS, "eval_step: loss_kind %d", (int)loss_kind);
+  NUNET_REQUIRE(loss_kind != NUNET_LOSS_LOVASZ_HINGE || K == 1, "eval_step: the Lovasz hinge takes one class (the reference squeezes dim 1), got %d", (int)K);
+  NUNET_REQUIRE(loss_kind != NUNET_LOSS_LOVASZ_HINGE || hw <= (1ll << 22), "eval_step: the Lovasz hinge takes up to 2^22 pixels per image, got %lld", (long long)hw);
+  NUNET_REQUIRE(logits && target && ws && loss_out && meters, "eval_step: null pointer");
+  NUNET_REQUIRE(((uintptr_t)ws & 255) == 0 && ((uintptr_t)meters & 7) == 0, "eval_step: workspace must be 256-byte and meters 8-byte aligned");
+  NUNET_REQUIRE(ws_bytes >= nunet_eval_step_ws_bytes(N, K, hw, heads, loss_kind), "eval_step: workspace of %zu bytes, nunet_eval_step_ws_bytes = %zu", ws_bytes,
+                nunet_eval_step_ws_bytes(N, K, hw, heads, loss_kind));
+  hipStream_t st = (hipStream_t)s;
+  const size_t hws = eval_head_ws(N, K, hw, loss_kind);
+  char* base = (char*)ws;
+  float* unit = (float*)(base + (size_t)heads * hws);
+  void* seg_ws = (char*)unit + eval_unit_ws(N, hw, loss_kind);
+  nunet_seg_sums* batch = (nunet_seg_sums*)((char*)seg_ws + align_up(nunet_seg_metrics_ws_bytes(N, K, hw), 256));
+  const int64_t per = (int64_t)K * hw, n_head = (int64_t)N * per;
+  for (int k = 0; k < heads; ++k) {
+    const float* lg = logits + (size_t)k * n_head;
+    float* hw_ws = (float*)(base + (size_t)k * hws);
+    int rc;
+    if (loss_kind == NUNET_LOSS_LOVASZ_HINGE) rc = nunet_lovasz_hinge_fwd(lg, target, N, hw, hw_ws, hws, unit, loss_out + k, s);
+    else if (loss_kind == NUNET_LOSS_BCE_LOGITS) rc = nunet_bce_logits_fwd(lg, target, n_head, hw_ws, hws, loss_out + k, s);
+    else rc = nunet_bce_dice_fwd(lg, target, N, per, hw_ws, hws, loss_out + k, s);
+    if (rc) return rc;
+  }
+  seg_metrics_launch(logits + (size_t)(heads - 1) * n_head, target, N, K, hw, iou_logit_threshold, seg_ws, batch, 0, st);
+  NUNET_LAUNCH(eval_finalize_kernel, dim3(1), dim3(64), 0, st, loss_out, heads, (const nunet_seg_sums*)batch, meters, N, K, hw);
+  return nunet_check_launch("eval_step");
 }
 
 // ---------------------------------------------------------------------------

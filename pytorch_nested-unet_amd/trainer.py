@@ -115,7 +115,7 @@ class TrainStep:
         self.logits = torch.empty((self.heads, n, self.ncls, h, w), dtype=torch.float32, device=dev)
         self.dlogits = torch.empty_like(self.logits)
         self.per = self.ncls * h * w
-        kinds = {"BCEDiceLoss": L.LOSS_BCE_DICE, "LovaszHingeLoss": L.LOSS_LOVASZ_HINGE, "BCEWithLogitsLoss": L.LOSS_BCE_LOGITS}
+        kinds = LOSS_KINDS
         if loss not in kinds:
             raise L.NunetError("TrainStep: loss %r is not one of %s" % (loss, sorted(kinds)))
         if loss == "LovaszHingeLoss" and self.ncls != 1:
@@ -773,6 +773,162 @@ class TrainStep:
         k = max(self.steps, 1)
         m = self.meters.tolist()
         return m[0] / k, m[1] / k
+
+
+LOSS_KINDS = {"BCEDiceLoss": L.LOSS_BCE_DICE, "LovaszHingeLoss": L.LOSS_LOVASZ_HINGE, "BCEWithLogitsLoss": L.LOSS_BCE_LOGITS}
+
+
+class _EvalBatch:
+    """The buffers of one validation batch size: a Plan of its own (not Engine.plans: the training step's recorded program and
+    lane state live on the cached plan of the same key), static input / target / logits, the loss workspace and outputs."""
+
+    def __init__(self, ev, n):
+        from .engine import Plan
+        model, eng, dev = ev.model, ev.eng, ev.eng.device
+        self.n = n
+        self.pl = Plan(n, ev.h, ev.w, ev.cin, ev.ncls, getattr(model, "deep_supervision", False), model.compute_dtype, model._unet, dev)
+        if self.pl.nparams != eng.flat_params.numel() or self.pl.nbnbuf != eng.bnbuf.numel() or self.pl.nbn != len(eng.bns):
+            raise L.NunetError("EvalStep: plan/module parameter layout mismatch: %d vs %d params" % (self.pl.nparams, eng.flat_params.numel()))
+        self.heads = self.pl.heads
+        self.x = torch.zeros((n, ev.cin, ev.h, ev.w), dtype=torch.float32, device=dev)
+        self.t = torch.zeros((n, ev.ncls, ev.h, ev.w), dtype=torch.float32, device=dev)
+        self.logits = torch.zeros((self.heads, n, ev.ncls, ev.h, ev.w), dtype=torch.float32, device=dev)
+        nb = L.lib().nunet_eval_step_ws_bytes(n, ev.ncls, ev.h * ev.w, self.heads, ev.loss_kind)
+        self.ws = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)        # (the caching allocator hands out 512-byte aligned blocks)
+        self.loss_out = torch.zeros(self.heads + 1, dtype=torch.float32, device=dev)    # per head, then their mean
+        self.graph = None
+
+    def repack(self, eng):
+        L.check(L.lib().nunet_plan_repack(self.pl.handle, L.ptr(eng.flat_params), L.ptr(self.pl.arena), L.nbytes(self.pl.arena), L.stream()), "plan_repack")
+
+    def issue(self, ev):
+        """forward in eval mode on the packed weights of this plan's arena (training = 2), then the validation step"""
+        lib, eng, pl, st = L.lib(), ev.eng, self.pl, L.stream()
+        L.check(lib.nunet_plan_forward(pl.handle, L.ptr(eng.flat_params), L.ptr(eng.bnbuf), L.ptr(eng.nbt), L.ptr(self.x), L.ptr(pl.arena),
+                                       L.nbytes(pl.arena), L.ptr(self.logits), 2, st), "plan_forward")
+        L.check(lib.nunet_eval_step(L.ptr(self.logits), L.ptr(self.t), self.n, ev.ncls, ev.h * ev.w, self.heads, ev.loss_kind, L.ptr(self.ws),
+                                    L.nbytes(self.ws), L.ptr(self.loss_out), L.ptr(ev.meters), ev.iou_thr, st), "eval_step")
+        pl.trained_forward = False
+
+
+class EvalStep:
+    """The validation loop of reference trains.py:150-188 without a host round trip per batch: the forward pass in eval mode,
+    the loss of every head (the stand-alone forwards' device code: the values of the `losses` modules, bit for bit), IoU, Dice
+    and accuracy of the last head and the AverageMeter sums, captured once as ONE hipGraph and replayed per batch; the meters
+    stay on the device and are read once per pass.
+
+    evaluate(x, t) over a split (device tensors [M, C, H, W] / [M, K, H, W]): one repack of the weights from the current fp32
+    parameters, the meters zeroed, a copy + replay per full batch, a tail of r < N images eagerly on a second plan of N = r
+    (created on first use; not padded: the K-split of grid-starved layers depends on N) - the launches the module path makes,
+    so `loss` and `iou` equal the module loop's to the bit. begin() / step(xb, tb) / result() are the same pass by hand, for
+    a caller that wants `.last_logits` of every batch (val.py's mask export).
+    use_graph=False issues the same launches eagerly."""
+
+    def __init__(self, model, batch_shape, loss="BCEDiceLoss", use_graph=True):
+        self.model = model
+        self.eng = model.engine()
+        n, cin, h, w = batch_shape
+        if cin != model.input_channels:
+            raise L.NunetError("EvalStep: batch_shape has %d channels, the model takes %d" % (cin, model.input_channels))
+        self.n, self.cin, self.h, self.w = n, cin, h, w
+        self.ncls = model.num_classes
+        if loss not in LOSS_KINDS:
+            raise L.NunetError("EvalStep: loss %r is not one of %s" % (loss, sorted(LOSS_KINDS)))
+        if loss == "LovaszHingeLoss" and self.ncls != 1:
+            raise L.NunetError("LovaszHingeLoss squeezes the class dimension (reference losses.py:126-127): num_classes must be 1")
+        if self.ncls > L.EVAL_MAX_CLASSES:
+            raise L.NunetError("EvalStep: %d classes, the metrics take up to %d" % (self.ncls, L.EVAL_MAX_CLASSES))
+        self.loss_name, self.loss_kind = loss, LOSS_KINDS[loss]
+        from .metrics import iou_logit_threshold
+        self.iou_thr = iou_logit_threshold()
+        self.use_graph = use_graph
+        self.meters = torch.zeros(C.sizeof(L.EvalMeters), dtype=torch.uint8, device=self.eng.device)
+        self.main = _EvalBatch(self, n)
+        self.tail = None
+        self._last = self.main
+        self._packed = set()
+        self.heads = self.main.heads
+
+    @property
+    def logits(self):
+        """[heads, N, K, H, W] of the static batch (the tail batch has its own: see last_logits)"""
+        return self.main.logits
+
+    @property
+    def last_logits(self):
+        """[n, K, H, W]: the last head's logits of the batch step() ran last"""
+        return self._last.logits[-1]
+
+    @property
+    def last_loss(self):
+        """device fp32 [heads + 1]: per head, then their mean, of the batch step() ran last"""
+        return self._last.loss_out
+
+    def _check_engine(self):
+        if self.model._engine is not self.eng or not self.eng.intact():
+            raise L.NunetError("the module's parameter arenas were re-homed (moved to another device / parameters replaced) "
+                               "after this EvalStep was built: it would read orphaned memory. Build a new EvalStep.")
+
+    def begin(self):
+        """Start a pass: repack the weights into this step's own arena (the parameters moved since the last pass), zero the meters."""
+        self._check_engine()
+        self.main.repack(self.eng)
+        self._packed = {self.main.n}
+        self.meters.zero_()
+        if self.use_graph and self.main.graph is None:
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                self.main.issue(self)          # eager once: one-time launch attributes are set outside the capture
+            torch.cuda.current_stream().wait_stream(s)
+            torch.cuda.synchronize()
+            self.main.graph = _NativeGraph(s, lambda: self.main.issue(self))
+            torch.cuda.synchronize()
+            self.meters.zero_()
+
+    def step(self, xb, tb):
+        """One batch of a pass: the static batch size replays the captured step, fewer images run eagerly on a plan of that size."""
+        r = xb.size(0)
+        if r == self.n:
+            b = self.main
+        else:
+            if r > self.n or r < 1:
+                raise L.NunetError("EvalStep: a batch of %d images (1 .. %d)" % (r, self.n))
+            if self.tail is None or self.tail.n != r:
+                self.tail = _EvalBatch(self, r)
+                self._packed.discard(r)
+            b = self.tail
+            if r not in self._packed:
+                b.repack(self.eng)
+                self._packed.add(r)
+        b.x.copy_(xb, non_blocking=True)
+        b.t.copy_(tb, non_blocking=True)
+        if b.graph is not None:
+            b.graph.replay()
+        else:
+            b.issue(self)
+        self._last = b
+
+    def result(self):
+        """The pass so far: OrderedDict(loss, iou, dice, acc: sample-weighted means of the batch values, the reference's
+        AverageMeter; samples; counts: per-class tp / fp / fn / tn lists; per_class: metrics.scores_from_counts of them,
+        dataset level). One host sync."""
+        from collections import OrderedDict
+        from .metrics import scores_from_counts
+        m = L.read_struct(self.meters, L.EvalMeters)
+        k = max(m.samples, 1.0)
+        out = OrderedDict([("loss", m.loss_sum / k), ("iou", m.iou_sum / k), ("dice", m.dice_sum / k), ("acc", m.acc_sum / k),
+                           ("samples", int(m.samples))])
+        K = self.ncls
+        out["counts"] = OrderedDict((nm, [int(v) for v in getattr(m, nm)[:K]]) for nm in ("tp", "fp", "fn", "tn"))
+        out["per_class"] = scores_from_counts(*out["counts"].values())
+        return out
+
+    def evaluate(self, x, t):
+        self.begin()
+        for k in range(0, x.size(0), self.n):
+            self.step(x[k:k + self.n], t[k:k + self.n])
+        return self.result()
 
 
 class _SegProgram:

@@ -7,6 +7,8 @@ Same artefacts as the reference: models/<name>/config.yml (trains.py:206-207),
 models/<name>/log.csv with columns epoch, lr, loss, iou, val_loss, val_iou (:304-311,331-339),
 models/<name>/model.pth = state_dict at the best val IoU (:344-349), early stopping (:351-354).
 The `lr` column logs the scheduler's current lr (the reference logs the constant initial lr, :332).
+Beside the fused step, validation (trains.py:150-188) runs as the captured EvalStep (--eval_step false: the module loop; the
+same val_loss and val_iou to the bit); --val_metrics true appends val_dice, val_acc to the epoch line and to log.csv.
 
 Data parallel (new capability; the reference is single-device, trains.py:223): launch one process per GPU,
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port 29500 \
@@ -30,8 +32,9 @@ import torch.distributed as dist
 
 import nunet_amd
 from nunet_amd import archs, losses, parallel
-from nunet_amd.metrics import iou_counts, iou_from_counts
-from nunet_amd.trainer import TrainStep, cosine_lr
+from nunet_amd import _lib as L
+from nunet_amd.metrics import iou_counts, iou_from_counts, seg_sums
+from nunet_amd.trainer import EvalStep, TrainStep, cosine_lr
 from nunet_amd.utils import AverageMeter, str2bool
 
 ARCH_NAMES = archs.__all__
@@ -80,6 +83,11 @@ def parse_args():
     p.add_argument('--device_pipeline', default=True, type=str2bool,
                    help='feed the fused step with the decoded uint8 batch and run Normalize, /255, rot90 / flips and the layout change on '
                         'the device (reference dataset.py:66-74, trains.py:258-266); False: float tensors prepared on the host')
+    p.add_argument('--eval_step', default=True, type=str2bool,
+                   help='with the fused step: validate through the captured EvalStep (forward, losses, IoU / Dice / accuracy and the '
+                        'meters on the device, one read per pass; same val_loss and val_iou to the bit); False: the module loop')
+    p.add_argument('--val_metrics', default=False, type=str2bool,
+                   help='also log val_dice (reference metrics.py dice_coef) and val_acc (pixel accuracy) per epoch, after images_per_sec')
     p.add_argument('--augment', default=False, type=str2bool, help='RandomRotate90 + Flip per sample (trains.py:258-259), device pipeline only')
     return p.parse_args()
 
@@ -116,11 +124,16 @@ def multistep_lr(base_lr, milestones, gamma, epoch):
     return base_lr * gamma ** sum(1 for m in milestones if epoch >= m)
 
 
-def validate(config, data, model, criterion):
-    """reference trains.py:150-188."""
-    avg = {'loss': AverageMeter(), 'iou': AverageMeter()}
-    model.eval()
+def validate(config, data, model, criterion, ev=None):
+    """reference trains.py:150-188. ev (an EvalStep): the same pass as captured replays, the meters read once; the module
+    loop below otherwise (two host round trips per batch; a third for Dice and accuracy under --val_metrics)."""
     x, t = data
+    if ev is not None:
+        r = ev.evaluate(x, t)
+        return OrderedDict((k, r[k]) for k in ('loss', 'iou', 'dice', 'acc'))
+    extra = config.get('val_metrics', False)
+    avg = {'loss': AverageMeter(), 'iou': AverageMeter(), 'dice': AverageMeter(), 'acc': AverageMeter()}
+    model.eval()
     bs = config['batch_size']
     with torch.no_grad():
         for k in range(0, x.size(0), bs):
@@ -134,7 +147,11 @@ def validate(config, data, model, criterion):
                 last = out
             avg['loss'].update(loss.item(), xb.size(0))
             avg['iou'].update(iou_from_counts(iou_counts(last.contiguous(), tb)), xb.size(0))
-    return OrderedDict([('loss', avg['loss'].avg), ('iou', avg['iou'].avg)])
+            if extra:
+                s = L.read_struct(seg_sums(last.contiguous(), tb), L.SegSums)
+                avg['dice'].update((2.0 * sum(s.soft_i) + 1e-5) / (sum(s.soft_p) + sum(s.soft_t) + 1e-5), xb.size(0))
+                avg['acc'].update((sum(s.tp) + sum(s.tn)) / float(last.numel()), xb.size(0))
+    return OrderedDict((k, avg[k].avg) for k in (('loss', 'iou', 'dice', 'acc') if extra else ('loss', 'iou')))
 
 
 def main():
@@ -204,7 +221,12 @@ def main():
         scaler = torch.amp.GradScaler('cuda', **scaling) if scaling else None
         clip_params = [p for p in model.parameters() if p.requires_grad]
 
-    log = OrderedDict([(k, []) for k in ('epoch', 'lr', 'loss', 'iou', 'val_loss', 'val_iou', 'images_per_sec')])
+    # validation: the captured EvalStep beside the fused step (its own plan and arena; built behind ts.capture)
+    ev = EvalStep(model, (bs, config['input_channels'], h, w), loss=config['loss']) if fused and config['eval_step'] else None
+    if ev is not None and rank == 0:
+        print('=> captured validation step (EvalStep)')
+    log_keys = ('epoch', 'lr', 'loss', 'iou', 'val_loss', 'val_iou', 'images_per_sec') + (('val_dice', 'val_acc') if config['val_metrics'] else ())
+    log = OrderedDict([(k, []) for k in log_keys])
     best_iou, trigger = 0, 0
     plateau = PlateauLR(config['lr'], config['factor'], config['patience'], config['min_lr'])
     g = torch.Generator().manual_seed(config['seed'])   # host-side permutation: identical for any device
@@ -283,7 +305,7 @@ def main():
                                  clipped=int((nv > clip).sum()))
         torch.cuda.synchronize()
         ips = steps * bs * world / (time.perf_counter() - t0)
-        val_log = validate(config, val, model, criterion)                # every rank: identical replicas, identical numbers
+        val_log = validate(config, val, model, criterion, ev)             # every rank: identical replicas, identical numbers
         if config['scheduler'] == 'ReduceLROnPlateau':
             plateau.step(val_log['loss'])                                # trains.py:325-326
         trigger += 1
@@ -291,10 +313,11 @@ def main():
         if rank == 0:
             print('Epoch [%d/%d] loss %.4f - iou %.4f - val_loss %.4f - val_iou %.4f - %.0f img/s'
                   % (epoch, config['epochs'], tl, ti, val_log['loss'], val_log['iou'], ips)
+                  + (' - val_dice %.4f - val_acc %.4f' % (val_log['dice'], val_log['acc']) if config['val_metrics'] else '')
                   + (' - loss scale %g, %d steps skipped' % scale_info if scale_info is not None else '')
                   + (' - grad norm %.4g/%.4g, %d steps clipped' % (norm_info['mean'], norm_info['peak'], norm_info['clipped'])
                      if norm_info is not None else ''))
-            for k, v in zip(log, (epoch, lr, tl, ti, val_log['loss'], val_log['iou'], ips)):
+            for k, v in zip(log, (epoch, lr, tl, ti, val_log['loss'], val_log['iou'], ips) + ((val_log['dice'], val_log['acc']) if config['val_metrics'] else ())):
                 log[k].append(v)
             with open('models/%s/log.csv' % config['name'], 'w') as f:
                 f.write(','.join(log.keys()) + '\n')

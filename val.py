@@ -12,8 +12,8 @@ import yaml
 
 import nunet_amd
 from nunet_amd import archs
-from nunet_amd.metrics import iou_counts, iou_from_counts, sigmoid_masks_u8
-from nunet_amd.utils import AverageMeter
+from nunet_amd.metrics import sigmoid_masks_u8
+from nunet_amd.trainer import EvalStep
 
 
 def main():
@@ -35,17 +35,20 @@ def main():
     img, msk = nunet_amd.synth.synth_split(config['val_size'], config['input_h'], config['input_w'],
                                            config['input_channels'], config['num_classes'], seed=2000)
     x, t = torch.from_numpy(img), torch.from_numpy(msk)
-    meter = AverageMeter()
     for c in range(config['num_classes']):
         os.makedirs(os.path.join('outputs', config['name'], str(c)), exist_ok=True)
     bs = config['batch_size']
+    loss = config.get('loss', 'BCEDiceLoss')
+    if loss == 'LovaszHingeLoss' and config['num_classes'] != 1:
+        loss = 'BCEDiceLoss'                                             # (the metrics do not depend on it)
+    # the validation step of train.py: forward, IoU / Dice / accuracy of the last head (val.py:92-93) and the meters on the device
+    ev = EvalStep(model, (min(bs, x.size(0)), config['input_channels'], config['input_h'], config['input_w']), loss=loss)
+    bs = ev.n
     with torch.no_grad():
+        ev.begin()
         for k in range(0, x.size(0), bs):
-            xb, tb = x[k:k + bs].cuda(), t[k:k + bs].cuda()
-            out = model(xb)
-            if config['deep_supervision']:
-                out = out[-1]                                            # val.py:92-93
-            meter.update(iou_from_counts(iou_counts(out.contiguous(), tb)), xb.size(0))
+            ev.step(x[k:k + bs].cuda(), t[k:k + bs].cuda())
+            out = ev.last_logits
             if not args.no_images:
                 from PIL import Image
                 masks = sigmoid_masks_u8(out).cpu().numpy()              # uint8 on the device: 4x fewer D2H bytes
@@ -53,7 +56,16 @@ def main():
                     for c in range(config['num_classes']):
                         Image.fromarray(masks[i, c]).save(
                             os.path.join('outputs', config['name'], str(c), 'val_%04d.jpg' % (k + i)))
-    print('IoU: %.4f' % meter.avg)
+    r = ev.result()
+    print('IoU: %.4f' % r['iou'])
+    print('Dice: %.4f' % r['dice'])
+    print('Acc: %.4f' % r['acc'])
+    if config['num_classes'] > 1:
+        names = list(r['per_class'])
+        print('class ' + ' '.join('%11s' % nm for nm in names))
+        for c in range(config['num_classes']):
+            print('%5d ' % c + ' '.join('%11.4f' % r['per_class'][nm][0][c] for nm in names))
+        print('micro ' + ' '.join('%11.4f' % r['per_class'][nm][1] for nm in names))
 
 
 if __name__ == '__main__':
