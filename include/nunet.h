@@ -134,6 +134,23 @@ typedef struct {
   int32_t item_shape;               /* output channels x input channels one work item covers: 0 / 11 = 32 x 32 (default), 21 = 64 x 32
                                      * (needs Cout % 64 == 0, else 32 x 32), 12 = 32 x 64 (needs Cin >= 64). Wider items read the two operand
                                      * tiles fewer times but keep fewer workgroups resident; nunet_conv3x3_wgrad_slabs depends on it. */
+  /* Optional OPERAND TRANSFORMS, applied between the global load and the LDS write of an operand tile, so that a tensor whose only
+   * reader is this kernel is never written to memory. Both need the 32 x 32 item shape (item_shape 0 / 11); all-zero = off.
+   *   x_tf = NUNET_TF_BN_RELU      input operand = relu(bn(src0)), src0 the RAW output of the block's first conv (C1 == 0): what the
+   *                                forward conv with in_tf = NUNET_TF_BN_RELU computed and could side-store (tf_store). Scale and shift
+   *                                come from x_mean_invstd - the mean | invstd that conv saved (tf_mean_invstd, a training forward: the
+   *                                conv bias cancels against the batch mean) - and x_gamma, x_beta, in the conv loader's operation order.
+   *   d_tf = NUNET_TF_BN_RELU_BWD  dY operand = BatchNorm+ReLU backward apply of `dy` (= dL/d relu(bn(d_y))), the tensor
+   *                                nunet_bn_relu_bwd_apply / a conv with in_tf = NUNET_TF_BN_RELU_BWD would write: sums from d_sums,
+   *                                saved statistics from d_mean_invstd. The workgroups of the first input-channel tile and K-slice
+   *                                write d_dbeta = sum dz, d_dgamma = sum dz * xhat, d_dbias = 0 where given (NULL: not written).
+   * Pixels outside the image, separator rows and channels past Cin / Cout stay ZERO: the padding is applied after the transform. */
+  int32_t x_tf, d_tf;
+  const float* x_mean_invstd; const float* x_gamma; const float* x_beta;   /* [2][C0], [C0], [C0] */
+  const void* d_y; int32_t d_py;                                           /* raw output of the conv whose weights this is the gradient of */
+  const int64_t* d_sums;                                                   /* fixed-point sums [rep][2][Cout]: sum dz, sum dz * xhat */
+  const float* d_mean_invstd; const float* d_gamma; const float* d_beta;   /* [2][Cout], [Cout], [Cout] */
+  float* d_dgamma; float* d_dbeta; float* d_dbias;                         /* [Cout] each or NULL */
 } nunet_wgrad_desc;
 
 /* Partial weight gradients: the contraction over pixels is split into nunet_conv3x3_wgrad_slabs(d) slices; slice s
@@ -577,6 +594,13 @@ int nunet_plan_set_lane_priority(nunet_plan* p, int32_t lowest);
  * ROCm's choice, and unchecked 1 process in 5 came up with a program at 4.8 ms per step instead of 1.7). */
 int nunet_plan_reset_lanes(nunet_plan* p);
 int nunet_plan_set_schedule(nunet_plan* p, int32_t schedule);
+/* Where the backward pass forms dy1 / dy2, the gradients wrt the raw conv outputs that only the weight gradients read:
+ *   0  the input-gradient convs side-store them from their BatchNorm-backward loaders (tf_store) and the weight-gradient pair
+ *      reads them back (the first block, which has no input gradient of conv1, always takes the other form for dy1);
+ *   1  no side store: the weight-gradient pair forms them in its own loaders from (dA, y) (nunet_wgrad_desc.d_tf).
+ * Same bits either way. Default 0, or the value of NUNET_WGRAD_DY when the plan is created. Refused (NUNET_EINVAL) while a
+ * backward pass is open (nunet_plan_backward_phase 1|8). */
+int nunet_plan_set_wgrad_dy(nunet_plan* p, int32_t in_loader);
 /* debug/test access to an intermediate: name like "x0_0", "x2_1" (block
  * outputs, NHWC). Returns byte offset into arena; fills pitch/channels. */
 int64_t nunet_plan_feature(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch,

@@ -73,10 +73,13 @@ int nunet_conv3x3_wgrad_launch_info(const nunet_wgrad_desc* d, nunet_wgrad_launc
  * kernel of the backward pass writes a slot after its last consumer has accumulated into it, so after nunet_plan_backward
  * every slot still holds the complete gradient its block's backward started from. Returns -1 when the plan has no block (i, j). */
 int64_t nunet_plan_feature_grad(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels);
-/* ... and of a1 = relu(bn1(conv1(input))) of block (i, j), the activation between its two convolutions, which a training forward
- * stores (dense: pitch == channels) for the weight gradient of conv2 and no later kernel writes. With x_{i,j} > 0 it gives a test
- * the ReLU decisions the pass actually took. */
-int64_t nunet_plan_block_act1(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels);
+/* a1 = relu(bn1(conv1(input))) of block (i, j), the activation between its two convolutions. No pass stores it: conv2 and the
+ * weight gradient of conv2 form it in their loaders from the raw conv output y1, which stays in the arena. This entry
+ * materialises it on demand after a TRAINING forward - nunet_bn_relu_fwd on y1 with the block's batch sums and the CURRENT
+ * gamma / beta in `params` (the running statistics are not touched) - into `out`, dense [N][H_i][W_i][C] in the plan's storage
+ * dtype. With x_{i,j} > 0 it gives a test the ReLU decisions the pass actually took. NUNET_EINVAL when the plan has no block (i, j). */
+int nunet_plan_block_act1(nunet_plan* p, const float* params, void* arena, size_t arena_bytes, int32_t i, int32_t j, void* out,
+                          nunet_stream_t s);
 
 /* Launch census of the last forward (pass 0) and the last backward (pass 1) the plan issued: one entry per 3x3 convolution
  * (forward conv or input gradient) and one per weight-gradient pair, in the order the plan handed them to its scheduler, with
@@ -95,6 +98,8 @@ typedef struct {
   int64_t splitk_ws_floats;         /* conv: K-split workspace offered (0: none) */
   nunet_conv_launch_info conv;
   nunet_wgrad_launch_info wgrad[2];
+  int32_t has_tf_store;             /* conv: the transformed input is also written out (nunet_conv_desc.tf_store) */
+  int32_t wgrad_tf[2];              /* weight-gradient pair: operand transforms of conv1's / conv2's problem, bit 0 = x_tf, bit 1 = d_tf */
 } nunet_plan_census_entry;
 int32_t nunet_plan_census_count(const nunet_plan* p, int32_t pass);
 int nunet_plan_census_get(const nunet_plan* p, int32_t pass, int32_t index, nunet_plan_census_entry* out);

@@ -68,7 +68,10 @@ class WgradDesc(C.Structure):
                 ("src0", _vp), ("C0", _i32), ("P0", _i32),
                 ("src1", _vp), ("C1", _i32), ("P1", _i32),
                 ("dy", _vp), ("Cout", _i32), ("PY", _i32),
-                ("dw", _vp), ("slab_stride", _i64), ("max_slabs", _i32), ("target_wgs", _i32), ("dw_floats", _i64), ("item_shape", _i32)]
+                ("dw", _vp), ("slab_stride", _i64), ("max_slabs", _i32), ("target_wgs", _i32), ("dw_floats", _i64), ("item_shape", _i32),
+                ("x_tf", _i32), ("d_tf", _i32), ("x_mean_invstd", _vp), ("x_gamma", _vp), ("x_beta", _vp),
+                ("d_y", _vp), ("d_py", _i32), ("d_sums", _vp), ("d_mean_invstd", _vp), ("d_gamma", _vp), ("d_beta", _vp),
+                ("d_dgamma", _vp), ("d_dbeta", _vp), ("d_dbias", _vp)]
 
 
 class ConvLaunchInfo(C.Structure):
@@ -96,7 +99,8 @@ class PlanCensusEntry(C.Structure):
     """nunet_plan_census_entry (include/nunet_diag.h): one convolution or weight-gradient pair the plan issued."""
     _fields_ = [("label", C.c_char * 32), ("kind", _i32), ("N", _i32), ("H", _i32), ("W", _i32),
                 ("C0", _i32), ("C1", _i32), ("D0", _i32), ("D1", _i32), ("in_tf", _i32), ("has_bn_y", _i32),
-                ("acc0_mask", _u32), ("splitk_ws_floats", _i64), ("conv", ConvLaunchInfo), ("wgrad", WgradLaunchInfo * 2)]
+                ("acc0_mask", _u32), ("splitk_ws_floats", _i64), ("conv", ConvLaunchInfo), ("wgrad", WgradLaunchInfo * 2),
+                ("has_tf_store", _i32), ("wgrad_tf", _i32 * 2)]
 
 
 (LOSS_ENTRY_BCE_DICE_FWD, LOSS_ENTRY_BCE_DICE_BWD, LOSS_ENTRY_LOSS_STEP, LOSS_ENTRY_IOU_COUNTS, LOSS_ENTRY_SIGMOID_U8,
@@ -257,11 +261,12 @@ _SIG = {
     "nunet_plan_repack": (_i32, [_vp, _vp, _vp, _sz, _vp]),
     "nunet_plan_feature": (_i64, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "nunet_plan_feature_grad": (_i64, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
-    "nunet_plan_block_act1": (_i64, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "nunet_plan_block_act1": (_i32, [_vp, _vp, _vp, _sz, _i32, _i32, _vp, _vp]),
     "nunet_plan_census_count": (_i32, [_vp, _i32]),
     "nunet_plan_census_get": (_i32, [_vp, _i32, _i32, C.POINTER(PlanCensusEntry)]),
     "nunet_plan_set_multistream": (_i32, [_vp, _i32]),
     "nunet_plan_set_schedule": (_i32, [_vp, _i32]),
+    "nunet_plan_set_wgrad_dy": (_i32, [_vp, _i32]),
     "nunet_plan_calibrate": (_i32, [_vp, _i32]),
     "nunet_plan_set_lane_priority": (_i32, [_vp, _i32]),
     "nunet_plan_reset_lanes": (_i32, [_vp]),

@@ -1258,6 +1258,12 @@ struct WgP {
   int nCoT, nCiT, ksplit, nMT;
   int SH; unsigned SHinv;
   unsigned invTX, invTY;   // fastdiv_inv(tilesX), fastdiv_inv(tilesY)
+  // operand transforms (XT / DT instantiations, nunet_wgrad_desc.x_tf / d_tf)
+  const float* x_mi; const float* x_gamma; const float* x_beta;
+  const void* d_y; int d_py;
+  const long long* d_fx; const float* d_mi; const float* d_gamma; const float* d_beta;
+  float* d_dgamma; float* d_dbeta; float* d_dbias;
+  float M;                 // N * H * W
 };
 
 // A work item covers (32 * A Cout) x (32 * B Cin) x 9 taps. In LDS the two operand tiles are stored as A (B) PLANES of
@@ -1296,15 +1302,24 @@ typedef __attribute__((ext_vector_type(8))) short s16x8;
 // global loads are in flight (registers) while the current one multiplies. Compared with 32 x 32 items
 // (A = B = 1) an item reads its dY tile once for 32 B input channels and its input tile once for 32 A
 // output channels, and one fragment feeds A (or B) MFMAs.
-template <typename T, bool ST, int A, int B>
+// XT / DT (nunet_wgrad_desc.x_tf / d_tf, 32 x 32 items only): an operand is TRANSFORMED in the registers it waits in between
+// its global load and its LDS write - the place where conv3x3_kernel applies its LT 1 / LT 2 loader transforms, with the same
+// device functions, so the tile in LDS holds the bits the conv's side store (tf_store) would have written:
+//   XT: input = relu(bn(src0)) of the raw first-conv output;  DT: dY = BatchNorm+ReLU backward apply of (dy = dA, d_y = raw y).
+// A thread's channel segment is the same for all its units, so the coefficients are a [6][32] table in LDS (x scale | x shift |
+// d scale | d shift | A | B of the item's 32 input / output channels) read once per tile write. The zero select of write_tile
+// comes AFTER the transform: the convolution pads the activation (a halo pixel is 0, not relu(shift)).
+template <typename T, bool ST, int A, int B, bool XT = false, bool DT = false>
 __device__ __forceinline__ void wgrad_body(const WgP& p, int bid) {
   typedef WgCfg<T, A, B> C;
+  static_assert(!(XT || DT) || (A == 1 && B == 1), "operand transforms: 32 x 32 items only");
   constexpr int NT = C::NT, BM = C::BM, EPV = C::EPV, SR = C::SR, UPR = C::UPR, UPD = C::UPD, UPX = C::UPX;
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
   T* const s_stage = reinterpret_cast<T*>(s_dyn);                                   // [2][STAGE]
   int* const s_hidx = reinterpret_cast<int*>(s_dyn + 2 * C::STAGE * sizeof(T));     // [BM]
   int* const s_mxy = s_hidx + BM;                                                   // [BM]
   int* const s_hxy = s_mxy + BM;                                                    // [HPMAX]
+  float* const s_tf = reinterpret_cast<float*>(s_hxy + C::HPMAX);                   // [6][32] (XT / DT)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
@@ -1344,21 +1359,38 @@ __device__ __forceinline__ void wgrad_body(const WgP& p, int bid) {
   // its address a 32-bit byte offset from a uniform base (host-checked to fit). Units outside the image read pixel 0
   // and are zeroed on the way into LDS.
   //   code: (ni << 20) | ((dy + 1) << 10) | (dx + 1) with dy, dx >= -1;  -2: no such unit
-  int dcode[C::NUD], acode[C::NUA], duoff[C::NUD], auoff[C::NUA];
-#pragma unroll
-  for (int k = 0; k < C::NUD; ++k) {
+  // LEAN (the DT instantiations): the codes are NOT held in registers but read back from the two LDS tables for every tile, and
+  // the pixel is formed from the coordinates (two multiply-adds per unit, no uoff): 14 registers less across the MFMA sweep,
+  // which is what the dY operand's second load per unit (y next to dA, 12 registers in flight) needs to stay within the
+  // 168 registers of three resident workgroups. Seven LDS reads per 128-pixel tile, issued ahead of the tile's global loads.
+  constexpr bool LEAN = DT;
+  auto unit_dcode = [&](int k) {
     const int u = tid + k * NT;
     const int cde = u < BM * UPD ? s_mxy[u / UPD] : -2;                 // (ni, ly, lx), -1: row past the tile
-    dcode[k] = cde >= 0 ? cde + (1 << 10) + 1 : cde;
-    duoff[k] = cde >= 0 ? ((cde >> 20) * p.H + ((cde >> 10) & 1023)) * p.W + (cde & 1023) : 0;
-  }
-#pragma unroll
-  for (int k = 0; k < C::NUA; ++k) {
+    return cde >= 0 ? cde + (1 << 10) + 1 : cde;
+  };
+  auto unit_acode = [&](int k) {
     const int u = tid + k * NT;
-    const int cde = u < C::HPMAX * UPX ? s_hxy[u / UPX] : -2;           // (ni, hy, hx): halo coordinates = tile coordinates + 1
-    acode[k] = cde;
-    auoff[k] = cde >= 0 ? ((cde >> 20) * p.H + ((cde >> 10) & 1023) - 1) * p.W + (cde & 1023) - 1 : 0;
+    return u < C::HPMAX * UPX ? s_hxy[u / UPX] : -2;                    // (ni, hy, hx): halo coordinates = tile coordinates + 1
+  };
+  int dcode[LEAN ? 1 : C::NUD], acode[LEAN ? 1 : C::NUA], duoff[LEAN ? 1 : C::NUD], auoff[LEAN ? 1 : C::NUA];
+  if constexpr (!LEAN) {
+#pragma unroll
+    for (int k = 0; k < C::NUD; ++k) {
+      dcode[k] = unit_dcode(k);
+      const int cde = dcode[k] - (1 << 10) - 1;
+      duoff[k] = dcode[k] >= 0 ? ((cde >> 20) * p.H + ((cde >> 10) & 1023)) * p.W + (cde & 1023) : 0;
+    }
+#pragma unroll
+    for (int k = 0; k < C::NUA; ++k) {
+      const int cde = unit_acode(k);
+      acode[k] = cde;
+      auoff[k] = cde >= 0 ? ((cde >> 20) * p.H + ((cde >> 10) & 1023) - 1) * p.W + (cde & 1023) - 1 : 0;
+    }
   }
+  // does staging unit k of this thread exist (the last unit of a thread may lie past the tile)?
+  auto d_exists = [&](int k) { if constexpr (LEAN) return tid + k * NT < BM * UPD; else return dcode[k] != -2; };
+  auto a_exists = [&](int k) { if constexpr (LEAN) return tid + k * NT < C::HPMAX * UPX; else return acode[k] != -2; };
   // the channel slices this item reads: one source per 16-byte unit of the forward input
   // (C0 is a multiple of 16, so a unit never straddles the two concat sources)
   const int segx = tid % UPX, segd = tid % UPD;   // same for all units of a thread (NT % UPX == 0, NT % UPD == 0)
@@ -1373,11 +1405,14 @@ __device__ __forceinline__ void wgrad_body(const WgP& p, int bid) {
   else { abase = (const char*)p.src1; apb = (unsigned)p.P1 * (unsigned)sizeof(T); acb = (unsigned)(cch - p.C0) * (unsigned)sizeof(T); }
   const char* const dbase = (const char*)p.dy;
   const unsigned dpb = (unsigned)p.PY * (unsigned)sizeof(T), dcb = (unsigned)(dvalid ? dch : 0) * (unsigned)sizeof(T);
+  const char* const ybase = (const char*)p.d_y;                                  // DT: the raw conv output next to dA
+  const unsigned ypb = (unsigned)p.d_py * (unsigned)sizeof(T);
   // LDS position of the thread's units inside a stage: plane (32-channel block) and 16-byte segment of the plane row
   const int dplane = segd / UPR, dseg = segd % UPR;
   const int xplane = segx / UPR, xseg = segx % UPR;
 
   Vec16<T> dreg[C::NUD], areg[C::NUA];
+  Vec16<T> yreg[DT ? C::NUD : 1];
   unsigned vmd = 0u, vma = 0u;               // bit k: dY / input unit k valid (of the tile held in the registers)
   // pixel of a unit (code, uoff) of the tile at (n0, y0, x0); -1: outside the image
   auto unit_pixel = [&](int code, int uoff, int n0, int y0, int x0, int gp0) {
@@ -1392,7 +1427,8 @@ __device__ __forceinline__ void wgrad_body(const WgP& p, int bid) {
     } else {
       const int y = y0 + dy, x = x0 + dx;
       const bool ok = (n0 + ni < p.N) & (y >= 0) & (y < p.H) & (x >= 0) & (x < p.W);
-      return ok ? gp0 + uoff : -1;
+      if constexpr (LEAN) return ok ? ((n0 + ni) * p.H + y) * p.W + x : -1;
+      else return ok ? gp0 + uoff : -1;
     }
   };
   auto load_tile = [&](int mt) {
@@ -1404,13 +1440,16 @@ __device__ __forceinline__ void wgrad_body(const WgP& p, int bid) {
     unsigned md = 0u, ma = 0u;
 #pragma unroll
     for (int k = 0; k < C::NUD; ++k) {
-      const int gp = (dcode[k] >= 0 && dvalid) ? unit_pixel(dcode[k], duoff[k], n0, y0, x0, gp0) : -1;
+      const int dc = LEAN ? unit_dcode(k) : dcode[LEAN ? 0 : k];
+      const int gp = (dc >= 0 && dvalid) ? unit_pixel(dc, LEAN ? 0 : duoff[LEAN ? 0 : k], n0, y0, x0, gp0) : -1;
       md |= gp >= 0 ? (1u << k) : 0u;
       dreg[k].raw = *reinterpret_cast<const u32x4*>(dbase + ((unsigned)(gp < 0 ? 0 : gp) * dpb + dcb));
+      if constexpr (DT) yreg[k].raw = *reinterpret_cast<const u32x4*>(ybase + ((unsigned)(gp < 0 ? 0 : gp) * ypb + dcb));
     }
 #pragma unroll
     for (int k = 0; k < C::NUA; ++k) {
-      const int gp = (acode[k] >= 0 && cvalid) ? unit_pixel(acode[k], auoff[k], n0, y0, x0, gp0) : -1;
+      const int ac = LEAN ? unit_acode(k) : acode[LEAN ? 0 : k];
+      const int gp = (ac >= 0 && cvalid) ? unit_pixel(ac, LEAN ? 0 : auoff[LEAN ? 0 : k], n0, y0, x0, gp0) : -1;
       ma |= gp >= 0 ? (1u << k) : 0u;
       areg[k].raw = *reinterpret_cast<const u32x4*>(abase + ((unsigned)(gp < 0 ? 0 : gp) * apb + acb));
     }
@@ -1419,23 +1458,113 @@ __device__ __forceinline__ void wgrad_body(const WgP& p, int bid) {
   auto write_tile = [&](int buf) {
     T* sd = s_stage + buf * C::STAGE;
     T* sa = sd + A * BM * SR;
+    typedef typename FV<T>::type V;
+    if constexpr (DT && !C::F32) {
+      // 16-bit types: the eight channels of a unit in two halves of four, so that only 16 coefficient registers (not 32) and
+      // half the fp32 temporaries are live at a time; element-wise conversions and fmas, the same bits as the whole-vector form
+      typedef typename Frag16<T>::V H8;
+      typedef __attribute__((ext_vector_type(4))) T H4;
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        const f32x4 sc = *reinterpret_cast<const f32x4*>(&s_tf[64 + dseg * EPV + 4 * hf]), sh = *reinterpret_cast<const f32x4*>(&s_tf[96 + dseg * EPV + 4 * hf]);
+        const f32x4 cA = *reinterpret_cast<const f32x4*>(&s_tf[128 + dseg * EPV + 4 * hf]), cB = *reinterpret_cast<const f32x4*>(&s_tf[160 + dseg * EPV + 4 * hf]);
+#pragma unroll
+        for (int k = 0; k < C::NUD; ++k) {
+          const H8 d8 = __builtin_bit_cast(H8, dreg[k].raw), y8 = __builtin_bit_cast(H8, yreg[k].raw);
+          const H4 d4 = hf ? __builtin_shufflevector(d8, d8, 4, 5, 6, 7) : __builtin_shufflevector(d8, d8, 0, 1, 2, 3);
+          const H4 y4 = hf ? __builtin_shufflevector(y8, y8, 4, 5, 6, 7) : __builtin_shufflevector(y8, y8, 0, 1, 2, 3);
+          const H4 o4 = __builtin_convertvector(bn_relu_bwd_apply<f32x4>(__builtin_convertvector(d4, f32x4), __builtin_convertvector(y4, f32x4), sc, sh, cA, cB), H4);
+          const uint2 ow = __builtin_bit_cast(uint2, o4);
+          dreg[k].raw[2 * hf] = ow.x; dreg[k].raw[2 * hf + 1] = ow.y;
+        }
+      }
+    } else if constexpr (DT) {
+      const V sc = ldf<T>(&s_tf[64 + dseg * EPV]), sh = ldf<T>(&s_tf[96 + dseg * EPV]), cA = ldf<T>(&s_tf[128 + dseg * EPV]), cB = ldf<T>(&s_tf[160 + dseg * EPV]);
+#pragma unroll
+      for (int k = 0; k < C::NUD; ++k) dreg[k] = vec_from_f<T>(bn_relu_bwd_apply<V>(vec_to_f<T>(dreg[k]), vec_to_f<T>(yreg[k]), sc, sh, cA, cB));
+    }
+    if constexpr (XT) {
+      const V sc = ldf<T>(&s_tf[xseg * EPV]), sh = ldf<T>(&s_tf[32 + xseg * EPV]);
+#pragma unroll
+      for (int k = 0; k < C::NUA; ++k) areg[k] = vec_from_f<T>(bn_relu_apply<V>(vec_to_f<T>(areg[k]), sc, sh));
+    }
+    // (the zero select stays behind the transforms: padding, separator rows and channels past Cin / Cout are zeros of the
+    //  TRANSFORMED operand)
 #pragma unroll
     for (int k = 0; k < C::NUD; ++k)
-      if ((k + 1) * NT <= BM * UPD || dcode[k] != -2) st16(&sd[(dplane * BM + (tid + k * NT) / UPD) * SR + dseg * EPV], (vmd >> k) & 1u ? dreg[k] : zero16<T>());
+      if ((k + 1) * NT <= BM * UPD || d_exists(k)) st16(&sd[(dplane * BM + (tid + k * NT) / UPD) * SR + dseg * EPV], (vmd >> k) & 1u ? dreg[k] : zero16<T>());
 #pragma unroll
     for (int k = 0; k < C::NUA; ++k)
-      if ((k + 1) * NT <= C::HPMAX * UPX || acode[k] != -2) st16(&sa[(xplane * C::HPMAX + (tid + k * NT) / UPX) * SR + xseg * EPV], (vma >> k) & 1u ? areg[k] : zero16<T>());
+      if ((k + 1) * NT <= C::HPMAX * UPX || a_exists(k)) st16(&sa[(xplane * C::HPMAX + (tid + k * NT) / UPX) * SR + xseg * EPV], (vma >> k) & 1u ? areg[k] : zero16<T>());
+  };
+  // Per-channel coefficients of the item's 32 input / output channels, derived by the first 32 threads AFTER the first tile's
+  // loads were issued (the two memory latencies overlap). XT: scale and shift as the LT 1 conv prologue forms them from the mean |
+  // invstd it saved; DT: as bn_relu_bwd_kernel<APPLY> / the LT 2 prologue form them from the fixed-point sums, and the workgroups
+  // of Cin tile 0, slice 0 write the three small gradient vectors of their channels.
+  auto tf_prologue = [&]() {
+    if constexpr (DT) {
+      // the replicas of the sums are fetched by nrep * 32 (replica, channel) pairs spread over the threads and meet in the stage area
+      // (idle until the first write_tile), as in the LT 2 conv prologue: fx_totals' sixteen loads per channel thread would be 64
+      // registers next to the first tile's loads in flight - the register peak of the kernel. (Integer sums: exact in any order.)
+      fx2_t* const s_fx = reinterpret_cast<fx2_t*>(s_dyn);     // [nrep][32][2]
+      const int nrep = bn_sum_replicas(p.Cout);
+      for (int t = tid; t < nrep * 32; t += NT) {
+        const int rr = t >> 5, c = co0 + (t & 31);
+#pragma unroll
+        for (int v = 0; v < 2; ++v)
+          s_fx[t * 2 + v] = c < p.Cout ? *reinterpret_cast<const fx2_t*>(p.d_fx + ((size_t)(rr * 2 + v) * p.Cout + c) * NUNET_FX_WORDS) : fx2_t{0, 0};
+      }
+      __syncthreads();
+    }
+    if (tid < 32) {
+      if constexpr (XT) {
+        const int c = ci0 + tid;
+        float sc = 0.f, sh = 0.f;
+        if (c < p.Cin) {
+          const float mean = p.x_mi[c], istd = p.x_mi[p.Cin + c];
+          sc = p.x_gamma[c] * istd; sh = __builtin_fmaf(-mean, sc, p.x_beta[c]);
+        }
+        s_tf[tid] = sc; s_tf[32 + tid] = sh;
+      }
+      if constexpr (DT) {
+        const int c = co0 + tid;
+        float sc = 0.f, sh = 0.f, cA = 0.f, cB = 0.f;
+        if (c < p.Cout) {
+          const float mean = p.d_mi[c], istd = p.d_mi[p.Cout + c];
+          sc = p.d_gamma[c] * istd; sh = __builtin_fmaf(-mean, sc, p.d_beta[c]);
+          const fx2_t* const s_fx = reinterpret_cast<const fx2_t*>(s_dyn);
+          const int nrep = bn_sum_replicas(p.Cout);
+          fx2_t q0 = s_fx[tid * 2], q1 = s_fx[tid * 2 + 1];
+          for (int rr = 1; rr < nrep; ++rr) { q0 += s_fx[(rr * 32 + tid) * 2]; q1 += s_fx[(rr * 32 + tid) * 2 + 1]; }
+          const double t1 = fx_value(q0[0], q0[1]), t2 = fx_value(q1[0], q1[1]);
+          bn_bwd_AB(mean, istd, sc, (float)(t1 / (double)p.M), (float)(t2 / (double)p.M), cA, cB);
+          if (cit == 0 && split == 0) {
+            // d beta = sum dz, d gamma = sum dz * xhat; the conv bias in front of a BatchNorm has gradient sum(dy) == 0
+            if (p.d_dbeta) p.d_dbeta[c] = (float)t1;
+            if (p.d_dgamma) p.d_dgamma[c] = (float)t2;
+            if (p.d_dbias) p.d_dbias[c] = 0.f;
+          }
+        }
+        s_tf[64 + tid] = sc; s_tf[96 + tid] = sh; s_tf[128 + tid] = cA; s_tf[160 + tid] = cB;
+      }
+    }
+    __syncthreads();
   };
 
   f32x16 acc[A][B][3];
+  auto zero_acc = [&]() {
 #pragma unroll
-  for (int a = 0; a < A; ++a)
+    for (int a = 0; a < A; ++a)
 #pragma unroll
-    for (int b = 0; b < B; ++b)
+      for (int b = 0; b < B; ++b)
 #pragma unroll
-      for (int t = 0; t < 3; ++t)
+        for (int t = 0; t < 3; ++t)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) acc[a][b][t][i] = 0.f;
+          for (int i = 0; i < 16; ++i) acc[a][b][t][i] = 0.f;
+  };
+  // (transformed instantiations: zeroed only after the coefficient prologue and the first tile write, whose temporaries would
+  //  otherwise sit on top of 48 live accumulator registers)
+  if constexpr (!(XT || DT)) zero_acc();
 
   // this wave's three taps: rows 3w..3w+2 of the 3x3 window = kernel row `wave`
   int toff[3];
@@ -1457,7 +1586,9 @@ __device__ __forceinline__ void wgrad_body(const WgP& p, int bid) {
   int mt = split;
   if (mt < p.nMT) load_tile(mt);
   int buf = 0;
+  if constexpr (XT || DT) tf_prologue();
   if (mt < p.nMT) write_tile(0);
+  if constexpr (XT || DT) zero_acc();
   __syncthreads();
   while (mt < p.nMT) {
     const int nmt = mt + p.ksplit;
@@ -1548,20 +1679,26 @@ __device__ __forceinline__ void wgrad_body(const WgP& p, int bid) {
   }
 }
 
-template <typename T, bool ST, int A, int B>
-__global__ __launch_bounds__(192) void wgrad_kernel(WgP p) { wgrad_body<T, ST, A, B>(p, xcd_remap((int)blockIdx.x, (int)gridDim.x)); }
+// Waves per SIMD a transformed instantiation promises (second argument of its __launch_bounds__): the plain 32 x 32 kernel of the
+// 16-bit types needs 120 + 48 registers, which is what lets three workgroups - nine waves, three of them on one SIMD - share a CU
+// beside their 43 KB of LDS each; the transformed ones must not fall below that (fp32: 84 KB of LDS, one workgroup either way).
+template <typename T, bool TF> constexpr int wgrad_min_waves() { return (TF && sizeof(T) == 2) ? 3 : 1; }
+
+template <typename T, bool ST, int A, int B, bool XT = false, bool DT = false>
+__global__ __launch_bounds__(192, (wgrad_min_waves<T, XT || DT>())) void wgrad_kernel(WgP p) { wgrad_body<T, ST, A, B, XT, DT>(p, xcd_remap((int)blockIdx.x, (int)gridDim.x)); }
 
 // Two independent weight-gradient problems in ONE launch (the two convolutions of a VGGBlock finish
 // their dY at the same point of the backward pass): one kernel boundary less per block and twice
 // the workgroups to fill the chip.
-template <typename T, bool ST, int A1, int B1, int A2, int B2>
-__global__ __launch_bounds__(192) void wgrad_pair_kernel(WgP pa, WgP pb, int na, int na_pad) {
+// (transforms of a pair: DA on conv1's dY; XB, DB on conv2's input and dY - what a VGGBlock's two weight gradients can ask for)
+template <typename T, bool ST, int A1, int B1, int A2, int B2, bool DA = false, bool XB = false, bool DB = false>
+__global__ __launch_bounds__(192, (wgrad_min_waves<T, DA || XB || DB>())) void wgrad_pair_kernel(WgP pa, WgP pb, int na, int na_pad) {
   // (problem a's share of the grid is padded to a multiple of 8 - at most 7 idle blocks - so that block -> XCD is (local block) % 8
   //  in both problems and each gets its own xcd_remap)
   if ((int)blockIdx.x < na_pad) {
     const int v = xcd_remap((int)blockIdx.x, na_pad);
-    if (v < na) wgrad_body<T, ST, A1, B1>(pa, v);
-  } else wgrad_body<T, ST, A2, B2>(pb, xcd_remap((int)blockIdx.x - na_pad, (int)gridDim.x - na_pad));
+    if (v < na) wgrad_body<T, ST, A1, B1, false, DA>(pa, v);
+  } else wgrad_body<T, ST, A2, B2, XB, DB>(pb, xcd_remap((int)blockIdx.x - na_pad, (int)gridDim.x - na_pad));
 }
 
 // Item shape of a problem, a pure function of its extents. The kernel is bound by the latency of its staging loads,
@@ -1581,7 +1718,7 @@ static WgTile wgrad_tile(const nunet_wgrad_desc* d) {
   return WgTile{1, 1};
 }
 template <typename T> static size_t wgrad_lds_bytes(WgTile t) {
-  return ((size_t)2 * (128 * t.A + 192 * t.B) * 32) * sizeof(T) + (size_t)(2 * 128 + 192) * sizeof(int);
+  return ((size_t)2 * (128 * t.A + 192 * t.B) * 32) * sizeof(T) + (size_t)(2 * 128 + 192) * sizeof(int) + (size_t)6 * 32 * sizeof(float);   // stages, index tables, XT / DT table
 }
 
 // K-split slices of a weight-gradient problem: enough work items for `target` workgroups, at most one
@@ -1616,6 +1753,10 @@ template <typename T> static long wgrad_setup(const nunet_wgrad_desc* d, WgP& p)
   p.nCiT = ceil_div(p.Cin, 32 * wt.B);
   p.nMT = g.tilesX * g.tilesY * g.tilesG;
   p.ksplit = wgrad_slices(d, g);
+  p.x_mi = d->x_mean_invstd; p.x_gamma = d->x_gamma; p.x_beta = d->x_beta;
+  p.d_y = d->d_y; p.d_py = d->d_py; p.d_fx = (const long long*)d->d_sums; p.d_mi = d->d_mean_invstd; p.d_gamma = d->d_gamma; p.d_beta = d->d_beta;
+  p.d_dgamma = d->d_dgamma; p.d_dbeta = d->d_dbeta; p.d_dbias = d->d_dbias;
+  p.M = (float)d->N * d->H * d->W;
   return (long)p.nCoT * p.nCiT * p.ksplit;
 }
 template <typename T> static void wgrad_prof(const nunet_wgrad_desc* d, const WgP& p, double& flops, double& bytes) {
@@ -1629,20 +1770,23 @@ template <typename T> static void wgrad_prof(const nunet_wgrad_desc* d, const Wg
 template <typename K> static void wgrad_allow_lds(K kernel, size_t bytes) {
   (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
-template <typename T, bool ST, int A, int B> static void launch_wgrad_one(long grid, const WgP& p, hipStream_t st) {
+template <typename T, bool ST, int A, int B, bool XT = false, bool DT = false> static void launch_wgrad_one(long grid, const WgP& p, hipStream_t st) {
   const size_t lds = wgrad_lds_bytes<T>(WgTile{A, B});
   static bool once = false;
-  if (!once) { wgrad_allow_lds(wgrad_kernel<T, ST, A, B>, lds); once = true; }
-  NUNET_LAUNCH((wgrad_kernel<T, ST, A, B>), dim3((unsigned)grid), dim3(192), lds, st, p);
+  if (!once) { wgrad_allow_lds(wgrad_kernel<T, ST, A, B, XT, DT>, lds); once = true; }
+  NUNET_LAUNCH((wgrad_kernel<T, ST, A, B, XT, DT>), dim3((unsigned)grid), dim3(192), lds, st, p);
 }
-template <typename T, bool ST, int A1, int B1, int A2, int B2> static void launch_wgrad_two(long ga, long gb, const WgP& pa, const WgP& pb, hipStream_t st) {
+template <typename T, bool ST, int A1, int B1, int A2, int B2, bool DA = false, bool XB = false, bool DB = false>
+static void launch_wgrad_two(long ga, long gb, const WgP& pa, const WgP& pb, hipStream_t st) {
   const size_t l1 = wgrad_lds_bytes<T>(WgTile{A1, B1}), l2 = wgrad_lds_bytes<T>(WgTile{A2, B2});
   const size_t lds = l1 > l2 ? l1 : l2;
   static bool once = false;
-  if (!once) { wgrad_allow_lds(wgrad_pair_kernel<T, ST, A1, B1, A2, B2>, lds); once = true; }
+  if (!once) { wgrad_allow_lds(wgrad_pair_kernel<T, ST, A1, B1, A2, B2, DA, XB, DB>, lds); once = true; }
   const long ga_pad = (ga + 7) / 8 * 8;
-  NUNET_LAUNCH((wgrad_pair_kernel<T, ST, A1, B1, A2, B2>), dim3((unsigned)(ga_pad + gb)), dim3(192), lds, st, pa, pb, (int)ga, (int)ga_pad);
+  NUNET_LAUNCH((wgrad_pair_kernel<T, ST, A1, B1, A2, B2, DA, XB, DB>), dim3((unsigned)(ga_pad + gb)), dim3(192), lds, st, pa, pb, (int)ga, (int)ga_pad);
 }
+// transform selector of a problem: bit 0 = XT, bit 1 = DT
+static inline int wgrad_tf(const nunet_wgrad_desc* d) { return (d->x_tf ? 1 : 0) | (d->d_tf ? 2 : 0); }
 
 template <typename T> static int launch_wgrad(const nunet_wgrad_desc* d, hipStream_t st) {
   WgP p;
@@ -1651,6 +1795,18 @@ template <typename T> static int launch_wgrad(const nunet_wgrad_desc* d, hipStre
   ProfScope ps(p.Cout == 32 ? PC_WGRAD_1x4 : PC_WGRAD_2x2, fl, by, st);
   const WgTile wt = wgrad_tile(d);
   const int key = wt.A * 10 + wt.B;
+  if (const int tf = wgrad_tf(d)) {        // 32 x 32 items (wgrad_check)
+    if (p.SH) {
+      if (tf == 1) launch_wgrad_one<T, true, 1, 1, true, false>(grid, p, st);
+      else if (tf == 2) launch_wgrad_one<T, true, 1, 1, false, true>(grid, p, st);
+      else launch_wgrad_one<T, true, 1, 1, true, true>(grid, p, st);
+    } else {
+      if (tf == 1) launch_wgrad_one<T, false, 1, 1, true, false>(grid, p, st);
+      else if (tf == 2) launch_wgrad_one<T, false, 1, 1, false, true>(grid, p, st);
+      else launch_wgrad_one<T, false, 1, 1, true, true>(grid, p, st);
+    }
+    return nunet_check_launch("wgrad3x3 (transformed operands)");
+  }
   if (p.SH) {
     if (key == 21) launch_wgrad_one<T, true, 2, 1>(grid, p, st);
     else if (key == 12) launch_wgrad_one<T, true, 1, 2>(grid, p, st);
@@ -1672,8 +1828,12 @@ template <typename T> static int launch_wgrad_pair(const WgPairArgs* w, hipStrea
   const WgTile ta = wgrad_tile(w->a), tb = wgrad_tile(w->b);
   const int key = (ta.A * 10 + ta.B) * 100 + tb.A * 10 + tb.B;
   // the item-shape pairs a VGGBlock produces (conv1 | conv2): 1x1 | 1x1, 2x1 | 2x1, and the mixed forms of the diagnostic rules;
-  // anything else (different tiling modes, other shape pairs): two launches
-  const bool fused = (pa.SH != 0) == (pb.SH != 0) && (key == 1111 || key == 1211 || key == 2121 || key == 2111 || key == 1121);
+  // anything else (different tiling modes, other shape pairs): two launches. With operand transforms: (none | DT) for conv1's
+  // problem with (XT | XT + DT) for conv2's - the forms a VGGBlock's backward asks for - are one launch, the rest two.
+  const int tfa = wgrad_tf(w->a), tfb = wgrad_tf(w->b);
+  const bool tf_pair = (tfa | tfb) != 0;
+  const bool fused = (pa.SH != 0) == (pb.SH != 0) &&
+                     (tf_pair ? (key == 1111 && (tfa & 1) == 0 && (tfb & 1) != 0) : (key == 1111 || key == 1211 || key == 2121 || key == 2111 || key == 1121));
   if (!fused) {
     int rc = launch_wgrad<T>(w->a, st);
     if (rc) return rc;
@@ -1683,6 +1843,21 @@ template <typename T> static int launch_wgrad_pair(const WgPairArgs* w, hipStrea
     return rc;
   }
   ProfScope ps(pa.Cout == 32 ? PC_WGRAD_1x4 : PC_WGRAD_2x2, fa + fb, ba + bb, st);
+  if (tf_pair) {
+    const int sel = (tfa >> 1) * 2 + (tfb >> 1);      // DA, DB
+    if (pa.SH) {
+      if (sel == 0) launch_wgrad_two<T, true, 1, 1, 1, 1, false, true, false>(ga, gb, pa, pb, st);
+      else if (sel == 1) launch_wgrad_two<T, true, 1, 1, 1, 1, false, true, true>(ga, gb, pa, pb, st);
+      else if (sel == 2) launch_wgrad_two<T, true, 1, 1, 1, 1, true, true, false>(ga, gb, pa, pb, st);
+      else launch_wgrad_two<T, true, 1, 1, 1, 1, true, true, true>(ga, gb, pa, pb, st);
+    } else {
+      if (sel == 0) launch_wgrad_two<T, false, 1, 1, 1, 1, false, true, false>(ga, gb, pa, pb, st);
+      else if (sel == 1) launch_wgrad_two<T, false, 1, 1, 1, 1, false, true, true>(ga, gb, pa, pb, st);
+      else if (sel == 2) launch_wgrad_two<T, false, 1, 1, 1, 1, true, true, false>(ga, gb, pa, pb, st);
+      else launch_wgrad_two<T, false, 1, 1, 1, 1, true, true, true>(ga, gb, pa, pb, st);
+    }
+    return nunet_check_launch("wgrad3x3 (pair, transformed operands)");
+  }
   if (pa.SH) {
     if (key == 1111) launch_wgrad_two<T, true, 1, 1, 1, 1>(ga, gb, pa, pb, st);
     else if (key == 1211) launch_wgrad_two<T, true, 1, 2, 1, 1>(ga, gb, pa, pb, st);
@@ -1716,6 +1891,19 @@ static int wgrad_check(const nunet_wgrad_desc* d, bool ptrs = true) {
   NUNET_REQUIRE(d->slab_stride == 0 || d->slab_stride >= 9LL * d->Cout * (d->C0 + d->C1), "wgrad: slab_stride smaller than one slab");
   NUNET_REQUIRE(d->max_slabs >= 0 && d->target_wgs >= 0, "wgrad: max_slabs / target_wgs");
   NUNET_REQUIRE(d->item_shape == 0 || d->item_shape == 11 || d->item_shape == 12 || d->item_shape == 21, "wgrad: item_shape %d (0 | 11 | 12 | 21)", d->item_shape);
+  NUNET_REQUIRE((d->x_tf == NUNET_TF_NONE || d->x_tf == NUNET_TF_BN_RELU) && (d->d_tf == NUNET_TF_NONE || d->d_tf == NUNET_TF_BN_RELU_BWD),
+                "wgrad: x_tf %d (0 | NUNET_TF_BN_RELU) / d_tf %d (0 | NUNET_TF_BN_RELU_BWD)", d->x_tf, d->d_tf);
+  if (d->x_tf || d->d_tf) {
+    NUNET_REQUIRE(d->item_shape == 0 || d->item_shape == 11, "wgrad: operand transforms need the 32 x 32 item shape, not item_shape %d", d->item_shape);
+    NUNET_REQUIRE(!d->x_tf || d->C1 == 0, "wgrad: x_tf needs a single source (C1 == 0)");
+    NUNET_REQUIRE(!ptrs || !d->x_tf || (d->x_mean_invstd && d->x_gamma && d->x_beta), "wgrad: x_tf needs x_mean_invstd, x_gamma, x_beta");
+    if (d->d_tf) {
+      NUNET_REQUIRE(!ptrs || (d->d_y && d->d_sums && d->d_mean_invstd && d->d_gamma && d->d_beta), "wgrad: d_tf needs d_y, d_sums, d_mean_invstd, d_gamma, d_beta");
+      NUNET_REQUIRE(d->d_py % epv == 0 && d->d_py >= d->Cout, "wgrad: d_py=%d (pitch of d_y: aligned, >= Cout)", d->d_py);
+      const unsigned long long px = (unsigned long long)d->N * d->H * d->W;
+      NUNET_REQUIRE(px * d->d_py * dtype_size(d->dtype) < (1ull << 32), "wgrad: d_y must span < 4 GB");
+    }
+  }
   if (ptrs) {
     // every slab the launch will write must fit what the caller says `dw` holds
     const long long stride = d->slab_stride > 0 ? d->slab_stride : 9LL * d->Cout * (d->C0 + d->C1);

@@ -363,7 +363,7 @@ struct Node {
   int out_slot;    // slot of X_i receiving the block output
   int up_slot;     // slot of X_{i+1} that is upsampled into the concat, -1: none
   ConvL c1, c2;
-  size_t y1, a1, y2, up, pin;  // arena byte offsets
+  size_t y1, y2, up, pin;      // arena byte offsets (a1 = relu(bn1(y1)) is never stored: its two readers form it in their loaders)
   size_t dy[2], da1, gup, gpin;   // ... backward scratch (dY of conv2 / conv1) of the BLOCK, so blocks of one level can run on different lanes
   size_t sk; long long sk_floats; // ... fp32 K-split slabs of the BLOCK (blocks of the grid-starved levels; 0 floats: none)
   // backward pass, decided at creation (plan_backward_facts): destinations that an earlier op of the pass wrote first are accumulated into
@@ -384,6 +384,7 @@ struct PlanRt {  // runtime objects owned by the plan (host side only)
   size_t events_used[2];
   int multistream;
   int schedule;                            // NUNET_SCHEDULE_LANES: an op runs on its block's lane; NUNET_SCHEDULE_LIST: Sched::run_list picks
+  int wgrad_dy;                            // nunet_plan_set_wgrad_dy: the weight gradients form dy1 / dy2 in their loaders (no side stores)
   bool lanes_external;
   std::vector<hipStream_t> cap_streams;   // never-reused streams for capture-time lane continuation
   size_t cap_next;
@@ -597,7 +598,7 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
     Node& n = P->exec[k];
     const int f = NBF[n.i];
     const size_t plane = (size_t)P->px[n.i] * f * P->es;
-    n.y1 = bump(cur, plane); n.a1 = bump(cur, plane); n.y2 = bump(cur, plane);
+    n.y1 = bump(cur, plane); n.y2 = bump(cur, plane);
     if (n.up_slot >= 0) n.up = bump(cur, (size_t)P->px[n.i] * NBF[n.i + 1] * P->es);
     if (n.in_prefix == 0 && n.i > 0) n.pin = bump(cur, (size_t)P->px[n.i] * NBF[n.i - 1] * P->es);
   }
@@ -651,6 +652,7 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
   rt->events_used[0] = rt->events_used[1] = 0;
   { const char* e = getenv("NUNET_MULTISTREAM"); rt->multistream = e ? atoi(e) : 1; }
   rt->schedule = NUNET_SCHEDULE_LANES;
+  { const char* e = getenv("NUNET_WGRAD_DY"); rt->wgrad_dy = e ? (atoi(e) != 0) : 0; }
   for (int l = 0; l < NLANES; ++l) {
     rt->lanes[l] = nullptr;
     if (hipStreamCreateWithFlags(&rt->lanes[l], hipStreamNonBlocking) != hipSuccess) { rt->lanes_ok = false; (void)hipGetLastError(); }
@@ -696,13 +698,6 @@ static int64_t slot_offset(const nunet_plan* p, const size_t* level, int32_t i, 
 }
 extern "C" int64_t nunet_plan_feature(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels) { return slot_offset(p, p ? p->X : nullptr, i, j, pitch, channels); }
 extern "C" int64_t nunet_plan_feature_grad(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels) { return slot_offset(p, p ? p->GX : nullptr, i, j, pitch, channels); }
-extern "C" int64_t nunet_plan_block_act1(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels) {
-  const int k = block_at(p, i, j);
-  if (k < 0) return -1;
-  if (pitch) *pitch = NBF[i];
-  if (channels) *channels = NBF[i];
-  return (int64_t)p->exec[k].a1;
-}
 extern "C" int32_t nunet_plan_census_count(const nunet_plan* p, int32_t pass) {
   return (p && p->rt && (pass == 0 || pass == 1)) ? (int32_t)p->rt->census[pass].size() : 0;
 }
@@ -744,7 +739,7 @@ enum {
   R_LVL = 330,                                   // B x L_STRIDE: the backward scratch of a block (L_*)
   R_SK = 470, R_PRM = 485                        // B each: split-K workspace; parameters stepped inside the pass
 };
-enum { B_Y1 = 0, B_A1, B_Y2, B_UP, B_PIN, B_ST1, B_ST2, B_STRIDE = 8 };
+enum { B_Y1 = 0, B_Y2, B_UP, B_PIN, B_ST1, B_ST2, B_STRIDE = 8 };
 enum { L_DY0 = 0, L_DY1, L_DA1, L_GUP, L_GPIN, L_STRIDE = 8 };
 static_assert(B_ST2 < B_STRIDE && L_GPIN < L_STRIDE && R_X + 5 * 5 <= R_GX && R_GX + 5 * 5 <= R_BLK && R_BLK + NUNET_MAX_BLOCKS * B_STRIDE <= R_IMG &&
               R_IMG < R_LOGITS && R_LOGITS < R_DLOGITS && R_DLOGITS < R_WP && R_WP + 5 <= R_GSW && R_GSW + 2 * NUNET_MAX_BLOCKS <= R_GSV &&
@@ -852,13 +847,14 @@ struct Sched {
     memcpy(e.label, cur_name, sizeof(e.label)); e.label[sizeof(e.label) - 1] = 0;
     e.kind = NUNET_CENSUS_CONV; e.N = d.N; e.H = d.H; e.W = d.W;
     e.C0 = d.C0; e.C1 = d.C1; e.D0 = d.D0; e.D1 = d.D1; e.in_tf = d.in_tf; e.has_bn_y = d.bn_y != nullptr; e.acc0_mask = d.acc0_mask;
-    e.splitk_ws_floats = d.splitk_ws ? d.splitk_ws_floats : 0;
+    e.splitk_ws_floats = d.splitk_ws ? d.splitk_ws_floats : 0; e.has_tf_store = d.tf_store != nullptr;
     if (nunet_conv3x3_launch_info(&d, &e.conv) == NUNET_OK) rt->census[pass & 1].push_back(e);
   }
   void census_wgrad(const nunet_wgrad_desc& a, const nunet_wgrad_desc& b) {
     nunet_plan_census_entry e; memset(&e, 0, sizeof(e));
     memcpy(e.label, cur_name, sizeof(e.label)); e.label[sizeof(e.label) - 1] = 0;
     e.kind = NUNET_CENSUS_WGRAD_PAIR; e.N = a.N; e.H = a.H; e.W = a.W;
+    e.wgrad_tf[0] = (a.x_tf ? 1 : 0) | (a.d_tf ? 2 : 0); e.wgrad_tf[1] = (b.x_tf ? 1 : 0) | (b.d_tf ? 2 : 0);
     if (nunet_conv3x3_wgrad_launch_info(&a, &e.wgrad[0]) == NUNET_OK && nunet_conv3x3_wgrad_launch_info(&b, &e.wgrad[1]) == NUNET_OK)
       rt->census[pass & 1].push_back(e);
   }
@@ -1217,6 +1213,10 @@ static void set_tf_bn_bwd(nunet_conv_desc& d, const BnView& v) {     // the appl
   d.tf_gamma = v.gamma; d.tf_beta = v.beta; d.tf_mean_invstd = v.mean_invstd;
   d.tf_dbias = v.gv; d.tf_dgamma = v.gv + v.C; d.tf_dbeta = v.gv + 2 * v.C;
 }
+static void set_wgrad_bn_bwd(nunet_wgrad_desc& w, const BnView& v) { // ... or on a weight gradient's way into LDS (w.dy = dA beforehand)
+  w.d_tf = NUNET_TF_BN_RELU_BWD; w.d_y = v.y; w.d_py = v.C; w.d_sums = v.fx;
+  w.d_mean_invstd = v.mean_invstd; w.d_gamma = v.gamma; w.d_beta = v.beta;
+}
 static int set_splitk(nunet_conv_desc& d, const nunet_plan* P, void* arena, int k) {   // block k's split-K workspace; returns its id (-1: none)
   const Node& n = P->exec[k];
   if (n.sk_floats > 0) { d.splitk_ws = (float*)AB(arena, n.sk); d.splitk_ws_floats = n.sk_floats; }
@@ -1281,8 +1281,8 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
       S.name("B%d%d.conv1", n.i, n.j);
       S.add_conv(lane, {in.r[0], in.r[1], in.r[2], in.r[3], in.r[4], R_WP + i}, {bn1.r_y, bn1.r_fx, rsk}, d, alg_cin);
     }
-    // ---- conv2: BatchNorm1 + ReLU applied to y1 on the way into LDS (archs1.py:23-28); the activation a1 is
-    // stored on the side for the weight gradient when a backward pass may follow -----------------------------------
+    // ---- conv2: BatchNorm1 + ReLU applied to y1 on the way into LDS (archs1.py:23-28). The activation a1 is not stored:
+    // its other reader, the weight gradient of conv2, forms it from y1 in its own loader (nunet_wgrad_desc.x_tf) --------
     {
       const ConvL& L = n.c2; const ConvL& L1 = n.c1;
       nunet_conv_desc d; memset(&d, 0, sizeof(d));
@@ -1293,13 +1293,12 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
       d.tf_gamma = bn1.gamma; d.tf_beta = bn1.beta; d.tf_conv_bias = params + L1.b_off;
       d.tf_running_mean = bnbuf + L1.rm_off; d.tf_running_var = bnbuf + L1.rv_off; d.tf_nbt = nbt ? nbt + L1.bn_index : nullptr;
       d.tf_mean_invstd = bn1.mean_invstd; d.tf_momentum = 0.1f; d.tf_eps = 1e-5f;
-      d.tf_store = training ? AB(arena, n.a1) : nullptr; d.tf_ps = f;
       d.wpack = wpack + (size_t)L.wf * es;
       d.dst0 = bn2.y; d.D0 = f; d.Q0 = f;
       d.stats = training ? bn2.fx : nullptr;
       const int rsk = set_splitk(d, P, arena, k);
       S.name("B%d%d.conv2", n.i, n.j);
-      S.add_conv(lane, {bn1.r_y, bn1.r_fx, R_WP + i}, {bn2.r_y, bn2.r_fx, rb + B_A1, rsk}, d);
+      S.add_conv(lane, {bn1.r_y, bn1.r_fx, R_WP + i}, {bn2.r_y, bn2.r_fx, rsk}, d);
     }
     // ---- BatchNorm2 + ReLU (+ 2x2 max-pool for the encoder column): the block output has many consumers
     // (convs of the same level, the upsample, the pool, a head) and is materialised once in its level-buffer slot ------
@@ -1719,6 +1718,9 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
     const BnView bn1 = bn_view(P, arena, params, k, 0, 1), bn2 = bn_view(P, arena, params, k, 1, 1);
     const Buf dy2 = {AB(arena, n.dy[0]), rl + L_DY0}, dy1 = {AB(arena, n.dy[1]), rl + L_DY1}, da1 = {AB(arena, n.da1), rl + L_DA1};
     const bool has_dgrad1 = !(i == 0 && n.in_prefix == 0);           // no gradient into the image
+    // who forms dy2 / dy1 (read by the weight gradients only): the input-gradient conv's loader as a side store, or the weight
+    // gradient's own loader from (dA, y). The first block has no dgrad1: its dy1 is always formed in the weight gradient.
+    const bool dy2_in_wgrad = rt->wgrad_dy != 0, dy1_in_wgrad = rt->wgrad_dy != 0 || !has_dgrad1;
 
     // ---- BatchNorm2 + ReLU backward, REDUCE pass: sum dz, sum dz * xhat over the block-output gradient (which several
     // consumers accumulated into its level-buffer slot) -> fixed-point sums; not when a head backward took it
@@ -1731,37 +1733,38 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
     }
 
     // ---- dgrad of conv2: the APPLY pass of BatchNorm2's backward happens on the way into LDS (dy2 is stored on the
-    // side for the weight gradient); the epilogue takes BatchNorm1's reduce pass on the da1 it stores (archs1.py:23-30)
+    // side for the weight gradient unless that forms it itself); the epilogue takes BatchNorm1's reduce pass on the da1 it
+    // stores (archs1.py:23-30)
     {
       nunet_conv_desc d; memset(&d, 0, sizeof(d));
       d.dtype = dt; d.N = c.N; d.H = H; d.W = W;
       d.src0 = gxo.p; d.C0 = f; d.P0 = P->PX[i];
       set_tf_bn_bwd(d, bn2);
-      d.tf_store = dy2.p; d.tf_ps = f;
+      d.tf_store = dy2_in_wgrad ? nullptr : dy2.p; d.tf_ps = f;
       d.wpack = wpack + (size_t)L2.wd * es;
       d.dst0 = da1.p; d.D0 = f; d.Q0 = f;
       d.bn_y = bn1.y; d.bn_py = f; d.bn_mean_invstd = bn1.mean_invstd;
       d.bn_gamma = bn1.gamma; d.bn_beta = bn1.beta; d.bn_sums = bn1.fx;
       const int rsk = set_splitk(d, P, arena, k);
       S.name("B%d%d.dgrad2", n.i, n.j);
-      S.add_conv(lane, {gxo.r, bn2.r_y, bn1.r_y, R_WP + i}, {dy2.r, da1.r, bn2.r_fx, bn1.r_fx, rsk}, d);
+      S.add_conv(lane, {gxo.r, bn2.r_y, bn1.r_y, R_WP + i}, {dy2_in_wgrad ? -1 : dy2.r, da1.r, bn2.r_fx, bn1.r_fx, rsk}, d);
     }
-    // ---- dgrad of conv1 with BatchNorm1's apply pass on the way in; the first block has no input gradient and
-    // runs the stand-alone apply pass for its weight gradient instead
+    // ---- dgrad of conv1 with BatchNorm1's apply pass on the way in; the first block has no input gradient: the apply pass
+    // (and the three small gradient vectors of BatchNorm1) are taken by its weight gradient's loader
     if (has_dgrad1) {
       const Cat g = block_in(P, arena, k, true);
       nunet_conv_desc d; memset(&d, 0, sizeof(d));
       d.dtype = dt; d.N = c.N; d.H = H; d.W = W;
       d.src0 = da1.p; d.C0 = f; d.P0 = f;
       set_tf_bn_bwd(d, bn1);
-      d.tf_store = dy1.p; d.tf_ps = f;
+      d.tf_store = dy1_in_wgrad ? nullptr : dy1.p; d.tf_ps = f;
       d.wpack = wpack + (size_t)L1.wd * es;
       d.dst0 = g.p[0]; d.D0 = g.c[0]; d.Q0 = g.pitch[0];
       d.dst1 = g.p[1]; d.D1 = g.c[1]; d.Q1 = g.pitch[1];
       if (n.in_prefix > 0) { d.acc_slot_w = f; d.acc0_mask = n.acc0_mask; }
       const int rsk = set_splitk(d, P, arena, k);
       S.name("B%d%d.dgrad1", n.i, n.j);
-      S.add_conv(lane, {da1.r, bn1.r_y, bn1.r_fx, R_WP + i}, {dy1.r, g.r[0], g.r[1], g.r[2], g.r[3], g.r[4], rsk}, d);
+      S.add_conv(lane, {da1.r, bn1.r_y, bn1.r_fx, R_WP + i}, {dy1_in_wgrad ? -1 : dy1.r, g.r[0], g.r[1], g.r[2], g.r[3], g.r[4], rsk}, d);
       if (n.in_prefix == 0) {
         // through MaxPool2d(2,2) into x_{i-1,0}
         const Buf x = slot_of(P, arena, false, i - 1, 0), gx = slot_of(P, arena, true, i - 1, 0);
@@ -1777,14 +1780,6 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
           return nunet_upsample2x_bwd(dt, c.N, P->hl[i + 1], P->wl[i + 1], NBF[i + 1], g.p[1], NBF[i + 1], gx.p, P->PX[i + 1], n.acc_up, ls);
         });
       }
-    } else {
-      nunet_bn_bwd_desc b1; memset(&b1, 0, sizeof(b1));
-      b1.dtype = dt; b1.N = c.N; b1.H = H; b1.W = W; b1.C = f;
-      b1.da = da1.p; b1.PDA = f; set_bn(b1, bn1);
-      b1.dbias = bn1.gv; b1.dgamma = bn1.gv + bn1.C; b1.dbeta = bn1.gv + 2 * bn1.C;
-      b1.dy = dy1.p; b1.PDY = f;
-      S.name("B%d%d.bnA1", n.i, n.j);
-      S.add(lane, 0, 9.f, {da1.r, bn1.r_y, bn1.r_fx}, {dy1.r}, [=](hipStream_t ls) { return nunet_bn_relu_bwd_apply(&b1, ls); });
     }
     // ---- both weight gradients of the block in one launch (leaves of the dependency graph: only the slab reduce
     // reads them); conv1's problem first: it may carry the first layer's algorithmic Cin for the profiler
@@ -1792,9 +1787,16 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
       const Cat in = block_in(P, arena, k, false);
       nunet_wgrad_desc w1, w2; memset(&w1, 0, sizeof(w1)); memset(&w2, 0, sizeof(w2));
       w1.dtype = w2.dtype = dt; w1.N = w2.N = c.N; w1.H = w2.H = H; w1.W = w2.W = W;
-      w2.src0 = AB(arena, n.a1); w2.C0 = f; w2.P0 = f;
+      // conv2's input a1 = relu(bn1(y1)), formed in the loader from the raw y1 and the statistics the forward saved
+      w2.src0 = bn1.y; w2.C0 = f; w2.P0 = f;
+      w2.x_tf = NUNET_TF_BN_RELU; w2.x_mean_invstd = bn1.mean_invstd; w2.x_gamma = bn1.gamma; w2.x_beta = bn1.beta;
       set_src(w1, in);
       w1.dy = dy1.p; w2.dy = dy2.p; w1.Cout = w2.Cout = f; w1.PY = w2.PY = f;
+      if (dy2_in_wgrad) { w2.dy = gxo.p; w2.PY = P->PX[i]; set_wgrad_bn_bwd(w2, bn2); }      // (dgrad2's loader keeps the small gradient vectors)
+      if (dy1_in_wgrad) {
+        w1.dy = da1.p; w1.PY = f; set_wgrad_bn_bwd(w1, bn1);
+        if (!has_dgrad1) { w1.d_dbias = bn1.gv; w1.d_dgamma = bn1.gv + bn1.C; w1.d_dbeta = bn1.gv + 2 * bn1.C; }
+      }
       w1.dw = L1.ks > 1 ? slabs + L1.slab : gsr + L1.gs; w1.slab_stride = 9LL * L1.cout * L1.cinpad; w1.max_slabs = L1.ks; w1.target_wgs = L1.wg_target;
       w2.dw = L2.ks > 1 ? slabs + L2.slab : gsr + L2.gs; w2.slab_stride = 9LL * L2.cout * L2.cinpad; w2.max_slabs = L2.ks; w2.target_wgs = L2.wg_target;
       w1.dw_floats = (int64_t)L1.ks * w1.slab_stride; w2.dw_floats = (int64_t)L2.ks * w2.slab_stride;
@@ -1807,7 +1809,12 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
       int wl = wlane, r_gate = -1;     // (measured +1.9 % on the step)
       if (!P->cfg.unet && n.j > 0 && n.i + n.j == 4 && n.i <= 2 && (phases & 3) == 3 && !S.list) { wl = 4; r_gate = R_GX + 3 * 5 + 1; }
       const float wcost = 8.f + (float)(2.0 * 9 * ((double)L1.cinpad + L2.cinpad) * f * (double)c.N * H * W / 3.5e8);
-      S.add(wl, 1, wcost, {rb + B_A1, dy2.r, dy1.r, in.r[0], in.r[1], in.r[2], in.r[3], in.r[4], r_gate}, {R_GSW + 2 * k, R_GSW + 2 * k + 1},
+      // (read set: 6 + 5 + 1 ids at most, the capacity of an op; a side-stored dy stands for its (dA, y, sums) triple)
+      const int rd[12] = {bn1.r_y, dy2_in_wgrad ? gxo.r : dy2.r, dy2_in_wgrad ? bn2.r_y : -1, dy2_in_wgrad ? bn2.r_fx : -1,
+                          dy1_in_wgrad ? da1.r : dy1.r, dy1_in_wgrad ? bn1.r_fx : -1, in.r[0], in.r[1], in.r[2], in.r[3], in.r[4], r_gate};
+      // (the first block's conv1 problem writes BatchNorm1's small gradient vectors, which the sums' id covers)
+      const int wr[3] = {R_GSW + 2 * k, R_GSW + 2 * k + 1, has_dgrad1 ? -1 : bn1.r_fx};
+      S.add_v(wl, 1, wcost, rd, 12, wr, 3,
             [=](hipStream_t ls) {
               g_prof_alg_cin = alg_cin; int r = nunet_conv3x3_wgrad_pair(&w1, &w2, ls); g_prof_alg_cin = 0;
               // the block's K-split slabs are summed right behind it on the same lane: 15 small launches hidden beside the
@@ -1978,6 +1985,33 @@ extern "C" int nunet_plan_set_schedule(nunet_plan* P, int32_t schedule) {
                 "plan_set_schedule: schedule %d is neither NUNET_SCHEDULE_LANES (0) nor NUNET_SCHEDULE_LIST (2)", schedule);
   rt_of(P)->schedule = schedule;
   return NUNET_OK;
+}
+
+extern "C" int nunet_plan_set_wgrad_dy(nunet_plan* P, int32_t in_loader) {
+  NUNET_REQUIRE(P, "plan_set_wgrad_dy: null plan");
+  NUNET_REQUIRE(in_loader == 0 || in_loader == 1, "plan_set_wgrad_dy: %d is neither 0 (side stores) nor 1 (weight-gradient loaders)", in_loader);
+  NUNET_REQUIRE(!rt_of(P)->open_sched, "plan_set_wgrad_dy: a backward pass is open (nunet_plan_backward_phase 1|8): its second phase reads what the first stored");
+  rt_of(P)->wgrad_dy = in_loader;
+  return NUNET_OK;
+}
+
+// a1 = relu(bn1(y1)) of block (i, j) on demand (nunet_diag.h): the stand-alone BatchNorm kernel on the raw conv output, with the
+// batch sums of the last training forward; the saved mean | invstd it rewrites are the values the forward left there
+extern "C" int nunet_plan_block_act1(nunet_plan* P, const float* params, void* arena, size_t arena_bytes, int32_t i, int32_t j, void* out, nunet_stream_t s) {
+  NUNET_REQUIRE(P && params && arena && out, "plan_block_act1: null pointer");
+  ARENA_CHECK("plan_block_act1");
+  const int k = block_at(P, i, j);
+  NUNET_REQUIRE(k >= 0, "plan_block_act1: the plan has no block (%d, %d)", (int)i, (int)j);
+  const nunet_plan_cfg& c = P->cfg;
+  const Node& n = P->exec[k];
+  const BnView bn1 = bn_view(P, arena, params, k, 0, 0);
+  nunet_bn_fwd_desc b; memset(&b, 0, sizeof(b));
+  b.dtype = c.dtype; b.N = c.N; b.H = P->hl[i]; b.W = P->wl[i]; b.C = NBF[i];
+  b.y = bn1.y; b.PY = NBF[i]; b.conv_bias = params + n.c1.b_off; b.stats = bn1.fx;
+  b.gamma = bn1.gamma; b.beta = bn1.beta;
+  b.save_mean_invstd = bn1.mean_invstd; b.training = 1; b.momentum = 0.1f; b.eps = 1e-5f;
+  b.a = out; b.PA = NBF[i];
+  return nunet_bn_relu_fwd(&b, s);
 }
 
 extern "C" int nunet_plan_set_multistream(nunet_plan* P, int32_t enable) {

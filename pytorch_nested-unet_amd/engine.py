@@ -29,6 +29,7 @@ class Plan:
         self.arena_bytes = lib.nunet_plan_arena_bytes(self.handle)
         self.arena = torch.empty(self.arena_bytes, dtype=torch.uint8, device=device)
         self.trained_forward = False
+        self.params = None          # the owner's flat fp32 parameter arena (Engine.plan sets it; block_act1 reads gamma / beta)
 
     def __del__(self):
         try:
@@ -47,8 +48,23 @@ class Plan:
         return self._slot(L.lib().nunet_plan_feature_grad, i, j)
 
     def block_act1(self, i, j):
-        """relu(bn1(conv1(.))) of block (i, j) as the training forward stored it, [N,H_i,W_i,C] NHWC (tests/debug)."""
-        return self._slot(L.lib().nunet_plan_block_act1, i, j)
+        """relu(bn1(conv1(.))) of block (i, j), [N,H_i,W_i,C] NHWC in a tensor of its own (tests/debug). No pass stores it:
+        it is materialised here from the raw conv output the last training forward left in the arena, with that forward's batch
+        statistics and the current gamma / beta."""
+        if self.params is None or not self.trained_forward:
+            raise L.NunetError("block_act1 needs a training-mode forward of this plan through its Engine first")
+        pitch, ch = C.c_int32(), C.c_int32()
+        if L.lib().nunet_plan_feature(self.handle, i, j, C.byref(pitch), C.byref(ch)) < 0:
+            raise L.NunetError("no block (%d, %d)" % (i, j))
+        out = torch.empty((self.n, self.h >> i, self.w >> i, ch.value), dtype=L.TORCH_DTYPE[self.dtype], device=self.arena.device)
+        L.check(L.lib().nunet_plan_block_act1(self.handle, L.ptr(self.params), L.ptr(self.arena), L.nbytes(self.arena), i, j,
+                                              L.ptr(out), L.stream()), "nunet_plan_block_act1")
+        return out
+
+    def set_wgrad_dy(self, in_loader):
+        """Where the backward pass forms dy1 / dy2: False = side stores of the input-gradient convs, True = the weight
+        gradients' own loaders (nunet_plan_set_wgrad_dy). Same bits either way."""
+        L.check(L.lib().nunet_plan_set_wgrad_dy(self.handle, 1 if in_loader else 0), "nunet_plan_set_wgrad_dy")
 
     def census(self, backward):
         """The convolutions / weight-gradient pairs of the last forward (False) / backward (True): [PlanCensusEntry] (tests/debug)."""
@@ -126,6 +142,7 @@ class Engine:
             if pl.nparams != self.flat_params.numel() or pl.nbnbuf != self.bnbuf.numel() or pl.nbn != len(self.bns):
                 raise L.NunetError("plan/module parameter layout mismatch: %d vs %d params" %
                                    (pl.nparams, self.flat_params.numel()))
+            pl.params = self.flat_params
             self.plans[key] = pl
         return pl
 
