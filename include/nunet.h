@@ -40,7 +40,7 @@ enum {
   NUNET_ENODEV = -3   /* no gfx950 device / code object */
 };
 
-int nunet_version(void);   /* 103: BCEWithLogitsLoss in the loss step; nunet_seg_metrics and nunet_eval_step were added under the same number (additions only). 102: schedule 1 (single-stream) and recording mode 0 (event segments) of 101 are refused, nunet_graph_info reports nodes, edges, lanes */
+int nunet_version(void);   /* 104: nunet_plan_opt_step lost its `repack` argument and nunet_plan_set_inpass_opt is gone (the step always leaves the repack to the next forward). 103: BCEWithLogitsLoss in the loss step; nunet_seg_metrics and nunet_eval_step were added under the same number (additions only). 102: schedule 1 (single-stream) and recording mode 0 (event segments) of 101 are refused, nunet_graph_info reports nodes, edges, lanes */
 const char* nunet_last_error(void);
 
 /* ------------------------------------------------------------------------ */
@@ -389,7 +389,7 @@ typedef struct {
 /* Adam bookkeeping of one step, a 1-thread kernel: *step_dev += 1 (fp32, torch's capturable step), then adam_scal for that
  * step from the device lr (bias corrections in double, rounded to fp32 once). Kernel arguments are frozen when a step is
  * captured, so t and lr live on the device; issue it on the caller's stream ahead of the step's forward pass, so that every
- * update launch of the step - in-pass ones included - sees the same t. */
+ * update launch of the step sees the same t. */
 int nunet_adam_prepare(const float* lr_dev, double beta1, double beta2, float* step_dev, float* adam_scal, nunet_stream_t s);
 /* Flat Adam step over n fp32 elements (p, g and the state in the same flat order); g is read as g * grad_scale. Refuses a
  * scaler or a clip: those go through nunet_opt_step. */
@@ -509,8 +509,7 @@ int32_t nunet_plan_num_heads(const nunet_plan* p);
  * input:  NCHW fp32. logits: [heads][N][K][H][W] fp32.
  * arena / arena_bytes: the caller's buffer of at least nunet_plan_arena_bytes(p) bytes (NUNET_EINVAL when smaller), 256-byte aligned.
  * training: bit 0 = training mode (batch statistics, running-stat update); bit 1 = the packed weights in `arena`
- * are current (left so by nunet_plan_opt_step with repack = 1, the in-pass step or nunet_plan_repack on these parameters): skip
- * the repack; bit 2 = the image
+ * are current (left so by nunet_plan_repack on these parameters): skip the repack; bit 2 = the image
  * was staged into the arena by nunet_plan_stage_u8 (`input` is ignored and may be NULL). */
 int nunet_plan_forward(nunet_plan* p, const float* params, float* bnbuf, int64_t* nbt,
                        const float* input, void* arena, size_t arena_bytes, float* logits, int32_t training,
@@ -547,20 +546,12 @@ int nunet_plan_grad_scratch(const nunet_plan* p, int64_t* byte_offset, int64_t* 
 int nunet_plan_bucket0_wait(nunet_plan* p, nunet_stream_t s);
 /* Fused optimiser step (any nunet_optim) on the plan's buffers, one launch replacing unpack (nunet_plan_backward_phase bit 2) +
  * nunet_opt_step: gradient scratch (optionally exchanged between ranks) -> the step on the fp32 master parameters (lr from
- * device memory, grad_scale = 1/world). repack = 0: the next nunet_plan_forward repacks as usual; repack = 1: both packed weight
- * layouts are written too, and the next forward may set bit 1 of `training`. `grads` (flat OIHW, may be NULL) receives the
+ * device memory, grad_scale = 1/world); the next nunet_plan_forward repacks as usual. `grads` (flat OIHW, may be NULL) receives the
  * scaled gradients. SGD needs state0 whatever the momentum. With opt->scaler set (loss scaling) the gradients are read as
  * g * grad_scale * inv_scale, and a step with found_inf set writes only `grads` (nunet_scaler). With opt->clip set they are
  * read as that times clip->coef (nunet_clip), and `grads` receive the clipped gradient. */
 int nunet_plan_opt_step(nunet_plan* p, float* params, const nunet_optim* opt, void* arena, size_t arena_bytes, float grad_scale,
-                        float* grads, int32_t repack, nunet_stream_t s);
-/* The optimiser step INSIDE the backward pass: once parameters are set here, every whole backward pass steps each VGGBlock's
- * parameters (the arithmetic of nunet_plan_opt_step with repack = 1) as an op scheduled behind that block's weight gradients,
- * beside the rest of the pass, and the heads at its end. The caller then does not call nunet_plan_opt_step and sets bit 1 of the
- * next forward's training flags (weights current). Single-process training only (a data-parallel step exchanges the gradients
- * before the update). The struct is copied. params = NULL: off, whatever `opt` is (NULL included). No scaler and no clip: a
- * step already half applied inside the pass can neither be skipped nor rescaled. */
-int nunet_plan_set_inpass_opt(nunet_plan* p, float* params, const nunet_optim* opt, float grad_scale, float* grads);
+                        float* grads, nunet_stream_t s);
 /* Square norm of the gradient in the plan's native-layout scratch (after the backward pass and, data parallel, the exchange):
  * one double partial per workgroup in `ws`, for nunet_clip_finalize with nparts = nunet_plan_grad_sqnorm_ws_bytes / 8. Only
  * real parameters count: the [tap][co][ci] entries with ci < cin (not the padding up to cinpad), conv bias / gamma / beta, and

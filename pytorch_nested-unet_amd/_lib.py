@@ -254,8 +254,7 @@ _SIG = {
     "nunet_plan_backward_phase": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _i32, _i32, _vp]),
     "nunet_plan_grad_scratch": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "nunet_plan_bucket0_wait": (_i32, [_vp, _vp]),
-    "nunet_plan_opt_step": (_i32, [_vp, _vp, C.POINTER(Optim), _vp, _sz, _f32, _vp, _i32, _vp]),
-    "nunet_plan_set_inpass_opt": (_i32, [_vp, _vp, C.POINTER(Optim), _f32, _vp]),
+    "nunet_plan_opt_step": (_i32, [_vp, _vp, C.POINTER(Optim), _vp, _sz, _f32, _vp, _vp]),
     "nunet_plan_grad_sqnorm_ws_bytes": (C.c_size_t, [_vp]),
     "nunet_plan_grad_sqnorm": (_i32, [_vp, _vp, _sz, _vp, _sz, _vp]),
     "nunet_plan_repack": (_i32, [_vp, _vp, _vp, _sz, _vp]),

@@ -37,7 +37,7 @@ int nunet_check_launch(const char* what) {
   return NUNET_OK;
 }
 extern "C" const char* nunet_last_error(void) { return g_err; }
-extern "C" int nunet_version(void) { return 103; }
+extern "C" int nunet_version(void) { return 104; }
 
 static inline int grid_for(int64_t items, int block, int cap = 256 * 16) {
   int64_t g = ceil_div64(items, block);

@@ -37,7 +37,7 @@ struct UnpackTab { int n; int accumulate; UnpackEnt e[MAXENT]; };
 // prefix sum of tiles per entry for the block -> tile map. A tile lives in LDS as s[co_local][ci_local * 9 + tap]:
 // its OIHW rows (parameters, flat gradients) are contiguous runs of 32 * 9 floats, the native gradient scratch
 // [tap][co][cinpad] and both packed layouts are contiguous along ci (wf) or co (wd). The unpack kernels' blocks past
-// the last tile own one UnpackTab entry each (tail_entry); update_kernel numbers its head blocks there instead.
+// the last tile own one UnpackTab entry each (tail_entry).
 // ---------------------------------------------------------------------------------------------------------
 constexpr int TILE_LD = 32 * 9 + 1;
 struct Tile { int e, co0, ci0, cw, rw; };   // table entry, tile origin; cw / rw: real input channels / output rows in the tile (cw <= 0: pure padding)
@@ -53,13 +53,14 @@ __device__ __forceinline__ Tile tile_of(const PackTab& tab, int bid) {
   return t;
 }
 
-// 1x1 head: [nslab][tot] partial slabs (already OIHW order, tot <= 8 classes * 33 = 264), summed by one block of B threads in a
+// 1x1 head: [nslab][tot] partial slabs (already OIHW order, tot <= 8 classes * 33 = 264), summed by one block of B = 256 threads in a
 // fixed order: B / ne threads share an element's slabs (a single thread walking all 256 slabs is a chain of 256
 // dependent-latency loads: that loop alone made the earlier fused kernels 100 us long), thread (part, e) adds slabs part,
 // part + parts, ... in order, the parts meet in LDS (B floats) and are added in order q = 0 .. parts - 1. The owning thread
-// calls f(element, sum). The order depends on B: 256 and 512 give different bits.
-template <int B, typename F>
+// calls f(element, sum). The order depends on B, so every caller is a 256-thread block.
+template <typename F>
 __device__ __forceinline__ void head_slab_sum(const float* __restrict__ dw, int tot, int nslab, float* lds, F f) {
+  constexpr int B = 256;
   for (int e0 = 0; e0 < tot; e0 += B) {
     const int ne = min(B, tot - e0);
     const int parts = B / ne;                     // threads per element
@@ -87,7 +88,7 @@ __device__ __forceinline__ void tail_entry(const UnpackEnt& en, const float* __r
   const float* dw = scratch + en.src;
   const int nw = en.cout * en.cin * en.taps;
   if (en.nslab > 1) {
-    head_slab_sum<256>(dw, nw + en.nvec * en.cout, en.nslab, lds, f);
+    head_slab_sum(dw, nw + en.nvec * en.cout, en.nslab, lds, f);
     return;
   }
   const float* vsrc = dw + (long long)en.taps * en.cout * en.cinpad;
@@ -233,15 +234,11 @@ __global__ __launch_bounds__(256) void unpack_tiled_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Fused optimiser step: native-layout gradient scratch -> optimiser step on the fp32 master parameters -> both packed
-// 16-bit weight layouts of the NEXT forward/backward, one launch (separate unpack, step and pack launches ran one after
-// the other with nothing to overlap them). The tile's gradients and its OIHW parameters meet in two LDS tiles; the
-// optimiser state is streamed from HBM. The block of input-channel tile 0 also steps the layer's conv bias and BatchNorm
-// gamma / beta; blocks past the last tile own the 1x1 heads (sum of their gradient slabs over 512 threads, then the same
-// step). torch.optim.SGD semantics (reference trains.py:229-231).
+// Fused optimiser step (unpack_sgd_tiled_kernel, below the plan): native-layout gradient scratch -> optimiser step on
+// the fp32 master parameters, one launch; the next forward repacks the 16-bit weight layouts. torch.optim.SGD
+// semantics (reference trains.py:229-231).
 // ---------------------------------------------------------------------------------------------------------
-struct UpdP { float* params; const float* scratch; float* grads; float gscale; int nconv;
-              int bid_off; };   // first block's index in the whole-model block numbering (a launch may cover one VGGBlock's tiles, or the heads)
+struct UpdP { float* params; const float* scratch; float* grads; float gscale; };
 
 // one element of the fused kernels outside the LDS tiles, at flat index idx: the scaled gradient to the flat arena when the
 // caller wants it, then the step unless loss scaling skipped it (live false)
@@ -250,55 +247,6 @@ __device__ __forceinline__ void step_elem(const UpdP& u, const O& o, bool live, 
   g *= gs;
   if (u.grads) u.grads[idx] = g;
   if (live) u.params[idx] = opt_elem(o, u.params[idx], g, idx);
-}
-
-template <typename T, typename O>
-__global__ __launch_bounds__(512) void update_kernel(UpdP u, O o, T* __restrict__ arena, PackTab tab, UnpackTab ut) {
-  __shared__ float s_t[32][TILE_LD];
-  __shared__ float s_g[32][TILE_LD];
-  float gs = u.gscale;
-  const bool live = o.begin(gs);   // false: a step skipped by loss scaling, which stores the unscaled gradients only
-  if (!live && !u.grads) return;
-  const int bid = (int)blockIdx.x + u.bid_off;
-  if (bid >= tab.ntiles) {
-    const UnpackEnt en = ut.e[u.nconv + bid - tab.ntiles];
-    head_slab_sum<512>(u.scratch + en.src, en.cout * en.cin * en.taps + en.nvec * en.cout, en.nslab, &s_t[0][0],
-                       [&](int i, float g) { step_elem(u, o, live, gs, en.dst + i, g); });
-    return;
-  }
-  const Tile t = tile_of(tab, bid);
-  const PackEnt en = tab.e[t.e];
-  const UnpackEnt ue = ut.e[t.e];
-  const float* dw = u.scratch + ue.src;
-  load_oihw_tile(s_t, u.params + en.src, en, t);
-  gather_scratch_tile(s_g, dw, en, t);
-  __syncthreads();
-#pragma unroll 6
-  for (int i = threadIdx.x; i < 32 * 288; i += blockDim.x) {
-    const int ro = i / 288, k = i - ro * 288;
-    if (ro < t.rw && k < t.cw * 9) {
-      const long long idx = en.src + ((long long)(t.co0 + ro) * en.cin + t.ci0) * 9 + k;
-      const float g = s_g[ro][k] * gs;
-      if (u.grads) u.grads[idx] = g;
-      if (live) {
-        const float pn = opt_elem(o, s_t[ro][k], g, idx);
-        u.params[idx] = pn;
-        s_t[ro][k] = pn;
-      }
-    }
-  }
-  if (t.ci0 == 0) {
-    // conv bias, BN gamma, BN beta of the output channels of this tile (they follow the weights in both arenas)
-    const long long nw = (long long)en.cout * en.cin * 9;
-    for (int i = threadIdx.x; i < ue.nvec * t.rw; i += blockDim.x) {
-      const int v = i / t.rw, c = t.co0 + (i - v * t.rw);
-      const long long idx = ue.dst + nw + (long long)v * en.cout + c;
-      step_elem(u, o, live, gs, idx, dw[9LL * en.cout * en.cinpad + (long long)v * en.cout + c]);
-    }
-  }
-  __syncthreads();
-  if (!live) return;               // (uniform) the packed weights keep matching the unchanged parameters
-  store_packed_tile(s_t, arena, en, t);
 }
 
 // block -> tile prefix table of a PackTab: entry i owns blocks [tile0[i], tile0[i + 1]) of the tile kernels, one per 32 x 32
@@ -391,8 +339,6 @@ struct PlanRt {  // runtime objects owned by the plan (host side only)
   // NUNET_STAMPS=1 diagnostic: a 1-thread kernel after every scheduled op writes the 100 MHz wall clock,
   // so the real timeline of an (unprofiled) hipGraph replay can be read back (tools/stamp_timeline.py)
   unsigned long long* stamps;              // device, [2][STAMP_CAP]
-  // nunet_plan_set_inpass_opt: the optimiser step of every VGGBlock as an op of the backward pass (params == NULL: off)
-  struct { float* params; float gscale; float* grads; nunet_optim opt; } upd;
   int lane_low_priority;                   // side lanes of the flag-synchronised program at the lowest stream priority (default 1)
   int calibrating;                         // nunet_plan_calibrate: single lane + stamps, to measure every op's isolated cost
   std::map<std::string, float> op_cost[2]; // measured cost (us) by op name, per pass; empty: the built-in estimates
@@ -646,7 +592,6 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
   rt->stamps = nullptr;
   rt->calibrating = 0;
   rt->lane_low_priority = 1;
-  memset(&rt->upd, 0, sizeof(rt->upd));
   rt->open_sched = nullptr;
   rt->seg_lanes[0] = rt->seg_lanes[1] = rt->seg_lanes[2] = nullptr;
   rt->events_used[0] = rt->events_used[1] = 0;
@@ -737,14 +682,14 @@ enum {
   R_GSW = 240, R_GSV = 280,                      // B x 2 each (conv1, conv2): weight gradients; BatchNorm-backward sums + small-vector gradients
   R_GSH = 310,                                   // NUNET_MAX_HEADS: the gradients of a head
   R_LVL = 330,                                   // B x L_STRIDE: the backward scratch of a block (L_*)
-  R_SK = 470, R_PRM = 485                        // B each: split-K workspace; parameters stepped inside the pass
+  R_SK = 470                                     // B: split-K workspace
 };
 enum { B_Y1 = 0, B_Y2, B_UP, B_PIN, B_ST1, B_ST2, B_STRIDE = 8 };
 enum { L_DY0 = 0, L_DY1, L_DA1, L_GUP, L_GPIN, L_STRIDE = 8 };
 static_assert(B_ST2 < B_STRIDE && L_GPIN < L_STRIDE && R_X + 5 * 5 <= R_GX && R_GX + 5 * 5 <= R_BLK && R_BLK + NUNET_MAX_BLOCKS * B_STRIDE <= R_IMG &&
               R_IMG < R_LOGITS && R_LOGITS < R_DLOGITS && R_DLOGITS < R_WP && R_WP + 5 <= R_GSW && R_GSW + 2 * NUNET_MAX_BLOCKS <= R_GSV &&
               R_GSV + 2 * NUNET_MAX_BLOCKS <= R_GSH && R_GSH + NUNET_MAX_HEADS <= R_LVL && R_LVL + NUNET_MAX_BLOCKS * L_STRIDE <= R_SK &&
-              R_SK + NUNET_MAX_BLOCKS <= R_PRM && R_PRM + NUNET_MAX_BLOCKS <= NRES, "resource-id ranges overlap at this capacity");
+              R_SK + NUNET_MAX_BLOCKS <= NRES, "resource-id ranges overlap at this capacity");
 
 struct Sched {
   hipStream_t main_s;
@@ -1244,7 +1189,7 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
   if (!staged) CK(nunet_nchw_to_nhwc(input, c.N, c.input_channels, c.H, c.W, dt, AB(arena, P->off_img), 32, (nunet_stream_t)st));
 
   Sched S; S.init(P, st, 0);
-  const bool skip_pack = (training_flags & 2) != 0;   // the caller vouches that nunet_plan_opt_step(repack 1) / _repack left the packed weights current
+  const bool skip_pack = (training_flags & 2) != 0;   // the caller vouches that nunet_plan_repack left the packed weights current
   if (!skip_pack) {
     S.name("pack");
     S.add(0, 0, 15.f, {}, {R_WP + 0, R_WP + 1, R_WP + 2, R_WP + 3, R_WP + 4}, [=](hipStream_t ls) {
@@ -1411,43 +1356,6 @@ extern "C" int nunet_plan_grad_scratch(const nunet_plan* P, int64_t* byte_offset
   return NUNET_OK;
 }
 
-// blocks [bid0, bid0 + nblocks) of update_kernel's whole-model numbering: all of it (nunet_plan_opt_step, repack 1), one VGGBlock's
-// tiles or the heads (the in-pass step)
-template <typename T, typename O> static int launch_update_kernel(nunet_plan* P, void* arena, float* params, const O& o, float grad_scale, float* grads,
-                                                      int bid0, int nblocks, double bytes, hipStream_t st) {
-  if (nblocks <= 0) return NUNET_OK;
-  UpdP u;
-  u.params = params; u.scratch = (const float*)AB(arena, P->off_gs); u.grads = grads;
-  u.gscale = grad_scale; u.nconv = P->ptab.n; u.bid_off = bid0;
-  ProfScope ps(PC_SGD, 0, bytes, st);
-  NUNET_LAUNCH((update_kernel<T, O>), dim3(nblocks), dim3(512), 0, st, u, o, (T*)AB(arena, P->off_wpack), P->ptab, P->utab);
-  return nunet_check_launch(bid0 == 0 && nblocks == P->ptab.ntiles + P->utab.n - P->ptab.n ? "plan_opt_step" : "plan_opt_step (in pass)");
-}
-
-// In-pass step of blocks [bid0, bid0 + nblocks) with the optimiser nunet_plan_set_inpass_opt left in the plan
-template <typename U> static int launch_update(nunet_plan* P, void* arena, const U& s, int bid0, int nblocks, hipStream_t st) {
-  return opt_dispatch(&s.opt, [&](const auto& o) { return NUNET_DISPATCH(P->cfg.dtype, launch_update_kernel, P, arena, s.params, o, s.gscale, s.grads, bid0, nblocks, 0.0, st); });
-}
-
-// The optimiser step as part of the backward pass: with parameters set here, every whole pass (nunet_plan_backward, or
-// nunet_plan_backward_phase with bits 0 and 1) steps each VGGBlock's parameters - and repacks its 16-bit weights - as an op of
-// the pass, scheduled behind that block's weight gradients, and the heads at the end. The caller then neither calls
-// nunet_plan_opt_step nor lets the next forward repack (training flag bit 1). Single-process training only: a
-// data-parallel step exchanges the gradients first. params == NULL switches it off (`opt` is then not looked at).
-extern "C" int nunet_plan_set_inpass_opt(nunet_plan* P, float* params, const nunet_optim* opt, float grad_scale, float* grads) {
-  NUNET_REQUIRE(P, "plan_set_inpass_opt: null plan");
-  if (params) {
-    CK(opt_check(opt, "plan_set_inpass_opt", true));
-    NUNET_REQUIRE(!opt->scaler, "plan_set_inpass_opt: a step applied inside the backward pass cannot be skipped by loss scaling");
-    NUNET_REQUIRE(!opt->clip, "plan_set_inpass_opt: a step applied inside the backward pass cannot be rescaled by gradient clipping");
-  }
-  auto& s = rt_of(P)->upd;
-  memset(&s, 0, sizeof(s));
-  if (!params) return NUNET_OK;
-  s.params = params; s.gscale = grad_scale; s.grads = grads; s.opt = *opt;
-  return NUNET_OK;
-}
-
 // Optimiser step straight from the gradient scratch: replaces nunet_plan_backward_phase bit 2 +
 // nunet_opt_step; the weights are repacked by the next nunet_plan_forward as usual.
 // unpack_tiled_kernel with the optimiser step as the epilogue of its store phase: the tile's gradients meet the OIHW
@@ -1513,24 +1421,22 @@ template <typename O> static int launch_unpack_step(nunet_plan* P, void* arena, 
                                                     double bytes, hipStream_t st) {
   UpdP u;
   u.params = params; u.scratch = (const float*)AB(arena, P->off_gs); u.grads = grads;
-  u.gscale = grad_scale; u.nconv = P->ptab.n; u.bid_off = 0;
+  u.gscale = grad_scale;
   ProfScope ps(PC_SGD, 0, bytes, st);
   NUNET_LAUNCH((unpack_sgd_tiled_kernel<O>), dim3(P->ptab.ntiles + P->utab.n), dim3(256), 0, st, u, o, P->ptab, P->utab);
   return nunet_check_launch("plan_opt_step");
 }
 
-// The fused step on the plan's own buffers with any optimiser, gradient scratch -> step -> fp32 master parameters: repack 0 is
-// unpack_sgd_tiled_kernel (the next forward repacks), repack 1 is update_kernel, which also writes both packed weight layouts
-// (the next nunet_plan_forward may then be called with bit 1 of `training` set). `grads` (flat OIHW arena) is optional: when
-// given it receives the (scaled) gradients as nunet_plan_backward would have left them. Adam streams its second state buffer on top.
+// The fused step on the plan's own buffers with any optimiser, gradient scratch -> step -> fp32 master parameters
+// (unpack_sgd_tiled_kernel; the next forward repacks). `grads` (flat OIHW arena) is optional: when given it receives the
+// (scaled) gradients as nunet_plan_backward would have left them. Adam streams its second state buffer on top.
 extern "C" int nunet_plan_opt_step(nunet_plan* P, float* params, const nunet_optim* opt, void* arena, size_t arena_bytes, float grad_scale,
-                                   float* grads, int32_t repack, nunet_stream_t s) {
+                                   float* grads, nunet_stream_t s) {
   NUNET_REQUIRE(P && params && arena, "plan_opt_step: null pointer");
   CK(opt_check(opt, "plan_opt_step", true));
   ARENA_CHECK("plan_opt_step");
   return opt_dispatch(opt, [&](const auto& o) {
-    const double bytes = (double)P->nparams * ((repack ? 24.0 : 20.0) + (grads ? 4.0 : 0.0) + 8.0 * (o.NS - 1));
-    if (repack) return NUNET_DISPATCH(P->cfg.dtype, launch_update_kernel, P, arena, params, o, grad_scale, grads, 0, P->ptab.ntiles + P->utab.n - P->ptab.n, bytes, (hipStream_t)s);
+    const double bytes = (double)P->nparams * (20.0 + (grads ? 4.0 : 0.0) + 8.0 * (o.NS - 1));
     return launch_unpack_step(P, arena, params, o, grad_scale, grads, bytes, (hipStream_t)s);
   });
 }
@@ -1538,7 +1444,7 @@ extern "C" int nunet_plan_opt_step(nunet_plan* P, float* params, const nunet_opt
 // Square norm of the gradient scratch for gradient clipping (include/nunet.h nunet_clip): the unpack kernels'
 // block -> (layer, 32 x 32 tile | vector tail | head) map, read-only. A conv tile sums the squares of its real [tap][co][ci]
 // entries (ci < cin: the padding up to cinpad does not count) straight from the scratch, 16-byte loads along ci; a tail block
-// takes the layer's conv bias, gamma and beta; a head block sums the slabs first (head_slab_sum<256>, so in unpack_sgd_tiled_kernel's order) and
+// takes the layer's conv bias, gamma and beta; a head block sums the slabs first (head_slab_sum, so in unpack_sgd_tiled_kernel's order) and
 // squares the sum. Products exact in double, a thread's elements in index order, then block256_sum_f64: one partial per
 // workgroup, plain store (a pure-padding tile stores 0).
 __global__ __launch_bounds__(256) void plan_sqnorm_kernel(const float* __restrict__ scratch, PackTab tab, UnpackTab ut, double* __restrict__ ws) {
@@ -1587,8 +1493,7 @@ extern "C" int nunet_plan_grad_sqnorm(nunet_plan* P, const void* arena, size_t a
 }
 
 // Repack the 16-bit weight layouts from the fp32 master parameters (what nunet_plan_forward does first unless told
-// that they are current): needed once before a loop that relies on nunet_plan_opt_step(repack 1), and after the parameters were
-// changed by anything else (checkpoint load, a stock optimiser).
+// that they are current): needed before a forward that is told so (bit 1 of its `training` flags).
 extern "C" int nunet_plan_repack(nunet_plan* P, const float* params, void* arena, size_t arena_bytes, nunet_stream_t s) {
   NUNET_REQUIRE(P && params && arena, "plan_repack: null pointer");
   ARENA_CHECK("plan_repack");
@@ -1696,9 +1601,6 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
                                 h.acc, gsr + h.gs, HEAD_SLABS, kt >= 0 ? &bd : nullptr, ls);
     });
   }
-  // in-pass optimiser step: only a WHOLE pass may carry it (a data-parallel caller exchanges the gradients between the phases)
-  const auto upd = rt_of(P)->upd;
-  const bool inpass = upd.params != nullptr && (phases & 3) == 3;
   // NUNET_DEBUG_SPIN_US (tests only): a spin kernel of that many microseconds heads phase 2 on the chain lane, so that
   // "bucket 0 is complete well before the pass ends" can be asserted with a margin (tests/test_dist_gpu.py)
   static int spin_us = -1;
@@ -1822,30 +1724,6 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
               return r ? r : launch_reduce(P, arena, k, k, ls);
             });
     }
-    // ---- in-pass optimiser step (nunet_plan_set_inpass_opt): this block's two convolutions are stepped - scratch -> step ->
-    // both packed 16-bit layouts - as soon as their gradients are complete, beside the rest of the backward pass, instead of in
-    // one launch over all layers after it (43 us) plus the next forward's repack (15 us), with nothing to overlap either
-    if (inpass) {
-      int r0 = -1;
-      for (size_t r = 0; r < P->reg.size(); ++r) if (P->reg[r] == k) r0 = (int)r;
-      if (r0 >= 0) {
-        const PackTab& tab = P->ptab;
-        const int t0 = tab.tile0[2 * r0], t1 = tab.tile0[2 * r0 + 2];
-        const long long np = 9LL * (L1.cout * L1.cinpad + L2.cout * L2.cinpad);
-        S.name("B%d%d.upd", n.i, n.j);
-        S.add(wlane, 1, 4.f + (float)(np * 28.0 / 3.0e6), {R_GSW + 2 * k, R_GSW + 2 * k + 1, bn1.r_fx, bn2.r_fx}, {R_PRM + k}, [=](hipStream_t ls) {
-          return launch_update(P, arena, upd, t0, t1 - t0, ls);
-        });
-      }
-    }
-  }
-  if (inpass && (phases & 1) && !P->heads.empty()) {
-    // the 1x1 heads: blocks past the last tile of the update kernel's numbering
-    int rs[12]; int nr = 0;
-    for (size_t h = 0; h < P->heads.size() && nr < 12; ++h) rs[nr++] = R_GSH + (int)h;
-    const int nh = P->utab.n - P->ptab.n, nt = P->ptab.ntiles;
-    S.name("heads.upd");
-    S.add_v(0, 1, 5.f, rs, nr, nullptr, 0, [=](hipStream_t ls) { return launch_update(P, arena, upd, nt, nh, ls); });
   }
   int rc = S.run();
   if (leave_open && rc == NUNET_OK && !S.failed) {

@@ -40,6 +40,16 @@ def dp_layout_from_env(environ):
     return (1, True) if mode == "auto" else (int(mode), False)
 
 
+def fused_update_from(arg, environ):
+    """The optimiser step layout from TrainStep's fused_update argument, or NUNET_FUSED_UPDATE when that is None: unset -> 2;
+    0 and 2 are accepted, any other value raises. No GPU use."""
+    v = environ.get("NUNET_FUSED_UPDATE", "2") if arg is None else arg
+    if str(v) not in ("0", "2"):
+        raise L.NunetError("TrainStep: fused_update %r: the optimiser step layouts are 0, unpack + the flat step on the flat "
+                           "gradients, and 2, the step fused into the unpack of the gradient scratch" % (v,))
+    return int(v)
+
+
 class TrainStep:
     def __init__(self, model, batch_shape, lr=1e-3, momentum=0.9, weight_decay=1e-4, nesterov=False,
                  use_graph=True, process_group=None, keep_grads=True, fused_update=None, loss="BCEDiceLoss", input_u8=False,
@@ -63,7 +73,7 @@ class TrainStep:
         captured step and keeps the faster (self.executor_choice); data-parallel training keeps (False, 'lanes'), whose graph can
         hold the RCCL exchange. NUNET_SCHEDULE (lanes | list) / NUNET_SEGMENTED (0 | flags) force a form (tools); any other value raises.
         optimizer: 'SGD' (momentum, weight_decay, nesterov; reference trains.py:229-231) or 'Adam' (betas, eps, weight_decay as
-        L2 decay in the gradient, amsgrad off; trains.py:225-227). Either runs inside the step in every fused_update layout;
+        L2 decay in the gradient, amsgrad off; trains.py:225-227). Either runs inside the step in both fused_update layouts;
         Adam keeps flat exp_avg / exp_avg_sq, a device step counter and the step's two bias-correction scalars, refreshed by a
         1-thread launch at the head of every step (nunet_adam_prepare). optimizer_state_dict() / load_optimizer_state_dict()
         speak torch.optim's state-dict format.
@@ -72,13 +82,12 @@ class TrainStep:
         captured step: the loss gradient is seeded with the scale, the final gradient scratch is checked for inf / NaN, the update
         unscales it - or, on an overflow, writes nothing (the step is skipped) - and a 1-thread launch backs the scale off or grows
         it as torch's scaler.update() does. No host synchronisation per step; scaler_stats() / scaler_state_dict() read the state.
-        Under scaling the in-pass update (fused_update 3) falls back to 2: a step half applied inside the pass cannot be skipped.
         clip_grad_norm: None (default: no clipping, today's launches) or max_norm > 0 of torch.nn.utils.clip_grad_norm_(params,
         max_norm) over all parameters, applied inside the captured step between the unscale and the optimiser step: one read-only
         pass takes the 2-norm of the final (rank-mean, unscaled) gradient in double, in a fixed summation order; a one-workgroup
         launch forms coef = min(1, max_norm / (norm + 1e-6)) and the statistics; the update reads g * coef. float('inf')
         measures and never clips (bit-identical to None). set_clip_grad_norm() changes the threshold of a captured step,
-        grad_norm_stats() reads the norms. Like scaling, clipping turns fused_update 3 into 2."""
+        grad_norm_stats() reads the norms."""
         self.model = model
         self.eng = model.engine()
         dev = self.eng.device
@@ -189,24 +198,16 @@ class TrainStep:
             self.dp_mode = 1             # a gloo exchange is a host round trip: it cannot sit inside the step's graph
         self.dp_choice = None        # {layout: ms per step} when the layout was chosen by measurement
         self.use_graph = use_graph
-        # optimiser step layout: 0 = unpack, SGD, (next forward's) pack as three streaming launches; 2 (default) = unpack
-        # with the SGD step as its epilogue (nunet_plan_opt_step, repack 0: 46 us against 59 us for the pair); 1 = one tile kernel
-        # that also repacks the weights (nunet_plan_opt_step, repack 1). The flat OIHW gradients (p.grad views) are materialised with
-        # keep_grads=True in the fused layouts; in every layout they hold the rank-MEAN gradient (as
+        # optimiser step layout: 0 = unpack, the flat step, (next forward's) pack as three streaming launches; 2 (default) = unpack
+        # with the step as its epilogue (nunet_plan_opt_step: 46 us against 59 us for the pair). The flat OIHW gradients (p.grad
+        # views) are materialised with keep_grads=True in the fused layout; in both layouts they hold the rank-MEAN gradient (as
         # DistributedDataParallel leaves p.grad).
-        # 3 = the optimiser step INSIDE the backward pass (nunet_plan_set_inpass_opt): every VGGBlock is stepped and repacked
-        # as an op of the pass behind its weight gradients, beside the rest of the pass; single-process training only (a
-        # data-parallel step exchanges the gradients before the update: it falls back to 2).
-        self.fused_update = int(os.environ.get("NUNET_FUSED_UPDATE", "2")) if fused_update is None else int(fused_update)   
-        if self.fused_update == 3 and (self.dp or self.scaler_cfg is not None or self._clip is not None):
-            self.fused_update = 2
+        self.fused_update = fused_update_from(fused_update, os.environ)
         if self._clip is not None:       # one double per workgroup of the square-norm launch of this layout
             nb = (L.lib().nunet_plan_grad_sqnorm_ws_bytes(self.pl.handle) if self.fused_update
                   else L.lib().nunet_grad_sqnorm_ws_bytes(self.eng.flat_params.numel()))
             self._clip_ws = torch.zeros(nb // 8, dtype=torch.float64, device=dev)
         self.keep_grads = keep_grads
-        self._inpass_set = False
-        self._packed = False          # the arena's packed weights match the fp32 parameters
         self.g_fb = None
         self.g_opt = None
         self._buckets = self._grad_scratch() if self.dp else None
@@ -226,7 +227,6 @@ class TrainStep:
         nbt = eng.nbt.to(torch.float64)          # (gloo / RCCL both take floating tensors; counts are exact in fp64)
         broadcast_flat_(nbt, src, self.pg)
         eng.nbt.copy_(nbt.to(torch.int64))
-        self._packed = False
 
     def sync_bn_buffers(self, src=0):
         """BatchNorm running statistics policy under data parallel: rank `src`'s buffers are the model's. Call before
@@ -242,10 +242,9 @@ class TrainStep:
     def _fwd_loss(self):
         lib, eng, pl = L.lib(), self.eng, self.pl
         st = L.stream()
-        flags = 3 if (self.fused_update in (1, 3) and self._packed) else 1
+        flags = 1
         if self.optimizer == "Adam" and self._scaler is None:     # (under loss scaling: behind the overflow check, _opt)
-            # t += 1 and this step's bias corrections, ahead of the forward pass: every update launch of the step (in-pass ones on
-            # any lane included) is ordered behind it
+            # t += 1 and this step's bias corrections, ahead of the forward pass: the update launch of the step is ordered behind it
             L.check(lib.nunet_adam_prepare(L.ptr(self.lr), self.betas[0], self.betas[1], L.ptr(self.adam_step), L.ptr(self.adam_scal), st),
                     "adam_prepare")
         if self.input_u8:
@@ -275,24 +274,6 @@ class TrainStep:
         self._fwd_loss()
         self._bwd(3 if self.fused_update else 7)
 
-    def sync_weights(self):
-        """Repack the plan's 16-bit weights from the fp32 parameters: call after changing the parameters by anything
-        other than step() (load_state_dict, a stock optimiser) when fused_update is on."""
-        self._arm_inpass_update()
-        if self.fused_update in (1, 3):
-            L.check(L.lib().nunet_plan_repack(self.pl.handle, L.ptr(self.eng.flat_params), L.ptr(self.pl.arena), L.nbytes(self.pl.arena), L.stream()), "plan_repack")
-            self._packed = True
-
-    def _arm_inpass_update(self):
-        """fused_update 3: hand the plan the optimiser's state so that its backward pass carries the step (off otherwise)."""
-        on = self.fused_update == 3
-        if on == self._inpass_set:
-            return
-        eng = self.eng
-        L.check(L.lib().nunet_plan_set_inpass_opt(self.pl.handle, L.ptr(eng.flat_params) if on else None, C.byref(self._optim),
-                                                  1.0 / self.world, L.ptr(eng.flat_grads) if self.keep_grads else None), "plan_set_inpass_opt")
-        self._inpass_set = on
-
     def _aux_state(self):
         """The scaler and clip words, where present: snapshotted by capture() and broadcast with the replica state."""
         return [t for t in (self._scaler, self._clip) if t is not None]
@@ -319,14 +300,12 @@ class TrainStep:
             if self.optimizer == "Adam":
                 L.check(lib.nunet_adam_prepare_scaled(L.ptr(self.lr), self.betas[0], self.betas[1], L.ptr(self.adam_step), L.ptr(self.adam_scal),
                                                       sc, st), "adam_prepare_scaled")
-        # (layout 3: already done, block by block, inside the backward pass)
-        if self.fused_update in (1, 2):    # gradient scratch -> step in one launch; layout 1 (repack 1) also repacks the weights
+        if self.fused_update:              # layout 2: gradient scratch -> step in one launch
             if self._clip is not None:
                 self._clip_coef(True, 1.0 / self.world)
             L.check(lib.nunet_plan_opt_step(pl.handle, L.ptr(eng.flat_params), C.byref(self._optim), L.ptr(pl.arena), L.nbytes(pl.arena),
-                                            1.0 / self.world, L.ptr(eng.flat_grads) if self.keep_grads else None,
-                                            1 if self.fused_update == 1 else 0, st), "plan_opt_step")
-        elif not self.fused_update:        # layout 0: the flat gradients that backward phase 4 unpacked
+                                            1.0 / self.world, L.ptr(eng.flat_grads) if self.keep_grads else None, st), "plan_opt_step")
+        else:                              # layout 0: the flat gradients that backward phase 4 unpacked
             if self.world > 1:
                 eng.flat_grads.mul_(1.0 / self.world)      # p.grad = rank mean in every layout
             if self._clip is not None:
@@ -414,7 +393,6 @@ class TrainStep:
         state = [eng.flat_params, eng.bnbuf, eng.nbt, self.meters] + self.opt_state + self._aux_state()
         snap = [t.clone() for t in state]
         steps0 = self.steps
-        self.sync_weights()            # from here on every step leaves the packed weights current
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -445,7 +423,6 @@ class TrainStep:
             for dst, src in zip(state, snap):
                 dst.copy_(src)
         self.steps = steps0
-        self.sync_weights()            # the restored parameters, repacked
 
     def _set_schedule(self, schedule):
         self.schedule = schedule
@@ -651,8 +628,6 @@ class TrainStep:
             else:
                 self.g_fb.replay()
         else:
-            if self.fused_update in (1, 3) and not self._packed:
-                self.sync_weights()
             self._eager_step()
         self.steps += 1
 

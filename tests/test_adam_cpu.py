@@ -116,8 +116,7 @@ def test_adam_abi_rejects_bad_arguments():
     bad = [_optim(beta1=1.0), _optim(beta1=-0.1), _optim(beta2=1.0), _optim(eps=0.0), _optim(eps=-1e-8),
            _optim(state0=None), _optim(state1=None), _optim(adam_scal=None), _optim(kind=7), _optim(kind=L.OPT_SGD, lr=None)]
     for o in bad:
-        assert lib.nunet_plan_opt_step(fake, fake, C.byref(o), fake, 1 << 40, 1.0, None, 0, s) == -1
-        assert lib.nunet_plan_set_inpass_opt(fake, fake, C.byref(o), 1.0, None) == -1
+        assert lib.nunet_plan_opt_step(fake, fake, C.byref(o), fake, 1 << 40, 1.0, None, s) == -1
     for o in bad[:-2]:
         assert lib.nunet_adam_step(fake, fake, C.byref(o), 16, 1.0, s) == -1
     assert lib.nunet_adam_step(fake, fake, C.byref(_optim(kind=L.OPT_SGD)), 16, 1.0, s) == -1      # not an Adam optimiser
@@ -128,16 +127,14 @@ def test_adam_abi_rejects_bad_arguments():
     assert lib.nunet_adam_prepare(fake, 0.9, -0.5, fake, fake, s) == -1
     assert lib.nunet_adam_prepare(None, 0.9, 0.999, fake, fake, s) == -1
     assert lib.nunet_adam_prepare(fake, 0.9, 0.999, None, fake, s) == -1
-    assert lib.nunet_plan_opt_step(None, fake, C.byref(_optim()), fake, 1 << 40, 1.0, None, 0, s) == -1
-    assert lib.nunet_plan_set_inpass_opt(None, fake, C.byref(_optim()), 1.0, None) == -1
-    assert lib.nunet_plan_opt_step(fake, fake, None, fake, 1 << 40, 1.0, None, 0, s) == -1
+    assert lib.nunet_plan_opt_step(None, fake, C.byref(_optim()), fake, 1 << 40, 1.0, None, s) == -1
+    assert lib.nunet_plan_opt_step(fake, fake, None, fake, 1 << 40, 1.0, None, s) == -1
     assert b"null optimiser" in lib.nunet_last_error()
 
 
 def test_plan_optimiser_entries_disarm_and_sgd_state():
-    """The plan's optimiser entries on a real plan. params = NULL switches the in-pass step off whatever the optimiser argument
-    is (NULL included). The plan kernels load SGD's momentum buffer whatever the momentum, so they refuse state0 = NULL; the
-    flat kernel reads it only when momentum != 0, so nunet_opt_step lets that descriptor through - seen without a device as the
+    """The plan's optimiser entry on a real plan. The plan kernel loads SGD's momentum buffer whatever the momentum, so it
+    refuses state0 = NULL; the flat kernel reads it only when momentum != 0, so nunet_opt_step lets that descriptor through - seen without a device as the
     next refusal in line (n <= 0), while with momentum != 0 the missing buffer is what it reports."""
     lib = L.lib()
     fake = C.c_void_p(0x1000)
@@ -145,13 +142,8 @@ def test_plan_optimiser_entries_disarm_and_sgd_state():
     plan = lib.nunet_plan_create(C.byref(cfg))
     assert plan
     try:
-        assert lib.nunet_plan_set_inpass_opt(plan, None, None, 1.0, None) == 0
-        assert lib.nunet_plan_set_inpass_opt(plan, None, C.byref(_optim()), 1.0, None) == 0
         sgd = _optim(kind=L.OPT_SGD, momentum=0.0, adam_scal=None, state0=None, state1=None)
-        for repack in (0, 1):
-            assert lib.nunet_plan_opt_step(plan, fake, C.byref(sgd), fake, 1 << 40, 1.0, None, repack, None) == -1
-            assert b"state0" in lib.nunet_last_error()
-        assert lib.nunet_plan_set_inpass_opt(plan, fake, C.byref(sgd), 1.0, None) == -1
+        assert lib.nunet_plan_opt_step(plan, fake, C.byref(sgd), fake, 1 << 40, 1.0, None, None) == -1
         assert b"state0" in lib.nunet_last_error()
     finally:
         lib.nunet_plan_destroy(plan)

@@ -69,7 +69,7 @@ def test_launch_info_query_on_the_host():
     negative entries stay refused"""
     lib = L.lib()
     assert (L.LOSS_ENTRY_BCE_LOGITS_FWD, L.LOSS_ENTRY_BCE_LOGITS_BWD, L.LOSS_BCE_LOGITS) == (5, 6, 2)
-    assert lib.nunet_version() == 103
+    assert lib.nunet_version() == 104
     o = L.LossLaunchInfo()
     for case in BC.ALONE_CASES:
         n = BC.count(case)

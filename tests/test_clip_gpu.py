@@ -143,7 +143,7 @@ CONFIGS = {
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 @pytest.mark.parametrize("config", sorted(CONFIGS))
 def test_plan_scratch_norm_equals_the_norm_of_p_grad(synth, config, dtype):
-    """TrainStep(lr=0, use_graph=False, clip_grad_norm=inf), 2x32x32, in every update layout: the reported norm equals
+    """TrainStep(lr=0, use_graph=False, clip_grad_norm=inf), 2x32x32, in both update layouts: the reported norm equals
     vector_norm(cat(p.grad.double())) to 1e-6 (padding of cin up to cinpad - 16 in fp32, 32 in bf16 - does not count; heads are
     summed from their slabs before they are squared), and is bit-identical when the step runs again from the same parameters."""
     c = CONFIGS[config]
@@ -152,7 +152,7 @@ def test_plan_scratch_norm_equals_the_norm_of_p_grad(synth, config, dtype):
     else:
         st = synth.closed_form_state(c["ncls"], c["cin"], c["ds"], True)
     (x, t), = _batches(synth, 2, 32, c["ncls"], [101], cin=c["cin"])
-    for fused_update in (0, 1, 2):
+    for fused_update in (0, 2):
         m = _module(st, c["ncls"], dtype, c["cin"], c["ds"], c["arch"])
         ts = TrainStep(m, (2, c["cin"], 32, 32), lr=0.0, use_graph=False, fused_update=fused_update, clip_grad_norm=INF)
         print("executor_choice", ts.executor_choice)
@@ -172,7 +172,7 @@ def test_plan_scratch_norm_equals_the_norm_of_p_grad(synth, config, dtype):
 # -- 3. inf is the identity ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 @pytest.mark.parametrize("optimizer", ["SGD", "Adam"])
-@pytest.mark.parametrize("fused_update", [0, 1, 2])
+@pytest.mark.parametrize("fused_update", [0, 2])
 def test_inf_is_the_identity(synth, dtype, optimizer, fused_update):
     """clip_grad_norm=inf: after 3 graph steps parameters, gradients, optimiser state, BN buffers and meters are bit-identical
     to clip_grad_norm=None; nothing was clipped, three steps were counted."""
@@ -211,7 +211,7 @@ def unclipped(synth):
     return dict(st=st, x=x, t=t, n0=n0, grads=grads)
 
 
-@pytest.mark.parametrize("fused_update", [0, 1, 2])
+@pytest.mark.parametrize("fused_update", [0, 2])
 @pytest.mark.parametrize("optimizer", ["SGD", "SGD-nesterov", "Adam"])
 def test_binding_clip_against_torch(unclipped, optimizer, fused_update):
     """One real step with clip_grad_norm = 0.25 n0 against clones of the parameters with .grad = g, clip_grad_norm_, and one

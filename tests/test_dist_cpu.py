@@ -11,7 +11,7 @@ import nunet_amd
 from dist_cases import free_port
 from nunet_amd import _lib as L
 from nunet_amd import parallel
-from nunet_amd.trainer import dp_layout_from_env
+from nunet_amd.trainer import dp_layout_from_env, fused_update_from
 
 
 def _worker(rank, world, port, q):
@@ -120,3 +120,18 @@ def test_dp_layout_from_env_takes_the_two_layouts_that_exist():
     for bad in ("0", "2", "4", "fast"):
         with pytest.raises(L.NunetError, match="NUNET_DP_MODE %r" % bad):
             dp_layout_from_env({"NUNET_DP_MODE": bad})
+
+
+def test_fused_update_from_takes_the_two_layouts_that_exist():
+    """fused_update / NUNET_FUSED_UPDATE: unset -> layout 2; 0 and 2 as given, by argument (which wins) or by environment; the removed
+    layouts (1: step + repack in one kernel; 3: the step inside the backward pass) and anything else raise, naming both layouts."""
+    assert fused_update_from(None, {}) == 2
+    assert fused_update_from(0, {}) == 0 and fused_update_from(2, {}) == 2
+    assert fused_update_from(None, {"NUNET_FUSED_UPDATE": "0"}) == 0
+    assert fused_update_from(None, {"NUNET_FUSED_UPDATE": "2"}) == 2
+    assert fused_update_from(0, {"NUNET_FUSED_UPDATE": "2"}) == 0
+    for bad in (1, 3, "1", "3", "x"):
+        for arg, env in ((bad, {}), (None, {"NUNET_FUSED_UPDATE": str(bad)})):
+            with pytest.raises(L.NunetError, match=r"layouts are 0, .* and 2, ") as e:
+                fused_update_from(arg, env)
+            assert repr(bad if arg is not None else str(bad)) in str(e.value)

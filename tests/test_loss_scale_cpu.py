@@ -115,15 +115,8 @@ def test_abi_refuses_bad_arguments(lib):
     assert lib.nunet_opt_step(fake, fake, C.byref(opt), 16, 1.0, None) == EINVAL
     opt = L.Optim(kind=L.OPT_ADAM, beta1=0.9, beta2=0.999, eps=1e-8, adam_scal=fake.value, state0=fake.value, state1=None)
     assert lib.nunet_opt_step(fake, fake, C.byref(opt), 16, 1.0, None) == EINVAL
-    # the flat Adam entry and the in-pass step refuse a scaler: neither can honour a skipped step the way the scaled entries do
+    # the flat Adam entry refuses a scaler: it cannot honour a skipped step the way the scaled entries do
     opt = L.Optim(kind=L.OPT_ADAM, beta1=0.9, beta2=0.999, eps=1e-8, adam_scal=fake.value, state0=fake.value, state1=fake.value,
                   scaler=fake.value)
     ok, info = einval(lib.nunet_adam_step(fake, fake, C.byref(opt), 16, 1.0, None), "nunet_opt_step")
     assert ok, info
-    cfg = L.PlanCfg(2, 32, 32, 3, 1, 0, L.F32, 0)
-    plan = lib.nunet_plan_create(C.byref(cfg))
-    try:
-        ok, info = einval(lib.nunet_plan_set_inpass_opt(plan, fake, C.byref(opt), 1.0, None), "loss scaling")
-        assert ok, info
-    finally:
-        lib.nunet_plan_destroy(plan)

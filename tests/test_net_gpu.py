@@ -521,12 +521,12 @@ def test_training_step_is_bit_reproducible(dtype, synth):
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("mode", [1, 2])
+@pytest.mark.parametrize("mode", [2])
 def test_fused_update_equals_unpack_sgd_pack(dtype, mode, synth):
-    """nunet_plan_opt_step with repack 1 (mode 1: scratch -> SGD -> repacked weights in one launch) and repack 0 (mode 2: scratch ->
-    SGD) against the launches they replace (unpack into the OIHW gradient arena + nunet_opt_step), applied to the SAME
-    gradient scratch from the SAME state: parameters, momentum and gradients agree to rounding (momentum, weight decay,
-    nesterov on); after mode 1 the next forward with the repack skipped gives the logits of a forward that repacks."""
+    """nunet_plan_opt_step (mode 2: scratch -> SGD) against the launches it replaces (unpack into the OIHW gradient arena +
+    nunet_opt_step), applied to the SAME gradient scratch from the SAME state: parameters, momentum and gradients agree to
+    rounding (momentum, weight decay, nesterov on); after the step a forward told that nunet_plan_repack left the packed
+    weights current (training flags 1 | 2) gives the logits of a forward that repacks itself."""
     from nunet_amd.trainer import TrainStep
     cfg = GOLDEN_CASES["a_n2_32x32_k1"]
     m, st, x, t = build(cfg, synth, dtype=dtype)
@@ -542,19 +542,23 @@ def test_fused_update_equals_unpack_sgd_pack(dtype, mode, synth):
     pa, ma, ga = eng.flat_params.clone(), ts.mom.clone(), eng.flat_grads.clone()
     eng.flat_params.copy_(p0); ts.mom.copy_(m0); eng.flat_grads.zero_()
     ts.fused_update = mode
-    ts._opt()                                      # nunet_plan_opt_step (repack 1 / 0) on the same scratch
+    ts._opt()                                      # nunet_plan_opt_step on the same scratch
     torch.cuda.synchronize()
     pb, mb, gb = eng.flat_params.clone(), ts.mom.clone(), eng.flat_grads.clone()
     assert float((ga - gb).abs().max()) <= 1e-5 * float(ga.abs().max())     # (the head slabs are summed in a different order)
     assert float((pa - pb).abs().max()) <= 1e-5 * float(pa.abs().max())
     assert float((ma - mb).abs().max()) <= 1e-5 * float(ma.abs().max()) + 1e-9
-    if mode == 1:
-        ts._packed = True
-        ts._fwd_loss()                             # repack skipped: uses the weights plan_update packed
-        l1 = ts.logits.clone()
-        ts._packed = False
-        ts._fwd_loss()                             # repacks from the fp32 parameters
-        assert torch.equal(l1, ts.logits)          # same packed weights, deterministic reductions: bit-identical
+    lib, pl = L.lib(), ts.pl
+
+    def forward(flags):
+        L.check(lib.nunet_plan_forward(pl.handle, L.ptr(eng.flat_params), L.ptr(eng.bnbuf), L.ptr(eng.nbt), L.ptr(ts.x), L.ptr(pl.arena),
+                                       L.nbytes(pl.arena), L.ptr(ts.logits), flags, L.stream()), "plan_forward")
+        torch.cuda.synchronize()
+        return ts.logits.clone()
+    L.check(lib.nunet_plan_repack(pl.handle, L.ptr(eng.flat_params), L.ptr(pl.arena), L.nbytes(pl.arena), L.stream()), "plan_repack")
+    l1 = forward(1 | 2)                            # repack skipped: uses the weights nunet_plan_repack packed
+    l2 = forward(1)                                # repacks from the fp32 parameters
+    assert torch.equal(l1, l2)                     # same packed weights, deterministic reductions: bit-identical
 
 
 def _head_slab_sum_host(slabs, B):
@@ -579,10 +583,10 @@ def _head_slab_sum_host(slabs, B):
 @pytest.mark.parametrize("ncls", [1, 4, 8])
 def test_head_slab_sum_order_in_every_layout(ncls, synth):
     """The head gradient is the sum of 256 slabs in a fixed order that depends on the block size of the kernel that forms it:
-    256 threads in layout 0 (unpack_tiled_kernel) and layout 2 (unpack_sgd_tiled_kernel), 512 in layout 1 (update_kernel).
-    ncls 1, 4, 8 give 33, 132 and 264 elements: many parts per element; one part; two chunks (256 + 8) for 256 threads and
-    one chunk for 512. The flat head gradients equal a host emulation of that order bit for bit, and every other entry
-    (conv weights, bias, gamma, beta: copies of the scratch) is bit-identical across the three layouts."""
+    256 threads in layout 0 (unpack_tiled_kernel) and layout 2 (unpack_sgd_tiled_kernel).
+    ncls 1, 4, 8 give 33, 132 and 264 elements: many parts per element; one part; two chunks (256 + 8).
+    The flat head gradients equal a host emulation of that order bit for bit, and every other entry
+    (conv weights, bias, gamma, beta: copies of the scratch) is bit-identical across the two layouts."""
     from nunet_amd.trainer import TrainStep
     m, st, x, t = build((2, 16, 16, 3, ncls, False, True, True), synth)
     m.train()
@@ -594,51 +598,20 @@ def test_head_slab_sum_order_in_every_layout(ncls, synth):
     nh = eng.flat_params.numel() - tot             # the head is the last parameter pair, and the first scratch entry
     slabs = ts._grad_scratch()[0][:256 * tot].view(256, tot).cpu().numpy()
     e256 = torch.from_numpy(_head_slab_sum_host(slabs, 256))
-    e512 = torch.from_numpy(_head_slab_sum_host(slabs, 512))
     assert float(e256.abs().max()) > 0
     p0, m0 = eng.flat_params.clone(), ts.mom.clone()
     grads = {}
     ts._bwd(4)                                     # layout 0: unpack into the flat arena
     torch.cuda.synchronize()
     grads[0] = eng.flat_grads.cpu()
-    for mode in (2, 1):
-        eng.flat_params.copy_(p0); ts.mom.copy_(m0); eng.flat_grads.zero_()
-        ts.fused_update = mode
-        ts._opt()                                  # nunet_plan_opt_step (repack 0 / 1) on the same scratch, grad_scale 1
-        torch.cuda.synchronize()
-        grads[mode] = eng.flat_grads.cpu()
+    eng.flat_params.copy_(p0); ts.mom.copy_(m0); eng.flat_grads.zero_()
+    ts.fused_update = 2
+    ts._opt()                                      # nunet_plan_opt_step on the same scratch, grad_scale 1
+    torch.cuda.synchronize()
+    grads[2] = eng.flat_grads.cpu()
     assert torch.equal(grads[0][nh:], e256)
     assert torch.equal(grads[2][nh:], e256)
-    assert torch.equal(grads[1][nh:], e512)
-    assert torch.equal(grads[0][:nh], grads[2][:nh]) and torch.equal(grads[0][:nh], grads[1][:nh])
-
-
-@pytest.mark.parametrize("dtype", ["bf16", "fp32"])
-@pytest.mark.parametrize("ds", [False, True])
-def test_optimiser_step_inside_the_backward_pass(dtype, ds, synth):
-    """fused_update=3 (nunet_plan_set_inpass_opt): every VGGBlock - and the heads - stepped and repacked as an op of the backward
-    pass, behind its weight gradients. It is the arithmetic of nunet_plan_opt_step with repack 1 (mode 1), launched in slices: after three captured
-    steps parameters, momentum, p.grad, BatchNorm buffers and losses are BIT-identical to mode 1's, under every executor."""
-    from nunet_amd.trainer import TrainStep
-    n, hw = 16, 96
-    torch.manual_seed(21)
-    sd = {k: v.clone() for k, v in nunet_amd.archs.NestedUNet(1, 3, ds).state_dict().items()}
-    batches = [synth.synth_batch(n, hw, hw, 3, 1, seed=500 + k) for k in range(3)]
-    outs = []
-    for mode, seg, sched in ((1, False, "lanes"), (3, False, "lanes"), (3, "flags", "list")):
-        m = nunet_amd.archs.NestedUNet(1, 3, ds, dtype=dtype)
-        m.load_state_dict(sd)
-        m = m.to(DEV).train()
-        ts = TrainStep(m, (n, 3, hw, hw), lr=1e-2, momentum=0.9, weight_decay=1e-4, nesterov=True, fused_update=mode, segmented=seg, schedule=sched)
-        ts.capture(torch.from_numpy(batches[0][0]).to(DEV), torch.from_numpy(batches[0][1]).to(DEV))
-        for img, msk in batches:
-            ts.step(torch.from_numpy(img).to(DEV), torch.from_numpy(msk).to(DEV))
-        torch.cuda.synchronize()
-        outs.append([t.clone() for t in (ts.eng.flat_params, ts.mom, ts.eng.flat_grads, ts.eng.bnbuf, ts.loss_out)])
-        del ts, m
-    for other in outs[1:]:
-        for a, b, nm in zip(outs[0], other, ("params", "momentum", "grads", "bn buffers", "loss")):
-            assert torch.equal(a, b), nm
+    assert torch.equal(grads[0][:nh], grads[2][:nh])
 
 
 @pytest.mark.parametrize("ds", [False, True])

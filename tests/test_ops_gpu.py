@@ -993,8 +993,7 @@ def test_undersized_workspaces_are_refused_without_a_launch():
         assert lib.nunet_plan_backward(p, L.ptr(params), L.ptr(logits), L.ptr(arena), L.nbytes(arena), L.ptr(params), 0, L.stream()) == -1
         lr = torch.zeros(1, device=DEV)
         opt = L.Optim(kind=L.OPT_SGD, momentum=0.9, weight_decay=1e-4, nesterov=0, lr=L.ptr(lr).value, state0=L.ptr(bnb).value)
-        assert lib.nunet_plan_opt_step(p, L.ptr(params), C.byref(opt), L.ptr(arena), L.nbytes(arena), 1.0, None, 0, L.stream()) == -1
-        assert lib.nunet_plan_opt_step(p, L.ptr(params), C.byref(opt), L.ptr(arena), L.nbytes(arena), 1.0, None, 1, L.stream()) == -1
+        assert lib.nunet_plan_opt_step(p, L.ptr(params), C.byref(opt), L.ptr(arena), L.nbytes(arena), 1.0, None, L.stream()) == -1
         assert lib.nunet_plan_repack(p, L.ptr(params), L.ptr(arena), L.nbytes(arena), L.stream()) == -1
     finally:
         lib.nunet_plan_destroy(p)
