@@ -40,7 +40,7 @@ enum {
   NUNET_ENODEV = -3   /* no gfx950 device / code object */
 };
 
-int nunet_version(void);   /* 104: nunet_plan_opt_step lost its `repack` argument and nunet_plan_set_inpass_opt is gone (the step always leaves the repack to the next forward). 103: BCEWithLogitsLoss in the loss step; nunet_seg_metrics and nunet_eval_step were added under the same number (additions only). 102: schedule 1 (single-stream) and recording mode 0 (event segments) of 101 are refused, nunet_graph_info reports nodes, edges, lanes */
+int nunet_version(void);   /* 104 (additions under the same number: nunet_plan_create_pruned, nunet_plan_depth, nunet_eval_step_heads): nunet_plan_opt_step lost its `repack` argument and nunet_plan_set_inpass_opt is gone (the step always leaves the repack to the next forward). 103: BCEWithLogitsLoss in the loss step; nunet_seg_metrics and nunet_eval_step were added under the same number (additions only). 102: schedule 1 (single-stream) and recording mode 0 (event segments) of 101 are refused, nunet_graph_info reports nodes, edges, lanes */
 const char* nunet_last_error(void);
 
 /* ------------------------------------------------------------------------ */
@@ -348,6 +348,17 @@ typedef struct nunet_eval_meters {
 size_t nunet_eval_step_ws_bytes(int32_t N, int32_t K, int64_t hw, int32_t heads, int32_t loss_kind);
 int nunet_eval_step(const float* logits, const float* target, int32_t N, int32_t K, int64_t hw, int32_t heads, int32_t loss_kind,
                     void* ws, size_t ws_bytes, float* loss_out, nunet_eval_meters* meters, float iou_logit_threshold, nunet_stream_t s);
+/* nunet_eval_step that also scores EVERY head: loss_out and meters receive exactly what nunet_eval_step writes, bit for bit;
+ * head_meters: `heads` (1 .. 4) DEVICE nunet_eval_meters, zeroed by the caller before the first batch - entry k receives exactly
+ * what nunet_eval_step would add if called with heads = 1 on head k's logits alone (its own loss, IoU, Dice, accuracy, per-class
+ * counts and soft sums). The segmentation sums take a head dimension - a workgroup reads its slice of `target` once and walks
+ * the heads' logits over it, with nunet_seg_metrics' partition of the pixels and summation order per head - and one finalising
+ * launch serves all heads: as many launches as nunet_eval_step, no atomics, no pre-zeroing of ws. ws: the _heads_ws_bytes query,
+ * 256-byte aligned. Every argument is checked before the first launch. */
+size_t nunet_eval_step_heads_ws_bytes(int32_t N, int32_t K, int64_t hw, int32_t heads, int32_t loss_kind);
+int nunet_eval_step_heads(const float* logits, const float* target, int32_t N, int32_t K, int64_t hw, int32_t heads, int32_t loss_kind,
+                          void* ws, size_t ws_bytes, float* loss_out, nunet_eval_meters* meters, nunet_eval_meters* head_meters,
+                          float iou_logit_threshold, nunet_stream_t s);
 /* Mask export of the evaluation driver (reference val.py:100-105): out[i] = uint8(sigmoid(logits[i]) * 255), bit-exact
  * against the reference's sigmoid: thresholds[k-1] (k = 1..255, fp32, device) = the smallest logit whose byte is >= k as
  * the REFERENCE computes it (the caller derives them once by bisection with the reference's sigmoid); NaN maps to 0. */
@@ -494,6 +505,18 @@ typedef struct {
 } nunet_plan_cfg;
 
 nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg);
+/* Inference plan of a deep-supervision NestedUNet cut back to the sub-network that feeds head `depth` (1 .. 4; cfg->deep_supervision
+ * must be 1 and cfg->unet 0, else NULL with a message): the blocks x_{i,j} with i + j <= depth in the full plan's order, then
+ * final<depth> alone - nunet_plan_num_heads is 1, logits are [1][N][K][H][W]. The PARAMETER LAYOUT IS THE FULL MODEL'S:
+ * nunet_plan_param_count / _bnbuf_count / _bn_layers report the whole deep-supervision model and every kept layer sits at its
+ * offset there, so the caller passes the same params / bnbuf / nbt. The arena holds only what an eval forward of the kept blocks
+ * touches (image, forward weight packs, level buffers of levels 0 .. depth, raw conv outputs, split-K workspaces): smaller than
+ * the full plan's at every depth. The launches are the ones the full eval forward issues for the kept blocks, so the logits
+ * equal logits[depth - 1] of the full plan's eval forward bit for bit. Eval forwards only: nunet_plan_forward with bit 0 set,
+ * nunet_plan_backward(_phase), _opt_step, _grad_sqnorm (its ws query returns 0), _grad_scratch, _bucket0_wait, _set_wgrad_dy and
+ * _block_act1 return NUNET_EINVAL before anything is launched or read; nunet_plan_feature is -1 for a pruned block. */
+nunet_plan* nunet_plan_create_pruned(const nunet_plan_cfg* cfg, int32_t depth);
+int32_t nunet_plan_depth(const nunet_plan* p);   /* 1 .. 4 for a pruned plan, 0 for one from nunet_plan_create */
 void nunet_plan_destroy(nunet_plan* p);
 size_t nunet_plan_arena_bytes(const nunet_plan* p);
 /* number of fp32 parameters / BN running-stat floats / BN layers, in

@@ -227,6 +227,8 @@ _SIG = {
     "nunet_seg_metrics_launch_info": (_i32, [_i32, _i32, _i64, C.POINTER(LossLaunchInfo)]),
     "nunet_eval_step_ws_bytes": (C.c_size_t, [_i32, _i32, _i64, _i32, _i32]),
     "nunet_eval_step": (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _i32, _vp, _sz, _vp, _vp, _f32, _vp]),
+    "nunet_eval_step_heads_ws_bytes": (C.c_size_t, [_i32, _i32, _i64, _i32, _i32]),
+    "nunet_eval_step_heads": (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _i32, _vp, _sz, _vp, _vp, _vp, _f32, _vp]),
     "nunet_sigmoid_u8": (_i32, [_vp, _vp, _vp, _i64, _vp]),
     "nunet_sgd_step": (_i32, [_vp, _vp, _vp, _i64, _vp, _f32, _f32, _i32, _i32, _f32, _vp]),
     "nunet_adam_prepare": (_i32, [_vp, C.c_double, C.c_double, _vp, _vp, _vp]),
@@ -242,6 +244,8 @@ _SIG = {
     "nunet_preprocess_u8": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
     "nunet_nchw_to_nhwc": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "nunet_plan_create": (_vp, [C.POINTER(PlanCfg)]),
+    "nunet_plan_create_pruned": (_vp, [C.POINTER(PlanCfg), _i32]),
+    "nunet_plan_depth": (_i32, [_vp]),
     "nunet_plan_destroy": (None, [_vp]),
     "nunet_plan_arena_bytes": (C.c_size_t, [_vp]),
     "nunet_plan_param_count": (_i64, [_vp]),

@@ -61,14 +61,38 @@ class _PlanNet(nn.Module):
             self._engine = Engine(self, dev)
         return self._engine
 
-    def plan_for(self, input):
+    def plan_for(self, input, depth=None):
         if input.dim() != 4 or input.size(1) != self.input_channels:
             raise L.NunetError("expected input [N,%d,H,W], got %s" % (self.input_channels, tuple(input.shape)))
         n, _, h, w = input.shape
         return self.engine().plan(n, h, w, self.input_channels, self.num_classes,
-                                  getattr(self, 'deep_supervision', False), self.compute_dtype, self._unet)
+                                  getattr(self, 'deep_supervision', False), self.compute_dtype, self._unet, depth=depth)
 
-    def forward(self, input):
+    def check_depth(self, depth, need_eval=True):
+        """Raise unless this module can run pruned to `depth`: a deep-supervision NestedUNet in eval mode, depth in 1..4."""
+        if self._unet:
+            raise L.NunetError("depth=%r: the plain UNet has no nested sub-networks to prune to (NestedUNet only)" % (depth,))
+        if not getattr(self, 'deep_supervision', False):
+            raise L.NunetError("depth=%r needs a model built with deep_supervision=True: without it there is no final%s head"
+                               % (depth, depth))
+        if isinstance(depth, bool) or not isinstance(depth, int) or not 1 <= depth <= 4:
+            raise L.NunetError("depth must be one of 1, 2, 3, 4 (the heads final1..final4), got %r" % (depth,))
+        if need_eval and self.training:
+            raise L.NunetError("depth=%d is an inference path: call model.eval() first (a pruned network is not trained)" % depth)
+
+    def _forward_pruned(self, input, depth):
+        self.check_depth(depth)
+        eng = self.engine()
+        input = input.contiguous()
+        if input.dtype != torch.float32:
+            input = input.float()
+        return eng.forward(self.plan_for(input, depth), input, False)[0]
+
+    def forward(self, input, depth=None):
+        """depth=L (1..4, deep-supervision NestedUNet in eval mode): the logits [N, K, H, W] of final<L> from the network
+        pruned to the blocks that feed it - bit-equal to forward(input)[L - 1] at a fraction of the launches."""
+        if depth is not None:
+            return self._forward_pruned(input, depth)
         eng = self.engine()
         if input.requires_grad:
             raise L.NunetError("gradient w.r.t. the input image is not part of this path")

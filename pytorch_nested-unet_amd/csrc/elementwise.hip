@@ -1589,7 +1589,56 @@ __global__ __launch_bounds__(256) void seg_metrics_partial_kernel(const float* _
   if (threadIdx.x < 3) w->s[threadIdx.x] = ((s_d[0][threadIdx.x] + s_d[1][threadIdx.x]) + s_d[2][threadIdx.x]) + s_d[3][threadIdx.x];
   else if (threadIdx.x < 7) { const int q = threadIdx.x - 3; w->c[q] = ((s_c[0][q] + s_c[1][q]) + s_c[2][q]) + s_c[3][q]; }
 }
+// The head dimension of nunet_eval_step_heads: the same partition of a plane's pixels over the workgroups and the same order of
+// every sum as the kernel above, for HEADS logits tensors [HEADS][N][K][hw] over ONE read of the targets - a thread loads its
+// target value once and walks the heads' logits over it; head h's partials go to slab h (ws + h * N * K * SEG_GX), so slab h
+// holds exactly what seg_metrics_partial_kernel leaves for head h's logits alone.
+template <int HEADS>
+__global__ __launch_bounds__(256) void seg_metrics_partial_heads_kernel(const float* __restrict__ x, const float* __restrict__ t, int64_t hw, float thr, SegPart* __restrict__ ws) {
+  const int k = blockIdx.y, n = blockIdx.z, K = gridDim.y;
+  const int64_t plane = (int64_t)n * K + k;
+  const int64_t n_head = (int64_t)gridDim.z * K * hw;
+  const float* xs = x + plane * hw;
+  const float* ts = t + plane * hw;
+  double si[HEADS], sp[HEADS], st[HEADS];
+  unsigned tp[HEADS], fp[HEADS], fn[HEADS], tn[HEADS];
+#pragma unroll
+  for (int h = 0; h < HEADS; ++h) { si[h] = 0.0; sp[h] = 0.0; st[h] = 0.0; tp[h] = 0; fp[h] = 0; fn[h] = 0; tn[h] = 0; }
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < hw; i += (int64_t)gridDim.x * blockDim.x) {
+    const float tv = ts[i];
+    const bool b = tv > 0.5f;
+#pragma unroll
+    for (int h = 0; h < HEADS; ++h) {
+      const float xv = xs[h * n_head + i];
+      const double pv = (double)sigmoidf_(xv);
+      si[h] += pv * (double)tv; sp[h] += pv; st[h] += (double)tv;
+      const bool a = xv >= thr;
+      tp[h] += (a && b) ? 1u : 0u; fp[h] += (a && !b) ? 1u : 0u; fn[h] += (!a && b) ? 1u : 0u; tn[h] += (!a && !b) ? 1u : 0u;
+    }
+  }
+  __shared__ double s_d[HEADS][4][3];
+  __shared__ unsigned s_c[HEADS][4][4];
+  const int wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int h = 0; h < HEADS; ++h) {
+    const double a0 = wave_sum_f64(si[h]), a1 = wave_sum_f64(sp[h]), a2 = wave_sum_f64(st[h]);
+    unsigned c0 = tp[h], c1 = fp[h], c2 = fn[h], c3 = tn[h];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { c0 += __shfl_xor(c0, o); c1 += __shfl_xor(c1, o); c2 += __shfl_xor(c2, o); c3 += __shfl_xor(c3, o); }
+    if ((threadIdx.x & 63) == 0) { s_d[h][wv][0] = a0; s_d[h][wv][1] = a1; s_d[h][wv][2] = a2; s_c[h][wv][0] = c0; s_c[h][wv][1] = c1; s_c[h][wv][2] = c2; s_c[h][wv][3] = c3; }
+  }
+  __syncthreads();
+  const int h = threadIdx.x >> 3, q7 = threadIdx.x & 7;      // eight threads per head: three doubles, four counts
+  if (h < HEADS) {
+    SegPart* w = ws + ((int64_t)h * gridDim.z * K + plane) * SEG_GX + blockIdx.x;
+    if (q7 < 3) w->s[q7] = ((s_d[h][0][q7] + s_d[h][1][q7]) + s_d[h][2][q7]) + s_d[h][3][q7];
+    else if (q7 < 7) { const int q = q7 - 3; w->c[q] = ((s_c[h][0][q] + s_c[h][1][q]) + s_c[h][2][q]) + s_c[h][3][q]; }
+  }
+}
+// (workgroup blockIdx.x finishes slab blockIdx.x into out[blockIdx.x]: one workgroup for the single tensor of nunet_seg_metrics,
+// one per head for nunet_eval_step_heads)
 __global__ __launch_bounds__(256) void seg_metrics_final_kernel(const SegPart* __restrict__ ws, int gx, int N, int K, nunet_seg_sums* __restrict__ out, int accumulate) {
+  ws += (int64_t)blockIdx.x * N * K * SEG_GX; out += blockIdx.x;
   const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
   __shared__ double s_d[4][NUNET_EVAL_MAX_CLASSES][3];
   __shared__ unsigned long long s_c[4][NUNET_EVAL_MAX_CLASSES][4];
@@ -1694,13 +1743,9 @@ extern "C" size_t nunet_eval_step_ws_bytes(int32_t N, int32_t K, int64_t hw, int
   return (size_t)heads * eval_head_ws(N, K, hw, loss_kind) + eval_unit_ws(N, hw, loss_kind) + align_up(nunet_seg_metrics_ws_bytes(N, K, hw), 256) +
          align_up(sizeof(nunet_seg_sums), 256);
 }
-__global__ void eval_finalize_kernel(float* __restrict__ loss_out, int heads, const nunet_seg_sums* __restrict__ b, nunet_eval_meters* __restrict__ m, int N, int K, int64_t hw) {
+// one thread: the batch values of one logits tensor from its sums `b`, and the AverageMeter update of `m` with them and `mean`
+__device__ __forceinline__ void eval_meter_update(float mean, const nunet_seg_sums* __restrict__ b, nunet_eval_meters* __restrict__ m, int N, int K, int64_t hw) {
 #pragma clang fp contract(off)      // sum += value * N as AverageMeter evaluates it: the product rounded, then the add
-  if (threadIdx.x != 0) return;
-  float mean = loss_out[0];                       // sum(criterion(o, t) for o in out) / len(out): left to right, one division
-  for (int k = 1; k < heads; ++k) mean += loss_out[k];
-  mean = mean / (float)heads;
-  loss_out[heads] = mean;
   unsigned long long tp = 0, fp = 0, fn = 0, tn = 0;
   double si = 0.0, sp = 0.0, st = 0.0;
   for (int k = 0; k < K; ++k) {
@@ -1716,6 +1761,33 @@ __global__ void eval_finalize_kernel(float* __restrict__ loss_out, int heads, co
   m->loss_sum += (double)mean * w; m->iou_sum += iou * w; m->dice_sum += dice * w; m->acc_sum += acc * w;
   m->samples += w;
   m->last_iou = iou; m->last_dice = dice; m->last_acc = acc;
+}
+__device__ __forceinline__ float eval_head_mean(const float* __restrict__ loss, int heads) {
+#pragma clang fp contract(off)
+  float mean = loss[0];                           // sum(criterion(o, t) for o in out) / len(out): left to right, one division
+  for (int k = 1; k < heads; ++k) mean += loss[k];
+  return mean / (float)heads;
+}
+__global__ void eval_finalize_kernel(float* __restrict__ loss_out, int heads, const nunet_seg_sums* __restrict__ b, nunet_eval_meters* __restrict__ m, int N, int K, int64_t hw) {
+  if (threadIdx.x != 0) return;
+  const float mean = eval_head_mean(loss_out, heads);
+  loss_out[heads] = mean;
+  eval_meter_update(mean, b, m, N, K, hw);
+}
+// The head dimension of the finalising launch: workgroup h < heads updates head_meters[h] as a one-head step over head h would
+// (its loss is the mean of one value), workgroup `heads` does what eval_finalize_kernel does - the head mean into
+// loss_out[heads], `meters` from the last head's sums. b: the sums of the heads, [heads].
+__global__ void eval_finalize_heads_kernel(float* __restrict__ loss_out, int heads, const nunet_seg_sums* __restrict__ b, nunet_eval_meters* __restrict__ m,
+                                           nunet_eval_meters* __restrict__ hm, int N, int K, int64_t hw) {
+  if (threadIdx.x != 0) return;
+  const int h = blockIdx.x;
+  if (h < heads) {
+    eval_meter_update(eval_head_mean(loss_out + h, 1), b + h, hm + h, N, K, hw);
+  } else {
+    const float mean = eval_head_mean(loss_out, heads);
+    loss_out[heads] = mean;
+    eval_meter_update(mean, b + (heads - 1), m, N, K, hw);
+  }
 }
 extern "C" int nunet_eval_step(const float* logits, const float* target, int32_t N, int32_t K, int64_t hw, int32_t heads, int32_t loss_kind,
                                void* ws, size_t ws_bytes, float* loss_out, nunet_eval_meters* meters, float iou_logit_threshold, nunet_stream_t s) {
@@ -1747,6 +1819,61 @@ extern "C" int nunet_eval_step(const float* logits, const float* target, int32_t
   seg_metrics_launch(logits + (size_t)(heads - 1) * n_head, target, N, K, hw, iou_logit_threshold, seg_ws, batch, 0, st);
   NUNET_LAUNCH(eval_finalize_kernel, dim3(1), dim3(64), 0, st, loss_out, heads, (const nunet_seg_sums*)batch, meters, N, K, hw);
   return nunet_check_launch("eval_step");
+}
+
+// nunet_eval_step with the metrics of EVERY head (a validation pass then shows which depth of a deep-supervision UNet++ would
+// do): the same loss forwards, the segmentation sums with a head dimension (one read of the targets), one finalising launch for
+// all heads - as many launches as nunet_eval_step makes. Workspace: nunet_eval_step's with one seg_metrics slab and one
+// nunet_seg_sums per head.
+#define NUNET_EVAL_MAX_HEADS 4
+extern "C" size_t nunet_eval_step_heads_ws_bytes(int32_t N, int32_t K, int64_t hw, int32_t heads, int32_t loss_kind) {
+  if (N <= 0 || K <= 0 || K > NUNET_EVAL_MAX_CLASSES || hw <= 0 || heads < 1 || heads > NUNET_EVAL_MAX_HEADS) return 0;
+  return (size_t)heads * eval_head_ws(N, K, hw, loss_kind) + eval_unit_ws(N, hw, loss_kind) +
+         align_up((size_t)heads * nunet_seg_metrics_ws_bytes(N, K, hw), 256) + align_up((size_t)heads * sizeof(nunet_seg_sums), 256);
+}
+extern "C" int nunet_eval_step_heads(const float* logits, const float* target, int32_t N, int32_t K, int64_t hw, int32_t heads, int32_t loss_kind,
+                                     void* ws, size_t ws_bytes, float* loss_out, nunet_eval_meters* meters, nunet_eval_meters* head_meters,
+                                     float iou_logit_threshold, nunet_stream_t s) {
+  if (int rc = seg_metrics_check("eval_step_heads", N, K, hw)) return rc;
+  NUNET_REQUIRE(heads >= 1 && heads <= NUNET_EVAL_MAX_HEADS, "eval_step_heads: %d heads (1 .. %d)", (int)heads, NUNET_EVAL_MAX_HEADS);
+  NUNET_REQUIRE(loss_kind == NUNET_LOSS_BCE_DICE || loss_kind == NUNET_LOSS_LOVASZ_HINGE || loss_kind == NUNET_LOSS_BCE_LOGITS, "eval_step_heads: loss_kind %d", (int)loss_kind);
+  NUNET_REQUIRE(loss_kind != NUNET_LOSS_LOVASZ_HINGE || K == 1, "eval_step_heads: the Lovasz hinge takes one class (the reference squeezes dim 1), got %d", (int)K);
+  NUNET_REQUIRE(loss_kind != NUNET_LOSS_LOVASZ_HINGE || hw <= (1ll << 22), "eval_step_heads: the Lovasz hinge takes up to 2^22 pixels per image, got %lld", (long long)hw);
+  NUNET_REQUIRE(logits && target && ws && loss_out && meters && head_meters, "eval_step_heads: null pointer");
+  NUNET_REQUIRE(((uintptr_t)ws & 255) == 0 && ((uintptr_t)meters & 7) == 0 && ((uintptr_t)head_meters & 7) == 0,
+                "eval_step_heads: workspace must be 256-byte and meters 8-byte aligned");
+  NUNET_REQUIRE(ws_bytes >= nunet_eval_step_heads_ws_bytes(N, K, hw, heads, loss_kind), "eval_step_heads: workspace of %zu bytes, nunet_eval_step_heads_ws_bytes = %zu",
+                ws_bytes, nunet_eval_step_heads_ws_bytes(N, K, hw, heads, loss_kind));
+  hipStream_t st = (hipStream_t)s;
+  const size_t hws = eval_head_ws(N, K, hw, loss_kind);
+  char* base = (char*)ws;
+  float* unit = (float*)(base + (size_t)heads * hws);
+  SegPart* seg_ws = (SegPart*)((char*)unit + eval_unit_ws(N, hw, loss_kind));
+  nunet_seg_sums* batch = (nunet_seg_sums*)((char*)seg_ws + align_up((size_t)heads * nunet_seg_metrics_ws_bytes(N, K, hw), 256));
+  const int64_t per = (int64_t)K * hw, n_head = (int64_t)N * per;
+  for (int k = 0; k < heads; ++k) {
+    const float* lg = logits + (size_t)k * n_head;
+    float* hw_ws = (float*)(base + (size_t)k * hws);
+    int rc;
+    if (loss_kind == NUNET_LOSS_LOVASZ_HINGE) rc = nunet_lovasz_hinge_fwd(lg, target, N, hw, hw_ws, hws, unit, loss_out + k, s);
+    else if (loss_kind == NUNET_LOSS_BCE_LOGITS) rc = nunet_bce_logits_fwd(lg, target, n_head, hw_ws, hws, loss_out + k, s);
+    else rc = nunet_bce_dice_fwd(lg, target, N, per, hw_ws, hws, loss_out + k, s);
+    if (rc) return rc;
+  }
+  const int gx = seg_metrics_gx(hw);
+  {
+    ProfScope ps(PC_LOSS, 0, (double)N * K * hw * 4 * (heads + 1), st);
+    const dim3 grid(gx, K, N);
+    switch (heads) {
+      case 1: NUNET_LAUNCH(seg_metrics_partial_heads_kernel<1>, grid, dim3(256), 0, st, logits, target, hw, iou_logit_threshold, seg_ws); break;
+      case 2: NUNET_LAUNCH(seg_metrics_partial_heads_kernel<2>, grid, dim3(256), 0, st, logits, target, hw, iou_logit_threshold, seg_ws); break;
+      case 3: NUNET_LAUNCH(seg_metrics_partial_heads_kernel<3>, grid, dim3(256), 0, st, logits, target, hw, iou_logit_threshold, seg_ws); break;
+      default: NUNET_LAUNCH(seg_metrics_partial_heads_kernel<4>, grid, dim3(256), 0, st, logits, target, hw, iou_logit_threshold, seg_ws); break;
+    }
+    NUNET_LAUNCH(seg_metrics_final_kernel, dim3(heads), dim3(256), 0, st, (const SegPart*)seg_ws, gx, N, K, batch, 0);
+  }
+  NUNET_LAUNCH(eval_finalize_heads_kernel, dim3(heads + 1), dim3(64), 0, st, loss_out, heads, (const nunet_seg_sums*)batch, meters, head_meters, N, K, hw);
+  return nunet_check_launch("eval_step_heads");
 }
 
 // ---------------------------------------------------------------------------

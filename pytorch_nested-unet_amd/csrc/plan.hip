@@ -356,6 +356,7 @@ struct nunet_plan;
 static PlanRt* rt_of(nunet_plan* P);
 struct nunet_plan {
   nunet_plan_cfg cfg;
+  int depth;                    // 0: the whole network; 1..4: pruned to the blocks x_{i,j}, i + j <= depth, that feed head `depth` (eval forward only)
   int es;                       // element size of T
   int hl[5], wl[5]; long long px[5];
   int nslots[5], PX[5];
@@ -412,7 +413,10 @@ static bool plan_backward_facts(nunet_plan* P) {
   return true;
 }
 
-extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
+// depth 0: the whole network. depth 1..4 (nunet_plan_create_pruned): parameters, BatchNorm buffers and heads are laid out for
+// the whole deep-supervision model, so every kept layer reads the caller's flat arrays at the offsets of the full plan; the
+// execution list, the pack table and the arena hold the kept blocks only, and nothing of the backward pass.
+static nunet_plan* plan_create_impl(const nunet_plan_cfg* cfg, int depth) {
   if (!cfg) { nunet_set_error("plan_create: null cfg"); return nullptr; }
   if (cfg->N <= 0 || cfg->H <= 0 || cfg->W <= 0 || cfg->H % 16 || cfg->W % 16) {
     nunet_set_error("plan_create: H=%d W=%d must be positive multiples of 16 (four 2x2 pools, archs1.py:114-131)", cfg->H, cfg->W);
@@ -423,12 +427,16 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
   if (cfg->dtype < 0 || cfg->dtype > 2) { nunet_set_error("plan_create: bad dtype"); return nullptr; }
   nunet_plan* P = new nunet_plan();
   P->cfg = *cfg;
+  P->depth = depth;
   P->es = dtype_size(cfg->dtype);
   const bool unet = cfg->unet != 0;
+  const bool pruned = depth > 0;
+  auto kept = [&](const Node& n) { return !pruned || n.i + n.j <= depth; };
   for (int i = 0; i < 5; ++i) {
     P->hl[i] = cfg->H >> i; P->wl[i] = cfg->W >> i;
     P->px[i] = (long long)cfg->N * P->hl[i] * P->wl[i];
     P->nslots[i] = unet ? (i == 4 ? 1 : 2) : 5 - i;
+    if (pruned) P->nslots[i] = i <= depth ? depth + 1 - i : 0;
     P->PX[i] = P->nslots[i] * NBF[i];
   }
   // ---- nodes in execution order ------------------------------------------------
@@ -456,17 +464,19 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
   // ---- parameter / buffer offsets in registration order -------------------------
   long long po = 0, bo = 0, gs = 0, sv = 0; int bn = 0;
   long long wp = 0;
-  auto setup_conv = [&](ConvL& c, int cin, int cout, bool need_wd) {
+  auto setup_conv = [&](ConvL& c, int cin, int cout, bool need_wd, bool packed) {
     c.cin = cin; c.cout = cout; c.cinpad = cin < 32 ? 32 : cin;
     c.w_off = po; po += (long long)cout * cin * 9;
     c.b_off = po; po += cout;
     c.g_off = po; po += cout;
     c.be_off = po; po += cout;
     c.rm_off = bo; bo += cout; c.rv_off = bo; bo += cout; c.bn_index = bn++;
+    c.wf = -1; c.wd = -1; c.gs = -1;
+    c.stats = sv; c.save = sv; c.bsum = sv; sv += 2LL * cout;
+    if (!packed) return;       // a pruned block: its parameters keep their place in the flat arrays, the arena holds nothing of it
     c.wf = wp; wp += 9LL * cout * c.cinpad; wp = (wp + 127) / 128 * 128;
     if (need_wd) { c.wd = wp; wp += 9LL * cout * cin; wp = (wp + 127) / 128 * 128; } else c.wd = -1;
-    c.gs = -1;   // assigned below, in gradient-ready order
-    c.stats = sv; c.save = sv; c.bsum = sv; sv += 2LL * cout;
+    // (c.gs is assigned below, in gradient-ready order)
   };
   for (size_t r = 0; r < P->reg.size(); ++r) {
     Node& n = P->exec[P->reg[r]];
@@ -474,8 +484,8 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
     int cin;
     if (n.in_prefix == 0) cin = n.i == 0 ? cfg->input_channels : NBF[n.i - 1];
     else cin = n.in_prefix * f + NBF[n.i + 1];
-    setup_conv(n.c1, cin, f, !(n.i == 0 && n.j == 0));
-    setup_conv(n.c2, f, f, true);
+    setup_conv(n.c1, cin, f, !pruned && !(n.i == 0 && n.j == 0), kept(n));
+    setup_conv(n.c2, f, f, !pruned, kept(n));
   }
   const int nheads = (cfg->deep_supervision && !unet) ? 4 : 1;
   for (int k = 0; k < nheads; ++k) {
@@ -484,23 +494,35 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
     h.b_off = po; po += cfg->num_classes;
     h.gs = -1;
     h.slot = unet ? 1 : (nheads == 4 ? k + 1 : 4);
-    P->heads.push_back(h);
+    h.acc = 0; h.bnr_block = -1;
+    if (!pruned || h.slot == depth) P->heads.push_back(h);      // final<depth> alone, at its offset in the full model
+  }
+  if (pruned) {
+    // the execution list shrinks to the kept blocks, still in anti-diagonal order; the registration order follows it
+    std::vector<Node> keep;
+    for (const Node& n : P->exec) if (kept(n)) keep.push_back(n);
+    P->exec.swap(keep);
+    P->reg.clear();
+    for (int j = 0; j < 5; ++j)
+      for (int i = 0; i < 5; ++i)
+        for (size_t k = 0; k < P->exec.size(); ++k)
+          if (P->exec[k].i == i && P->exec[k].j == j) P->reg.push_back((int)k);
   }
   if (P->exec.size() > NUNET_MAX_BLOCKS || P->heads.size() > NUNET_MAX_HEADS) {
     nunet_set_error("plan_create: %zu blocks / %zu heads, the lane scheduler's resource ids cover %d / %d", P->exec.size(), P->heads.size(), NUNET_MAX_BLOCKS, NUNET_MAX_HEADS);
     delete P; return nullptr;
   }
-  if (!plan_backward_facts(P)) { delete P; return nullptr; }
+  if (!pruned && !plan_backward_facts(P)) { delete P; return nullptr; }
   // Gradient scratch in the order gradients COMPLETE during backward (heads, then blocks in reverse
   // execution order): the first bucket = heads + the last anti-diagonal (75 % of the bytes,
   // SURVEY.md §3.4) is a contiguous prefix, ready for an early all-reduce.
-  for (size_t k = 0; k < P->heads.size(); ++k) {
+  for (size_t k = 0; k < P->heads.size() && !pruned; ++k) {
     P->heads[k].gs = gs; gs += (long long)HEAD_SLABS * ((long long)cfg->num_classes * NBF[0] + cfg->num_classes);
   }
   P->first_phase_nodes = unet ? 4 : 5;
   P->gs_bucket0 = 0;
   long long slab = 0;
-  for (int k = (int)P->exec.size() - 1; k >= 0; --k) {
+  for (int k = (int)P->exec.size() - 1; k >= 0 && !pruned; --k) {
     Node& n = P->exec[k];
     for (int cv = 1; cv >= 0; --cv) {
       ConvL& c = cv ? n.c2 : n.c1;
@@ -526,19 +548,21 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
   P->wpack_elems = wp;
 
   // ---- arena ---------------------------------------------------------------------
+  // (a pruned plan: no BatchNorm sums or saved statistics, no gradient scratch, no weight-gradient slabs, no gradient
+  // levels and no backward scratch - an eval forward touches none of them - and level buffers of the kept slots only)
   size_t cur = 0;
-  P->stats_floats = (size_t)sv;
+  P->stats_floats = pruned ? 0 : (size_t)sv;
   P->off_fx = bump(cur, 2 * fx_region_bytes(P));   // [forward statistics | backward sums], replicated fixed-point accumulators
   P->gs_floats = (size_t)gs;
   P->off_gs = bump(cur, P->gs_floats * 4);
   P->slab_floats = slab;
   P->off_slab = bump(cur, (size_t)slab * 4);
-  P->off_save = bump(cur, (size_t)sv * 4);
+  P->off_save = bump(cur, pruned ? 0 : (size_t)sv * 4);
   P->off_wpack = bump(cur, (size_t)wp * P->es);
   P->off_img = bump(cur, (size_t)P->px[0] * 32 * P->es);
   for (int i = 0; i < 5; ++i) {
     P->X[i] = bump(cur, (size_t)P->px[i] * P->PX[i] * P->es);
-    P->GX[i] = bump(cur, (size_t)P->px[i] * P->PX[i] * P->es);
+    P->GX[i] = pruned ? P->X[i] : bump(cur, (size_t)P->px[i] * P->PX[i] * P->es);
   }
   for (size_t k = 0; k < P->exec.size(); ++k) {
     Node& n = P->exec[k];
@@ -548,7 +572,7 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
     if (n.up_slot >= 0) n.up = bump(cur, (size_t)P->px[n.i] * NBF[n.i + 1] * P->es);
     if (n.in_prefix == 0 && n.i > 0) n.pin = bump(cur, (size_t)P->px[n.i] * NBF[n.i - 1] * P->es);
   }
-  for (size_t k = 0; k < P->exec.size(); ++k) {
+  for (size_t k = 0; k < P->exec.size() && !pruned; ++k) {
     Node& n = P->exec[k];
     const int i = n.i;
     const size_t plane = (size_t)P->px[i] * NBF[i] * P->es;
@@ -576,12 +600,13 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
   auto add_conv = [&](const ConvL& c) {
     PackEnt& pe = P->ptab.e[P->ptab.n++];
     pe.src = c.w_off; pe.wf = c.wf; pe.wd = c.wd; pe.cout = c.cout; pe.cin = c.cin; pe.cinpad = c.cinpad;
+    if (pruned) return;
     UnpackEnt& ue = P->utab.e[P->utab.n++];
     ue.src = c.gs; ue.dst = c.w_off; ue.cout = c.cout; ue.cin = c.cin; ue.cinpad = c.cinpad; ue.taps = 9; ue.nvec = 3; ue.nslab = 1;
   };
   for (size_t r = 0; r < P->reg.size(); ++r) { add_conv(P->exec[P->reg[r]].c1); add_conv(P->exec[P->reg[r]].c2); }
   pack_tiles(P->ptab);
-  for (size_t k = 0; k < P->heads.size(); ++k) {
+  for (size_t k = 0; k < P->heads.size() && !pruned; ++k) {
     UnpackEnt& ue = P->utab.e[P->utab.n++];
     ue.src = P->heads[k].gs; ue.dst = P->heads[k].w_off; ue.cout = cfg->num_classes; ue.cin = NBF[0]; ue.cinpad = NBF[0]; ue.taps = 1; ue.nvec = 1; ue.nslab = HEAD_SLABS;
   }
@@ -605,6 +630,21 @@ extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) {
   P->rt = rt;
   return P;
 }
+
+extern "C" nunet_plan* nunet_plan_create(const nunet_plan_cfg* cfg) { return plan_create_impl(cfg, 0); }
+
+extern "C" nunet_plan* nunet_plan_create_pruned(const nunet_plan_cfg* cfg, int32_t depth) {
+  if (!cfg) { nunet_set_error("plan_create_pruned: null cfg"); return nullptr; }
+  if (depth < 1 || depth > 4) { nunet_set_error("plan_create_pruned: depth %d is not one of 1..4 (the heads final1..final4, archs1.py:105-109)", (int)depth); return nullptr; }
+  if (cfg->unet) { nunet_set_error("plan_create_pruned: the plain UNet has no nested sub-networks to prune to"); return nullptr; }
+  if (!cfg->deep_supervision) { nunet_set_error("plan_create_pruned: pruning to depth %d needs deep_supervision = 1 (a model without it has no final%d head)", (int)depth, (int)depth); return nullptr; }
+  return plan_create_impl(cfg, depth);
+}
+extern "C" int32_t nunet_plan_depth(const nunet_plan* p) { return p ? p->depth : 0; }
+
+// Entries of the training path on a pruned plan: refused before any launch and before any buffer is looked at
+#define REFUSE_PRUNED(what) \
+  NUNET_REQUIRE(P->depth == 0, what ": the plan is pruned to depth %d (nunet_plan_create_pruned): it runs eval forwards only", P->depth)
 
 
 static PlanRt* rt_of(nunet_plan* P) { return P->rt; }
@@ -642,7 +682,7 @@ static int64_t slot_offset(const nunet_plan* p, const size_t* level, int32_t i, 
   return (int64_t)(level[i] + (size_t)p->exec[k].out_slot * NBF[i] * p->es);
 }
 extern "C" int64_t nunet_plan_feature(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels) { return slot_offset(p, p ? p->X : nullptr, i, j, pitch, channels); }
-extern "C" int64_t nunet_plan_feature_grad(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels) { return slot_offset(p, p ? p->GX : nullptr, i, j, pitch, channels); }
+extern "C" int64_t nunet_plan_feature_grad(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels) { return (p && p->depth) ? -1 : slot_offset(p, p ? p->GX : nullptr, i, j, pitch, channels); }
 extern "C" int32_t nunet_plan_census_count(const nunet_plan* p, int32_t pass) {
   return (p && p->rt && (pass == 0 || pass == 1)) ? (int32_t)p->rt->census[pass].size() : 0;
 }
@@ -1110,7 +1150,7 @@ int Sched::run_list() {
 // by level, by anti-diagonal, by column, one or two side lanes).
 static int lane_of(const nunet_plan* P, const Node& n) {
   if (P->cfg.unet) return n.i;
-  if (n.j == 0 || n.i + n.j == 4) return 0;
+  if (n.j == 0 || n.i + n.j == (P->depth ? P->depth : 4)) return 0;   // (a pruned plan's chain ends on its last anti-diagonal)
   return n.i + n.j;           // side blocks: diagonals 1..3 -> lanes 1..3
 }
 
@@ -1146,8 +1186,10 @@ static BnView bn_view(const nunet_plan* P, void* arena, const float* params, int
   const Node& n = P->exec[k];
   const ConvL& L = cv ? n.c2 : n.c1;
   const int rb = R_BLK + k * B_STRIDE;
-  return {AB(arena, cv ? n.y2 : n.y1), rb + (cv ? B_Y2 : B_Y1), L.cout, params + L.g_off, params + L.be_off, (float*)AB(arena, P->off_save) + L.save,
-          (int64_t*)fx_of(arena, P, pass, pass ? L.bsum : L.stats), pass ? R_GSV + 2 * k + cv : rb + (cv ? B_ST2 : B_ST1),
+  const bool pruned = P->depth > 0;   // no saved statistics and no fixed-point sums in a pruned plan's arena: an eval forward reads neither
+  return {AB(arena, cv ? n.y2 : n.y1), rb + (cv ? B_Y2 : B_Y1), L.cout, params + L.g_off, params + L.be_off,
+          pruned ? nullptr : (float*)AB(arena, P->off_save) + L.save,
+          pruned ? nullptr : (int64_t*)fx_of(arena, P, pass, pass ? L.bsum : L.stats), pass ? R_GSV + 2 * k + cv : rb + (cv ? B_ST2 : B_ST1),
           pass ? (float*)AB(arena, P->off_gs) + L.gs + 9LL * L.cout * L.cinpad : nullptr};
 }
 template <typename D> static void set_bn(D& b, const BnView& v) {   // nunet_bnr_desc / nunet_bn_bwd_desc: the reduce pass's view
@@ -1176,7 +1218,9 @@ static int set_splitk(nunet_conv_desc& d, const nunet_plan* P, void* arena, int 
 extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnbuf, int64_t* nbt, const float* input, void* arena, size_t arena_bytes, float* logits, int32_t training_flags, nunet_stream_t s) {
   const int32_t training = training_flags & 1;
   const bool staged = (training_flags & 4) != 0;       // the image already sits in the arena (nunet_plan_stage_u8): no layout launch
-  NUNET_REQUIRE(P && params && (input || staged) && arena && logits, "plan_forward: null pointer");
+  NUNET_REQUIRE(P, "plan_forward: null plan");
+  NUNET_REQUIRE(!(training && P->depth), "plan_forward: training mode on a plan pruned to depth %d (nunet_plan_create_pruned): it runs eval forwards only", P->depth);
+  NUNET_REQUIRE(params && (input || staged) && arena && logits, "plan_forward: null pointer");
   ARENA_CHECK("plan_forward");
   NUNET_REQUIRE(bnbuf, "plan_forward: bnbuf (running stats) required");
   hipStream_t st = (hipStream_t)s;
@@ -1349,7 +1393,9 @@ extern "C" int nunet_plan_backward(nunet_plan* P, const float* params, const flo
 }
 
 extern "C" int nunet_plan_grad_scratch(const nunet_plan* P, int64_t* byte_offset, int64_t* bucket0_floats, int64_t* total_floats) {
-  NUNET_REQUIRE(P && byte_offset && bucket0_floats && total_floats, "plan_grad_scratch: null pointer");
+  NUNET_REQUIRE(P, "plan_grad_scratch: null plan");
+  REFUSE_PRUNED("plan_grad_scratch");
+  NUNET_REQUIRE(byte_offset && bucket0_floats && total_floats, "plan_grad_scratch: null pointer");
   *byte_offset = (int64_t)P->off_gs;
   *bucket0_floats = P->gs_bucket0;
   *total_floats = (int64_t)P->gs_floats;
@@ -1432,8 +1478,10 @@ template <typename O> static int launch_unpack_step(nunet_plan* P, void* arena, 
 // (scaled) gradients as nunet_plan_backward would have left them. Adam streams its second state buffer on top.
 extern "C" int nunet_plan_opt_step(nunet_plan* P, float* params, const nunet_optim* opt, void* arena, size_t arena_bytes, float grad_scale,
                                    float* grads, nunet_stream_t s) {
-  NUNET_REQUIRE(P && params && arena, "plan_opt_step: null pointer");
-  CK(opt_check(opt, "plan_opt_step", true));
+  NUNET_REQUIRE(P, "plan_opt_step: null plan");
+  CK(opt_check(opt, "plan_opt_step", true));      // (the caller's descriptor first: a bad one is reported whatever the plan is)
+  REFUSE_PRUNED("plan_opt_step");
+  NUNET_REQUIRE(params && arena, "plan_opt_step: null pointer");
   ARENA_CHECK("plan_opt_step");
   return opt_dispatch(opt, [&](const auto& o) {
     const double bytes = (double)P->nparams * (20.0 + (grads ? 4.0 : 0.0) + 8.0 * (o.NS - 1));
@@ -1479,9 +1527,11 @@ __global__ __launch_bounds__(256) void plan_sqnorm_kernel(const float* __restric
   const double tot = block256_sum_f64(acc, s_w);
   if (threadIdx.x == 0) ws[blockIdx.x] = tot;
 }
-extern "C" size_t nunet_plan_grad_sqnorm_ws_bytes(const nunet_plan* P) { return P ? (size_t)(P->ptab.ntiles + P->utab.n) * sizeof(double) : 0; }
+extern "C" size_t nunet_plan_grad_sqnorm_ws_bytes(const nunet_plan* P) { return (P && !P->depth) ? (size_t)(P->ptab.ntiles + P->utab.n) * sizeof(double) : 0; }
 extern "C" int nunet_plan_grad_sqnorm(nunet_plan* P, const void* arena, size_t arena_bytes, double* ws, size_t ws_bytes, nunet_stream_t s) {
-  NUNET_REQUIRE(P && arena && ws, "plan_grad_sqnorm: null pointer");
+  NUNET_REQUIRE(P, "plan_grad_sqnorm: null plan");
+  REFUSE_PRUNED("plan_grad_sqnorm");
+  NUNET_REQUIRE(arena && ws, "plan_grad_sqnorm: null pointer");
   ARENA_CHECK("plan_grad_sqnorm");
   NUNET_REQUIRE(((uintptr_t)ws & 7) == 0, "plan_grad_sqnorm: ws must be 8-byte aligned");
   NUNET_REQUIRE(ws_bytes >= nunet_plan_grad_sqnorm_ws_bytes(P), "plan_grad_sqnorm: workspace of %zu bytes, nunet_plan_grad_sqnorm_ws_bytes = %zu",
@@ -1556,10 +1606,12 @@ static int launch_reduce(nunet_plan* P, void* arena, int k_lo, int k_hi, hipStre
 //   3     whole pass                    7      whole pass + unpack (nunet_plan_backward)        4   unpack only
 //   1|8   phase 1, pass left open       2|16   continue the open pass with phase 2 and join
 extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, const float* dlogits, void* arena, size_t arena_bytes, float* grads, int32_t accumulate, int32_t phases, nunet_stream_t s) {
+  if (P) REFUSE_PRUNED("plan_backward");
   if (phases != 3 && phases != 7 && phases != 4 && phases != (1 | 8) && phases != (2 | 16)) {
     nunet_set_error("plan_backward: phases %d is not one of 3, 7, 4, 1|8 = 9, 2|16 = 18", (int)phases); return NUNET_EINVAL;
   }
-  NUNET_REQUIRE(P && params && dlogits && arena && grads, "plan_backward: null pointer");
+  NUNET_REQUIRE(P, "plan_backward: null plan");
+  NUNET_REQUIRE(params && dlogits && arena && grads, "plan_backward: null pointer");
   ARENA_CHECK("plan_backward");
   hipStream_t st = (hipStream_t)s;
   const nunet_plan_cfg& c = P->cfg;
@@ -1757,6 +1809,7 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
 // not used (it joins the capture here, as a lane continuation does).
 extern "C" int nunet_plan_bucket0_wait(nunet_plan* P, nunet_stream_t s) {
   NUNET_REQUIRE(P, "plan_bucket0_wait: null plan");
+  REFUSE_PRUNED("plan_bucket0_wait");
   NUNET_REQUIRE(rt_of(P)->open_sched, "plan_bucket0_wait: no open pass (nunet_plan_backward_phase 1|8 comes first)");
   for (hipEvent_t e : rt_of(P)->b0_events)
     if (hipStreamWaitEvent((hipStream_t)s, e, 0) != hipSuccess) { nunet_set_error("plan_bucket0_wait: %s", hipGetErrorString(hipGetLastError())); return NUNET_ELAUNCH; }
@@ -1867,6 +1920,7 @@ extern "C" int nunet_plan_set_schedule(nunet_plan* P, int32_t schedule) {
 
 extern "C" int nunet_plan_set_wgrad_dy(nunet_plan* P, int32_t in_loader) {
   NUNET_REQUIRE(P, "plan_set_wgrad_dy: null plan");
+  REFUSE_PRUNED("plan_set_wgrad_dy");
   NUNET_REQUIRE(in_loader == 0 || in_loader == 1, "plan_set_wgrad_dy: %d is neither 0 (side stores) nor 1 (weight-gradient loaders)", in_loader);
   NUNET_REQUIRE(!rt_of(P)->open_sched, "plan_set_wgrad_dy: a backward pass is open (nunet_plan_backward_phase 1|8): its second phase reads what the first stored");
   rt_of(P)->wgrad_dy = in_loader;
@@ -1876,7 +1930,9 @@ extern "C" int nunet_plan_set_wgrad_dy(nunet_plan* P, int32_t in_loader) {
 // a1 = relu(bn1(y1)) of block (i, j) on demand (nunet_diag.h): the stand-alone BatchNorm kernel on the raw conv output, with the
 // batch sums of the last training forward; the saved mean | invstd it rewrites are the values the forward left there
 extern "C" int nunet_plan_block_act1(nunet_plan* P, const float* params, void* arena, size_t arena_bytes, int32_t i, int32_t j, void* out, nunet_stream_t s) {
-  NUNET_REQUIRE(P && params && arena && out, "plan_block_act1: null pointer");
+  NUNET_REQUIRE(P, "plan_block_act1: null plan");
+  REFUSE_PRUNED("plan_block_act1");
+  NUNET_REQUIRE(params && arena && out, "plan_block_act1: null pointer");
   ARENA_CHECK("plan_block_act1");
   const int k = block_at(P, i, j);
   NUNET_REQUIRE(k >= 0, "plan_block_act1: the plan has no block (%d, %d)", (int)i, (int)j);

@@ -15,12 +15,20 @@ from . import _lib as L
 
 
 class Plan:
-    def __init__(self, n, h, w, cin, ncls, ds, dtype, unet, device):
+    def __init__(self, n, h, w, cin, ncls, ds, dtype, unet, device, depth=None):
+        """depth (1..4): the inference plan pruned to the sub-network of head `depth` (nunet_plan_create_pruned) - one head,
+        a smaller arena, the parameter layout of the whole deep-supervision model; None: the whole network."""
         lib = L.lib()
         cfg = L.PlanCfg(n, h, w, cin, ncls, 1 if ds else 0, dtype, 1 if unet else 0)
-        self.handle = lib.nunet_plan_create(C.byref(cfg))
-        if not self.handle:
-            raise L.NunetError("nunet_plan_create: " + lib.nunet_last_error().decode())
+        if depth is None:
+            self.handle = lib.nunet_plan_create(C.byref(cfg))
+            if not self.handle:
+                raise L.NunetError("nunet_plan_create: " + lib.nunet_last_error().decode())
+        else:
+            self.handle = lib.nunet_plan_create_pruned(C.byref(cfg), int(depth))
+            if not self.handle:
+                raise L.NunetError("nunet_plan_create_pruned: " + lib.nunet_last_error().decode())
+        self.depth = depth
         self.n, self.h, self.w, self.ncls, self.dtype = n, h, w, ncls, dtype
         self.heads = lib.nunet_plan_num_heads(self.handle)
         self.nparams = lib.nunet_plan_param_count(self.handle)
@@ -134,11 +142,11 @@ class Engine:
         return (p0.data_ptr() == base and pl.data_ptr() == base + 4 * self.param_off[-1]
                 and self.bns[0].running_mean.data_ptr() == self.bnbuf.data_ptr())
 
-    def plan(self, n, h, w, cin, ncls, ds, dtype, unet):
-        key = (n, h, w, dtype)
+    def plan(self, n, h, w, cin, ncls, ds, dtype, unet, depth=None):
+        key = (n, h, w, dtype) if depth is None else (n, h, w, dtype, int(depth))
         pl = self.plans.get(key)
         if pl is None:
-            pl = Plan(n, h, w, cin, ncls, ds, dtype, unet, self.device)
+            pl = Plan(n, h, w, cin, ncls, ds, dtype, unet, self.device, depth=depth)
             if pl.nparams != self.flat_params.numel() or pl.nbnbuf != self.bnbuf.numel() or pl.nbn != len(self.bns):
                 raise L.NunetError("plan/module parameter layout mismatch: %d vs %d params" %
                                    (pl.nparams, self.flat_params.numel()))

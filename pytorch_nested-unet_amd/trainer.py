@@ -761,14 +761,16 @@ class _EvalBatch:
         from .engine import Plan
         model, eng, dev = ev.model, ev.eng, ev.eng.device
         self.n = n
-        self.pl = Plan(n, ev.h, ev.w, ev.cin, ev.ncls, getattr(model, "deep_supervision", False), model.compute_dtype, model._unet, dev)
+        self.pl = Plan(n, ev.h, ev.w, ev.cin, ev.ncls, getattr(model, "deep_supervision", False), model.compute_dtype, model._unet, dev,
+                       depth=ev.depth)
         if self.pl.nparams != eng.flat_params.numel() or self.pl.nbnbuf != eng.bnbuf.numel() or self.pl.nbn != len(eng.bns):
             raise L.NunetError("EvalStep: plan/module parameter layout mismatch: %d vs %d params" % (self.pl.nparams, eng.flat_params.numel()))
         self.heads = self.pl.heads
         self.x = torch.zeros((n, ev.cin, ev.h, ev.w), dtype=torch.float32, device=dev)
         self.t = torch.zeros((n, ev.ncls, ev.h, ev.w), dtype=torch.float32, device=dev)
         self.logits = torch.zeros((self.heads, n, ev.ncls, ev.h, ev.w), dtype=torch.float32, device=dev)
-        nb = L.lib().nunet_eval_step_ws_bytes(n, ev.ncls, ev.h * ev.w, self.heads, ev.loss_kind)
+        ws_query = L.lib().nunet_eval_step_heads_ws_bytes if ev.per_head else L.lib().nunet_eval_step_ws_bytes
+        nb = ws_query(n, ev.ncls, ev.h * ev.w, self.heads, ev.loss_kind)
         self.ws = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)        # (the caching allocator hands out 512-byte aligned blocks)
         self.loss_out = torch.zeros(self.heads + 1, dtype=torch.float32, device=dev)    # per head, then their mean
         self.graph = None
@@ -781,8 +783,13 @@ class _EvalBatch:
         lib, eng, pl, st = L.lib(), ev.eng, self.pl, L.stream()
         L.check(lib.nunet_plan_forward(pl.handle, L.ptr(eng.flat_params), L.ptr(eng.bnbuf), L.ptr(eng.nbt), L.ptr(self.x), L.ptr(pl.arena),
                                        L.nbytes(pl.arena), L.ptr(self.logits), 2, st), "plan_forward")
-        L.check(lib.nunet_eval_step(L.ptr(self.logits), L.ptr(self.t), self.n, ev.ncls, ev.h * ev.w, self.heads, ev.loss_kind, L.ptr(self.ws),
-                                    L.nbytes(self.ws), L.ptr(self.loss_out), L.ptr(ev.meters), ev.iou_thr, st), "eval_step")
+        if ev.per_head:
+            L.check(lib.nunet_eval_step_heads(L.ptr(self.logits), L.ptr(self.t), self.n, ev.ncls, ev.h * ev.w, self.heads, ev.loss_kind,
+                                              L.ptr(self.ws), L.nbytes(self.ws), L.ptr(self.loss_out), L.ptr(ev.meters), L.ptr(ev.head_meters),
+                                              ev.iou_thr, st), "eval_step_heads")
+        else:
+            L.check(lib.nunet_eval_step(L.ptr(self.logits), L.ptr(self.t), self.n, ev.ncls, ev.h * ev.w, self.heads, ev.loss_kind, L.ptr(self.ws),
+                                        L.nbytes(self.ws), L.ptr(self.loss_out), L.ptr(ev.meters), ev.iou_thr, st), "eval_step")
         pl.trained_forward = False
 
 
@@ -797,9 +804,22 @@ class EvalStep:
     (created on first use; not padded: the K-split of grid-starved layers depends on N) - the launches the module path makes,
     so `loss` and `iou` equal the module loop's to the bit. begin() / step(xb, tb) / result() are the same pass by hand, for
     a caller that wants `.last_logits` of every batch (val.py's mask export).
-    use_graph=False issues the same launches eagerly."""
+    use_graph=False issues the same launches eagerly.
 
-    def __init__(self, model, batch_shape, loss="BCEDiceLoss", use_graph=True):
+    depth=L (1..4, a deep-supervision NestedUNet): the step's plans - static batch and tail - are pruned to the sub-network of
+    head L (nunet_plan_create_pruned): one head, so result() and last_logits are head L's. per_head=True (a deep-supervision
+    NestedUNet, no depth): the step issues nunet_eval_step_heads, result()["heads"] lists loss / iou / dice / acc / counts /
+    per_class of every head - entry L - 1 is what EvalStep(depth=L) reports - and every other field is unchanged."""
+
+    def __init__(self, model, batch_shape, loss="BCEDiceLoss", use_graph=True, depth=None, per_head=False):
+        if depth is not None:
+            model.check_depth(depth, need_eval=False)     # (the step always runs the eval forward, whatever mode the module is in)
+        if per_head:
+            if depth is not None:
+                raise L.NunetError("EvalStep: per_head=True scores the four heads of the whole network; depth=%r leaves one head" % (depth,))
+            if model._unet or not getattr(model, "deep_supervision", False):
+                raise L.NunetError("EvalStep: per_head=True needs a NestedUNet built with deep_supervision=True (one head otherwise)")
+        self.depth, self.per_head = depth, bool(per_head)
         self.model = model
         self.eng = model.engine()
         n, cin, h, w = batch_shape
@@ -817,7 +837,11 @@ class EvalStep:
         from .metrics import iou_logit_threshold
         self.iou_thr = iou_logit_threshold()
         self.use_graph = use_graph
-        self.meters = torch.zeros(C.sizeof(L.EvalMeters), dtype=torch.uint8, device=self.eng.device)
+        # one buffer: the step's meters, then (per_head) one nunet_eval_meters per head - one fill to zero them, one copy to read them
+        msz = C.sizeof(L.EvalMeters)
+        self._meters_all = torch.zeros((5 if self.per_head else 1) * msz, dtype=torch.uint8, device=self.eng.device)
+        self.meters = self._meters_all[:msz]
+        self.head_meters = self._meters_all[msz:] if self.per_head else None
         self.main = _EvalBatch(self, n)
         self.tail = None
         self._last = self.main
@@ -849,7 +873,7 @@ class EvalStep:
         self._check_engine()
         self.main.repack(self.eng)
         self._packed = {self.main.n}
-        self.meters.zero_()
+        self._zero_meters()
         if self.use_graph and self.main.graph is None:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
@@ -859,7 +883,10 @@ class EvalStep:
             torch.cuda.synchronize()
             self.main.graph = _NativeGraph(s, lambda: self.main.issue(self))
             torch.cuda.synchronize()
-            self.meters.zero_()
+            self._zero_meters()
+
+    def _zero_meters(self):
+        self._meters_all.zero_()
 
     def step(self, xb, tb):
         """One batch of a pass: the static batch size replays the captured step, fewer images run eagerly on a plan of that size."""
@@ -890,13 +917,22 @@ class EvalStep:
         dataset level). One host sync."""
         from collections import OrderedDict
         from .metrics import scores_from_counts
-        m = L.read_struct(self.meters, L.EvalMeters)
-        k = max(m.samples, 1.0)
-        out = OrderedDict([("loss", m.loss_sum / k), ("iou", m.iou_sum / k), ("dice", m.dice_sum / k), ("acc", m.acc_sum / k),
-                           ("samples", int(m.samples))])
         K = self.ncls
-        out["counts"] = OrderedDict((nm, [int(v) for v in getattr(m, nm)[:K]]) for nm in ("tp", "fp", "fn", "tn"))
-        out["per_class"] = scores_from_counts(*out["counts"].values())
+
+        def fields(m, with_samples):
+            k = max(m.samples, 1.0)
+            d = OrderedDict([("loss", m.loss_sum / k), ("iou", m.iou_sum / k), ("dice", m.dice_sum / k), ("acc", m.acc_sum / k)])
+            if with_samples:
+                d["samples"] = int(m.samples)
+            d["counts"] = OrderedDict((nm, [int(v) for v in getattr(m, nm)[:K]]) for nm in ("tp", "fp", "fn", "tn"))
+            d["per_class"] = scores_from_counts(*d["counts"].values())
+            return d
+
+        sz = C.sizeof(L.EvalMeters)
+        raw = self._meters_all.cpu().numpy().tobytes()
+        out = fields(L.EvalMeters.from_buffer_copy(raw[:sz]), True)
+        if self.per_head:
+            out["heads"] = [fields(L.EvalMeters.from_buffer_copy(raw[(h + 1) * sz:(h + 2) * sz]), False) for h in range(self.heads)]
         return out
 
     def evaluate(self, x, t):

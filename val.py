@@ -2,9 +2,14 @@
 """Evaluation driver — counterpart of reference val.py:31-109: rebuild the model from
 models/<name>/config.yml, load model.pth, run the validation split, print the mean IoU and write
 sigmoid(output)*255 masks per class to outputs/<name>/<class>/<id>.jpg (val.py:100-105; PIL here,
-cv2 is not in the image)."""
+cv2 is not in the image).
+
+A checkpoint trained with --deep_supervision true can be cut back at inference time: --depth L (1..4) evaluates and exports
+masks from the network pruned to the blocks that feed head L; --per_head true adds one IoU / Dice / Acc / loss line per head
+of the whole network, so one validation pass shows which depth would do."""
 import argparse
 import os
+import sys
 
 import numpy as np
 import torch
@@ -14,12 +19,17 @@ import nunet_amd
 from nunet_amd import archs
 from nunet_amd.metrics import sigmoid_masks_u8
 from nunet_amd.trainer import EvalStep
+from nunet_amd.utils import str2bool
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--name', default=None, help='model name')
     ap.add_argument('--no_images', action='store_true')
+    ap.add_argument('--depth', default=None, type=int, choices=(1, 2, 3, 4),
+                    help='evaluate the network pruned to head L (needs a checkpoint trained with --deep_supervision true)')
+    ap.add_argument('--per_head', default=False, type=str2bool,
+                    help='also print IoU / Dice / Acc / loss of every head (needs --deep_supervision true)')
     args = ap.parse_args()
     with open('models/%s/config.yml' % args.name) as f:
         config = yaml.load(f, Loader=yaml.FullLoader)
@@ -27,6 +37,10 @@ def main():
     for k in config:
         print('%s: %s' % (k, str(config[k])))
     print('-' * 20)
+    if (args.depth is not None or args.per_head) and not (config['deep_supervision'] and config['arch'] == 'NestedUNet'):
+        print('error: --depth / --per_head need a NestedUNet checkpoint trained with --deep_supervision true '
+              '(models/%s: arch %s, deep_supervision %s)' % (args.name, config['arch'], config['deep_supervision']))
+        sys.exit(2)
     model = archs.__dict__[config['arch']](config['num_classes'], config['input_channels'], config['deep_supervision'],
                                            dtype=config.get('dtype', 'fp32'))
     model.load_state_dict(torch.load('models/%s/model.pth' % config['name'], map_location='cpu'))
@@ -42,7 +56,10 @@ def main():
     if loss == 'LovaszHingeLoss' and config['num_classes'] != 1:
         loss = 'BCEDiceLoss'                                             # (the metrics do not depend on it)
     # the validation step of train.py: forward, IoU / Dice / accuracy of the last head (val.py:92-93) and the meters on the device
-    ev = EvalStep(model, (min(bs, x.size(0)), config['input_channels'], config['input_h'], config['input_w']), loss=loss)
+    shape = (min(bs, x.size(0)), config['input_channels'], config['input_h'], config['input_w'])
+    ev = EvalStep(model, shape, loss=loss, depth=args.depth)
+    # (the per-head table comes from the whole network: a pass of its own beside the pruned one)
+    ev_heads = EvalStep(model, shape, loss=loss, per_head=True) if args.per_head else None
     bs = ev.n
     with torch.no_grad():
         ev.begin()
@@ -57,6 +74,8 @@ def main():
                         Image.fromarray(masks[i, c]).save(
                             os.path.join('outputs', config['name'], str(c), 'val_%04d.jpg' % (k + i)))
     r = ev.result()
+    if args.depth is not None:
+        print('depth: %d' % args.depth)
     print('IoU: %.4f' % r['iou'])
     print('Dice: %.4f' % r['dice'])
     print('Acc: %.4f' % r['acc'])
@@ -66,6 +85,12 @@ def main():
         for c in range(config['num_classes']):
             print('%5d ' % c + ' '.join('%11.4f' % r['per_class'][nm][0][c] for nm in names))
         print('micro ' + ' '.join('%11.4f' % r['per_class'][nm][1] for nm in names))
+    if ev_heads is not None:
+        with torch.no_grad():
+            rh = ev_heads.evaluate(x.cuda(), t.cuda())
+        print('head %9s %9s %9s %9s' % ('IoU', 'Dice', 'Acc', 'loss'))
+        for k, h in enumerate(rh['heads']):
+            print('%4d %9.4f %9.4f %9.4f %9.4f' % (k + 1, h['iou'], h['dice'], h['acc'], h['loss']))
 
 
 if __name__ == '__main__':
