@@ -40,7 +40,7 @@ enum {
   NUNET_ENODEV = -3   /* no gfx950 device / code object */
 };
 
-int nunet_version(void);   /* 104 (additions under the same number: nunet_plan_create_pruned, nunet_plan_depth, nunet_eval_step_heads): nunet_plan_opt_step lost its `repack` argument and nunet_plan_set_inpass_opt is gone (the step always leaves the repack to the next forward). 103: BCEWithLogitsLoss in the loss step; nunet_seg_metrics and nunet_eval_step were added under the same number (additions only). 102: schedule 1 (single-stream) and recording mode 0 (event segments) of 101 are refused, nunet_graph_info reports nodes, edges, lanes */
+int nunet_version(void);   /* 104 (additions under the same number: nunet_plan_create_pruned, nunet_plan_depth, nunet_eval_step_heads; nunet_ema_init, nunet_ema_prepare, nunet_ema_lerp and the ema / ema_params fields of nunet_optim, behind state1): nunet_plan_opt_step lost its `repack` argument and nunet_plan_set_inpass_opt is gone (the step always leaves the repack to the next forward). 103: BCEWithLogitsLoss in the loss step; nunet_seg_metrics and nunet_eval_step were added under the same number (additions only). 102: schedule 1 (single-stream) and recording mode 0 (event segments) of 101 are refused, nunet_graph_info reports nodes, edges, lanes */
 const char* nunet_last_error(void);
 
 /* ------------------------------------------------------------------------ */
@@ -394,6 +394,9 @@ typedef struct {
   const float* adam_scal;  /* Adam: device {step_size, 1/sqrt(bias_correction2)} (nunet_adam_prepare) */
   float* state0;
   float* state1;
+  /* (the EMA pair sits with the state pointers, in front of scaler / clip: those two stay the trailing pair of the struct) */
+  const struct nunet_ema* ema;         /* weight EMA (nunet_ema below) riding in the update launch; NULL: none, the kernels without one */
+  float* ema_params;                   /* the averaged parameters, flat fp32 in parameter order; needed exactly when ema is set */
   const struct nunet_scaler* scaler;   /* dynamic loss scaling (nunet_scaler below); NULL: none, the arithmetic of no scaling */
   const struct nunet_clip* clip;       /* gradient-norm clipping (nunet_clip below); NULL: none, no arithmetic changes */
 } nunet_optim;
@@ -403,7 +406,7 @@ typedef struct {
  * update launch of the step sees the same t. */
 int nunet_adam_prepare(const float* lr_dev, double beta1, double beta2, float* step_dev, float* adam_scal, nunet_stream_t s);
 /* Flat Adam step over n fp32 elements (p, g and the state in the same flat order); g is read as g * grad_scale. Refuses a
- * scaler or a clip: those go through nunet_opt_step. */
+ * scaler, a clip or an ema: those go through nunet_opt_step. */
 int nunet_adam_step(float* p, const float* g, const nunet_optim* opt, int64_t n, float grad_scale, nunet_stream_t s);
 
 /* ------------------------------------------------------------------------ */
@@ -444,7 +447,8 @@ int nunet_adam_prepare_scaled(const float* lr_dev, double beta1, double beta2, f
 /* Flat optimiser step of any kind over n fp32 elements (SGD: nunet_sgd_step's arithmetic; Adam: nunet_adam_step's); g is read
  * as g * grad_scale. With opt->scaler set, the step is skipped on found_inf and g is left holding g * grad_scale * inv_scale
  * (the unscaled gradient) in any case. With opt->clip set, the gradient is read as that times clip->coef, and g is left holding
- * the clipped (unscaled) gradient, as torch's in-place clip leaves p.grad. */
+ * the clipped (unscaled) gradient, as torch's in-place clip leaves p.grad. With opt->ema set (nunet_ema below), the same launch
+ * also moves opt->ema_params towards the parameter it stores; p, g and the optimiser state are what they are without it. */
 int nunet_opt_step(float* p, float* g, const nunet_optim* opt, int64_t n, float grad_scale, nunet_stream_t s);
 
 /* ------------------------------------------------------------------------ */
@@ -478,6 +482,43 @@ int nunet_grad_sqnorm(const float* g, int64_t n, double* ws, size_t ws_bytes, nu
  * scaler->inv_scale : 1)); clip->coef, norm, norm_peak, norm_sum, steps, clipped - or, with scaler->found_inf set, coef = 1 only. */
 int nunet_clip_finalize(const double* ws, int32_t nparts, float grad_scale, const nunet_scaler* scaler, nunet_clip* clip,
                         nunet_stream_t s);
+
+/* ------------------------------------------------------------------------ */
+/* Weight EMA: torch.optim.swa_utils.AveragedModel + get_ema_multi_avg_fn    */
+/* ------------------------------------------------------------------------ */
+/* An exponential moving average of the parameters (and, by nunet_ema_lerp, of the BatchNorm running statistics), kept inside
+ * the step. After every APPLIED optimiser step, with p' the parameter the update stores:
+ *   n_averaged == 0:  ema = p' (a bit-exact copy, AveragedModel's first update_parameters);
+ *   otherwise:        ema = ema + w * (p' - ema) in fp32, w = float(1.0 - d_t) formed in double and rounded once,
+ *                     d_t = decay, or with warmup min(decay, (1 + n_averaged) / (10 + n_averaged));
+ *   n_averaged += 1.
+ * A step skipped by loss scaling (found_inf) writes nothing: neither the average nor n_averaged.
+ * The launches of a step: nunet_ema_prepare (one thread: this step's w and mode from n_averaged, then the bump) after
+ * nunet_scaler_check and before the update; the update with nunet_optim.ema / ema_params set, which carries the average along
+ * (8 bytes per parameter): nunet_plan_opt_step as one more state stream, lerped towards the parameter it holds in registers when
+ * it stores it, nunet_opt_step behind the unchanged walk of the flat step, every thread over the elements it has just stored;
+ * nunet_ema_lerp over the BatchNorm buffers behind it. Every launch reads w and the mode from device memory, so a captured
+ * step replays with a changing w. The state, 32 bytes of DEVICE memory (8-byte aligned): */
+enum { NUNET_EMA_SKIP = 0, NUNET_EMA_LERP = 1, NUNET_EMA_COPY = 2 };
+typedef struct nunet_ema {
+  double decay;             /* in [0, 1); read every step (a double: torch forms 1 - decay from a Python float) */
+  int32_t warmup;           /* nonzero: d_t = min(decay, (1 + n_averaged) / (10 + n_averaged)) */
+  int32_t n_averaged;       /* applied updates so far (AveragedModel.n_averaged) */
+  float w;                  /* this step's lerp weight, written by nunet_ema_prepare */
+  uint32_t live;            /* this step's mode, written by nunet_ema_prepare: NUNET_EMA_SKIP (step skipped by loss scaling: nothing
+                             * is written), NUNET_EMA_LERP or NUNET_EMA_COPY (the first update) */
+  int32_t reserved[2];
+} nunet_ema;
+/* Write *ema on the device (a 1-thread kernel): decay, warmup, n_averaged as given, w = 0, live = NUNET_EMA_SKIP. Refuses a
+ * decay outside [0, 1) and a negative n_averaged. */
+int nunet_ema_init(nunet_ema* ema, double decay, int32_t warmup, int32_t n_averaged, nunet_stream_t s);
+/* This step's w and mode from n_averaged, then n_averaged += 1 - or, with scaler != NULL and scaler->found_inf set, mode
+ * NUNET_EMA_SKIP and nothing else. One thread; issue it after nunet_scaler_check and before the update launches. */
+int nunet_ema_prepare(nunet_ema* ema, const struct nunet_scaler* scaler, nunet_stream_t s);
+/* ema[i] = src[i] (copy mode) or ema[i] + w * (src[i] - ema[i]) over n fp32 values, or nothing on a skipped step: the mode and
+ * w nunet_ema_prepare left in *state. 16-byte loads and stores over the aligned middle, scalars in front of and behind it
+ * (all scalars where ema and src are not congruent modulo 16 bytes). For the BatchNorm running statistics of a step. */
+int nunet_ema_lerp(float* ema, const float* src, int64_t n, const nunet_ema* state, nunet_stream_t s);
 
 /* ------------------------------------------------------------------------ */
 /* layout helpers                                                            */
@@ -572,7 +613,8 @@ int nunet_plan_bucket0_wait(nunet_plan* p, nunet_stream_t s);
  * device memory, grad_scale = 1/world); the next nunet_plan_forward repacks as usual. `grads` (flat OIHW, may be NULL) receives the
  * scaled gradients. SGD needs state0 whatever the momentum. With opt->scaler set (loss scaling) the gradients are read as
  * g * grad_scale * inv_scale, and a step with found_inf set writes only `grads` (nunet_scaler). With opt->clip set they are
- * read as that times clip->coef (nunet_clip), and `grads` receive the clipped gradient. */
+ * read as that times clip->coef (nunet_clip), and `grads` receive the clipped gradient. With opt->ema set the launch carries
+ * opt->ema_params as one more state stream (nunet_ema): every path - 16-byte tiles, scalar tiles, tail entries, heads. */
 int nunet_plan_opt_step(nunet_plan* p, float* params, const nunet_optim* opt, void* arena, size_t arena_bytes, float grad_scale,
                         float* grads, nunet_stream_t s);
 /* Square norm of the gradient in the plan's native-layout scratch (after the backward pass and, data parallel, the exchange):

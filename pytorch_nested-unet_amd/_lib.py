@@ -171,13 +171,17 @@ class Optim(C.Structure):
     """nunet_optim: which optimiser a generic step entry runs, its hyper-parameters and state pointers."""
     _fields_ = [("kind", _i32), ("momentum", _f32), ("beta1", C.c_double), ("beta2", C.c_double),
                 ("eps", _f32), ("weight_decay", _f32), ("nesterov", _i32),
-                ("lr", _vp), ("adam_scal", _vp), ("state0", _vp), ("state1", _vp), ("scaler", _vp), ("clip", _vp)]
+                ("lr", _vp), ("adam_scal", _vp), ("state0", _vp), ("state1", _vp), ("ema", _vp), ("ema_params", _vp), ("scaler", _vp), ("clip", _vp)]
 
 
 SCALER_WORDS = 8    # nunet_scaler: 32 bytes of device memory, [scale f32, inv_scale f32, growth_tracker i32, found_inf u32, skipped i32, 3 reserved]
 
 
 CLIP_WORDS = 8      # nunet_clip: 32 bytes of device memory, [max_norm f32, coef f32, norm f32, norm_peak f32, norm_sum f64 (2 words), clipped i32, steps i32]
+
+
+EMA_WORDS = 8       # nunet_ema: 32 bytes of device memory, [decay f64 (2 words), warmup i32, n_averaged i32, w f32, live u32, 2 reserved]
+EMA_SKIP, EMA_LERP, EMA_COPY = 0, 1, 2      # NUNET_EMA_* in include/nunet.h: the `live` word
 
 
 class PlanCfg(C.Structure):
@@ -237,6 +241,9 @@ _SIG = {
     "nunet_scaler_check": (_i32, [_vp, _i64, _vp, _vp]),
     "nunet_scaler_update": (_i32, [_vp, C.c_double, C.c_double, _i32, _vp]),
     "nunet_adam_prepare_scaled": (_i32, [_vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
+    "nunet_ema_init": (_i32, [_vp, C.c_double, _i32, _i32, _vp]),
+    "nunet_ema_prepare": (_i32, [_vp, _vp, _vp]),
+    "nunet_ema_lerp": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "nunet_opt_step": (_i32, [_vp, _vp, C.POINTER(Optim), _i64, _f32, _vp]),
     "nunet_grad_sqnorm_ws_bytes": (C.c_size_t, [_i64]),
     "nunet_grad_sqnorm": (_i32, [_vp, _i64, _vp, _sz, _vp]),

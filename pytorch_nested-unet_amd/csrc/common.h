@@ -436,6 +436,29 @@ struct OptAdam {  // torch.optim.Adam, amsgrad=False, maximize=False, L2 decay i
     return p - step_size * (m / denom);                     // param.addcdiv_(exp_avg, denom, value=-step_size)
   }
 };
+// Weight EMA (nunet_optim.ema != NULL, nunet_ema): a wrapper around either functor with the averaged parameters as one more
+// state stream. one() runs the wrapped step, then moves the last stream towards the parameter it returns - copied on the
+// first update, lerped with this step's w otherwise; both words were written by ema_prepare_kernel in an earlier launch, so
+// the choice is uniform over the launch. A skipped step is the wrapped functor's: begin() returns false and nothing is stored.
+// The plan's tile kernel (plan.hip) runs it as it is; the flat step (elementwise.hip launch_flat) unwraps it.
+template <typename O> struct OptEma {
+  static constexpr int NS = O::NS + 1;
+  float* st[O::NS + 1];     // the wrapped functor's streams, then ema_params
+  O in;
+  const nunet_ema* em;
+  float w;
+  bool copy;
+  __device__ __forceinline__ bool begin(float& gscale) {
+    w = em->w; copy = em->live == NUNET_EMA_COPY;
+    return in.begin(gscale);
+  }
+  __device__ __forceinline__ float one(float p, float g, float* s) const {
+    const float pn = in.one(p, g, s);
+    const float e = s[O::NS];
+    s[O::NS] = copy ? pn : e + w * (pn - e);
+    return pn;
+  }
+};
 // one element at flat index idx: state in, step, state out; returns the new parameter (the caller stores it)
 template <typename O> __device__ __forceinline__ float opt_elem(const O& o, float p, float g, long long idx) {
   float s[O::NS];
@@ -458,6 +481,9 @@ static inline int opt_check(const nunet_optim* o, const char* what, bool need_sg
   NUNET_REQUIRE(sgd || (o->adam_scal && o->state0 && o->state1), "%s: Adam needs adam_scal, state0 (exp_avg) and state1 (exp_avg_sq)", what);
   NUNET_REQUIRE(sgd || (o->beta1 >= 0.0 && o->beta1 < 1.0 && o->beta2 >= 0.0 && o->beta2 < 1.0), "%s: betas must lie in [0, 1)", what);
   NUNET_REQUIRE(sgd || o->eps > 0.f, "%s: eps must be > 0", what);
+  NUNET_REQUIRE(!o->ema || o->ema_params, "%s: an ema needs ema_params (the averaged parameters)", what);
+  NUNET_REQUIRE(o->ema || !o->ema_params, "%s: ema_params without an ema", what);
+  NUNET_REQUIRE(((uintptr_t)o->ema & 7) == 0 && ((uintptr_t)o->ema_params & 3) == 0, "%s: ema must be 8-byte aligned, ema_params 4-byte aligned", what);
   return NUNET_OK;
 }
 static inline OptSgd opt_sgd(const nunet_optim* d) {
@@ -471,6 +497,14 @@ static inline OptAdam opt_adam(const nunet_optim* d) {
   o.omb1 = (float)(1.0 - d->beta1); o.b2 = (float)d->beta2; o.omb2 = (float)(1.0 - d->beta2);
   return o;
 }
-template <class F> static inline int opt_dispatch(const nunet_optim* o, F&& f) {   // f(functor of o->kind); `o` has passed opt_check
+template <typename O> static inline OptEma<O> opt_ema(const O& in, const nunet_optim* d) {
+  OptEma<O> o; memset(&o, 0, sizeof(o));
+  for (int k = 0; k < O::NS; ++k) o.st[k] = in.st[k];
+  o.st[O::NS] = d->ema_params; o.in = in; o.em = d->ema;
+  return o;
+}
+// f(functor of o->kind, wrapped in OptEma when o->ema is set); `o` has passed opt_check
+template <class F> static inline int opt_dispatch(const nunet_optim* o, F&& f) {
+  if (o->ema) return o->kind == NUNET_OPT_ADAM ? f(opt_ema(opt_adam(o), o)) : f(opt_ema(opt_sgd(o), o));
   return o->kind == NUNET_OPT_ADAM ? f(opt_adam(o)) : f(opt_sgd(o));
 }

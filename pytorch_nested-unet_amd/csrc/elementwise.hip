@@ -1954,20 +1954,24 @@ extern "C" int nunet_loss_launch_info(int32_t entry, int32_t N, int64_t per_or_n
 // ---------------------------------------------------------------------------
 // SGD with momentum / weight decay / nesterov (torch.optim.SGD semantics)
 // ---------------------------------------------------------------------------
+// (the body is a macro so that sgd_ema_kernel below repeats it token for token: a step with a weight EMA must leave the bits of
+//  the step without one, and how the compiler contracts this arithmetic depends on the code it is inlined into)
+#define SGD_KERNEL_BODY                                                                                                        \
+  const float lr = lr_dev[0];                                                                                                  \
+  if (!scale_begin(sc, cl, gscale)) return;  /* loss scaling: a skipped step writes nothing; clipping: coef folded in */      \
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {              \
+    float pv = p[i];                                                                                                           \
+    float gv = g[i] * gscale + wd * pv;                                                                                        \
+    if (mom != 0.f) {                                                                                                          \
+      const float b = first ? gv : mom * m[i] + gv;                                                                            \
+      m[i] = b;                                                                                                                \
+      gv = nesterov ? gv + mom * b : b;                                                                                        \
+    }                                                                                                                          \
+    p[i] = pv - lr * gv;                                                                                                       \
+  }
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, int64_t n, const float* __restrict__ lr_dev, float mom, float wd, int nesterov, int first, float gscale,
                                                   const nunet_scaler* __restrict__ sc, const nunet_clip* __restrict__ cl) {
-  const float lr = lr_dev[0];
-  if (!scale_begin(sc, cl, gscale)) return;  // loss scaling: a skipped step writes nothing; clipping: coef folded in
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    float pv = p[i];
-    float gv = g[i] * gscale + wd * pv;
-    if (mom != 0.f) {
-      const float b = first ? gv : mom * m[i] + gv;
-      m[i] = b;
-      gv = nesterov ? gv + mom * b : b;
-    }
-    p[i] = pv - lr * gv;
-  }
+  SGD_KERNEL_BODY
 }
 
 // ---------------------------------------------------------------------------
@@ -2000,38 +2004,84 @@ extern "C" int nunet_adam_prepare_scaled(const float* lr_dev, double beta1, doub
 }
 
 // Flat step: four elements per thread as 16-byte runs when every array is 16-byte aligned, scalar tail for n % 4
+// (a macro for the reason SGD_KERNEL_BODY is one: adam_ema_kernel below repeats it token for token)
+#define ADAM_KERNEL_BODY                                                                                                       \
+  if (!o.begin(gscale)) return;              /* loss scaling: a skipped step writes nothing */                                \
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;                   \
+  const int64_t n4 = vec ? n / 4 : 0;                                                                                          \
+  for (int64_t i = tid; i < n4; i += nth) {                                                                                    \
+    f32x4 pv = reinterpret_cast<const f32x4*>(p)[i];                                                                           \
+    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];                                                                     \
+    f32x4 mv = reinterpret_cast<const f32x4*>(o.st[0])[i], vv = reinterpret_cast<const f32x4*>(o.st[1])[i];                    \
+    _Pragma("unroll")                                                                                                          \
+    for (int j = 0; j < 4; ++j) {                                                                                              \
+      float s[2] = {mv[j], vv[j]};                                                                                             \
+      pv[j] = o.one(pv[j], gv[j] * gscale, s);                                                                                 \
+      mv[j] = s[0];                                                                                                            \
+      vv[j] = s[1];                                                                                                            \
+    }                                                                                                                          \
+    reinterpret_cast<f32x4*>(o.st[0])[i] = mv;                                                                                 \
+    reinterpret_cast<f32x4*>(o.st[1])[i] = vv;                                                                                 \
+    reinterpret_cast<f32x4*>(p)[i] = pv;                                                                                       \
+  }                                                                                                                            \
+  for (int64_t i = 4 * n4 + tid; i < n; i += nth) p[i] = opt_elem(o, p[i], g[i] * gscale, i);
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, OptAdam o, int64_t n, float gscale, int vec) {
-  if (!o.begin(gscale)) return;              // loss scaling: a skipped step writes nothing
+  ADAM_KERNEL_BODY
+}
+
+// The flat step with a weight EMA (nunet_optim.ema): the body of the step without one - the same tokens, so p and the optimiser
+// state are the bits of that step whatever the compiler makes of the arithmetic - and behind it, in the same launch, every
+// thread moves the average towards the parameters it has just stored (its own elements, in the same order: four per thread
+// as a 16-byte run where the step took them so, single elements else). OptEma (common.h) is unwrapped here: the plan's tile
+// kernel is the one that carries the average as a stream of the functor.
+__device__ __forceinline__ void ema_follow(float* __restrict__ ema, const float* p, int64_t n, int vec, int evec, float w, bool copy) {
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
   const int64_t n4 = vec ? n / 4 : 0;
   for (int64_t i = tid; i < n4; i += nth) {
-    f32x4 pv = reinterpret_cast<const f32x4*>(p)[i];
-    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
-    f32x4 mv = reinterpret_cast<const f32x4*>(o.st[0])[i], vv = reinterpret_cast<const f32x4*>(o.st[1])[i];
+    const f32x4 pv = reinterpret_cast<const f32x4*>(p)[i];
+    if (evec) {
+      f32x4 ev = reinterpret_cast<const f32x4*>(ema)[i];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float s[2] = {mv[j], vv[j]};
-      pv[j] = o.one(pv[j], gv[j] * gscale, s);
-      mv[j] = s[0];
-      vv[j] = s[1];
+      for (int j = 0; j < 4; ++j) ev[j] = copy ? pv[j] : ev[j] + w * (pv[j] - ev[j]);
+      reinterpret_cast<f32x4*>(ema)[i] = ev;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { const float e = ema[4 * i + j]; ema[4 * i + j] = copy ? pv[j] : e + w * (pv[j] - e); }
     }
-    reinterpret_cast<f32x4*>(o.st[0])[i] = mv;
-    reinterpret_cast<f32x4*>(o.st[1])[i] = vv;
-    reinterpret_cast<f32x4*>(p)[i] = pv;
   }
-  for (int64_t i = 4 * n4 + tid; i < n; i += nth) p[i] = opt_elem(o, p[i], g[i] * gscale, i);
+  for (int64_t i = 4 * n4 + tid; i < n; i += nth) { const float e = ema[i]; ema[i] = copy ? p[i] : e + w * (p[i] - e); }
+}
+__global__ __launch_bounds__(256) void sgd_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, int64_t n, const float* __restrict__ lr_dev, float mom, float wd, int nesterov, int first, float gscale,
+                                                      const nunet_scaler* __restrict__ sc, const nunet_clip* __restrict__ cl, float* __restrict__ ema,
+                                                      const nunet_ema* __restrict__ em) {
+  SGD_KERNEL_BODY
+  ema_follow(ema, p, n, 0, 0, em->w, em->live == NUNET_EMA_COPY);
+}
+__global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, OptAdam o, int64_t n, float gscale, int vec, float* __restrict__ ema,
+                                                       int evec, const nunet_ema* __restrict__ em) {
+  ADAM_KERNEL_BODY
+  ema_follow(ema, p, n, vec, evec, em->w, em->live == NUNET_EMA_COPY);
 }
 
-// The flat step (layout 0) of a validated nunet_optim, either kind: one launch of sgd_kernel / adam_kernel
+// The flat step (layout 0) of a validated nunet_optim, either kind: one launch of sgd_kernel / adam_kernel, or of
+// sgd_ema_kernel / adam_ema_kernel when the descriptor carries an ema
 static void launch_flat(float* p, const float* g, const nunet_optim* opt, int64_t n, float grad_scale, int first, hipStream_t st) {
   const dim3 grid(grid_for(n, 256 * 4, 2048)), blk(256);
   opt_dispatch(opt, [&](auto o) {
-    ProfScope ps(PC_SGD, 0, (double)n * (o.NS == 2 ? 28 : 20), st);
-    if constexpr (std::is_same<decltype(o), OptSgd>::value) {
+    using O = decltype(o);
+    ProfScope ps(PC_SGD, 0, (double)n * (12 + 8 * O::NS), st);
+    if constexpr (std::is_same<O, OptSgd>::value) {
       NUNET_LAUNCH(sgd_kernel, grid, blk, 0, st, p, g, o.st[0], n, o.lr_dev, o.momc, o.wd, o.nesterov, first, grad_scale, o.sc, o.cl);
-    } else {
+    } else if constexpr (std::is_same<O, OptAdam>::value) {
       const int vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)o.st[0] | (uintptr_t)o.st[1]) & 15) == 0;
       NUNET_LAUNCH(adam_kernel, grid, blk, 0, st, p, g, o, n, grad_scale, vec);
+    } else if constexpr (std::is_same<O, OptEma<OptSgd>>::value) {
+      NUNET_LAUNCH(sgd_ema_kernel, grid, blk, 0, st, p, g, o.in.st[0], n, o.in.lr_dev, o.in.momc, o.in.wd, o.in.nesterov, first, grad_scale, o.in.sc, o.in.cl,
+                   o.st[1], o.em);
+    } else {
+      const int vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)o.in.st[0] | (uintptr_t)o.in.st[1]) & 15) == 0;     // (adam_kernel's)
+      const int evec = vec && ((uintptr_t)o.st[2] & 15) == 0;
+      NUNET_LAUNCH(adam_ema_kernel, grid, blk, 0, st, p, g, o.in, n, grad_scale, vec, o.st[2], evec, o.em);
     }
     return (int)NUNET_OK;
   });
@@ -2049,6 +2099,7 @@ extern "C" int nunet_adam_step(float* p, const float* g, const nunet_optim* opt,
   NUNET_REQUIRE(opt->kind == NUNET_OPT_ADAM, "adam_step: optimiser kind %d is not NUNET_OPT_ADAM", (int)opt->kind);
   NUNET_REQUIRE(!opt->scaler, "adam_step: loss scaling goes through nunet_opt_step");
   NUNET_REQUIRE(!opt->clip, "adam_step: gradient clipping goes through nunet_opt_step");
+  NUNET_REQUIRE(!opt->ema, "adam_step: a weight EMA goes through nunet_opt_step");
   if (const int rc = opt_check(opt, "adam_step", false)) return rc;
   launch_flat(p, g, opt, n, grad_scale, 0, (hipStream_t)s);
   return nunet_check_launch("adam_step");
@@ -2135,6 +2186,84 @@ extern "C" int nunet_opt_step(float* p, float* g, const nunet_optim* opt, int64_
     NUNET_LAUNCH(unscale_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, st, g, n, grad_scale, opt->scaler, opt->clip, vec);
   }
   return nunet_check_launch("opt_step");
+}
+
+// ---------------------------------------------------------------------------
+// Weight EMA (torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn on the device; include/nunet.h nunet_ema)
+// ---------------------------------------------------------------------------
+__global__ void ema_init_kernel(nunet_ema* __restrict__ e, double decay, int warmup, int n_averaged) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  e->decay = decay; e->warmup = warmup; e->n_averaged = n_averaged;
+  e->w = 0.f; e->live = NUNET_EMA_SKIP; e->reserved[0] = 0; e->reserved[1] = 0;
+}
+extern "C" int nunet_ema_init(nunet_ema* ema, double decay, int32_t warmup, int32_t n_averaged, nunet_stream_t s) {
+  NUNET_REQUIRE(ema && ((uintptr_t)ema & 7) == 0, "ema_init: ema must be a non-null, 8-byte aligned device pointer");
+  NUNET_REQUIRE(decay >= 0.0 && decay < 1.0, "ema_init: decay must lie in [0, 1) (got %g)", decay);
+  NUNET_REQUIRE(n_averaged >= 0, "ema_init: n_averaged must be >= 0 (got %d)", (int)n_averaged);
+  NUNET_LAUNCH(ema_init_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, ema, decay, warmup ? 1 : 0, (int)n_averaged);
+  return nunet_check_launch("ema_init");
+}
+
+// One thread: this step's mode and w from n_averaged (the first update copies; then w = float(1 - d_t), the difference formed
+// in double and rounded once, as torch's lerp_ receives its Python-float weight), then the bump. A step skipped by loss
+// scaling gets mode SKIP and counts nowhere.
+__global__ void ema_prepare_kernel(nunet_ema* __restrict__ e, const nunet_scaler* __restrict__ sc) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  if (sc && sc->found_inf) { e->live = NUNET_EMA_SKIP; return; }
+  const int n = e->n_averaged;
+  if (n == 0) {
+    e->w = 1.f;
+    e->live = NUNET_EMA_COPY;
+  } else {
+    double d = e->decay;
+    if (e->warmup) {
+      const double dw = (1.0 + (double)n) / (10.0 + (double)n);
+      d = dw < d ? dw : d;
+    }
+    e->w = (float)(1.0 - d);
+    e->live = NUNET_EMA_LERP;
+  }
+  e->n_averaged = n + 1;
+}
+extern "C" int nunet_ema_prepare(nunet_ema* ema, const nunet_scaler* scaler, nunet_stream_t s) {
+  NUNET_REQUIRE(ema && ((uintptr_t)ema & 7) == 0, "ema_prepare: ema must be a non-null, 8-byte aligned device pointer");
+  NUNET_REQUIRE(((uintptr_t)scaler & 3) == 0, "ema_prepare: scaler must be 4-byte aligned");
+  NUNET_LAUNCH(ema_prepare_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, ema, scaler);
+  return nunet_check_launch("ema_prepare");
+}
+
+// ema <- src (copy mode) or ema + w * (src - ema): 16-byte runs over the middle that starts `head` floats in (where both
+// pointers reach a 16-byte boundary; vec 0: they never do together), scalars in front of and behind it
+__global__ __launch_bounds__(256) void ema_lerp_kernel(float* __restrict__ ema, const float* __restrict__ src, int64_t n, int64_t head, int vec,
+                                                       const nunet_ema* __restrict__ e) {
+  const uint32_t mode = e->live;
+  if (mode == NUNET_EMA_SKIP) return;        // a step skipped by loss scaling writes nothing
+  const bool copy = mode == NUNET_EMA_COPY;
+  const float w = e->w;
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+  const int64_t n4 = vec ? (n - head) / 4 : 0;
+  f32x4* e4 = reinterpret_cast<f32x4*>(ema + head);
+  const f32x4* s4 = reinterpret_cast<const f32x4*>(src + head);
+  for (int64_t i = tid; i < n4; i += nth) {
+    const f32x4 sv = s4[i];
+    f32x4 ev = e4[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ev[j] = copy ? sv[j] : ev[j] + w * (sv[j] - ev[j]);
+    e4[i] = ev;
+  }
+  for (int64_t i = tid; i < head; i += nth) ema[i] = copy ? src[i] : ema[i] + w * (src[i] - ema[i]);
+  for (int64_t i = head + 4 * n4 + tid; i < n; i += nth) ema[i] = copy ? src[i] : ema[i] + w * (src[i] - ema[i]);
+}
+extern "C" int nunet_ema_lerp(float* ema, const float* src, int64_t n, const nunet_ema* state, nunet_stream_t s) {
+  NUNET_REQUIRE(ema && src && state && n > 0, "ema_lerp: bad args");
+  NUNET_REQUIRE((((uintptr_t)ema | (uintptr_t)src) & 3) == 0 && ((uintptr_t)state & 7) == 0,
+                "ema_lerp: ema and src must be 4-byte aligned, state 8-byte aligned");
+  const int vec = ((uintptr_t)ema & 15) == ((uintptr_t)src & 15);
+  int64_t head = vec ? (int64_t)(((16 - ((uintptr_t)ema & 15)) & 15) / 4) : 0;     // scalars in front of the first 16-byte boundary
+  if (head > n) head = n;
+  ProfScope ps(PC_SGD, 0, (double)n * 12, (hipStream_t)s);
+  NUNET_LAUNCH(ema_lerp_kernel, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, (hipStream_t)s, ema, src, n, head, vec, state);
+  return nunet_check_launch("ema_lerp");
 }
 
 // ---------------------------------------------------------------------------

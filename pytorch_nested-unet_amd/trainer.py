@@ -54,7 +54,7 @@ class TrainStep:
     def __init__(self, model, batch_shape, lr=1e-3, momentum=0.9, weight_decay=1e-4, nesterov=False,
                  use_graph=True, process_group=None, keep_grads=True, fused_update=None, loss="BCEDiceLoss", input_u8=False,
                  schedule=None, segmented=None, optimizer="SGD", betas=(0.9, 0.999), eps=1e-8, loss_scale=None,
-                 clip_grad_norm=None):
+                 clip_grad_norm=None, ema_decay=None, ema_warmup=False):
         """loss: 'BCEDiceLoss' (reference losses.py:103-117, the default of trains.py:58), 'LovaszHingeLoss'
         (losses.py:120-129, the loss of the reference's published table README.md:102-108; one class only) or
         'BCEWithLogitsLoss' (torch.nn.BCEWithLogitsLoss(), trains.py:27-28,210-211; any num_classes: its gradient needs no
@@ -87,7 +87,18 @@ class TrainStep:
         pass takes the 2-norm of the final (rank-mean, unscaled) gradient in double, in a fixed summation order; a one-workgroup
         launch forms coef = min(1, max_norm / (norm + 1e-6)) and the statistics; the update reads g * coef. float('inf')
         measures and never clips (bit-identical to None). set_clip_grad_norm() changes the threshold of a captured step,
-        grad_norm_stats() reads the norms."""
+        grad_norm_stats() reads the norms.
+        ema_decay: None (default: no averaging, today's launches) or a decay in [0, 1): an exponential moving average of the
+        weights, torch.optim.swa_utils.AveragedModel(model, multi_avg_fn=get_ema_multi_avg_fn(decay), use_buffers=True) with one
+        update_parameters(model) per applied step, inside the captured step. self.ema_params / self.ema_bnbuf (flat fp32, the
+        order of Engine.flat_params / Engine.bnbuf) start as copies of the live arenas; the first applied step copies, every
+        later one moves them by w = float(1 - d_t) towards the updated parameters (in the update launch, which holds them in
+        registers) and the BatchNorm running statistics this step's forward left (one small launch); a step skipped by loss
+        scaling leaves the average and n_averaged untouched. ema_warmup: d_t = min(decay, (1 + n_averaged) / (10 + n_averaged)).
+        num_batches_tracked is NOT averaged: ema_state_dict() carries the live model's value (torch's integer branch truncates
+        the average of a counter to nonsense, and the eval forward never reads it). Under data parallel the average is a
+        deterministic function of identical parameters: no collective. EvalStep(weights=(ts.ema_params, ts.ema_bnbuf))
+        validates the averaged model; ema_state_dict() / load_ema_state_dict() / ema_stats() speak to the host."""
         self.model = model
         self.eng = model.engine()
         dev = self.eng.device
@@ -170,6 +181,19 @@ class TrainStep:
                 raise L.NunetError("TrainStep: clip_grad_norm must be > 0 or None (got %r)" % (clip_grad_norm,))
             self._clip = torch.zeros(L.CLIP_WORDS, dtype=torch.int32, device=dev)
             self._clip[0:2] = torch.tensor([float(clip_grad_norm), 1.0], dtype=torch.float32).view(torch.int32).to(dev)
+        # weight EMA: the averaged arenas and the nunet_ema words on the device (decay, warmup, n_averaged, this step's w and mode)
+        self._ema = None
+        self.ema_params = self.ema_bnbuf = None
+        self.ema_decay, self.ema_warmup = None, bool(ema_warmup)
+        if ema_decay is not None:
+            from . import ema as EMA
+            self.ema_decay = EMA.check_decay(ema_decay)
+            self.ema_params = self.eng.flat_params.clone()
+            self.ema_bnbuf = self.eng.bnbuf.clone()
+            self._ema = torch.zeros(L.EMA_WORDS, dtype=torch.int32, device=dev)
+            self._write_ema(0)
+            self._optim.ema = L.ptr(self._ema).value
+            self._optim.ema_params = L.ptr(self.ema_params).value
         if self._scaler is not None:
             self._optim.scaler = L.ptr(self._scaler).value
         if self._clip is not None:
@@ -220,10 +244,13 @@ class TrainStep:
 
     def broadcast_state(self, src=0):
         """Rank `src`'s parameters, optimiser state (momentum; Adam's moments and step), loss-scaler state, clip state (max_norm
-        and statistics) and BatchNorm buffers become every rank's (construction time; also after loading a checkpoint on one rank)."""
+        and statistics), weight EMA (decay, warmup, n_averaged, the averaged parameters and BatchNorm statistics) and BatchNorm
+        buffers become every rank's (construction time; also after loading a checkpoint on one rank)."""
         eng = self.eng
-        for t in [eng.flat_params] + self.opt_state + [eng.bnbuf] + self._aux_state():
+        for t in [eng.flat_params] + self.opt_state + [eng.bnbuf] + self._aux_state() + self._ema_arenas():
             broadcast_flat_(t, src, self.pg)
+        if self._ema is not None and self.world > 1:
+            self.ema_decay, self.ema_warmup = self._read_ema()[:2]
         nbt = eng.nbt.to(torch.float64)          # (gloo / RCCL both take floating tensors; counts are exact in fp64)
         broadcast_flat_(nbt, src, self.pg)
         eng.nbt.copy_(nbt.to(torch.int64))
@@ -234,6 +261,8 @@ class TrainStep:
         if self.world > 1:
             eng = self.eng
             broadcast_flat_(eng.bnbuf, src, self.pg)
+            if self._ema is not None:        # (the averaged statistics follow the statistics they average: per replica, rank `src`'s win)
+                broadcast_flat_(self.ema_bnbuf, src, self.pg)
             nbt = eng.nbt.to(torch.float64)
             broadcast_flat_(nbt, src, self.pg)
             eng.nbt.copy_(nbt.to(torch.int64))
@@ -275,8 +304,12 @@ class TrainStep:
         self._bwd(3 if self.fused_update else 7)
 
     def _aux_state(self):
-        """The scaler and clip words, where present: snapshotted by capture() and broadcast with the replica state."""
-        return [t for t in (self._scaler, self._clip) if t is not None]
+        """The scaler, clip and EMA words, where present: snapshotted by capture() and broadcast with the replica state."""
+        return [t for t in (self._scaler, self._clip, self._ema) if t is not None]
+
+    def _ema_arenas(self):
+        """The averaged parameters and BatchNorm statistics, where present (snapshotted and broadcast like the state words)."""
+        return [] if self._ema is None else [self.ema_params, self.ema_bnbuf]
 
     def _clip_coef(self, plan, grad_scale):
         """This step's clip factor: the square norm of the plan's gradient scratch (plan=True) or of the flat gradients, one
@@ -292,7 +325,9 @@ class TrainStep:
     def _opt(self):
         """The optimiser step, behind the complete (exchanged) gradient scratch. Under loss scaling and / or gradient clipping in
         torch's order: overflow check, Adam's bookkeeping unless skipped, the norm of the unscaled gradient and the clip factor,
-        the update (unscaled by inv_scale, clipped by coef; nothing written on a skipped step), the scale update."""
+        the update (unscaled by inv_scale, clipped by coef; nothing written on a skipped step), the scale update. With a weight
+        EMA: its one-thread bookkeeping (this step's w and mode, n_averaged) ahead of the norm, the averaged parameters inside
+        the update launch, the averaged BatchNorm statistics behind it."""
         lib, eng, pl, st = L.lib(), self.eng, self.pl, L.stream()
         sc = L.ptr(self._scaler)
         if sc is not None:
@@ -300,6 +335,8 @@ class TrainStep:
             if self.optimizer == "Adam":
                 L.check(lib.nunet_adam_prepare_scaled(L.ptr(self.lr), self.betas[0], self.betas[1], L.ptr(self.adam_step), L.ptr(self.adam_scal),
                                                       sc, st), "adam_prepare_scaled")
+        if self._ema is not None:
+            L.check(lib.nunet_ema_prepare(L.ptr(self._ema), sc, st), "ema_prepare")
         if self.fused_update:              # layout 2: gradient scratch -> step in one launch
             if self._clip is not None:
                 self._clip_coef(True, 1.0 / self.world)
@@ -312,6 +349,8 @@ class TrainStep:
                 self._clip_coef(False, 1.0)
             L.check(lib.nunet_opt_step(L.ptr(eng.flat_params), L.ptr(eng.flat_grads), C.byref(self._optim), eng.flat_params.numel(), 1.0, st),
                     "opt_step")
+        if self._ema is not None:
+            L.check(lib.nunet_ema_lerp(L.ptr(self.ema_bnbuf), L.ptr(eng.bnbuf), eng.bnbuf.numel(), L.ptr(self._ema), st), "ema_lerp")
         if sc is not None:
             cfg = self.scaler_cfg
             L.check(lib.nunet_scaler_update(sc, cfg["growth_factor"], cfg["backoff_factor"], cfg["growth_interval"], st), "scaler_update")
@@ -378,8 +417,8 @@ class TrainStep:
     def capture(self, inp, target):
         """Capture forward+loss+backward(+SGD) into hipGraphs. Needs one REAL batch for the
         eager warm-up (an all-zero batch gives degenerate BatchNorm variances). Parameters,
-        BN running statistics, momentum and meters are snapshotted before and restored after,
-        so warm-up and capture leave no trace in the training trajectory."""
+        BN running statistics, momentum, meters and the weight EMA (averaged arenas, n_averaged) are
+        snapshotted before and restored after, so warm-up and capture leave no trace in the training trajectory."""
         if not self.use_graph:
             return
         eng = self.eng
@@ -390,7 +429,7 @@ class TrainStep:
         else:
             self.x.copy_(inp)
             self.t.copy_(target)
-        state = [eng.flat_params, eng.bnbuf, eng.nbt, self.meters] + self.opt_state + self._aux_state()
+        state = [eng.flat_params, eng.bnbuf, eng.nbt, self.meters] + self.opt_state + self._aux_state() + self._ema_arenas()
         snap = [t.clone() for t in state]
         steps0 = self.steps
         s = torch.cuda.Stream()
@@ -697,6 +736,50 @@ class TrainStep:
         return dict(last=float(f[2]), mean=float(w[4:6].view(torch.float64).item()) / max(steps, 1), peak=float(f[3]),
                     clipped=int(w[6]), steps=steps)
 
+    # -- weight EMA ------------------------------------------------------------------
+    def _need_ema(self, what):
+        if self._ema is None:
+            raise L.NunetError("%s: this TrainStep was built without a weight EMA (ema_decay=None)" % what)
+
+    def _write_ema(self, n_averaged):
+        """Set the device EMA words: this step's decay and warmup, n_averaged as given, w and the mode cleared."""
+        L.check(L.lib().nunet_ema_init(L.ptr(self._ema), self.ema_decay, 1 if self.ema_warmup else 0, int(n_averaged), L.stream()), "ema_init")
+
+    def _read_ema(self):
+        """(decay, warmup, n_averaged, w, mode) of the device words; one host sync."""
+        torch.cuda.current_stream().synchronize()
+        w = self._ema.cpu()
+        return (float(w[0:2].view(torch.float64).item()), bool(w[2]), int(w[3]), float(w[4:5].view(torch.float32).item()), int(w[5]))
+
+    def ema_stats(self):
+        """dict(n_averaged, w): the applied updates so far and the lerp weight of the last one (1.0 after the first, which
+        copies; 0.0 before any); one host sync. None without a weight EMA."""
+        if self._ema is None:
+            return None
+        _, _, n, w, _ = self._read_ema()
+        return dict(n_averaged=n, w=w)
+
+    def ema_state_dict(self):
+        """The averaged model as a state dict: model.state_dict()'s keys, shapes and dtypes, the parameters from ema_params,
+        the BatchNorm running statistics from ema_bnbuf, num_batches_tracked from the live model (it is not averaged: see
+        __init__). The tensors are copies. One host sync."""
+        from . import ema as EMA
+        self._need_ema("ema_state_dict")
+        torch.cuda.current_stream().synchronize()
+        return EMA.state_dict_from_flat(self.model, self.eng, self.ema_params, self.ema_bnbuf)
+
+    def load_ema_state_dict(self, sd, n_averaged=None):
+        """Inverse of ema_state_dict(): the parameters and running statistics of `sd` become the average (num_batches_tracked
+        is ignored). n_averaged: the count to continue from (0: the next applied step copies); None keeps this step's. Under
+        data parallel, call it on every rank (or on one, then broadcast_state())."""
+        from . import ema as EMA
+        self._need_ema("load_ema_state_dict")
+        EMA.flat_from_state_dict(self.model, self.eng, sd, self.ema_params, self.ema_bnbuf)
+        if n_averaged is not None:
+            if int(n_averaged) < 0:
+                raise L.NunetError("load_ema_state_dict: n_averaged must be >= 0 (got %r)" % (n_averaged,))
+            self._write_ema(int(n_averaged))
+
     # -- loss scaling ----------------------------------------------------------------
     def _write_scaler(self, scale, tracker, skipped=None):
         """Set the device scaler words (scale, its inverse as torch forms it, growth tracker; found_inf cleared)."""
@@ -775,13 +858,13 @@ class _EvalBatch:
         self.loss_out = torch.zeros(self.heads + 1, dtype=torch.float32, device=dev)    # per head, then their mean
         self.graph = None
 
-    def repack(self, eng):
-        L.check(L.lib().nunet_plan_repack(self.pl.handle, L.ptr(eng.flat_params), L.ptr(self.pl.arena), L.nbytes(self.pl.arena), L.stream()), "plan_repack")
+    def repack(self, ev):
+        L.check(L.lib().nunet_plan_repack(self.pl.handle, L.ptr(ev.flat_params), L.ptr(self.pl.arena), L.nbytes(self.pl.arena), L.stream()), "plan_repack")
 
     def issue(self, ev):
         """forward in eval mode on the packed weights of this plan's arena (training = 2), then the validation step"""
         lib, eng, pl, st = L.lib(), ev.eng, self.pl, L.stream()
-        L.check(lib.nunet_plan_forward(pl.handle, L.ptr(eng.flat_params), L.ptr(eng.bnbuf), L.ptr(eng.nbt), L.ptr(self.x), L.ptr(pl.arena),
+        L.check(lib.nunet_plan_forward(pl.handle, L.ptr(ev.flat_params), L.ptr(ev.bnbuf), L.ptr(eng.nbt), L.ptr(self.x), L.ptr(pl.arena),
                                        L.nbytes(pl.arena), L.ptr(self.logits), 2, st), "plan_forward")
         if ev.per_head:
             L.check(lib.nunet_eval_step_heads(L.ptr(self.logits), L.ptr(self.t), self.n, ev.ncls, ev.h * ev.w, self.heads, ev.loss_kind,
@@ -809,9 +892,14 @@ class EvalStep:
     depth=L (1..4, a deep-supervision NestedUNet): the step's plans - static batch and tail - are pruned to the sub-network of
     head L (nunet_plan_create_pruned): one head, so result() and last_logits are head L's. per_head=True (a deep-supervision
     NestedUNet, no depth): the step issues nunet_eval_step_heads, result()["heads"] lists loss / iou / dice / acc / counts /
-    per_class of every head - entry L - 1 is what EvalStep(depth=L) reports - and every other field is unchanged."""
+    per_class of every head - entry L - 1 is what EvalStep(depth=L) reports - and every other field is unchanged.
 
-    def __init__(self, model, batch_shape, loss="BCEDiceLoss", use_graph=True, depth=None, per_head=False):
+    weights=(flat_params, bnbuf): the step reads these arenas - flat fp32 device tensors in the order and size of
+    Engine.flat_params / Engine.bnbuf, e.g. (ts.ema_params, ts.ema_bnbuf) of a TrainStep with a weight EMA - instead of the
+    module's own: repack and forward take the parameter and BatchNorm arenas as arguments, so another set of weights needs no
+    second module. num_batches_tracked stays the engine's (eval never reads it). depth= and per_head= work as without."""
+
+    def __init__(self, model, batch_shape, loss="BCEDiceLoss", use_graph=True, depth=None, per_head=False, weights=None):
         if depth is not None:
             model.check_depth(depth, need_eval=False)     # (the step always runs the eval forward, whatever mode the module is in)
         if per_head:
@@ -822,6 +910,19 @@ class EvalStep:
         self.depth, self.per_head = depth, bool(per_head)
         self.model = model
         self.eng = model.engine()
+        self.flat_params, self.bnbuf = self.eng.flat_params, self.eng.bnbuf
+        if weights is not None:
+            if not isinstance(weights, (tuple, list)) or len(weights) != 2:
+                raise L.NunetError("EvalStep: weights must be a (flat_params, bnbuf) pair of device tensors")
+            fp, bb = weights
+            for t, like, nm in ((fp, self.eng.flat_params, "flat_params"), (bb, self.eng.bnbuf, "bnbuf")):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous():
+                    raise L.NunetError("EvalStep: weights %s must be a flat contiguous fp32 tensor" % nm)
+                if t.numel() != like.numel():
+                    raise L.NunetError("EvalStep: weights %s has %d values, the model's arena %d" % (nm, t.numel(), like.numel()))
+                if t.device != like.device:
+                    raise L.NunetError("EvalStep: weights %s lives on %s, the model on %s" % (nm, t.device, like.device))
+            self.flat_params, self.bnbuf = fp, bb
         n, cin, h, w = batch_shape
         if cin != model.input_channels:
             raise L.NunetError("EvalStep: batch_shape has %d channels, the model takes %d" % (cin, model.input_channels))
@@ -871,7 +972,7 @@ class EvalStep:
     def begin(self):
         """Start a pass: repack the weights into this step's own arena (the parameters moved since the last pass), zero the meters."""
         self._check_engine()
-        self.main.repack(self.eng)
+        self.main.repack(self)
         self._packed = {self.main.n}
         self._zero_meters()
         if self.use_graph and self.main.graph is None:
@@ -901,7 +1002,7 @@ class EvalStep:
                 self._packed.discard(r)
             b = self.tail
             if r not in self._packed:
-                b.repack(self.eng)
+                b.repack(self)
                 self._packed.add(r)
         b.x.copy_(xb, non_blocking=True)
         b.t.copy_(tb, non_blocking=True)

@@ -76,6 +76,12 @@ def parse_args():
     p.add_argument('--growth_interval', default=2000, type=int, help='clean steps between scale growths (--loss_scale dynamic)')
     p.add_argument('--clip_grad_norm', default=0.0, type=float,
                    help='max_norm of torch.nn.utils.clip_grad_norm_ over all parameters, inside the fused step (0: off)')
+    p.add_argument('--ema_decay', default=0.0, type=float,
+                   help='decay of an exponential moving average of the weights and BatchNorm statistics, kept inside the fused step '
+                        '(torch.optim.swa_utils.AveragedModel + get_ema_multi_avg_fn; 0: off). The averaged model is validated every '
+                        'epoch (ema_val_loss, ema_val_iou) and saved as model_ema.pth at its best val IoU')
+    p.add_argument('--ema_warmup', default=False, type=str2bool,
+                   help='with --ema_decay: the decay of update t is min(ema_decay, (1 + t) / (10 + t))')
     p.add_argument('--train_size', default=512, type=int)
     p.add_argument('--val_size', default=128, type=int)
     p.add_argument('--seed', default=41, type=int)
@@ -189,16 +195,19 @@ def main():
     u8 = fused and config['device_pipeline'] and config['input_channels'] == 3 and config['num_classes'] == 1
     scaling = None if config['loss_scale'] == 'none' else dict(init_scale=config['init_scale'], growth_interval=config['growth_interval'])
     clip = config['clip_grad_norm'] if config['clip_grad_norm'] > 0 else None
+    ema = config['ema_decay'] if config['ema_decay'] > 0 else None
+    if ema is not None and not fused:
+        raise SystemExit('--ema_decay averages inside the fused step: multi-class LovaszHingeLoss is not fused')
     if fused:
         model.train()
         if config['optimizer'] == 'Adam':      # torch.optim.Adam(params, lr, weight_decay) with its default betas / eps (trains.py:225-227)
             ts = TrainStep(model, (bs, config['input_channels'], h, w), lr=config['lr'], weight_decay=config['weight_decay'],
                            loss=config['loss'], input_u8=u8, optimizer='Adam', loss_scale=scaling,
-                           clip_grad_norm=clip)
+                           clip_grad_norm=clip, ema_decay=ema, ema_warmup=config['ema_warmup'])
         else:
             ts = TrainStep(model, (bs, config['input_channels'], h, w), lr=config['lr'], momentum=config['momentum'],
                            weight_decay=config['weight_decay'], nesterov=config['nesterov'], loss=config['loss'], input_u8=u8,
-                           loss_scale=scaling, clip_grad_norm=clip)
+                           loss_scale=scaling, clip_grad_norm=clip, ema_decay=ema, ema_warmup=config['ema_warmup'])
         if u8:
             # the decoded set (what the reference's Dataset holds after cv2.imread, dataset.py:56-64) lives in HBM as uint8
             raw, m8 = nunet_amd.synth.synth_blob_pairs_u8(config['train_size'], h, w, seed=1000)
@@ -208,9 +217,11 @@ def main():
         else:
             ts.capture(train[0][:bs], train[1][:bs])
         if rank == 0:
-            print('=> fused training step (TrainStep): %s, %s%s%s' % (config['optimizer'], config['loss'],
-                                                                      ', dynamic loss scaling' if scaling else '',
-                                                                      ', grad norm clipped at %g' % clip if clip else ''))
+            print('=> fused training step (TrainStep): %s, %s%s%s%s' % (config['optimizer'], config['loss'],
+                                                                        ', dynamic loss scaling' if scaling else '',
+                                                                        ', grad norm clipped at %g' % clip if clip else '',
+                                                                        ', weight EMA %g%s' % (ema, ' with warm-up' if config['ema_warmup'] else '')
+                                                                        if ema else ''))
     else:
         params = filter(lambda p: p.requires_grad, model.parameters())
         if config['optimizer'] == 'Adam':
@@ -225,7 +236,12 @@ def main():
     ev = EvalStep(model, (bs, config['input_channels'], h, w), loss=config['loss']) if fused and config['eval_step'] else None
     if ev is not None and rank == 0:
         print('=> captured validation step (EvalStep)')
-    log_keys = ('epoch', 'lr', 'loss', 'iou', 'val_loss', 'val_iou', 'images_per_sec') + (('val_dice', 'val_acc') if config['val_metrics'] else ())
+    # the averaged weights through a second EvalStep that reads the TrainStep's averaged arenas (no second module)
+    ev_ema = (EvalStep(model, (bs, config['input_channels'], h, w), loss=config['loss'], weights=(ts.ema_params, ts.ema_bnbuf))
+              if ema is not None else None)
+    log_keys = (('epoch', 'lr', 'loss', 'iou', 'val_loss', 'val_iou', 'images_per_sec') + (('val_dice', 'val_acc') if config['val_metrics'] else ())
+                + (('ema_val_loss', 'ema_val_iou') if ema is not None else ()))
+    best_ema_iou = 0
     log = OrderedDict([(k, []) for k in log_keys])
     best_iou, trigger = 0, 0
     plateau = PlateauLR(config['lr'], config['factor'], config['patience'], config['min_lr'])
@@ -306,6 +322,7 @@ def main():
         torch.cuda.synchronize()
         ips = steps * bs * world / (time.perf_counter() - t0)
         val_log = validate(config, val, model, criterion, ev)             # every rank: identical replicas, identical numbers
+        ema_log = validate(config, val, model, criterion, ev_ema) if ev_ema is not None else None
         if config['scheduler'] == 'ReduceLROnPlateau':
             plateau.step(val_log['loss'])                                # trains.py:325-326
         trigger += 1
@@ -316,8 +333,10 @@ def main():
                   + (' - val_dice %.4f - val_acc %.4f' % (val_log['dice'], val_log['acc']) if config['val_metrics'] else '')
                   + (' - loss scale %g, %d steps skipped' % scale_info if scale_info is not None else '')
                   + (' - grad norm %.4g/%.4g, %d steps clipped' % (norm_info['mean'], norm_info['peak'], norm_info['clipped'])
-                     if norm_info is not None else ''))
-            for k, v in zip(log, (epoch, lr, tl, ti, val_log['loss'], val_log['iou'], ips) + ((val_log['dice'], val_log['acc']) if config['val_metrics'] else ())):
+                     if norm_info is not None else '')
+                  + (' - ema_val_loss %.4f - ema_val_iou %.4f' % (ema_log['loss'], ema_log['iou']) if ema_log is not None else ''))
+            for k, v in zip(log, (epoch, lr, tl, ti, val_log['loss'], val_log['iou'], ips) + ((val_log['dice'], val_log['acc']) if config['val_metrics'] else ())
+                            + ((ema_log['loss'], ema_log['iou']) if ema_log is not None else ())):
                 log[k].append(v)
             with open('models/%s/log.csv' % config['name'], 'w') as f:
                 f.write(','.join(log.keys()) + '\n')
@@ -326,6 +345,11 @@ def main():
             if improved:
                 torch.save(model.state_dict(), 'models/%s/model.pth' % config['name'])
                 print("=> saved best model")
+            if ema_log is not None and ema_log['iou'] > best_ema_iou:
+                torch.save(ts.ema_state_dict(), 'models/%s/model_ema.pth' % config['name'])
+                print("=> saved best EMA model")
+        if ema_log is not None and ema_log['iou'] > best_ema_iou:
+            best_ema_iou = ema_log['iou']
         if improved:
             best_iou = val_log['iou']
             trigger = 0

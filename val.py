@@ -6,7 +6,9 @@ cv2 is not in the image).
 
 A checkpoint trained with --deep_supervision true can be cut back at inference time: --depth L (1..4) evaluates and exports
 masks from the network pruned to the blocks that feed head L; --per_head true adds one IoU / Dice / Acc / loss line per head
-of the whole network, so one validation pass shows which depth would do."""
+of the whole network, so one validation pass shows which depth would do.
+
+--ema true evaluates models/<name>/model_ema.pth, the averaged weights train.py --ema_decay saved at their best val IoU."""
 import argparse
 import os
 import sys
@@ -30,6 +32,8 @@ def main():
                     help='evaluate the network pruned to head L (needs a checkpoint trained with --deep_supervision true)')
     ap.add_argument('--per_head', default=False, type=str2bool,
                     help='also print IoU / Dice / Acc / loss of every head (needs --deep_supervision true)')
+    ap.add_argument('--ema', default=False, type=str2bool,
+                    help='evaluate model_ema.pth, the weight EMA of a run trained with --ema_decay, instead of model.pth')
     args = ap.parse_args()
     with open('models/%s/config.yml' % args.name) as f:
         config = yaml.load(f, Loader=yaml.FullLoader)
@@ -43,7 +47,11 @@ def main():
         sys.exit(2)
     model = archs.__dict__[config['arch']](config['num_classes'], config['input_channels'], config['deep_supervision'],
                                            dtype=config.get('dtype', 'fp32'))
-    model.load_state_dict(torch.load('models/%s/model.pth' % config['name'], map_location='cpu'))
+    ckpt = 'models/%s/%s' % (config['name'], 'model_ema.pth' if args.ema else 'model.pth')
+    if args.ema and not os.path.exists(ckpt):
+        print('error: --ema true needs %s: train with --ema_decay D (this run: ema_decay %s)' % (ckpt, config.get('ema_decay', 0.0)))
+        sys.exit(2)
+    model.load_state_dict(torch.load(ckpt, map_location='cpu'))
     model = model.cuda()
     model.eval()
     img, msk = nunet_amd.synth.synth_split(config['val_size'], config['input_h'], config['input_w'],
@@ -76,6 +84,8 @@ def main():
     r = ev.result()
     if args.depth is not None:
         print('depth: %d' % args.depth)
+    if args.ema:
+        print('weights: EMA (model_ema.pth)')
     print('IoU: %.4f' % r['iou'])
     print('Dice: %.4f' % r['dice'])
     print('Acc: %.4f' % r['acc'])
