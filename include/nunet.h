@@ -40,7 +40,7 @@ enum {
   NUNET_ENODEV = -3   /* no gfx950 device / code object */
 };
 
-int nunet_version(void);   /* 104 (additions under the same number: nunet_plan_create_pruned, nunet_plan_depth, nunet_eval_step_heads; nunet_ema_init, nunet_ema_prepare, nunet_ema_lerp and the ema / ema_params fields of nunet_optim, behind state1): nunet_plan_opt_step lost its `repack` argument and nunet_plan_set_inpass_opt is gone (the step always leaves the repack to the next forward). 103: BCEWithLogitsLoss in the loss step; nunet_seg_metrics and nunet_eval_step were added under the same number (additions only). 102: schedule 1 (single-stream) and recording mode 0 (event segments) of 101 are refused, nunet_graph_info reports nodes, edges, lanes */
+int nunet_version(void);   /* 104 (additions under the same number: nunet_plan_create_pruned, nunet_plan_depth, nunet_eval_step_heads; nunet_ema_init, nunet_ema_prepare, nunet_ema_lerp and the ema / ema_params fields of nunet_optim, behind state1; nunet_color_aug_u8, nunet_preprocess_u8_color, nunet_plan_stage_u8_color): nunet_plan_opt_step lost its `repack` argument and nunet_plan_set_inpass_opt is gone (the step always leaves the repack to the next forward). 103: BCEWithLogitsLoss in the loss step; nunet_seg_metrics and nunet_eval_step were added under the same number (additions only). 102: schedule 1 (single-stream) and recording mode 0 (event segments) of 101 are refused, nunet_graph_info reports nodes, edges, lanes */
 const char* nunet_last_error(void);
 
 /* ------------------------------------------------------------------------ */
@@ -530,6 +530,27 @@ int nunet_ema_lerp(float* ema, const float* src, int64_t n, const nunet_ema* sta
 int nunet_preprocess_u8(const uint8_t* u8_nhwc, int32_t N, int32_t H, int32_t W, int32_t C,
                         const float* mean, const float* stdv, const int32_t* aug, float post_scale,
                         float* out_nchw, nunet_stream_t s);
+/* Colour augmentation of the reference's train transform (trains.py:260-264: OneOf([HueSaturationValue(), RandomBrightness(),
+ * RandomContrast()], p=1)), one op per sample with up to three fp32 parameters, read from DEVICE memory at run time (a captured
+ * step replays with new ones). Any op value other than the three below acts as NONE. Every op maps a uint8 RGB pixel to a
+ * uint8 RGB pixel independently of its position. The arithmetic is this project's definition (input pipeline),
+ * modelled on albumentations' uint8 paths and OpenCV's 8-bit RGB2HSV / HSV2RGB (hue range 180), not verified against them:
+ *   HSV         p0, p1, p2 = hue, saturation, value shift. Integer RGB -> HSV, the shifts in double (hue wraps at 180,
+ *               saturation and value clamp to [0, 255], all truncated), HSV -> RGB in fp32 with every operation rounded on its
+ *               own, bytes rounded to nearest even. The conversion runs with zero shifts too (the round trip is not the identity).
+ *   BRIGHTNESS  p0 = float(beta * 255.0): every channel trunc(clamp((float)u + p0, 0, 255)), no add when p0 == 0
+ *   CONTRAST    p0 = alpha: every channel trunc(clamp((float)u * p0, 0, 255)), no multiply when p0 == 1 */
+enum { NUNET_COLOR_NONE = 0, NUNET_COLOR_HSV = 1, NUNET_COLOR_BRIGHTNESS = 2, NUNET_COLOR_CONTRAST = 3 };
+typedef struct nunet_color_aug { int32_t op; float p0, p1, p2; } nunet_color_aug;   /* 16 bytes, DEVICE memory, one per sample */
+/* uint8 NHWC -> uint8 NHWC, sample n through color[n]; dst == src is allowed. C must be 3. */
+int nunet_color_aug_u8(const uint8_t* src, int32_t N, int32_t H, int32_t W, int32_t C, const nunet_color_aug* color,
+                       uint8_t* dst, nunet_stream_t s);
+/* nunet_preprocess_u8 with the colour op of color[n] applied to the fetched source pixel first: bit for bit
+ * nunet_color_aug_u8 followed by nunet_preprocess_u8. Images only: C must be 3, mean and stdv given. color == NULL (or every
+ * op NONE) gives nunet_preprocess_u8's output bit for bit. */
+int nunet_preprocess_u8_color(const uint8_t* u8_nhwc, int32_t N, int32_t H, int32_t W, int32_t C,
+                              const float* mean, const float* stdv, const int32_t* aug, const nunet_color_aug* color,
+                              float post_scale, float* out_nchw, nunet_stream_t s);
 /* NCHW fp32 -> NHWC dtype with channel padding (zeros) up to cpad */
 int nunet_nchw_to_nhwc(const float* x, int32_t N, int32_t C, int32_t H, int32_t W,
                        int32_t dtype, void* y, int32_t cpad, nunet_stream_t s);
@@ -584,6 +605,11 @@ int nunet_plan_forward(nunet_plan* p, const float* params, float* bnbuf, int64_t
  * nunet_plan_forward, which bit 2 of `training` then skips). aug: as nunet_preprocess_u8 (NULL = none). */
 int nunet_plan_stage_u8(nunet_plan* p, const uint8_t* u8_nhwc, const float* mean, const float* stdv, const int32_t* aug,
                         float post_scale, void* arena, size_t arena_bytes, nunet_stream_t s);
+/* nunet_plan_stage_u8 with the colour op of color[n] applied to the fetched source pixel first (as nunet_preprocess_u8_color:
+ * bit for bit nunet_color_aug_u8 followed by nunet_plan_stage_u8, one launch). The plan's input_channels must be 3, mean and
+ * stdv given. color == NULL (or every op NONE) gives nunet_plan_stage_u8's image bit for bit. */
+int nunet_plan_stage_u8_color(nunet_plan* p, const uint8_t* u8_nhwc, const float* mean, const float* stdv, const int32_t* aug,
+                              const nunet_color_aug* color, float post_scale, void* arena, size_t arena_bytes, nunet_stream_t s);
 /* grads: flat fp32 in params order. accumulate: += instead of assign. */
 int nunet_plan_backward(nunet_plan* p, const float* params, const float* dlogits, void* arena, size_t arena_bytes,
                         float* grads, int32_t accumulate, nunet_stream_t s);

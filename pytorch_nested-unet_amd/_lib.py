@@ -184,6 +184,10 @@ EMA_WORDS = 8       # nunet_ema: 32 bytes of device memory, [decay f64 (2 words)
 EMA_SKIP, EMA_LERP, EMA_COPY = 0, 1, 2      # NUNET_EMA_* in include/nunet.h: the `live` word
 
 
+COLOR_WORDS = 4     # nunet_color_aug: 16 bytes of device memory per sample, [op i32, p0 f32, p1 f32, p2 f32] - an int32 [N,4] tensor, floats bit-cast
+COLOR_NONE, COLOR_HSV, COLOR_BRIGHTNESS, COLOR_CONTRAST = 0, 1, 2, 3      # NUNET_COLOR_* in include/nunet.h
+
+
 class PlanCfg(C.Structure):
     _fields_ = [("N", _i32), ("H", _i32), ("W", _i32),
                 ("input_channels", _i32), ("num_classes", _i32), ("deep_supervision", _i32),
@@ -249,6 +253,8 @@ _SIG = {
     "nunet_grad_sqnorm": (_i32, [_vp, _i64, _vp, _sz, _vp]),
     "nunet_clip_finalize": (_i32, [_vp, _i32, _f32, _vp, _vp, _vp]),
     "nunet_preprocess_u8": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
+    "nunet_color_aug_u8": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "nunet_preprocess_u8_color": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp]),
     "nunet_nchw_to_nhwc": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "nunet_plan_create": (_vp, [C.POINTER(PlanCfg)]),
     "nunet_plan_create_pruned": (_vp, [C.POINTER(PlanCfg), _i32]),
@@ -261,6 +267,7 @@ _SIG = {
     "nunet_plan_num_heads": (_i32, [_vp]),
     "nunet_plan_forward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _i32, _vp]),
     "nunet_plan_stage_u8": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _sz, _vp]),
+    "nunet_plan_stage_u8_color": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _sz, _vp]),
     "nunet_plan_backward": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _i32, _vp]),
     "nunet_plan_backward_phase": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _i32, _i32, _vp]),
     "nunet_plan_grad_scratch": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),

@@ -256,6 +256,79 @@ __device__ __forceinline__ void bn_running_update(float* rm, float* rv, int c, f
   rv[c] = cc + d;
 }
 
+// ---------------------------------------------------------------------------
+// Colour augmentation of the sample pipeline: OneOf([HueSaturationValue(), RandomBrightness(), RandomContrast()], p=1) of the
+// reference's train transform (trains.py:260-264), one op per sample from a nunet_color_aug in device memory. The arithmetic
+// is this project's definition (input pipeline), modelled on albumentations' uint8 paths and OpenCV's 8-bit
+// RGB2HSV / HSV2RGB with hue range 180: integer forward conversion through two division tables, the shifts in double (exact:
+// a small integer plus an fp32 value), the inverse in fp32 with every operation rounded on its own. One uint8 RGB pixel in,
+// one out, no dependence on position - so it commutes with rot90 / flips and a loader applies it to the source pixel it has
+// just fetched. nunet_color_aug_u8, nunet_preprocess_u8_color (elementwise.hip) and nunet_plan_stage_u8_color (plan.hip) share it.
+// ---------------------------------------------------------------------------
+// sdiv[i] = rint((255 << 12) / (double)i), hdiv[i] = rint((180 << 12) / (6.0 * i)), both 0 at i = 0. Neither quotient has a
+// fraction of one half (that needs 2^13 | i resp. 2^14 | i), so rounding the integer quotient to nearest gives the same values.
+struct ColorDivTables {
+  int32_t sdiv[256], hdiv[256];
+  constexpr ColorDivTables() : sdiv{}, hdiv{} {
+    for (int i = 1; i < 256; ++i) {
+      sdiv[i] = (2 * (255 << 12) + i) / (2 * i);
+      hdiv[i] = (2 * (180 << 12) + 6 * i) / (12 * i);
+    }
+  }
+};
+static __constant__ const ColorDivTables g_color_div = ColorDivTables();
+
+__device__ __forceinline__ uint8_t color_byte_rn(float x) {   // clamp(rint(x * 255), 0, 255), ties to even
+  return (uint8_t)fminf(fmaxf(rintf(__fmul_rn(x, 255.f)), 0.f), 255.f);
+}
+__device__ __forceinline__ void color_aug_pixel(int op, float p0, float p1, float p2, uint8_t& r8, uint8_t& g8, uint8_t& b8) {
+#pragma clang fp contract(off)
+  if (op == NUNET_COLOR_BRIGHTNESS || op == NUNET_COLOR_CONTRAST) {
+    // albumentations brightness_contrast_adjust, uint8 LUT, beta_by_max: p0 = beta * 255 (BRIGHTNESS) or alpha (CONTRAST)
+    const float alpha = op == NUNET_COLOR_CONTRAST ? p0 : 1.f, b255 = op == NUNET_COLOR_BRIGHTNESS ? p0 : 0.f;
+    float f[3] = {(float)r8, (float)g8, (float)b8};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (alpha != 1.f) f[c] = f[c] * alpha;
+      if (b255 != 0.f) f[c] = f[c] + b255;
+      f[c] = fminf(fmaxf(f[c], 0.f), 255.f);
+    }
+    r8 = (uint8_t)f[0]; g8 = (uint8_t)f[1]; b8 = (uint8_t)f[2];
+  } else if (op == NUNET_COLOR_HSV) {
+    const int r = r8, g = g8, b = b8;
+    const int v = max(r, max(g, b)), vmin = min(r, min(g, b)), diff = v - vmin;
+    const int s = (diff * g_color_div.sdiv[v] + 2048) >> 12;
+    const int hn = v == r ? g - b : v == g ? b - r + 2 * diff : r - g + 4 * diff;
+    int h = (hn * g_color_div.hdiv[diff] + 2048) >> 12;
+    if (h < 0) h += 180;
+    // the shifts (albumentations' hue / saturation / value LUTs), in double
+    const double xh = (double)h + (double)p0;
+    const int h2 = (int)(xh < 0.0 ? xh + 180.0 : xh >= 180.0 ? xh - 180.0 : xh);
+    const int s2 = (int)fmin(fmax((double)s + (double)p1, 0.0), 255.0);
+    const int v2 = (int)fmin(fmax((double)v + (double)p2, 0.0), 255.0);
+    // HSV -> RGB in fp32
+    float H = (float)h2 * (6.f / 180.f);
+    if (H >= 6.f) H = H - 6.f;
+    const float S = (float)s2 * (1.f / 255.f), V = (float)v2 * (1.f / 255.f);
+    const float secf = floorf(H);
+    const bool in6 = secf >= 0.f && secf <= 5.f;          // a sector outside 0..5 (shifts beyond +-180): sector 0, fraction 0
+    const int sec = in6 ? (int)secf : 0;
+    const float fr = in6 ? H - secf : 0.f;
+    const float p = V * (1.f - S);
+    const float q = V * (1.f - S * fr);
+    const float t = V * (1.f - S * (1.f - fr));
+    const float R = sec == 0 || sec == 5 ? V : sec == 1 ? q : sec == 4 ? t : p;
+    const float G = sec == 1 || sec == 2 ? V : sec == 0 ? t : sec == 3 ? q : p;
+    const float B = sec == 3 || sec == 4 ? V : sec == 2 ? t : sec == 5 ? q : p;
+    r8 = color_byte_rn(R); g8 = color_byte_rn(G); b8 = color_byte_rn(B);
+  }
+}
+// the colour op of sample n on one pixel (color != NULL)
+__device__ __forceinline__ void color_aug_sample(const nunet_color_aug* __restrict__ color, int n, uint8_t& r, uint8_t& g, uint8_t& b) {
+  const nunet_color_aug c = color[n];
+  color_aug_pixel(c.op, c.p0, c.p1, c.p2, r, g, b);
+}
+
 template <typename T> struct Vec16 {
   // zero-initialised: set() of a 16-bit element read-modify-writes its 32-bit word, and doing that on an
   // indeterminate word is undefined (it miscompiled for fp16 on the odd elements of words 0 and 1)

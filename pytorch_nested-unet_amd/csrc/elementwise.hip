@@ -140,6 +140,67 @@ extern "C" int nunet_preprocess_u8(const uint8_t* u8_nhwc, int32_t N, int32_t H,
   return nunet_check_launch("preprocess_u8");
 }
 
+// Colour augmentation (common.h, color_aug_pixel). One thread per pixel: it reads its three bytes before it writes them, so
+// the stand-alone pass may run in place.
+__global__ __launch_bounds__(256) void color_aug_u8_kernel(const uint8_t* u, long long npix, long long hw,
+                                                            const nunet_color_aug* __restrict__ color, uint8_t* out) {
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < npix; i += (long long)gridDim.x * blockDim.x) {
+    uint8_t r = u[i * 3], g = u[i * 3 + 1], b = u[i * 3 + 2];
+    color_aug_sample(color, (int)(i / hw), r, g, b);
+    out[i * 3] = r; out[i * 3 + 1] = g; out[i * 3 + 2] = b;
+  }
+}
+extern "C" int nunet_color_aug_u8(const uint8_t* src, int32_t N, int32_t H, int32_t W, int32_t C, const nunet_color_aug* color, uint8_t* dst,
+                                  nunet_stream_t s) {
+  NUNET_REQUIRE(src && dst && color, "color_aug_u8: null pointer");
+  NUNET_REQUIRE(N > 0 && H > 0 && W > 0, "color_aug_u8: N=%d H=%d W=%d must be positive", N, H, W);
+  NUNET_REQUIRE(C == 3, "color_aug_u8: the colour ops are defined on RGB: C=%d must be 3", C);
+  const long long hw = (long long)H * W, npix = (long long)N * hw;
+  hipStream_t st = (hipStream_t)s;
+  ProfScope ps(PC_LAYOUT, 0, (double)npix * 6, st);
+  NUNET_LAUNCH(color_aug_u8_kernel, dim3(grid_for(npix, 256, 4096)), dim3(256), 0, st, src, npix, hw, color, dst);
+  return nunet_check_launch("color_aug_u8");
+}
+// preprocess_u8_kernel's arithmetic on the colour-augmented source pixel: one thread per destination pixel, which fetches the
+// source pixel's three bytes once and writes the three planes.
+__global__ __launch_bounds__(256) void preprocess_u8_color_kernel(const uint8_t* __restrict__ u, int N, int H, int W,
+                                                                   const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                                   const int32_t* __restrict__ aug, const nunet_color_aug* __restrict__ color,
+                                                                   float post_scale, float* __restrict__ out) {
+  const int64_t hw = (int64_t)H * W, npix = (int64_t)N * hw;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
+    const int x = (int)(i % W);
+    const int64_t t = i / W;
+    const int y = (int)(t % H);
+    const int n = (int)(t / H);
+    int sy = y, sx = x;                        // destination (y, x) <- source: undo flips, then the rotation (as preprocess_u8_kernel)
+    const int a = aug ? aug[n] : 0;
+    if (a & 8) sy = H - 1 - sy;
+    if (a & 4) sx = W - 1 - sx;
+    const int k = a & 3;
+    int ry = sy, rx = sx;
+    if (k == 1) { ry = sx; rx = W - 1 - sy; }
+    else if (k == 2) { ry = H - 1 - sy; rx = W - 1 - sx; }
+    else if (k == 3) { ry = H - 1 - sx; rx = sy; }
+    const uint8_t* src = u + (((int64_t)n * H + ry) * W + rx) * 3;
+    uint8_t px[3] = {src[0], src[1], src[2]};
+    color_aug_sample(color, n, px[0], px[1], px[2]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[((int64_t)n * 3 + c) * hw + (int64_t)y * W + x] = (((float)px[c] / 255.f - mean[c]) / stdv[c]) * post_scale;
+  }
+}
+extern "C" int nunet_preprocess_u8_color(const uint8_t* u8_nhwc, int32_t N, int32_t H, int32_t W, int32_t C, const float* mean, const float* stdv,
+                                         const int32_t* aug, const nunet_color_aug* color, float post_scale, float* out_nchw, nunet_stream_t s) {
+  NUNET_REQUIRE(u8_nhwc && out_nchw && N > 0 && H > 0 && W > 0, "preprocess_u8_color: bad args");
+  NUNET_REQUIRE(C == 3 && mean && stdv, "preprocess_u8_color: images only: C=%d must be 3, mean and stdv given", C);
+  if (!color) return nunet_preprocess_u8(u8_nhwc, N, H, W, C, mean, stdv, aug, post_scale, out_nchw, s);
+  const int64_t npix = (int64_t)N * H * W;
+  hipStream_t st = (hipStream_t)s;
+  ProfScope ps(PC_LAYOUT, 0, (double)npix * 15, st);
+  NUNET_LAUNCH(preprocess_u8_color_kernel, dim3(grid_for(npix, 256, 4096)), dim3(256), 0, st, u8_nhwc, N, H, W, mean, stdv, aug, color, post_scale, out_nchw);
+  return nunet_check_launch("preprocess_u8_color");
+}
+
 // ---------------------------------------------------------------------------
 // BatchNorm (+ReLU) (+2x2 max-pool) forward
 // ---------------------------------------------------------------------------

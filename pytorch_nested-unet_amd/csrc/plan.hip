@@ -1333,9 +1333,11 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
 // (zeros beyond C) as 16-byte stores. The arithmetic is nunet_preprocess_u8's followed by nunet_nchw_to_nhwc's rounding, so
 // the staged image is bit-identical to the float path's; only uint8 crosses PCIe and the per-step layout launch goes away.
 // ---------------------------------------------------------------------------------------------------------
-template <typename T>
+// COLOR (nunet_plan_stage_u8_color): the colour op of color[n] (common.h, color_aug_pixel) on the fetched source pixel first; C == 3.
+template <typename T, bool COLOR>
 __global__ __launch_bounds__(256) void stage_u8_kernel(const uint8_t* __restrict__ u, int N, int H, int W, int C, const float* __restrict__ mean,
-                                                       const float* __restrict__ stdv, const int32_t* __restrict__ aug, float post_scale, T* __restrict__ img) {
+                                                       const float* __restrict__ stdv, const int32_t* __restrict__ aug,
+                                                       const nunet_color_aug* __restrict__ color, float post_scale, T* __restrict__ img) {
   constexpr int EPV = Tr<T>::EPV;
   const long long npix = (long long)N * H * W;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < npix; i += (long long)gridDim.x * blockDim.x) {
@@ -1353,6 +1355,12 @@ __global__ __launch_bounds__(256) void stage_u8_kernel(const uint8_t* __restrict
     else if (k == 2) { ry = H - 1 - sy; rx = W - 1 - sx; }
     else if (k == 3) { ry = H - 1 - sx; rx = sy; }
     const uint8_t* src = u + (((long long)n * H + ry) * W + rx) * C;
+    uint8_t px[3];
+    if constexpr (COLOR) {
+      px[0] = src[0]; px[1] = src[1]; px[2] = src[2];
+      color_aug_sample(color, n, px[0], px[1], px[2]);
+      src = px;
+    }
     T* dst = img + i * 32;
 #pragma unroll
     for (int v = 0; v < 32 / EPV; ++v) {
@@ -1372,11 +1380,12 @@ __global__ __launch_bounds__(256) void stage_u8_kernel(const uint8_t* __restrict
   }
 }
 template <typename T> static int launch_stage_u8(const uint8_t* u, int N, int H, int W, int C, const float* mean, const float* stdv, const int32_t* aug,
-                                                 float post_scale, void* img, hipStream_t st) {
+                                                 const nunet_color_aug* color, float post_scale, void* img, hipStream_t st) {
   const long long npix = (long long)N * H * W;
   long long g = (npix + 255) / 256; if (g > 4096) g = 4096;
   ProfScope ps(PC_LAYOUT, 0, (double)npix * (C + 32.0 * sizeof(T)), st);
-  NUNET_LAUNCH((stage_u8_kernel<T>), dim3((unsigned)g), dim3(256), 0, st, u, N, H, W, C, mean, stdv, aug, post_scale, (T*)img);
+  if (color) NUNET_LAUNCH((stage_u8_kernel<T, true>), dim3((unsigned)g), dim3(256), 0, st, u, N, H, W, C, mean, stdv, aug, color, post_scale, (T*)img);
+  else NUNET_LAUNCH((stage_u8_kernel<T, false>), dim3((unsigned)g), dim3(256), 0, st, u, N, H, W, C, mean, stdv, aug, color, post_scale, (T*)img);
   return nunet_check_launch("plan_stage_u8");
 }
 extern "C" int nunet_plan_stage_u8(nunet_plan* P, const uint8_t* u8_nhwc, const float* mean, const float* stdv, const int32_t* aug, float post_scale,
@@ -1384,7 +1393,15 @@ extern "C" int nunet_plan_stage_u8(nunet_plan* P, const uint8_t* u8_nhwc, const 
   NUNET_REQUIRE(P && u8_nhwc && arena, "plan_stage_u8: null pointer");
   ARENA_CHECK("plan_stage_u8");
   const nunet_plan_cfg& c = P->cfg;
-  return NUNET_DISPATCH(c.dtype, launch_stage_u8, u8_nhwc, c.N, c.H, c.W, c.input_channels, mean, stdv, aug, post_scale, (void*)AB(arena, P->off_img), (hipStream_t)s);
+  return NUNET_DISPATCH(c.dtype, launch_stage_u8, u8_nhwc, c.N, c.H, c.W, c.input_channels, mean, stdv, aug, nullptr, post_scale, (void*)AB(arena, P->off_img), (hipStream_t)s);
+}
+extern "C" int nunet_plan_stage_u8_color(nunet_plan* P, const uint8_t* u8_nhwc, const float* mean, const float* stdv, const int32_t* aug,
+                                         const nunet_color_aug* color, float post_scale, void* arena, size_t arena_bytes, nunet_stream_t s) {
+  NUNET_REQUIRE(P && u8_nhwc && arena, "plan_stage_u8_color: null pointer");
+  ARENA_CHECK("plan_stage_u8_color");
+  const nunet_plan_cfg& c = P->cfg;
+  NUNET_REQUIRE(c.input_channels == 3 && mean && stdv, "plan_stage_u8_color: images only: input_channels=%d must be 3, mean and stdv given", c.input_channels);
+  return NUNET_DISPATCH(c.dtype, launch_stage_u8, u8_nhwc, c.N, c.H, c.W, c.input_channels, mean, stdv, aug, color, post_scale, (void*)AB(arena, P->off_img), (hipStream_t)s);
 }
 
 extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, const float* dlogits, void* arena, size_t arena_bytes, float* grads, int32_t accumulate, int32_t phases, nunet_stream_t s);

@@ -54,7 +54,7 @@ class TrainStep:
     def __init__(self, model, batch_shape, lr=1e-3, momentum=0.9, weight_decay=1e-4, nesterov=False,
                  use_graph=True, process_group=None, keep_grads=True, fused_update=None, loss="BCEDiceLoss", input_u8=False,
                  schedule=None, segmented=None, optimizer="SGD", betas=(0.9, 0.999), eps=1e-8, loss_scale=None,
-                 clip_grad_norm=None, ema_decay=None, ema_warmup=False):
+                 clip_grad_norm=None, ema_decay=None, ema_warmup=False, color_aug=False):
         """loss: 'BCEDiceLoss' (reference losses.py:103-117, the default of trains.py:58), 'LovaszHingeLoss'
         (losses.py:120-129, the loss of the reference's published table README.md:102-108; one class only) or
         'BCEWithLogitsLoss' (torch.nn.BCEWithLogitsLoss(), trains.py:27-28,210-211; any num_classes: its gradient needs no
@@ -64,6 +64,11 @@ class TrainStep:
         per-sample augmentation codes; Normalize, /255, the mask scaling, rot90 / flips and the layout change of the
         reference's sample pipeline (dataset.py:66-74, trains.py:258-266) run as the first two launches of the step's graph
         (step_u8). Only uint8 crosses PCIe and the per-step NCHW->NHWC launch of the float path is gone.
+        color_aug (needs input_u8 and input_channels == 3): False - today's two head launches; True - the staging launch is
+        nunet_plan_stage_u8_color, which applies one colour op per sample (the OneOf([HueSaturationValue, RandomBrightness,
+        RandomContrast]) of trains.py:260-264, modelled on albumentations / OpenCV) to the source pixel it
+        fetches, from a static int32 [N,4] device buffer that step_u8(..., color=) fills (dataset.draw_color_augmentation; None:
+        every op NONE, bit-identical to color_aug=False). The same number of launches.
         How the captured step is executed (all forms are bit-identical, tests/test_net_gpu.py):
           schedule  'lanes' - every op on its block's lane; 'list' - lanes chosen by a list scheduler over the hazard graph with
                     measured per-op costs (nunet_plan_calibrate)
@@ -132,6 +137,12 @@ class TrainStep:
             self.aug = torch.zeros(n, dtype=torch.int32, device=dev)
             self._mean = torch.tensor(np.resize(np.asarray(MEAN, np.float32), cin), device=dev)
             self._std = torch.tensor(np.resize(np.asarray(STD, np.float32), cin), device=dev)
+        self.color = None
+        if color_aug:
+            if not self.input_u8 or cin != 3:
+                raise L.NunetError("TrainStep: color_aug=True needs input_u8=True and RGB input (input_channels == 3): the colour ops "
+                                   "run on the uint8 pixel the staging launch fetches")
+            self.color = torch.zeros((n, L.COLOR_WORDS), dtype=torch.int32, device=dev)     # nunet_color_aug per sample, all NONE
         self.logits = torch.empty((self.heads, n, self.ncls, h, w), dtype=torch.float32, device=dev)
         self.dlogits = torch.empty_like(self.logits)
         self.per = self.ncls * h * w
@@ -278,8 +289,12 @@ class TrainStep:
                     "adam_prepare")
         if self.input_u8:
             # the sample pipeline on the device: image -> the plan's padded NHWC tile, mask -> {0,1} fp32 NCHW target
-            L.check(lib.nunet_plan_stage_u8(pl.handle, L.ptr(self.x_u8), L.ptr(self._mean), L.ptr(self._std), L.ptr(self.aug), 1.0 / 255.0,
-                                            L.ptr(pl.arena), L.nbytes(pl.arena), st), "plan_stage_u8")
+            if self.color is not None:
+                L.check(lib.nunet_plan_stage_u8_color(pl.handle, L.ptr(self.x_u8), L.ptr(self._mean), L.ptr(self._std), L.ptr(self.aug),
+                                                      L.ptr(self.color), 1.0 / 255.0, L.ptr(pl.arena), L.nbytes(pl.arena), st), "plan_stage_u8_color")
+            else:
+                L.check(lib.nunet_plan_stage_u8(pl.handle, L.ptr(self.x_u8), L.ptr(self._mean), L.ptr(self._std), L.ptr(self.aug), 1.0 / 255.0,
+                                                L.ptr(pl.arena), L.nbytes(pl.arena), st), "plan_stage_u8")
             L.check(lib.nunet_preprocess_u8(L.ptr(self.t_u8), self.n, self.h, self.w, self.ncls, None, None, L.ptr(self.aug), 1.0,
                                             L.ptr(self.t), st), "preprocess_u8 (masks)")
             flags |= 4
@@ -426,6 +441,8 @@ class TrainStep:
             self.x_u8.copy_(inp)
             self.t_u8.copy_(target)
             self.aug.zero_()
+            if self.color is not None:
+                self.color.zero_()
         else:
             self.x.copy_(inp)
             self.t.copy_(target)
@@ -642,11 +659,18 @@ class TrainStep:
             self.t.copy_(target, non_blocking=True)
         self._run()
 
-    def step_u8(self, images_u8, masks_u8, aug=None):
+    def step_u8(self, images_u8, masks_u8, aug=None, color=None):
         """One training iteration from the decoded uint8 batch (device tensors; images [N,H,W,C], masks [N,H,W,K] with
-        values {0,255}) and optional augmentation codes (dataset.draw_augmentation); needs input_u8=True."""
+        values {0,255}), optional augmentation codes (dataset.draw_augmentation) and, on a step built with color_aug=True,
+        optional colour codes (dataset.draw_color_augmentation; None: no colour op); needs input_u8=True."""
         if not self.input_u8:
             raise L.NunetError("step_u8 needs a TrainStep built with input_u8=True")
+        if color is not None:
+            if self.color is None:
+                raise L.NunetError("step_u8: color codes need a TrainStep built with color_aug=True")
+            if color.dtype != torch.int32 or tuple(color.shape) != tuple(self.color.shape):
+                raise L.NunetError("step_u8: color must be int32 %s (dataset.draw_color_augmentation), got %s %s"
+                                   % (tuple(self.color.shape), color.dtype, tuple(color.shape)))
         self.x_u8.copy_(images_u8, non_blocking=True)
         self.t_u8.copy_(masks_u8, non_blocking=True)
         if aug is None:
@@ -655,6 +679,11 @@ class TrainStep:
             if self.h != self.w and bool((aug & 1).any()):
                 raise L.NunetError("rot90 by an odd count needs square images")
             self.aug.copy_(aug, non_blocking=True)
+        if self.color is not None:
+            if color is None:
+                self.color.zero_()
+            else:
+                self.color.copy_(color, non_blocking=True)
         self._run()
 
     def _run(self):

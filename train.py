@@ -95,6 +95,9 @@ def parse_args():
     p.add_argument('--val_metrics', default=False, type=str2bool,
                    help='also log val_dice (reference metrics.py dice_coef) and val_acc (pixel accuracy) per epoch, after images_per_sec')
     p.add_argument('--augment', default=False, type=str2bool, help='RandomRotate90 + Flip per sample (trains.py:258-259), device pipeline only')
+    p.add_argument('--color_augment', default=False, type=str2bool,
+                   help='OneOf([HueSaturationValue, RandomBrightness, RandomContrast], p=1) per sample (trains.py:260-264; modelled on '
+                        'albumentations, see DESIGN.md), device pipeline only; drawn from the same generator stream as --augment')
     return p.parse_args()
 
 
@@ -193,6 +196,9 @@ def main():
     if world > 1 and not fused:
         raise SystemExit('data parallel runs the fused step: multi-class LovaszHingeLoss is not fused')
     u8 = fused and config['device_pipeline'] and config['input_channels'] == 3 and config['num_classes'] == 1
+    color = bool(config['color_augment'] and u8)
+    if config['color_augment'] and not u8:
+        raise SystemExit('--color_augment runs in the device pipeline (fused step, --device_pipeline, 3 input channels, 1 class)')
     scaling = None if config['loss_scale'] == 'none' else dict(init_scale=config['init_scale'], growth_interval=config['growth_interval'])
     clip = config['clip_grad_norm'] if config['clip_grad_norm'] > 0 else None
     ema = config['ema_decay'] if config['ema_decay'] > 0 else None
@@ -203,11 +209,11 @@ def main():
         if config['optimizer'] == 'Adam':      # torch.optim.Adam(params, lr, weight_decay) with its default betas / eps (trains.py:225-227)
             ts = TrainStep(model, (bs, config['input_channels'], h, w), lr=config['lr'], weight_decay=config['weight_decay'],
                            loss=config['loss'], input_u8=u8, optimizer='Adam', loss_scale=scaling,
-                           clip_grad_norm=clip, ema_decay=ema, ema_warmup=config['ema_warmup'])
+                           clip_grad_norm=clip, ema_decay=ema, ema_warmup=config['ema_warmup'], color_aug=color)
         else:
             ts = TrainStep(model, (bs, config['input_channels'], h, w), lr=config['lr'], momentum=config['momentum'],
                            weight_decay=config['weight_decay'], nesterov=config['nesterov'], loss=config['loss'], input_u8=u8,
-                           loss_scale=scaling, clip_grad_norm=clip, ema_decay=ema, ema_warmup=config['ema_warmup'])
+                           loss_scale=scaling, clip_grad_norm=clip, ema_decay=ema, ema_warmup=config['ema_warmup'], color_aug=color)
         if u8:
             # the decoded set (what the reference's Dataset holds after cv2.imread, dataset.py:56-64) lives in HBM as uint8
             raw, m8 = nunet_amd.synth.synth_blob_pairs_u8(config['train_size'], h, w, seed=1000)
@@ -267,7 +273,8 @@ def main():
                 idx = perm[lo:lo + bs]
                 if u8:
                     aug = nunet_amd.dataset.draw_augmentation(bs, aug_gen, 'cuda') if config['augment'] else None
-                    ts.step_u8(train_u8[0][idx], train_u8[1][idx], aug)
+                    col = nunet_amd.dataset.draw_color_augmentation(bs, aug_gen, 'cuda') if color else None
+                    ts.step_u8(train_u8[0][idx], train_u8[1][idx], aug, col)
                 else:
                     ts.step(train[0][idx], train[1][idx])
             tl, ti = ts.epoch_stats()
