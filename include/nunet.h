@@ -246,6 +246,11 @@ int nunet_upsample2x_bwd(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t
 int nunet_head_fwd(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t K,
                    const void* x, int32_t PX, const float* w, const float* b,
                    float* logits, nunet_stream_t s);
+/* nunet_bn_relu_fwd(d) and nunet_head_fwd on d->a in ONE launch, bit-identical to the two: everything the descriptor asks of
+ * nunet_bn_relu_fwd (the activation in d->a, saved mean / invstd, running statistics, num_batches_tracked; training and eval),
+ * and the head computed from the activation as rounded to the storage type and stored. d->pooled and d->up must be NULL
+ * (NUNET_EINVAL); C <= 64. For a block output whose only forward reader is its head: x0_4 of the network. */
+int nunet_head_fwd_bn(const nunet_bn_fwd_desc* d, int32_t K, const float* w, const float* b, float* logits, nunet_stream_t s);
 /* dx (+)= dlogits . w ; parameter gradients come back as `nslabs` partial slabs, one per workgroup:
  * dw_slabs[s][K*C + K] = [weights grad | bias grad] of slab s (fully overwritten); the caller sums the
  * slabs (the plan's unpack kernel does). No atomics: same-address float atomics from hundreds of

@@ -145,6 +145,28 @@ typedef struct {
   int64_t items;
 } nunet_upsample_launch_info_t;
 int nunet_upsample_launch_info(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t backward, nunet_upsample_launch_info_t* out);
+/* Launch geometry of nunet_head_fwd (with_bn = 0: a thread per pixel) or nunet_head_fwd_bn (with_bn = 1: C / (16 bytes) lanes per
+ * pixel, the grid of nunet_bn_relu_fwd), from the very expressions the launches use. A pure host function. items = pixels;
+ * trips_max / trips_min = the most / fewest pixels one thread (one lane group) walks - nunet_head_fwd_bn takes them four per loop pass. */
+int nunet_head_launch_info(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t with_bn, nunet_loss_launch_info_t* out);
+
+/* Forward-pass and scheduler choices of a plan, all bit-identical; each is read when a pass is issued, so set it before the
+ * first forward / capture. (Defaults also from the environment at plan creation: NUNET_HEAD_BN, NUNET_BN_UP, NUNET_WAIT_PRUNE.)
+ * head_bn (default 1): a head whose slot no block reads in the forward pass - the last head of a full plan, final<L> of a pruned
+ *   one - runs with its block's BatchNorm2 + ReLU as ONE launch (nunet_head_fwd_bn); 0: the two launches.
+ * bn_up: which blocks' BatchNorm2 launch also writes the x2 upsample their reader concatenates (nunet_bn_fwd_desc.up) instead of
+ *   that reader's stand-alone upsample launch: none, the four row ends of the critical chain (B40, B31, B22, B13; every decoder
+ *   hop of the plain UNet), or every block that is upsampled.
+ * wait_prune (default 1): the lane scheduler drops a cross-lane wait that lane order plus the waits already made imply; 0: every
+ *   requested wait is made. */
+enum { NUNET_BN_UP_NONE = 0, NUNET_BN_UP_CHAIN = 1, NUNET_BN_UP_ALL = 2 };
+int nunet_plan_set_head_bn(nunet_plan* p, int32_t enable);
+int nunet_plan_set_bn_up(nunet_plan* p, int32_t mode);
+int nunet_plan_set_wait_prune(nunet_plan* p, int32_t enable);
+/* The scheduler's wait decision over plain arrays (a pure host function). nops ops in issue order, op b on lane op_lane[b] (lanes
+ * are in-order) asks to wait for the ops edge_src[edge_off[b] .. edge_off[b + 1]), each issued before b. keep[e] = 1: the wait is
+ * made; 0: it is implied by lane order and the waits kept so far (a producer on b's own lane always is). At most 16 lanes. */
+int nunet_wait_prune_host(int32_t nlanes, int32_t nops, const int32_t* op_lane, const int32_t* edge_off, const int32_t* edge_src, uint8_t* keep);
 /* The work item that workgroup b of G takes first (common.h, xcd_remap: one contiguous item range per XCD), evaluated on the host. */
 int32_t nunet_xcd_remap_host(int32_t b, int32_t G);
 

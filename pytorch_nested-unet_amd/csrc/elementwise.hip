@@ -222,6 +222,25 @@ __device__ __forceinline__ void bn_channel_coeffs(const BnFwdP& p, int c, float 
   bn_stat_coeffs(a, c, mean, invstd, var, mean_full);
 }
 
+// per-channel scale / shift tables once per block (not per thread); block 0 also owns the running-stat update and the saved
+// mean/invstd for backward. Ends with the barrier that publishes the tables.
+__device__ __forceinline__ void bn_fwd_prologue(const BnFwdP& p, float M, float* s_sc, float* s_sh) {
+  for (int c = threadIdx.x; c < p.C; c += blockDim.x) {
+    float mean, invstd, var, mf;
+    bn_channel_coeffs(p, c, M, mean, invstd, var, mf);
+    const float sc = p.gamma[c] * invstd;
+    s_sc[c] = sc;
+    s_sh[c] = __builtin_fmaf(-mean, sc, p.beta[c]);
+    if (blockIdx.x == 0 && p.training) {
+      p.save[c] = mean;
+      p.save[p.C + c] = invstd;
+      if (p.rm) bn_running_update(p.rm, p.rv, c, p.momentum, mf, var, M);
+    }
+  }
+  if (blockIdx.x == 0 && p.training && threadIdx.x == 0 && p.nbt) *p.nbt += 1;
+  __syncthreads();
+}
+
 template <typename T, bool POOL>
 __global__ __launch_bounds__(256) void bn_relu_fwd_kernel(BnFwdP p) {
   constexpr int EPV = Tr<T>::EPV;
@@ -270,22 +289,7 @@ __global__ __launch_bounds__(256) void bn_relu_fwd_kernel(BnFwdP p) {
   };
   const int64_t q0 = (int64_t)blockIdx.x * ppb0 + pl0;
   if constexpr (POOL) { if (main_role && q0 < nq) qload(q0); }
-  // per-channel coefficients once per block (not per thread), block 0 also owns the
-  // running-stat update and the saved mean/invstd for backward
-  for (int c = threadIdx.x; c < p.C; c += blockDim.x) {
-    float mean, invstd, var, mf;
-    bn_channel_coeffs(p, c, M, mean, invstd, var, mf);
-    const float sc = p.gamma[c] * invstd;
-    s_sc[c] = sc;
-    s_sh[c] = __builtin_fmaf(-mean, sc, p.beta[c]);
-    if (blockIdx.x == 0 && p.training) {
-      p.save[c] = mean;
-      p.save[p.C + c] = invstd;
-      if (p.rm) bn_running_update(p.rm, p.rv, c, p.momentum, mf, var, M);
-    }
-  }
-  if (blockIdx.x == 0 && p.training && threadIdx.x == 0 && p.nbt) *p.nbt += 1;
-  __syncthreads();
+  bn_fwd_prologue(p, M, s_sc, s_sh);
   typedef typename FV<T>::type V;
   if (p.up && (int)blockIdx.x >= p.nb_main) {
     // ---- second role: nn.Upsample(x2, bilinear, align_corners) of the activation (archs1.py:83,116-131), straight from the raw
@@ -352,13 +356,20 @@ __global__ __launch_bounds__(256) void bn_relu_fwd_kernel(BnFwdP p) {
   }
 }
 
-template <typename T> static int launch_bn_fwd(const nunet_bn_fwd_desc* d, hipStream_t st) {
+static BnFwdP bn_fwd_params(const nunet_bn_fwd_desc* d) {
   BnFwdP p;
   p.y = d->y; p.PY = d->PY; p.conv_bias = d->conv_bias; p.stats = (const long long*)d->stats; p.gamma = d->gamma; p.beta = d->beta;
   p.rm = d->running_mean; p.rv = d->running_var; p.nbt = d->num_batches_tracked; p.save = d->save_mean_invstd;
   p.training = d->training; p.momentum = d->momentum; p.eps = d->eps;
   p.a = d->a; p.PA = d->PA; p.pooled = d->pooled; p.PP = d->PP;
   p.N = d->N; p.H = d->H; p.W = d->W; p.C = d->C;
+  p.up = nullptr; p.PU = 0; p.nb_main = 0; memset(&p.dcu, 0, sizeof(p.dcu));
+  return p;
+}
+// workgroups of the BatchNorm role without a pool: 256 / G pixels per workgroup and pass, four passes in flight per thread
+static int bn_fwd_grid(int64_t npix, int G) { return grid_for(npix, (256 / G) * 4, 2048); }
+template <typename T> static int launch_bn_fwd(const nunet_bn_fwd_desc* d, hipStream_t st) {
+  BnFwdP p = bn_fwd_params(d);
   const int G = d->C / Tr<T>::EPV;
   const int ppb = 256 / G;
   // optional second role of the launch: the x2 upsample of the activation (extra blocks behind the BatchNorm role's)
@@ -374,14 +385,14 @@ template <typename T> static int launch_bn_fwd(const nunet_bn_fwd_desc* d, hipSt
     p.nb_main = grid_for(nq, ppb * 2, 2048);
     NUNET_LAUNCH((bn_relu_fwd_kernel<T, true>), dim3(p.nb_main + nb_up), dim3(256), 0, st, p);
   } else {
-    const int64_t np = (int64_t)d->N * d->H * d->W;
-    p.nb_main = grid_for(np, ppb * 4, 2048);
+    p.nb_main = bn_fwd_grid((int64_t)d->N * d->H * d->W, G);
     NUNET_LAUNCH((bn_relu_fwd_kernel<T, false>), dim3(p.nb_main + nb_up), dim3(256), 0, st, p);
   }
   return nunet_check_launch("bn_relu_fwd");
 }
 static bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-extern "C" int nunet_bn_relu_fwd(const nunet_bn_fwd_desc* d, nunet_stream_t s) {
+// what nunet_bn_relu_fwd and nunet_head_fwd_bn both ask of the descriptor
+static int bn_fwd_check(const nunet_bn_fwd_desc* d) {
   NUNET_REQUIRE(d && d->y && d->a && d->gamma && d->beta, "bn_relu_fwd: null pointer");
   const int epv = 16 / dtype_size(d->dtype);
   NUNET_REQUIRE(pow2(d->C) && d->C >= epv && d->C / epv <= 256, "bn_relu_fwd: C=%d must be a power of two in [%d, %d]", d->C, epv, 256 * epv);
@@ -390,6 +401,11 @@ extern "C" int nunet_bn_relu_fwd(const nunet_bn_fwd_desc* d, nunet_stream_t s) {
   NUNET_REQUIRE(!d->up || d->PU % epv == 0, "bn_relu_fwd: fused upsample pitch alignment");
   if (d->training) NUNET_REQUIRE(d->stats && d->save_mean_invstd, "bn_relu_fwd: training needs stats and save buffers");
   else NUNET_REQUIRE(d->running_mean && d->running_var, "bn_relu_fwd: eval needs running stats");
+  return NUNET_OK;
+}
+extern "C" int nunet_bn_relu_fwd(const nunet_bn_fwd_desc* d, nunet_stream_t s) {
+  const int rc = bn_fwd_check(d);
+  if (rc) return rc;
   return NUNET_DISPATCH(d->dtype, launch_bn_fwd, d, (hipStream_t)s);
 }
 
@@ -1066,33 +1082,122 @@ extern "C" int32_t nunet_xcd_remap_host(int32_t b, int32_t G) { return xcd_remap
 // 1x1 heads. Lane = channel: 32-lane half-waves walk pixels.
 // ---------------------------------------------------------------------------
 #define HEAD_MAXK 8
-template <typename T>
-__global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ x, int PX, const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ logits, int N, int H, int W, int C, int K) {
-  // thread per pixel; C (=32) channels read as 16-byte vectors
+// A logit is ONE chain acc = fma(x[c], w[k][c], acc) over c ascending from acc = 0, then + b[k]: both forward kernels below
+// evaluate exactly that chain, so they leave the same bits.
+// Thread per pixel. CT = 32 (the heads of this network): the pixel's 32 / EPV vectors are all requested before the first use,
+// fully unrolled; CT = 0: any C <= 64, the same with the vectors beyond C predicated off. (The rolled loop of dependent 16-byte
+// loads this replaces moved 1 TB/s.)
+template <typename T, int CT>
+__global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ x, int PX, const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ logits, int N, int H, int W, int C_, int K) {
   constexpr int EPV = Tr<T>::EPV;
+  constexpr int NV = (CT ? CT : 64) / EPV;
+  const int C = CT ? CT : C_;
   __shared__ float s_w[HEAD_MAXK * 64];
   for (int i = threadIdx.x; i < K * C; i += blockDim.x) s_w[i] = w[i];
   __syncthreads();
   const int64_t hw = (int64_t)H * W, npix = (int64_t)N * hw;
   for (int64_t pix = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; pix < npix; pix += (int64_t)gridDim.x * blockDim.x) {
-    float acc[HEAD_MAXK];
+    Vec16<T> v[NV];
 #pragma unroll
-    for (int k = 0; k < HEAD_MAXK; ++k) acc[k] = 0.f;
-    for (int c0 = 0; c0 < C; c0 += EPV) {
-      const Vec16<T> v = ld16(x + pix * PX + c0);
+    for (int i = 0; i < NV; ++i)
+      if (CT || i * EPV < C) v[i] = ld16(x + pix * PX + i * EPV);
+    float xf[NV * EPV];
 #pragma unroll
-      for (int e = 0; e < EPV; ++e) {
-        const float xv = v.get(e);
+    for (int i = 0; i < NV; ++i) {
 #pragma unroll
-        for (int k = 0; k < HEAD_MAXK; ++k)
-          if (k < K) acc[k] += xv * s_w[k * C + c0 + e];
-      }
+      for (int e = 0; e < EPV; ++e) xf[i * EPV + e] = v[i].get(e);
     }
     const int n = npix < (1ll << 31) ? (int)((unsigned)pix / (unsigned)hw) : (int)(pix / hw);
     const int64_t rem = pix - n * hw;
+    // class by class, the weights from LDS (a rolled loop: unrolled over the classes, the compiler keeps all K * C weights in
+    // registers across the pixel loop - 256 of them, one wave per SIMD)
+#pragma unroll 1
+    for (int k = 0; k < K; ++k) {
+      float acc = 0.f;
 #pragma unroll
-    for (int k = 0; k < HEAD_MAXK; ++k)
-      if (k < K) logits[((int64_t)n * K + k) * hw + rem] = acc[k] + b[k];
+      for (int c = 0; c < NV * EPV; ++c)
+        if (CT || c < C) acc = __builtin_fmaf(xf[c], s_w[k * C + c], acc);
+      logits[((int64_t)n * K + k) * hw + rem] = acc + b[k];
+    }
+  }
+}
+// BatchNorm + ReLU of a block output AND the 1x1 head on it, one launch: bn_relu_fwd_kernel's un-pooled role (same thread map:
+// the G = C / EPV lanes of a pixel are neighbours, every 16-byte load and store of y and of the slot is part of a dense run;
+// same prologue, same bn_relu_apply), then the head from the value as ROUNDED to the storage type - what head_fwd_kernel would
+// read back from the slot. The logit's fma chain walks the pixel's G lanes in channel order: lane g takes the sum from lane
+// g - 1 (a shuffle), runs its EPV channels and hands it on; lane G - 1 adds the bias and stores. KT = compile-time class count
+// (0: K <= HEAD_MAXK at run time).
+struct HeadP { const float* w; const float* b; float* logits; int K; };
+template <typename T, int KT>
+__global__ __launch_bounds__(256) void head_fwd_bn_kernel(BnFwdP p, HeadP h) {
+  constexpr int EPV = Tr<T>::EPV;
+  constexpr int KM = KT > 0 ? KT : HEAD_MAXK;
+  typedef typename FV<T>::type V;
+  __shared__ __attribute__((aligned(16))) float s_sc[64], s_sh[64];
+  const int G = p.C / EPV;  // 256 % G == 0 and 64 % G == 0: a pixel's lanes sit in one wave
+  const int cg = threadIdx.x % G;
+  const int K = KT > 0 ? KT : h.K;
+  const float M = (float)p.N * p.H * p.W;
+  constexpr int U = 4;   // 16-byte loads kept in flight per thread
+  const int ppb = blockDim.x / G, pl = threadIdx.x / G;
+  const int hw = p.H * p.W;
+  const int64_t npix = (int64_t)p.N * hw;      // < 2^31 (checked on the host)
+  const int64_t stride = (int64_t)gridDim.x * ppb;
+  Vec16<T> v[U];
+  auto load_batch = [&](int64_t p0) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t pix = p0 + u * stride;
+      if (pix < npix) v[u] = ld16((const T*)p.y + pix * p.PY + cg * EPV);
+    }
+  };
+  // first batch of loads and the lane's head weights ahead of the coefficient prologue (latencies overlap)
+  int64_t pix0 = (int64_t)blockIdx.x * ppb + pl;
+  if (pix0 < npix) load_batch(pix0);
+  float wk[KM][EPV];
+#pragma unroll
+  for (int k = 0; k < KM; ++k) {
+#pragma unroll
+    for (int e = 0; e < EPV; ++e) wk[k][e] = k < K ? h.w[k * p.C + cg * EPV + e] : 0.f;
+  }
+  bn_fwd_prologue(p, M, s_sc, s_sh);
+  const V sc = ldf<T>(&s_sc[cg * EPV]), sh = ldf<T>(&s_sh[cg * EPV]);
+  while (pix0 < npix) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t pix = pix0 + u * stride;
+      const bool live = pix < npix;       // the same in all G lanes of a pixel; the shuffles below run in every lane
+      const Vec16<T> o = vec_from_f<T>(bn_relu_apply<V>(vec_to_f<T>(v[u]), sc, sh));
+      if (live) st16((T*)p.a + pix * p.PA + cg * EPV, o);
+      float acc[KM];
+#pragma unroll
+      for (int k = 0; k < KM; ++k) acc[k] = 0.f;
+      for (int g = 0; g < G; ++g) {
+        float t[KM];
+#pragma unroll
+        for (int k = 0; k < KM; ++k) t[k] = g > 0 ? __shfl_up(acc[k], 1) : 0.f;
+        if (cg == g) {
+#pragma unroll
+          for (int k = 0; k < KM; ++k) acc[k] = t[k];
+#pragma unroll
+          for (int e = 0; e < EPV; ++e) {
+            const float xv = o.get(e);
+#pragma unroll
+            for (int k = 0; k < KM; ++k)
+              if (KT > 0 || k < K) acc[k] = __builtin_fmaf(xv, wk[k][e], acc[k]);
+          }
+        }
+      }
+      if (live && cg == G - 1) {
+        const int n = (int)((unsigned)pix / (unsigned)hw);
+        const int rem = (int)pix - n * hw;
+#pragma unroll
+        for (int k = 0; k < KM; ++k)
+          if (KT > 0 || k < K) h.logits[((int64_t)n * K + k) * hw + rem] = acc[k] + h.b[k];
+      }
+    }
+    pix0 += U * stride;
+    if (pix0 < npix) load_batch(pix0);
   }
 }
 template <typename T, int KT, bool BNR>
@@ -1191,10 +1296,23 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const T* __restrict__ x, 
   }
   if constexpr (BNR) ba.finish(bn, s_part, G);
 }
+static int head_fwd_grid(int64_t npix) { return grid_for(npix, 256); }   // thread per pixel, grid-stride beyond 4096 workgroups
 template <typename T> static int launch_head_fwd(int N, int H, int W, int C, int K, const void* x, int PX, const float* w, const float* b, float* logits, hipStream_t st) {
   ProfScope ps(PC_HEAD, 2.0 * N * H * W * C * K, (double)N * H * W * (C * sizeof(T) + K * 4), st);
-  NUNET_LAUNCH((head_fwd_kernel<T>), dim3(grid_for((int64_t)N * H * W, 256)), dim3(256), 0, st, (const T*)x, PX, w, b, logits, N, H, W, C, K);
+  const dim3 grid(head_fwd_grid((int64_t)N * H * W));
+  if (C == 32) NUNET_LAUNCH((head_fwd_kernel<T, 32>), grid, dim3(256), 0, st, (const T*)x, PX, w, b, logits, N, H, W, C, K);
+  else NUNET_LAUNCH((head_fwd_kernel<T, 0>), grid, dim3(256), 0, st, (const T*)x, PX, w, b, logits, N, H, W, C, K);
   return nunet_check_launch("head_fwd");
+}
+template <typename T> static int launch_head_fwd_bn(const nunet_bn_fwd_desc* d, int K, const float* w, const float* b, float* logits, hipStream_t st) {
+  const BnFwdP p = bn_fwd_params(d);
+  const HeadP h = {w, b, logits, K};
+  const int64_t np = (int64_t)d->N * d->H * d->W;
+  ProfScope ps(PC_BN_FWD, 2.0 * np * d->C * K, (double)np * (2.0 * d->C * sizeof(T) + K * 4), st);
+  const dim3 grid(bn_fwd_grid(np, d->C / Tr<T>::EPV));
+  if (K == 1) NUNET_LAUNCH((head_fwd_bn_kernel<T, 1>), grid, dim3(256), 0, st, p, h);
+  else NUNET_LAUNCH((head_fwd_bn_kernel<T, 0>), grid, dim3(256), 0, st, p, h);
+  return nunet_check_launch("head_fwd_bn");
 }
 template <typename T> static int launch_head_bwd(int N, int H, int W, int C, int K, const void* x, int PX, const float* w, const float* dl, void* dx, int PDX, int acc, float* dw_slabs, int nslabs, const nunet_bnr_desc* bnr, hipStream_t st) {
   ProfScope ps(PC_HEAD, 4.0 * N * H * W * C * K, (double)N * H * W * (C * sizeof(T) * ((acc ? 3 : 2) + (bnr ? 1 : 0)) + K * 4), st);
@@ -1212,6 +1330,29 @@ extern "C" int nunet_head_fwd(int32_t dtype, int32_t N, int32_t H, int32_t W, in
   NUNET_REQUIRE(C > 0 && C <= 64 && C % (16 / dtype_size(dtype)) == 0 && K >= 1 && K <= HEAD_MAXK, "head_fwd: C=%d K=%d unsupported (C<=64, K<=%d)", C, K, HEAD_MAXK);
   NUNET_REQUIRE(PX % (16 / dtype_size(dtype)) == 0, "head_fwd: pitch");
   return NUNET_DISPATCH(dtype, launch_head_fwd, N, H, W, C, K, x, PX, w, b, logits, (hipStream_t)s);
+}
+extern "C" int nunet_head_fwd_bn(const nunet_bn_fwd_desc* d, int32_t K, const float* w, const float* b, float* logits, nunet_stream_t s) {
+  const int rc = bn_fwd_check(d);
+  if (rc) return rc;
+  NUNET_REQUIRE(w && b && logits, "head_fwd_bn: null pointer");
+  NUNET_REQUIRE(!d->pooled && !d->up, "head_fwd_bn: no fused pool and no fused upsample in this form");
+  NUNET_REQUIRE(d->C <= 64 && K >= 1 && K <= HEAD_MAXK, "head_fwd_bn: C=%d K=%d unsupported (C<=64, K<=%d)", d->C, K, HEAD_MAXK);
+  NUNET_REQUIRE((int64_t)d->N * d->H * d->W < (1LL << 31), "head_fwd_bn: too many pixels");
+  return NUNET_DISPATCH(d->dtype, launch_head_fwd_bn, d, K, w, b, logits, (hipStream_t)s);
+}
+extern "C" int nunet_head_launch_info(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t with_bn, nunet_loss_launch_info_t* out) {
+  NUNET_REQUIRE(out && N > 0 && H > 0 && W > 0, "head_launch_info: bad args");
+  NUNET_REQUIRE(dtype >= 0 && dtype <= 2, "bad dtype %d", dtype);
+  const int epv = 16 / dtype_size(dtype);
+  NUNET_REQUIRE(C >= epv && C <= 64 && C % epv == 0 && (!with_bn || pow2(C)), "head_launch_info: C=%d unsupported", C);
+  const int64_t npix = (int64_t)N * H * W;
+  // pixels one pass of the grid covers: a thread per pixel, or C / epv lanes per pixel
+  const int64_t per_pass = with_bn ? (int64_t)bn_fwd_grid(npix, C / epv) * (256 / (C / epv)) : (int64_t)head_fwd_grid(npix) * 256;
+  out->grid_x = with_bn ? bn_fwd_grid(npix, C / epv) : head_fwd_grid(npix); out->grid_y = out->grid_z = 1; out->block = 256;
+  out->items = npix;
+  out->trips_max = ceil_div64(npix, per_pass);
+  out->trips_min = npix / per_pass;
+  return NUNET_OK;
 }
 extern "C" int nunet_head_bwd_bnr(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t K, const void* x, int32_t PX, const float* w, const float* dlogits, void* dx, int32_t PDX, int32_t accumulate, float* dw_slabs, int32_t nslabs, const nunet_bnr_desc* bnr, nunet_stream_t s) {
   NUNET_REQUIRE(x && w && dlogits && dw_slabs && nslabs >= 1 && nslabs <= 4096, "head_bwd: bad args");

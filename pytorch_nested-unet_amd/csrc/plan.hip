@@ -333,6 +333,9 @@ struct PlanRt {  // runtime objects owned by the plan (host side only)
   int multistream;
   int schedule;                            // NUNET_SCHEDULE_LANES: an op runs on its block's lane; NUNET_SCHEDULE_LIST: Sched::run_list picks
   int wgrad_dy;                            // nunet_plan_set_wgrad_dy: the weight gradients form dy1 / dy2 in their loaders (no side stores)
+  int head_bn;                             // nunet_plan_set_head_bn: BatchNorm2 of a head-only block output rides in the head's launch (default 1)
+  int bn_up;                               // nunet_plan_set_bn_up: NUNET_BN_UP_* - which producers' BatchNorm2 launch also upsamples
+  int wait_prune;                          // nunet_plan_set_wait_prune: cross-lane waits that lane order already implies are dropped (default 1)
   bool lanes_external;
   std::vector<hipStream_t> cap_streams;   // never-reused streams for capture-time lane continuation
   size_t cap_next;
@@ -623,6 +626,10 @@ static nunet_plan* plan_create_impl(const nunet_plan_cfg* cfg, int depth) {
   { const char* e = getenv("NUNET_MULTISTREAM"); rt->multistream = e ? atoi(e) : 1; }
   rt->schedule = NUNET_SCHEDULE_LANES;
   { const char* e = getenv("NUNET_WGRAD_DY"); rt->wgrad_dy = e ? (atoi(e) != 0) : 0; }
+  // (the three below: environment overrides for A/B runs of unchanged programs, as the two above)
+  { const char* e = getenv("NUNET_HEAD_BN"); rt->head_bn = e ? (atoi(e) != 0) : 1; }
+  { const char* e = getenv("NUNET_BN_UP"); const int v = e ? atoi(e) : NUNET_BN_UP_NONE; rt->bn_up = v >= NUNET_BN_UP_NONE && v <= NUNET_BN_UP_ALL ? v : NUNET_BN_UP_NONE; }
+  { const char* e = getenv("NUNET_WAIT_PRUNE"); rt->wait_prune = e ? (atoi(e) != 0) : 1; }
   for (int l = 0; l < NLANES; ++l) {
     rt->lanes[l] = nullptr;
     if (hipStreamCreateWithFlags(&rt->lanes[l], hipStreamNonBlocking) != hipSuccess) { rt->lanes_ok = false; (void)hipGetLastError(); }
@@ -731,8 +738,63 @@ static_assert(B_ST2 < B_STRIDE && L_GPIN < L_STRIDE && R_X + 5 * 5 <= R_GX && R_
               R_GSV + 2 * NUNET_MAX_BLOCKS <= R_GSH && R_GSH + NUNET_MAX_HEADS <= R_LVL && R_LVL + NUNET_MAX_BLOCKS * L_STRIDE <= R_SK &&
               R_SK + NUNET_MAX_BLOCKS <= NRES, "resource-id ranges overlap at this capacity");
 
+// ---- Which cross-lane waits an op still needs -------------------------------------------------------------------------------
+// Lanes are in-order (a stream; while capturing, a chain of streams each forked from the lane's tail), and what a kernel wrote
+// is visible device-wide once it has ended (flag executor) - so "ends before" is transitive: an op that starts after
+// op B has ended, where B started after A had ended, needs no wait of its own for A. Every issued op gets a stamp: its lane, its
+// number on that lane, and the vector clock of its lane at that point - per lane, the number of the last op known to have ended
+// before this one starts. A requested wait (read after write, write after write, write after read alike) whose producer the
+// waiting lane's clock already covers is dropped; so is one that another wait of the same op covers; every wait that is kept
+// merges the producer's clock into the lane's. Host bookkeeping only; nunet_wait_prune_host runs it over plain arrays.
+#define WP_MAXL 16
+static_assert(NLANES <= WP_MAXL, "the wait pruner's clocks cover every lane");
+struct LaneStamp { int lane, seq; int clock[WP_MAXL]; };
+struct WaitPruner {
+  int know[WP_MAXL][WP_MAXL], seq[WP_MAXL];
+  void reset() { memset(know, 0, sizeof(know)); memset(seq, 0, sizeof(seq)); }
+  void absorb(int L, const LaneStamp& s) { for (int l = 0; l < WP_MAXL; ++l) know[L][l] = std::max(know[L][l], s.clock[l]); }
+  // the op about to start on lane L asks to wait for c[0..n): keep[q] = 1 for the waits it must make
+  void decide(int L, const LaneStamp* const* c, int n, unsigned char* keep) {
+    for (int q = 0; q < n; ++q) keep[q] = know[L][c[q]->lane] < c[q]->seq;
+    for (int q = 0; q < n; ++q) {
+      if (!keep[q]) continue;
+      for (int r = 0; r < n && keep[q]; ++r) {
+        if (r == q || !keep[r] || c[r]->clock[c[q]->lane] < c[q]->seq) continue;
+        const bool same = c[r]->lane == c[q]->lane && c[r]->seq == c[q]->seq;   // the same op asked for twice: the first stays
+        if (!same || r < q) keep[q] = 0;
+      }
+    }
+    for (int q = 0; q < n; ++q) if (keep[q]) absorb(L, *c[q]);
+  }
+  LaneStamp done(int L) {        // the op on lane L has been issued
+    LaneStamp s; s.lane = L; s.seq = ++seq[L]; know[L][L] = s.seq;
+    memcpy(s.clock, know[L], sizeof(s.clock));
+    return s;
+  }
+};
+extern "C" int nunet_wait_prune_host(int32_t nlanes, int32_t nops, const int32_t* op_lane, const int32_t* edge_off, const int32_t* edge_src, uint8_t* keep) {
+  NUNET_REQUIRE(op_lane && edge_off && keep && nlanes >= 1 && nlanes <= WP_MAXL && nops >= 0, "wait_prune_host: bad args (1..%d lanes)", WP_MAXL);
+  WaitPruner wp; wp.reset();
+  std::vector<LaneStamp> stamp((size_t)nops);
+  std::vector<const LaneStamp*> c;
+  for (int b = 0; b < nops; ++b) {
+    const int L = op_lane[b], e0 = edge_off[b], e1 = edge_off[b + 1];
+    NUNET_REQUIRE(L >= 0 && L < nlanes && e0 <= e1 && (e0 == e1 || edge_src), "wait_prune_host: op %d: lane %d, edges [%d, %d)", b, L, e0, e1);
+    c.clear();
+    for (int e = e0; e < e1; ++e) {
+      NUNET_REQUIRE(edge_src[e] >= 0 && edge_src[e] < b, "wait_prune_host: edge %d of op %d names op %d, which is not issued before it", e, b, edge_src[e]);
+      c.push_back(&stamp[edge_src[e]]);
+    }
+    if (!c.empty()) wp.decide(L, c.data(), (int)c.size(), keep + e0);
+    stamp[b] = wp.done(L);
+  }
+  return NUNET_OK;
+}
+
 struct Sched {
   hipStream_t main_s;
+  WaitPruner wp; bool prune;                       // see above; prune off: every requested wait is made (nunet_plan_set_wait_prune)
+  std::map<hipEvent_t, LaneStamp> stamp_of;        // the op each event of this pass marks the end of
   hipStream_t lane_s[NLANES];      // stream currently carrying each lane (fixed lanes when not capturing)
   hipEvent_t lane_tail[NLANES];    // event after the last op issued on the lane
   bool multi, capturing, failed;
@@ -771,7 +833,8 @@ struct Sched {
   void init(nunet_plan* P, hipStream_t s, int pass);
   // One wait per distinct event, never on an event of the stream itself.
   void want(hipEvent_t ev, hipStream_t ev_st, hipStream_t st) {
-    if (!ev || ev_st == st) return;
+    if (!ev) return;
+    if (ev_st == st) { if (prune) wp.absorb(cur_lane, stamp_of[ev]); return; }   // (stream order: what that op knew, this one knows)
     for (int k = 0; k < npend; ++k) if (pend[k] == ev) return;
     if (npend < 64) pend[npend++] = ev;
     else failed = true;        // a dropped wait would be a silent race between lanes: reported by the caller after the join
@@ -805,6 +868,14 @@ struct Sched {
       Res& R = res[w];
       want(R.w_ev, R.w_st, st);
       for (int l = 0; l < NLANES; ++l) want(R.r_ev[l], R.r_st[l], st);
+    }
+    if (prune && npend > 0) {
+      const LaneStamp* c[64]; unsigned char keep[64];
+      for (int k = 0; k < npend; ++k) c[k] = &stamp_of[pend[k]];
+      wp.decide(lane, c, npend, keep);
+      int m = 0;
+      for (int k = 0; k < npend; ++k) if (keep[k]) pend[m++] = pend[k];
+      npend = m;
     }
     if (capturing) {
       if (!used[lane] || npend > 0) {
@@ -882,6 +953,7 @@ struct Sched {
     if (capturing) graph_tag_tail(st, cur_lane);
     hipEvent_t ev = new_event();
     record_on(ev, st);
+    stamp_of[ev] = wp.done(cur_lane);
     lane_tail[cur_lane] = ev;
     for (int k = 0; k < nreads; ++k) { res[reads[k]].r_ev[cur_lane] = ev; res[reads[k]].r_st[cur_lane] = st; }
     for (int k = 0; k < nwrites; ++k) {
@@ -991,6 +1063,7 @@ void Sched::init(nunet_plan* P, hipStream_t s, int pass_) {
   list = rt->schedule == NUNET_SCHEDULE_LIST && !rt->calibrating;
   failed = false;
   capturing = false;
+  prune = rt->wait_prune != 0; wp.reset(); stamp_of.clear();
   pool = &rt->events[pass]; pool_used = &rt->events_used[pass];
   *pool_used = 0;
   memset(res, 0, sizeof(res));
@@ -1241,15 +1314,45 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
     });
   }
   // (The x2 upsample of a block output can ride in the producer's BatchNorm launch as a second block role - nunet_bn_fwd_desc.up,
-  // bit-identical, ten launches fewer per forward. Measured on MI355X, same box: single-lane step unchanged (2.557 vs 2.554 ms),
-  // multi-lane graph step SLOWER (8326 vs 8700 and 8041 vs 8232 img/s). The plan keeps the stand-alone launch.)
+  // bit-identical; which producers do is rt->bn_up. Measured on MI355X under the flag-synchronised, list-scheduled executor, 96x96
+  // batch 16 bf16, six alternating runs of 200 steps each: none / the chain's four row ends / all ten = 1.586 / 1.601 / 1.636 ms per
+  // step (min-max spread of one configuration 0.012 ms); 256x256 batch 32: none / chain = 15.25 / 15.63 ms. The fused launch pays
+  // the coefficient prologue in every upsample workgroup and holds the chain longer than the launch it saves: the default is none.)
+  const PlanRt* const prt = rt_of(P);
+  // the block that upsamples block k's output (-1: none), and whether k's BatchNorm2 launch does it for that block
+  auto up_reader = [&](int k) {
+    const Node& n = P->exec[k];
+    for (int q = 0; q < (int)P->exec.size(); ++q)
+      if (P->exec[q].up_slot >= 0 && P->exec[q].i + 1 == n.i && P->exec[q].up_slot == n.out_slot) return q;
+    return -1;
+  };
+  auto up_in_bn = [&](int k) {
+    const Node& n = P->exec[k];
+    if (prt->bn_up == NUNET_BN_UP_NONE || up_reader(k) < 0) return false;
+    return prt->bn_up == NUNET_BN_UP_ALL || P->cfg.unet || n.i + n.j == (P->depth ? P->depth : 4);   // _CHAIN: the row ends B40, B31, B22, B13
+  };
+  // A head whose slot no block reads in the forward pass (the last head of a full plan, final<L> of a pruned one) takes its
+  // block's BatchNorm2 + ReLU into its own launch (nunet_head_fwd_bn): head_block[k] = that block, or -1.
+  int head_block[NUNET_MAX_HEADS];
+  for (size_t h = 0; h < P->heads.size(); ++h) {
+    head_block[h] = -1;
+    if (!prt->head_bn) continue;
+    bool read = false;
+    for (const Node& q : P->exec) read |= q.i == 0 && q.in_prefix > P->heads[h].slot;
+    for (int k = 0; k < (int)P->exec.size() && !read; ++k)
+      if (P->exec[k].i == 0 && P->exec[k].out_slot == P->heads[h].slot && P->exec[k].in_prefix > 0) head_block[h] = k;
+  }
+  nunet_bn_fwd_desc head_bn[NUNET_MAX_HEADS];
   for (int k = 0; k < (int)P->exec.size(); ++k) {
     const Node& n = P->exec[k];
     const int i = n.i, f = NBF[i], H = P->hl[i], W = P->wl[i];
     const int lane = lane_of(P, n), rb = R_BLK + k * B_STRIDE;
     const Cat in = block_in(P, arena, k, false);
     const BnView bn1 = bn_view(P, arena, params, k, 0, 0), bn2 = bn_view(P, arena, params, k, 1, 0);
-    if (n.up_slot >= 0) {
+    int up_writer = -1;      // the block whose output this one upsamples
+    for (int q = 0; q < k && n.up_slot >= 0; ++q)
+      if (P->exec[q].i == i + 1 && P->exec[q].out_slot == n.up_slot) up_writer = q;
+    if (n.up_slot >= 0 && !(up_writer >= 0 && up_reader(up_writer) == k && up_in_bn(up_writer))) {
       const Buf x = slot_of(P, arena, false, i + 1, n.up_slot);
       S.name("B%d%d.upF", n.i, n.j);
       S.add(lane, 0, 7.f, {x.r}, {in.r[4]}, [=](hipStream_t ls) {
@@ -1307,8 +1410,17 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
         const int q = block_at(P, i + 1, 0);
         if (q >= 0) { const Cat nx = block_in(P, arena, q, false); b.pooled = nx.p[0]; b.PP = f; rpin = nx.r[0]; }
       }
+      int rup = -1;
+      if (up_in_bn(k)) {                // the reader's upsampled input, written here instead of by its stand-alone launch
+        const Cat nx = block_in(P, arena, up_reader(k), false);
+        b.up = nx.p[1]; b.PU = f; rup = nx.r[4];
+      }
+      bool in_head = false;
+      for (size_t h = 0; h < P->heads.size(); ++h)
+        if (head_block[h] == k) { head_bn[h] = b; in_head = true; }
+      if (in_head) continue;            // issued with the head below
       S.name("B%d%d.bnF2", n.i, n.j);
-      S.add(lane, 0, 6.f, {bn2.r_y, bn2.r_fx}, {out.r, rpin}, [=](hipStream_t ls) { return nunet_bn_relu_fwd(&b, ls); });
+      S.add(lane, 0, 6.f, {bn2.r_y, bn2.r_fx}, {out.r, rpin, rup}, [=](hipStream_t ls) { return nunet_bn_relu_fwd(&b, ls); });
     }
   }
   const long long plane = (long long)c.N * c.num_classes * c.H * c.W;
@@ -1316,6 +1428,15 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
     const Head hd = P->heads[k];
     const Buf x = slot_of(P, arena, false, 0, hd.slot);
     S.name("head%d.F", (int)k);
+    if (head_block[k] >= 0) {
+      // (the union of the two launches' resource ids; the slot stays materialised for Plan.feature and the backward pass)
+      const nunet_bn_fwd_desc b = head_bn[k];
+      const BnView bn2 = bn_view(P, arena, params, head_block[k], 1, 0);
+      S.add(0, 0, 8.f, {bn2.r_y, bn2.r_fx}, {x.r, R_LOGITS + 0}, [=](hipStream_t ls) {
+        return nunet_head_fwd_bn(&b, c.num_classes, params + hd.w_off, params + hd.b_off, logits + plane * k, ls);
+      });
+      continue;
+    }
     S.add(0, 0, 10.f, {x.r}, {R_LOGITS + 0}, [=](hipStream_t ls) {
       return nunet_head_fwd(dt, c.N, c.H, c.W, NBF[0], c.num_classes, x.p, P->PX[0], params + hd.w_off, params + hd.b_off, logits + plane * k, ls);
     });
@@ -1968,5 +2089,26 @@ extern "C" int nunet_plan_block_act1(nunet_plan* P, const float* params, void* a
 extern "C" int nunet_plan_set_multistream(nunet_plan* P, int32_t enable) {
   NUNET_REQUIRE(P, "plan_set_multistream: null plan");
   rt_of(P)->multistream = enable;
+  return NUNET_OK;
+}
+
+// The three forward / scheduler choices below (nunet_diag.h) are read when a pass is issued: set them before the first forward or capture.
+extern "C" int nunet_plan_set_head_bn(nunet_plan* P, int32_t enable) {
+  NUNET_REQUIRE(P, "plan_set_head_bn: null plan");
+  NUNET_REQUIRE(enable == 0 || enable == 1, "plan_set_head_bn: %d is neither 0 (two launches) nor 1 (nunet_head_fwd_bn)", enable);
+  rt_of(P)->head_bn = enable;
+  return NUNET_OK;
+}
+extern "C" int nunet_plan_set_bn_up(nunet_plan* P, int32_t mode) {
+  NUNET_REQUIRE(P, "plan_set_bn_up: null plan");
+  NUNET_REQUIRE(mode >= NUNET_BN_UP_NONE && mode <= NUNET_BN_UP_ALL, "plan_set_bn_up: %d is not one of NUNET_BN_UP_NONE (0), _CHAIN (1), _ALL (2)", mode);
+  rt_of(P)->bn_up = mode;
+  return NUNET_OK;
+}
+extern "C" int nunet_plan_set_wait_prune(nunet_plan* P, int32_t enable) {
+  NUNET_REQUIRE(P, "plan_set_wait_prune: null plan");
+  NUNET_REQUIRE(enable == 0 || enable == 1, "plan_set_wait_prune: %d is neither 0 (every requested wait) nor 1 (implied waits dropped)", enable);
+  NUNET_REQUIRE(!rt_of(P)->open_sched, "plan_set_wait_prune: a backward pass is open (nunet_plan_backward_phase 1|8)");
+  rt_of(P)->wait_prune = enable;
   return NUNET_OK;
 }
