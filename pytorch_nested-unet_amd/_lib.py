@@ -284,6 +284,7 @@ _SIG = {
     "nunet_plan_repack": (_i32, [_vp, _vp, _vp, _sz, _vp]),
     "nunet_plan_feature": (_i64, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "nunet_plan_feature_grad": (_i64, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "nunet_plan_image": (_i64, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "nunet_plan_block_act1": (_i32, [_vp, _vp, _vp, _sz, _i32, _i32, _vp, _vp]),
     "nunet_plan_census_count": (_i32, [_vp, _i32]),
     "nunet_plan_census_get": (_i32, [_vp, _i32, _i32, C.POINTER(PlanCensusEntry)]),

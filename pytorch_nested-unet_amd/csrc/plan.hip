@@ -690,6 +690,12 @@ static int64_t slot_offset(const nunet_plan* p, const size_t* level, int32_t i, 
 }
 extern "C" int64_t nunet_plan_feature(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels) { return slot_offset(p, p ? p->X : nullptr, i, j, pitch, channels); }
 extern "C" int64_t nunet_plan_feature_grad(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels) { return (p && p->depth) ? -1 : slot_offset(p, p ? p->GX : nullptr, i, j, pitch, channels); }
+extern "C" int64_t nunet_plan_image(const nunet_plan* p, int32_t* pitch, int32_t* channels) {
+  if (!p) return -1;
+  if (pitch) *pitch = 32;
+  if (channels) *channels = p->cfg.input_channels;
+  return (int64_t)p->off_img;
+}
 extern "C" int32_t nunet_plan_census_count(const nunet_plan* p, int32_t pass) {
   return (p && p->rt && (pass == 0 || pass == 1)) ? (int32_t)p->rt->census[pass].size() : 0;
 }

@@ -19,6 +19,16 @@ def _check_color(color, n, c):
         raise L.NunetError("the colour ops are defined on RGB images: C=%d must be 3" % c)
 
 
+def _check_aug(aug, n, h, w):
+    """The kernels read aug[i] for every sample i < n and, for an odd rot90 count, source row = destination column: refuse
+    anything but int32 [n] on the device, and an odd count on non-square images, before a launch."""
+    L.require_gpu_tensor(aug, torch.int32, "aug")
+    if tuple(aug.shape) != (n,):
+        raise L.NunetError("aug must be int32 [%d], one code per sample (draw_augmentation), got %s" % (n, tuple(aug.shape)))
+    if h != w and bool((aug & 1).any()):
+        raise L.NunetError("rot90 by an odd count needs square images")
+
+
 def preprocess_images(u8_nhwc, aug=None, mean=MEAN, std=STD, color=None):
     """uint8 [N,H,W,C] (device) -> float32 [N,C,H,W]: ((u/255 - mean)/std)/255, optional per-sample
     geometric augmentation codes (int32 [N]: rot90 count | hflip<<2 | vflip<<3) and colour codes (int32 [N,4],
@@ -30,9 +40,7 @@ def preprocess_images(u8_nhwc, aug=None, mean=MEAN, std=STD, color=None):
     s = torch.tensor(np.resize(np.asarray(std, np.float32), c), device=dev)
     out = torch.empty((n, c, h, w), dtype=torch.float32, device=dev)
     if aug is not None:
-        L.require_gpu_tensor(aug, torch.int32, "aug")
-        if h != w and bool((aug & 1).any()):
-            raise L.NunetError("rot90 by an odd count needs square images")
+        _check_aug(aug, n, h, w)
     if color is not None:
         _check_color(color, n, c)
         L.check(L.lib().nunet_preprocess_u8_color(L.ptr(u8_nhwc), n, h, w, c, L.ptr(m), L.ptr(s), L.ptr(aug), L.ptr(color), 1.0 / 255.0,
@@ -58,6 +66,8 @@ def preprocess_masks(u8_nhwc, aug=None):
     """uint8 {0,255} [N,H,W,K] -> float32 [N,K,H,W] in {0,1} (dataset.py:73), same augmentation codes."""
     L.require_gpu_tensor(u8_nhwc, torch.uint8, "masks")
     n, h, w, c = u8_nhwc.shape
+    if aug is not None:
+        _check_aug(aug, n, h, w)
     out = torch.empty((n, c, h, w), dtype=torch.float32, device=u8_nhwc.device)
     L.check(L.lib().nunet_preprocess_u8(L.ptr(u8_nhwc), n, h, w, c, None, None, L.ptr(aug), 1.0, L.ptr(out), L.stream()),
             "nunet_preprocess_u8")

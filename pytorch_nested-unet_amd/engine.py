@@ -55,6 +55,17 @@ class Plan:
         """dL/dx_{i,j} as an [N,H_i,W_i,C] NHWC view in the storage dtype, intact after backward (tests/debug)."""
         return self._slot(L.lib().nunet_plan_feature_grad, i, j)
 
+    def image(self):
+        """The staged input image as an [N,H,W,32] NHWC view in the storage dtype: what nunet_plan_stage_u8(_color) or the
+        layout launch of the last forward left for the first convolution; channels past input_channels are zeros (tests/debug)."""
+        pitch, ch = C.c_int32(), C.c_int32()
+        off = L.lib().nunet_plan_image(self.handle, C.byref(pitch), C.byref(ch))
+        if off < 0:
+            raise L.NunetError("nunet_plan_image: no plan")
+        flat = self.arena[off:].view(L.TORCH_DTYPE[self.dtype])
+        p = pitch.value
+        return flat.as_strided((self.n, self.h, self.w, p), (self.h * self.w * p, self.w * p, p, 1))
+
     def block_act1(self, i, j):
         """relu(bn1(conv1(.))) of block (i, j), [N,H_i,W_i,C] NHWC in a tensor of its own (tests/debug). No pass stores it:
         it is materialised here from the raw conv output the last training forward left in the arena, with that forward's batch

@@ -26,6 +26,7 @@ import torch.distributed as dist
 
 from . import _lib as L
 from . import loss_scale as LS
+from .dataset import _check_aug
 from .optim_state import flat_to_torch_state, torch_state_to_flat
 from .parallel import allreduce_flat_, broadcast_flat_
 
@@ -671,13 +672,13 @@ class TrainStep:
             if color.dtype != torch.int32 or tuple(color.shape) != tuple(self.color.shape):
                 raise L.NunetError("step_u8: color must be int32 %s (dataset.draw_color_augmentation), got %s %s"
                                    % (tuple(self.color.shape), color.dtype, tuple(color.shape)))
+        if aug is not None:
+            _check_aug(aug, self.n, self.h, self.w)       # before the static buffers change
         self.x_u8.copy_(images_u8, non_blocking=True)
         self.t_u8.copy_(masks_u8, non_blocking=True)
         if aug is None:
             self.aug.zero_()
         else:
-            if self.h != self.w and bool((aug & 1).any()):
-                raise L.NunetError("rot90 by an odd count needs square images")
             self.aug.copy_(aug, non_blocking=True)
         if self.color is not None:
             if color is None:
