@@ -556,6 +556,32 @@ int nunet_color_aug_u8(const uint8_t* src, int32_t N, int32_t H, int32_t W, int3
 int nunet_preprocess_u8_color(const uint8_t* u8_nhwc, int32_t N, int32_t H, int32_t W, int32_t C,
                               const float* mean, const float* stdv, const int32_t* aug, const nunet_color_aug* color,
                               float post_scale, float* out_nchw, nunet_stream_t s);
+/* Resize(input_h, input_w) of the reference's train and val transforms (trains.py:257-271) on RAGGED uint8 sources: a byte
+ * pool and one descriptor per sample, both in DEVICE memory and read at run time (a captured step replays with new sizes).
+ * Sample n is a tight HWC image of samples[n].H x samples[n].W x C bytes at pool + samples[n].offset. The arithmetic is this
+ * project's definition (input pipeline), modelled on OpenCV's 8-bit INTER_LINEAR and INTER_NEAREST, not verified
+ * against them. Along one axis with source extent S, destination extent D and destination index d (64-bit intermediates):
+ *   LINEAR   num = (2d+1)*S - D, den = 2*D. num < 0: s = 0, a1 = 0. Else s = num / den, r = num % den; s >= S-1: s = S-1,
+ *            a1 = 0; else a1 = (r*4096 + den) / (2*den). a0 = 2048 - a1, the second tap is min(s+1, S-1). Per channel
+ *            R(y, dx) = src[y][x0]*a0 + src[y][x1]*a1, out = (((b0*(R(y0,dx) >> 4)) >> 16) + ((b1*(R(y1,dx) >> 4)) >> 16) + 2) >> 2.
+ *   NEAREST  s = min(d*S / D, S-1) (no half-pixel shift); for masks.
+ * The reference augments, then resizes: aug[n] (as nunet_preprocess_u8; NULL = none) turns the source into a view, W x H after
+ * an odd rot90 count - no square source is needed - and the resize maps that view to Hd x Wd. color[n] (NULL = none; LINEAR
+ * and C == 3 only) applies to every fetched source tap. The host cannot see the descriptors: a thread whose descriptor has
+ * H < 1, W < 1, H or W > NUNET_RESIZE_MAX_EXTENT, offset < 0 or offset + H*W*C > pool_bytes reads nothing and takes the
+ * sample's resized bytes as zeros. Hd, Wd <= NUNET_RESIZE_MAX_EXTENT. */
+enum { NUNET_RESIZE_LINEAR = 0, NUNET_RESIZE_NEAREST = 1 };
+#define NUNET_RESIZE_MAX_EXTENT 16384
+typedef struct nunet_u8_sample { int64_t offset; int32_t H, W; } nunet_u8_sample;   /* 16 bytes, DEVICE memory, one per sample */
+/* ragged uint8 HWC sources -> uint8 [N][Hd][Wd][C] */
+int nunet_resize_u8(const uint8_t* pool, int64_t pool_bytes, const nunet_u8_sample* samples, int32_t N, int32_t C, int32_t Hd,
+                    int32_t Wd, int32_t mode, const int32_t* aug, const nunet_color_aug* color, uint8_t* dst_u8_nhwc,
+                    nunet_stream_t s);
+/* NEAREST resize into fp32 NCHW [N][C][Hd][Wd], one launch: bit for bit nunet_resize_u8 with NUNET_RESIZE_NEAREST and the
+ * same aug followed by nunet_preprocess_u8 with aug NULL (masks: mean and stdv NULL, post_scale 1). */
+int nunet_preprocess_u8_resize(const uint8_t* pool, int64_t pool_bytes, const nunet_u8_sample* samples, int32_t N, int32_t C,
+                               int32_t Hd, int32_t Wd, const float* mean, const float* stdv, const int32_t* aug,
+                               float post_scale, float* out_nchw, nunet_stream_t s);
 /* NCHW fp32 -> NHWC dtype with channel padding (zeros) up to cpad */
 int nunet_nchw_to_nhwc(const float* x, int32_t N, int32_t C, int32_t H, int32_t W,
                        int32_t dtype, void* y, int32_t cpad, nunet_stream_t s);
@@ -615,6 +641,13 @@ int nunet_plan_stage_u8(nunet_plan* p, const uint8_t* u8_nhwc, const float* mean
  * stdv given. color == NULL (or every op NONE) gives nunet_plan_stage_u8's image bit for bit. */
 int nunet_plan_stage_u8_color(nunet_plan* p, const uint8_t* u8_nhwc, const float* mean, const float* stdv, const int32_t* aug,
                               const nunet_color_aug* color, float post_scale, void* arena, size_t arena_bytes, nunet_stream_t s);
+/* The staging launch on ragged sources: N = the plan's N samples of input_channels channels, resized (LINEAR) to the plan's
+ * H x W behind aug and color, then normalised and stored as nunet_plan_stage_u8 stores. One launch: bit for bit nunet_resize_u8
+ * with NUNET_RESIZE_LINEAR, the same aug and color, followed by nunet_plan_stage_u8 with aug NULL. color != NULL needs
+ * input_channels == 3; mean and stdv may be NULL without it. */
+int nunet_plan_stage_u8_resize(nunet_plan* p, const uint8_t* pool, int64_t pool_bytes, const nunet_u8_sample* samples,
+                               const float* mean, const float* stdv, const int32_t* aug, const nunet_color_aug* color,
+                               float post_scale, void* arena, size_t arena_bytes, nunet_stream_t s);
 /* grads: flat fp32 in params order. accumulate: += instead of assign. */
 int nunet_plan_backward(nunet_plan* p, const float* params, const float* dlogits, void* arena, size_t arena_bytes,
                         float* grads, int32_t accumulate, nunet_stream_t s);

@@ -188,6 +188,11 @@ COLOR_WORDS = 4     # nunet_color_aug: 16 bytes of device memory per sample, [op
 COLOR_NONE, COLOR_HSV, COLOR_BRIGHTNESS, COLOR_CONTRAST = 0, 1, 2, 3      # NUNET_COLOR_* in include/nunet.h
 
 
+SAMPLE_WORDS = 4    # nunet_u8_sample: 16 bytes of device memory per sample, [offset i64 (2 words), H i32, W i32] - an int32 [N,4] tensor
+RESIZE_LINEAR, RESIZE_NEAREST = 0, 1        # NUNET_RESIZE_* in include/nunet.h
+RESIZE_MAX_EXTENT = 16384                   # NUNET_RESIZE_MAX_EXTENT
+
+
 class PlanCfg(C.Structure):
     _fields_ = [("N", _i32), ("H", _i32), ("W", _i32),
                 ("input_channels", _i32), ("num_classes", _i32), ("deep_supervision", _i32),
@@ -261,6 +266,8 @@ _SIG = {
     "nunet_preprocess_u8": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
     "nunet_color_aug_u8": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "nunet_preprocess_u8_color": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp]),
+    "nunet_resize_u8": (_i32, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "nunet_preprocess_u8_resize": (_i32, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
     "nunet_nchw_to_nhwc": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "nunet_plan_create": (_vp, [C.POINTER(PlanCfg)]),
     "nunet_plan_create_pruned": (_vp, [C.POINTER(PlanCfg), _i32]),
@@ -274,6 +281,7 @@ _SIG = {
     "nunet_plan_forward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _i32, _vp]),
     "nunet_plan_stage_u8": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _sz, _vp]),
     "nunet_plan_stage_u8_color": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _sz, _vp]),
+    "nunet_plan_stage_u8_resize": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _sz, _vp]),
     "nunet_plan_backward": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _i32, _vp]),
     "nunet_plan_backward_phase": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _i32, _i32, _vp]),
     "nunet_plan_grad_scratch": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),

@@ -329,6 +329,108 @@ __device__ __forceinline__ void color_aug_sample(const nunet_color_aug* __restri
   color_aug_pixel(c.op, c.p0, c.p1, c.p2, r, g, b);
 }
 
+// ---------------------------------------------------------------------------
+// Geometric augmentation, destination-driven: pixel (y, x) of the augmented view <- source pixel (ry, rx) of a [Hs][Ws]
+// image: undo the flips, then the rotation. aug = rot90 count (bits 0-1, counter-clockwise like np.rot90) | hflip (bit 2) |
+// vflip (bit 3). The view is [Hs][Ws] after an even rot90 count and [Ws][Hs] after an odd one. Every loader of the sample
+// pipeline (preprocess_u8, preprocess_u8_color, stage_u8 and the resizing entries) maps through this one function.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void aug_source_pixel(int a, int Hs, int Ws, int y, int x, int& ry, int& rx) {
+  const int k = a & 3;
+  const int Hv = (k & 1) ? Ws : Hs, Wv = (k & 1) ? Hs : Ws;
+  int sy = y, sx = x;
+  if (a & 8) sy = Hv - 1 - sy;
+  if (a & 4) sx = Wv - 1 - sx;
+  ry = sy; rx = sx;
+  if (k == 1) { ry = sx; rx = Ws - 1 - sy; }
+  else if (k == 2) { ry = Hs - 1 - sy; rx = Ws - 1 - sx; }
+  else if (k == 3) { ry = Hs - 1 - sx; rx = sy; }
+}
+
+// ---------------------------------------------------------------------------
+// Resize(input_h, input_w) of the reference's transforms (trains.py:265, 269) on ragged uint8 sources: sample n is a tight
+// HWC image at pool + samples[n].offset (nunet_u8_sample, device memory). The arithmetic is this project's definition
+// (input pipeline), modelled on OpenCV's 8-bit INTER_LINEAR (two passes, 11-bit coefficients) and INTER_NEAREST,
+// stated in integers. The reference augments the source and then resizes, so a destination pixel takes its taps in the
+// AUGMENTED view, each tap goes back through aug_source_pixel to the source bytes, and the colour op applies to each fetched
+// tap. nunet_resize_u8, nunet_preprocess_u8_resize (elementwise.hip) and nunet_plan_stage_u8_resize (plan.hip) share it.
+// ---------------------------------------------------------------------------
+// One axis, source extent S -> destination extent D, destination index d: taps s0, s1 and the weight a1 of s1 (a0 = 2048 - a1)
+__device__ __forceinline__ void resize_axis_taps(int S, int D, int d, int& s0, int& s1, int& a1) {
+  const long long num = (2ll * d + 1) * S - D, den = 2ll * D;
+  long long s = 0, a = 0;
+  if (num >= 0) {
+    s = num / den;
+    if (s >= S - 1) s = S - 1;
+    else a = ((num % den) * 4096 + den) / (2 * den);
+  }
+  s0 = (int)s; a1 = (int)a;
+  s1 = min(s0 + 1, S - 1);
+}
+struct ResizeTaps {
+  long long o[2][2];    // byte offsets into the pool of the source pixels behind the taps (y0|y1, x0|x1); o[0][0] < 0: bad descriptor
+  int ax1, ay1;         // weights of the second tap along x and y, 0 .. 2048
+};
+// a descriptor a thread may read through: inside the pool, extents 1 .. NUNET_RESIZE_MAX_EXTENT
+__device__ __forceinline__ bool resize_sample_ok(const nunet_u8_sample& d, int C, long long pool_bytes) {
+  return d.H >= 1 && d.W >= 1 && d.H <= NUNET_RESIZE_MAX_EXTENT && d.W <= NUNET_RESIZE_MAX_EXTENT && d.offset >= 0 &&
+         d.offset <= pool_bytes && (long long)d.H * d.W * C <= pool_bytes - d.offset;
+}
+template <bool NEAREST>
+__device__ __forceinline__ ResizeTaps resize_taps(const nunet_u8_sample& d, int C, long long pool_bytes, int a, int Hd, int Wd, int y, int x) {
+  ResizeTaps t;
+  t.ax1 = t.ay1 = 0;
+  if (!resize_sample_ok(d, C, pool_bytes)) { t.o[0][0] = t.o[0][1] = t.o[1][0] = t.o[1][1] = -1; return t; }
+  const int Hv = (a & 1) ? d.W : d.H, Wv = (a & 1) ? d.H : d.W;
+  int vy[2], vx[2];
+  if constexpr (NEAREST) {
+    vy[0] = vy[1] = (int)min((long long)y * Hv / Hd, (long long)Hv - 1);
+    vx[0] = vx[1] = (int)min((long long)x * Wv / Wd, (long long)Wv - 1);
+  } else {
+    resize_axis_taps(Hv, Hd, y, vy[0], vy[1], t.ay1);
+    resize_axis_taps(Wv, Wd, x, vx[0], vx[1], t.ax1);
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      int ry, rx;
+      aug_source_pixel(a, d.H, d.W, vy[j], vx[i], ry, rx);
+      t.o[j][i] = d.offset + ((long long)ry * d.W + rx) * C;
+    }
+  return t;
+}
+// the two passes on one channel's four bytes
+__device__ __forceinline__ uint8_t resize_lerp(int p00, int p01, int p10, int p11, int ax1, int ay1) {
+  const int r0 = (p00 * (2048 - ax1) + p01 * ax1) >> 4, r1 = (p10 * (2048 - ax1) + p11 * ax1) >> 4;
+  return (uint8_t)(((((2048 - ay1) * r0) >> 16) + ((ay1 * r1) >> 16) + 2) >> 2);
+}
+// channel c of the destination pixel behind t (no colour op); a bad descriptor gives 0 without a read
+template <bool NEAREST>
+__device__ __forceinline__ uint8_t resize_channel(const uint8_t* __restrict__ pool, const ResizeTaps& t, int c) {
+  if (t.o[0][0] < 0) return 0;
+  if constexpr (NEAREST) return pool[t.o[0][0] + c];
+  else return resize_lerp(pool[t.o[0][0] + c], pool[t.o[0][1] + c], pool[t.o[1][0] + c], pool[t.o[1][1] + c], t.ax1, t.ay1);
+}
+// the RGB destination pixel behind t, the colour op of `col` on every fetched tap first (bilinear only)
+__device__ __forceinline__ void resize_rgb_color(const uint8_t* __restrict__ pool, const ResizeTaps& t, const nunet_color_aug& col, uint8_t px[3]) {
+  px[0] = px[1] = px[2] = 0;
+  if (t.o[0][0] < 0) return;
+  uint8_t p[2][2][3];
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      p[j][i][0] = p[j][i][1] = p[j][i][2] = 0;
+      if ((i && t.ax1 == 0) || (j && t.ay1 == 0)) continue;      // a tap of weight 0 (every second tap of an equal-size source): no fetch, no colour op
+      const uint8_t* s = pool + t.o[j][i];
+      p[j][i][0] = s[0]; p[j][i][1] = s[1]; p[j][i][2] = s[2];
+      color_aug_pixel(col.op, col.p0, col.p1, col.p2, p[j][i][0], p[j][i][1], p[j][i][2]);
+    }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) px[c] = resize_lerp(p[0][0][c], p[0][1][c], p[1][0][c], p[1][1][c], t.ax1, t.ay1);
+}
+
 template <typename T> struct Vec16 {
   // zero-initialised: set() of a 16-bit element read-modify-writes its 32-bit word, and doing that on an
   // indeterminate word is undefined (it miscompiled for fp16 on the odd elements of words 0 and 1)

@@ -115,16 +115,8 @@ __global__ __launch_bounds__(256) void preprocess_u8_kernel(const uint8_t* __res
     const int y = (int)(t % H); t /= H;
     const int c = (int)(t % C);
     const int n = (int)(t / C);
-    // destination (y, x) <- source (sy, sx): undo flips, then the rotation
-    int sy = y, sx = x;
-    const int a = aug ? aug[n] : 0;
-    if (a & 8) sy = H - 1 - sy;
-    if (a & 4) sx = W - 1 - sx;
-    const int k = a & 3;                       // out = rot90(src, k)  (H == W when k is odd)
-    int ry = sy, rx = sx;
-    if (k == 1) { ry = sx; rx = W - 1 - sy; }
-    else if (k == 2) { ry = H - 1 - sy; rx = W - 1 - sx; }
-    else if (k == 3) { ry = H - 1 - sx; rx = sy; }
+    int ry, rx;                               // destination (y, x) <- source (ry, rx); H == W when the rot90 count is odd
+    aug_source_pixel(aug ? aug[n] : 0, H, W, y, x, ry, rx);
     const float v = (float)u[(((int64_t)n * H + ry) * W + rx) * C + c];
     const float m = mean ? mean[c] : 0.f, sd = stdv ? stdv[c] : 1.f;
     out[i] = ((v / 255.f - m) / sd) * post_scale;
@@ -173,15 +165,8 @@ __global__ __launch_bounds__(256) void preprocess_u8_color_kernel(const uint8_t*
     const int64_t t = i / W;
     const int y = (int)(t % H);
     const int n = (int)(t / H);
-    int sy = y, sx = x;                        // destination (y, x) <- source: undo flips, then the rotation (as preprocess_u8_kernel)
-    const int a = aug ? aug[n] : 0;
-    if (a & 8) sy = H - 1 - sy;
-    if (a & 4) sx = W - 1 - sx;
-    const int k = a & 3;
-    int ry = sy, rx = sx;
-    if (k == 1) { ry = sx; rx = W - 1 - sy; }
-    else if (k == 2) { ry = H - 1 - sy; rx = W - 1 - sx; }
-    else if (k == 3) { ry = H - 1 - sx; rx = sy; }
+    int ry, rx;                                // destination (y, x) <- source (ry, rx); H == W when the rot90 count is odd
+    aug_source_pixel(aug ? aug[n] : 0, H, W, y, x, ry, rx);
     const uint8_t* src = u + (((int64_t)n * H + ry) * W + rx) * 3;
     uint8_t px[3] = {src[0], src[1], src[2]};
     color_aug_sample(color, n, px[0], px[1], px[2]);
@@ -199,6 +184,83 @@ extern "C" int nunet_preprocess_u8_color(const uint8_t* u8_nhwc, int32_t N, int3
   ProfScope ps(PC_LAYOUT, 0, (double)npix * 15, st);
   NUNET_LAUNCH(preprocess_u8_color_kernel, dim3(grid_for(npix, 256, 4096)), dim3(256), 0, st, u8_nhwc, N, H, W, mean, stdv, aug, color, post_scale, out_nchw);
   return nunet_check_launch("preprocess_u8_color");
+}
+
+// Resize on ragged sources (common.h, resize_taps): one thread per DESTINATION pixel - the destination is small, and of a
+// large source only the four taps behind each pixel are touched. The thread forms its taps once and walks the channels.
+template <bool NEAREST, bool COLOR>
+__global__ __launch_bounds__(256) void resize_u8_kernel(const uint8_t* __restrict__ pool, long long pool_bytes,
+                                                         const nunet_u8_sample* __restrict__ samples, int N, int C, int Hd, int Wd,
+                                                         const int32_t* __restrict__ aug, const nunet_color_aug* __restrict__ color,
+                                                         uint8_t* __restrict__ out) {
+  const int64_t npix = (int64_t)N * Hd * Wd;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
+    const int x = (int)(i % Wd);
+    const int64_t q = i / Wd;
+    const int y = (int)(q % Hd);
+    const int n = (int)(q / Hd);
+    const ResizeTaps t = resize_taps<NEAREST>(samples[n], C, pool_bytes, aug ? aug[n] : 0, Hd, Wd, y, x);
+    uint8_t* o = out + i * C;
+    if constexpr (COLOR) {
+      uint8_t px[3];
+      resize_rgb_color(pool, t, color[n], px);
+      o[0] = px[0]; o[1] = px[1]; o[2] = px[2];
+    } else {
+      for (int c = 0; c < C; ++c) o[c] = resize_channel<NEAREST>(pool, t, c);
+    }
+  }
+}
+static int resize_args_ok(const char* what, const void* pool, int64_t pool_bytes, const void* samples, int32_t N, int32_t C, int32_t Hd, int32_t Wd) {
+  NUNET_REQUIRE(pool && samples, "%s: null pointer", what);
+  NUNET_REQUIRE(N > 0 && C > 0 && pool_bytes > 0, "%s: N=%d C=%d pool_bytes=%lld must be positive", what, N, C, (long long)pool_bytes);
+  NUNET_REQUIRE(Hd >= 1 && Wd >= 1 && Hd <= NUNET_RESIZE_MAX_EXTENT && Wd <= NUNET_RESIZE_MAX_EXTENT,
+                "%s: destination %d x %d: extents are 1 .. %d", what, Hd, Wd, NUNET_RESIZE_MAX_EXTENT);
+  return NUNET_OK;
+}
+extern "C" int nunet_resize_u8(const uint8_t* pool, int64_t pool_bytes, const nunet_u8_sample* samples, int32_t N, int32_t C, int32_t Hd,
+                               int32_t Wd, int32_t mode, const int32_t* aug, const nunet_color_aug* color, uint8_t* dst, nunet_stream_t s) {
+  if (int rc = resize_args_ok("resize_u8", pool, pool_bytes, samples, N, C, Hd, Wd)) return rc;
+  NUNET_REQUIRE(dst, "resize_u8: null pointer");
+  NUNET_REQUIRE(mode == NUNET_RESIZE_LINEAR || mode == NUNET_RESIZE_NEAREST, "resize_u8: mode %d is neither LINEAR (0) nor NEAREST (1)", mode);
+  NUNET_REQUIRE(!color || (mode == NUNET_RESIZE_LINEAR && C == 3), "resize_u8: the colour ops are defined on RGB images under LINEAR: mode=%d C=%d", mode, C);
+  const int64_t npix = (int64_t)N * Hd * Wd;
+  hipStream_t st = (hipStream_t)s;
+  ProfScope ps(PC_LAYOUT, 0, (double)npix * C * (mode == NUNET_RESIZE_LINEAR ? 5 : 2), st);
+  const dim3 grid(grid_for(npix, 256, 4096)), block(256);
+  if (mode == NUNET_RESIZE_NEAREST) NUNET_LAUNCH((resize_u8_kernel<true, false>), grid, block, 0, st, pool, (long long)pool_bytes, samples, N, C, Hd, Wd, aug, color, dst);
+  else if (color) NUNET_LAUNCH((resize_u8_kernel<false, true>), grid, block, 0, st, pool, (long long)pool_bytes, samples, N, C, Hd, Wd, aug, color, dst);
+  else NUNET_LAUNCH((resize_u8_kernel<false, false>), grid, block, 0, st, pool, (long long)pool_bytes, samples, N, C, Hd, Wd, aug, color, dst);
+  return nunet_check_launch("resize_u8");
+}
+// preprocess_u8_kernel's arithmetic on the NEAREST tap of a ragged source: one thread per output element
+__global__ __launch_bounds__(256) void preprocess_u8_resize_kernel(const uint8_t* __restrict__ pool, long long pool_bytes,
+                                                                    const nunet_u8_sample* __restrict__ samples, int N, int C, int Hd, int Wd,
+                                                                    const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                                    const int32_t* __restrict__ aug, float post_scale, float* __restrict__ out) {
+  const int64_t total = (int64_t)N * C * Hd * Wd;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int x = (int)(i % Wd);
+    int64_t q = i / Wd;
+    const int y = (int)(q % Hd); q /= Hd;
+    const int c = (int)(q % C);
+    const int n = (int)(q / C);
+    const ResizeTaps t = resize_taps<true>(samples[n], C, pool_bytes, aug ? aug[n] : 0, Hd, Wd, y, x);
+    const float v = (float)resize_channel<true>(pool, t, c);
+    const float m = mean ? mean[c] : 0.f, sd = stdv ? stdv[c] : 1.f;
+    out[i] = ((v / 255.f - m) / sd) * post_scale;
+  }
+}
+extern "C" int nunet_preprocess_u8_resize(const uint8_t* pool, int64_t pool_bytes, const nunet_u8_sample* samples, int32_t N, int32_t C,
+                                          int32_t Hd, int32_t Wd, const float* mean, const float* stdv, const int32_t* aug,
+                                          float post_scale, float* out_nchw, nunet_stream_t s) {
+  if (int rc = resize_args_ok("preprocess_u8_resize", pool, pool_bytes, samples, N, C, Hd, Wd)) return rc;
+  NUNET_REQUIRE(out_nchw, "preprocess_u8_resize: null pointer");
+  const int64_t total = (int64_t)N * C * Hd * Wd;
+  hipStream_t st = (hipStream_t)s;
+  ProfScope ps(PC_LAYOUT, 0, (double)total * 5, st);
+  NUNET_LAUNCH(preprocess_u8_resize_kernel, dim3(grid_for(total, 256, 4096)), dim3(256), 0, st, pool, (long long)pool_bytes, samples, N, C, Hd, Wd,
+               mean, stdv, aug, post_scale, out_nchw);
+  return nunet_check_launch("preprocess_u8_resize");
 }
 
 // ---------------------------------------------------------------------------

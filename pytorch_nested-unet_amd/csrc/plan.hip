@@ -1472,15 +1472,8 @@ __global__ __launch_bounds__(256) void stage_u8_kernel(const uint8_t* __restrict
     long long t = i / W;
     const int y = (int)(t % H);
     const int n = (int)(t / H);
-    int sy = y, sx = x;                       // destination (y, x) <- source: undo flips, then the rotation (as preprocess_u8_kernel)
-    const int a = aug ? aug[n] : 0;
-    if (a & 8) sy = H - 1 - sy;
-    if (a & 4) sx = W - 1 - sx;
-    const int k = a & 3;
-    int ry = sy, rx = sx;
-    if (k == 1) { ry = sx; rx = W - 1 - sy; }
-    else if (k == 2) { ry = H - 1 - sy; rx = W - 1 - sx; }
-    else if (k == 3) { ry = H - 1 - sx; rx = sy; }
+    int ry, rx;                                // destination (y, x) <- source (ry, rx); H == W when the rot90 count is odd
+    aug_source_pixel(aug ? aug[n] : 0, H, W, y, x, ry, rx);
     const uint8_t* src = u + (((long long)n * H + ry) * W + rx) * C;
     uint8_t px[3];
     if constexpr (COLOR) {
@@ -1529,6 +1522,70 @@ extern "C" int nunet_plan_stage_u8_color(nunet_plan* P, const uint8_t* u8_nhwc, 
   const nunet_plan_cfg& c = P->cfg;
   NUNET_REQUIRE(c.input_channels == 3 && mean && stdv, "plan_stage_u8_color: images only: input_channels=%d must be 3, mean and stdv given", c.input_channels);
   return NUNET_DISPATCH(c.dtype, launch_stage_u8, u8_nhwc, c.N, c.H, c.W, c.input_channels, mean, stdv, aug, color, post_scale, (void*)AB(arena, P->off_img), (hipStream_t)s);
+}
+// stage_u8_kernel on ragged sources (nunet_plan_stage_u8_resize): the pixel's bytes come from the bilinear resize of the
+// augmented source (common.h, resize_taps) instead of one fetch; the arithmetic behind the byte and the stores are stage_u8_kernel's.
+// One thread per destination pixel: it forms its four taps once, and of a large source only those taps are read.
+template <typename T, bool COLOR>
+__global__ __launch_bounds__(256) void stage_u8_resize_kernel(const uint8_t* __restrict__ pool, long long pool_bytes,
+                                                              const nunet_u8_sample* __restrict__ samples, int N, int H, int W, int C,
+                                                              const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                              const int32_t* __restrict__ aug, const nunet_color_aug* __restrict__ color,
+                                                              float post_scale, T* __restrict__ img) {
+  constexpr int EPV = Tr<T>::EPV;
+  const long long npix = (long long)N * H * W;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < npix; i += (long long)gridDim.x * blockDim.x) {
+    const int x = (int)(i % W);
+    long long q = i / W;
+    const int y = (int)(q % H);
+    const int n = (int)(q / H);
+    const ResizeTaps t = resize_taps<false>(samples[n], C, pool_bytes, aug ? aug[n] : 0, H, W, y, x);
+    uint8_t px[3];
+    if constexpr (COLOR) resize_rgb_color(pool, t, color[n], px);
+    T* dst = img + i * 32;
+#pragma unroll
+    for (int v = 0; v < 32 / EPV; ++v) {
+      Vec16<T> o;
+#pragma unroll
+      for (int e = 0; e < EPV; ++e) {
+        const int c = v * EPV + e;
+        float f = 0.f;
+        if (c < C) {
+          const float m = mean ? mean[c] : 0.f, sd = stdv ? stdv[c] : 1.f;
+          uint8_t b;
+          if constexpr (COLOR) b = px[c < 3 ? c : 0];
+          else b = resize_channel<false>(pool, t, c);
+          f = (((float)b / 255.f - m) / sd) * post_scale;
+        }
+        o.set(e, f);
+      }
+      st16(dst + v * EPV, o);
+    }
+  }
+}
+template <typename T> static int launch_stage_u8_resize(const uint8_t* pool, long long pool_bytes, const nunet_u8_sample* samples, int N, int H, int W, int C,
+                                                        const float* mean, const float* stdv, const int32_t* aug, const nunet_color_aug* color,
+                                                        float post_scale, void* img, hipStream_t st) {
+  const long long npix = (long long)N * H * W;
+  long long g = (npix + 255) / 256; if (g > 4096) g = 4096;
+  ProfScope ps(PC_LAYOUT, 0, (double)npix * (4.0 * C + 32.0 * sizeof(T)), st);
+  if (color) NUNET_LAUNCH((stage_u8_resize_kernel<T, true>), dim3((unsigned)g), dim3(256), 0, st, pool, pool_bytes, samples, N, H, W, C, mean, stdv, aug, color, post_scale, (T*)img);
+  else NUNET_LAUNCH((stage_u8_resize_kernel<T, false>), dim3((unsigned)g), dim3(256), 0, st, pool, pool_bytes, samples, N, H, W, C, mean, stdv, aug, color, post_scale, (T*)img);
+  return nunet_check_launch("plan_stage_u8_resize");
+}
+extern "C" int nunet_plan_stage_u8_resize(nunet_plan* P, const uint8_t* pool, int64_t pool_bytes, const nunet_u8_sample* samples, const float* mean,
+                                          const float* stdv, const int32_t* aug, const nunet_color_aug* color, float post_scale, void* arena,
+                                          size_t arena_bytes, nunet_stream_t s) {
+  NUNET_REQUIRE(P && pool && samples && arena, "plan_stage_u8_resize: null pointer");
+  ARENA_CHECK("plan_stage_u8_resize");
+  const nunet_plan_cfg& c = P->cfg;
+  NUNET_REQUIRE(pool_bytes > 0, "plan_stage_u8_resize: pool_bytes=%lld must be positive", (long long)pool_bytes);
+  NUNET_REQUIRE(c.H <= NUNET_RESIZE_MAX_EXTENT && c.W <= NUNET_RESIZE_MAX_EXTENT, "plan_stage_u8_resize: destination %d x %d: extents are 1 .. %d",
+                c.H, c.W, NUNET_RESIZE_MAX_EXTENT);
+  NUNET_REQUIRE(!color || (c.input_channels == 3 && mean && stdv), "plan_stage_u8_resize: colour ops need images: input_channels=%d must be 3, mean and stdv given",
+                c.input_channels);
+  return NUNET_DISPATCH(c.dtype, launch_stage_u8_resize, pool, (long long)pool_bytes, samples, c.N, c.H, c.W, c.input_channels, mean, stdv, aug, color,
+                        post_scale, (void*)AB(arena, P->off_img), (hipStream_t)s);
 }
 
 extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, const float* dlogits, void* arena, size_t arena_bytes, float* grads, int32_t accumulate, int32_t phases, nunet_stream_t s);

@@ -55,7 +55,7 @@ class TrainStep:
     def __init__(self, model, batch_shape, lr=1e-3, momentum=0.9, weight_decay=1e-4, nesterov=False,
                  use_graph=True, process_group=None, keep_grads=True, fused_update=None, loss="BCEDiceLoss", input_u8=False,
                  schedule=None, segmented=None, optimizer="SGD", betas=(0.9, 0.999), eps=1e-8, loss_scale=None,
-                 clip_grad_norm=None, ema_decay=None, ema_warmup=False, color_aug=False):
+                 clip_grad_norm=None, ema_decay=None, ema_warmup=False, color_aug=False, resize=False, source_capacity=None):
         """loss: 'BCEDiceLoss' (reference losses.py:103-117, the default of trains.py:58), 'LovaszHingeLoss'
         (losses.py:120-129, the loss of the reference's published table README.md:102-108; one class only) or
         'BCEWithLogitsLoss' (torch.nn.BCEWithLogitsLoss(), trains.py:27-28,210-211; any num_classes: its gradient needs no
@@ -70,6 +70,13 @@ class TrainStep:
         RandomContrast]) of trains.py:260-264, modelled on albumentations / OpenCV) to the source pixel it
         fetches, from a static int32 [N,4] device buffer that step_u8(..., color=) fills (dataset.draw_color_augmentation; None:
         every op NONE, bit-identical to color_aug=False). The same number of launches.
+        resize (needs input_u8; source_capacity = bytes of each of the two source pools): False - nothing changes. True - the
+        step's inputs are RAGGED: every sample at its own size, as a byte pool plus one descriptor per sample for the images and
+        for the masks (dataset.pack_ragged, FolderDataset.batch). The two head launches become nunet_plan_stage_u8_resize
+        (augment the source, colour op on every fetched tap, bilinear Resize to the plan's H x W, Normalize: the reference's whole
+        train transform, trains.py:257-267) and nunet_preprocess_u8_resize (masks, nearest) reading static pool and descriptor
+        buffers that step_u8_ragged() fills, so a captured step replays with new sizes. An odd rot90 count needs no square
+        source. The same number of launches; sources of the plan's own size give the bits of resize=False.
         How the captured step is executed (all forms are bit-identical, tests/test_net_gpu.py):
           schedule  'lanes' - every op on its block's lane; 'list' - lanes chosen by a list scheduler over the hazard graph with
                     measured per-op costs (nunet_plan_calibrate)
@@ -138,6 +145,19 @@ class TrainStep:
             self.aug = torch.zeros(n, dtype=torch.int32, device=dev)
             self._mean = torch.tensor(np.resize(np.asarray(MEAN, np.float32), cin), device=dev)
             self._std = torch.tensor(np.resize(np.asarray(STD, np.float32), cin), device=dev)
+        self.resize = bool(resize)
+        if self.resize:
+            if not self.input_u8:
+                raise L.NunetError("TrainStep: resize=True needs input_u8=True: the resize runs on the uint8 sources the staging launch fetches")
+            if source_capacity is None or int(source_capacity) < 1:
+                raise L.NunetError("TrainStep: resize=True needs source_capacity, the bytes of the largest batch of sources "
+                                   "(got %r)" % (source_capacity,))
+            self.source_capacity = int(source_capacity)
+            self.img_pool = torch.zeros(self.source_capacity, dtype=torch.uint8, device=dev)
+            self.mask_pool = torch.zeros(self.source_capacity, dtype=torch.uint8, device=dev)
+            self.img_desc = torch.zeros((n, L.SAMPLE_WORDS), dtype=torch.int32, device=dev)      # nunet_u8_sample per sample
+            self.mask_desc = torch.zeros((n, L.SAMPLE_WORDS), dtype=torch.int32, device=dev)
+            self._cin = cin
         self.color = None
         if color_aug:
             if not self.input_u8 or cin != 3:
@@ -290,14 +310,21 @@ class TrainStep:
                     "adam_prepare")
         if self.input_u8:
             # the sample pipeline on the device: image -> the plan's padded NHWC tile, mask -> {0,1} fp32 NCHW target
-            if self.color is not None:
+            if self.resize:
+                L.check(lib.nunet_plan_stage_u8_resize(pl.handle, L.ptr(self.img_pool), self.source_capacity, L.ptr(self.img_desc), L.ptr(self._mean),
+                                                       L.ptr(self._std), L.ptr(self.aug), L.ptr(self.color), 1.0 / 255.0, L.ptr(pl.arena),
+                                                       L.nbytes(pl.arena), st), "plan_stage_u8_resize")
+                L.check(lib.nunet_preprocess_u8_resize(L.ptr(self.mask_pool), self.source_capacity, L.ptr(self.mask_desc), self.n, self.ncls, self.h,
+                                                       self.w, None, None, L.ptr(self.aug), 1.0, L.ptr(self.t), st), "preprocess_u8_resize (masks)")
+            elif self.color is not None:
                 L.check(lib.nunet_plan_stage_u8_color(pl.handle, L.ptr(self.x_u8), L.ptr(self._mean), L.ptr(self._std), L.ptr(self.aug),
                                                       L.ptr(self.color), 1.0 / 255.0, L.ptr(pl.arena), L.nbytes(pl.arena), st), "plan_stage_u8_color")
             else:
                 L.check(lib.nunet_plan_stage_u8(pl.handle, L.ptr(self.x_u8), L.ptr(self._mean), L.ptr(self._std), L.ptr(self.aug), 1.0 / 255.0,
                                                 L.ptr(pl.arena), L.nbytes(pl.arena), st), "plan_stage_u8")
-            L.check(lib.nunet_preprocess_u8(L.ptr(self.t_u8), self.n, self.h, self.w, self.ncls, None, None, L.ptr(self.aug), 1.0,
-                                            L.ptr(self.t), st), "preprocess_u8 (masks)")
+            if not self.resize:
+                L.check(lib.nunet_preprocess_u8(L.ptr(self.t_u8), self.n, self.h, self.w, self.ncls, None, None, L.ptr(self.aug), 1.0,
+                                                L.ptr(self.t), st), "preprocess_u8 (masks)")
             flags |= 4
         L.check(lib.nunet_plan_forward(pl.handle, L.ptr(eng.flat_params), L.ptr(eng.bnbuf), L.ptr(eng.nbt),
                                        L.ptr(self.x), L.ptr(pl.arena), L.nbytes(pl.arena), L.ptr(self.logits), flags, st), "plan_forward")
@@ -438,7 +465,12 @@ class TrainStep:
         if not self.use_graph:
             return
         eng = self.eng
-        if self.input_u8:          # (uint8 images, uint8 masks)
+        if self.resize:            # ((image pool, descriptors), (mask pool, descriptors)): dataset.pack_ragged's pairs
+            self._load_ragged(inp[0], inp[1], target[0], target[1])
+            self.aug.zero_()
+            if self.color is not None:
+                self.color.zero_()
+        elif self.input_u8:        # (uint8 images, uint8 masks)
             self.x_u8.copy_(inp)
             self.t_u8.copy_(target)
             self.aug.zero_()
@@ -543,7 +575,7 @@ class TrainStep:
 
     def _as_step_runs(self, g):
         """A recorded program issued the way step() issues it: batch copy + replay from the caller's stream."""
-        buf = self.x_u8 if self.input_u8 else self.x
+        buf = self.img_pool if self.resize else self.x_u8 if self.input_u8 else self.x
         fresh = buf.clone()
         def one():
             buf.copy_(fresh, non_blocking=True)
@@ -666,6 +698,17 @@ class TrainStep:
         optional colour codes (dataset.draw_color_augmentation; None: no colour op); needs input_u8=True."""
         if not self.input_u8:
             raise L.NunetError("step_u8 needs a TrainStep built with input_u8=True")
+        if self.resize:
+            raise L.NunetError("this TrainStep was built with resize=True: feed it with step_u8_ragged(img_pool, img_desc, mask_pool, mask_desc, aug, color)")
+        self._check_codes(aug, color, self.h, self.w)
+        self.x_u8.copy_(images_u8, non_blocking=True)
+        self.t_u8.copy_(masks_u8, non_blocking=True)
+        self._set_codes(aug, color)
+        self._run()
+
+    def _check_codes(self, aug, color, h, w):
+        """Refuse malformed augmentation / colour codes before the static buffers change (h, w: the shape an odd rot90 count must
+        find square; the resizing step passes a square one, its sources need not be)."""
         if color is not None:
             if self.color is None:
                 raise L.NunetError("step_u8: color codes need a TrainStep built with color_aug=True")
@@ -673,9 +716,9 @@ class TrainStep:
                 raise L.NunetError("step_u8: color must be int32 %s (dataset.draw_color_augmentation), got %s %s"
                                    % (tuple(self.color.shape), color.dtype, tuple(color.shape)))
         if aug is not None:
-            _check_aug(aug, self.n, self.h, self.w)       # before the static buffers change
-        self.x_u8.copy_(images_u8, non_blocking=True)
-        self.t_u8.copy_(masks_u8, non_blocking=True)
+            _check_aug(aug, self.n, h, w)
+
+    def _set_codes(self, aug, color):
         if aug is None:
             self.aug.zero_()
         else:
@@ -685,6 +728,33 @@ class TrainStep:
                 self.color.zero_()
             else:
                 self.color.copy_(color, non_blocking=True)
+
+    def _load_ragged(self, img_pool, img_desc, mask_pool, mask_desc):
+        """Validate a ragged batch on the host (descriptors against their pool, pools against the capacity) and copy it into the
+        static buffers the captured launches read. Nothing is written when anything is refused."""
+        from .dataset import check_descriptors
+        for what, pool, desc, ch in (("image", img_pool, img_desc, self._cin), ("mask", mask_pool, mask_desc, self.ncls)):
+            if not isinstance(pool, torch.Tensor) or pool.dtype != torch.uint8 or pool.dim() != 1:
+                raise L.NunetError("step_u8_ragged: the %s pool must be a flat uint8 tensor (dataset.pack_ragged)" % what)
+            if pool.numel() > self.source_capacity:
+                raise L.NunetError("step_u8_ragged: the %s pool holds %d bytes, this TrainStep was built with source_capacity=%d"
+                                   % (what, pool.numel(), self.source_capacity))
+            check_descriptors(desc, pool.numel(), ch, self.n)
+        self.img_pool[:img_pool.numel()].copy_(img_pool, non_blocking=True)
+        self.mask_pool[:mask_pool.numel()].copy_(mask_pool, non_blocking=True)
+        self.img_desc.copy_(torch.as_tensor(img_desc), non_blocking=True)
+        self.mask_desc.copy_(torch.as_tensor(mask_desc), non_blocking=True)
+
+    def step_u8_ragged(self, img_pool, img_desc, mask_pool, mask_desc, aug=None, color=None):
+        """One training iteration from ragged decoded samples: the byte pools (flat uint8, host or device) and HOST descriptors
+        (int32 [N,4]) of the images and of the masks, as dataset.pack_ragged / FolderDataset.batch return them, optional
+        augmentation codes (an odd rot90 count needs no square source) and colour codes; needs resize=True. Descriptors are
+        checked against their pool and the pools against source_capacity before anything is copied or launched."""
+        if not self.resize:
+            raise L.NunetError("step_u8_ragged needs a TrainStep built with input_u8=True, resize=True")
+        self._check_codes(aug, color, 1, 1)
+        self._load_ragged(img_pool, img_desc, mask_pool, mask_desc)
+        self._set_codes(aug, color)
         self._run()
 
     def _run(self):

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Training driver for the MI355X UNet++ path — the counterpart of reference trains.py
 (flags :31-103, loop :106-188, main :191-356) on the seeded synthetic blob dataset
-(pytorch_nested-unet_amd/synth.py; DSB2018 is not available offline).
+(pytorch_nested-unet_amd/synth.py; DSB2018 is not available offline), or - --dataset NAME - on a folder in the reference's layout,
+inputs/NAME/images/*<img_ext> and inputs/NAME/masks/<class>/*<mask_ext> (dataset.FolderDataset): images of any size, decoded on the
+host, resized on the device inside the captured step (TrainStep(resize=True)). --source_size LO,HI runs that path on the blobs.
 
 Same artefacts as the reference: models/<name>/config.yml (trains.py:206-207),
 models/<name>/log.csv with columns epoch, lr, loss, iou, val_loss, val_iou (:304-311,331-339),
@@ -98,7 +100,44 @@ def parse_args():
     p.add_argument('--color_augment', default=False, type=str2bool,
                    help='OneOf([HueSaturationValue, RandomBrightness, RandomContrast], p=1) per sample (trains.py:260-264; modelled on '
                         'albumentations, see DESIGN.md), device pipeline only; drawn from the same generator stream as --augment')
+    p.add_argument('--img_ext', default='.png', help='image file extension of a folder dataset (trains.py:67)')
+    p.add_argument('--mask_ext', default='.png', help='mask file extension of a folder dataset (trains.py:69)')
+    p.add_argument('--source_size', default=None, type=str,
+                   help='LO,HI: draw the synthetic blobs at per-sample heights and widths from LO..HI and let the device resize them to '
+                        'input_h x input_w (the path a folder dataset takes, without files)')
     return p.parse_args()
+
+
+def ragged_sets(config):
+    """(train samples, val samples) as lists of (image uint8 [H,W,3], mask uint8 [H,W,K]) at their own sizes: a folder in the
+    reference's layout (inputs/<dataset>/images, masks/<class>; split as trains.py:255), or the synthetic blobs at sizes drawn
+    from --source_size."""
+    import numpy as np
+    if config['dataset'] != 'synthetic_blobs':
+        sets = [nunet_amd.dataset.FolderDataset(config['dataset'], config['img_ext'], config['mask_ext'], config['num_classes'], split=s)
+                for s in ('train', 'val')]
+        return tuple([ds[i] for i in range(len(ds))] for ds in sets)
+    lo, hi = (int(v) for v in config['source_size'].split(','))
+    if not 1 <= lo <= hi <= L.RESIZE_MAX_EXTENT:
+        raise SystemExit('--source_size %s: LO,HI with 1 <= LO <= HI <= %d' % (config['source_size'], L.RESIZE_MAX_EXTENT))
+    out = []
+    for count, seed in ((config['train_size'], 1000), (config['val_size'], 2000)):
+        g = np.random.default_rng(seed)
+        sizes = g.integers(lo, hi + 1, (count, 2))
+        pairs = [nunet_amd.synth.synth_blob_pairs_u8(1, int(h), int(w), seed=seed + 1 + i) for i, (h, w) in enumerate(sizes)]
+        out.append([(img[0], msk[0]) for img, msk in pairs])
+    return tuple(out)
+
+
+def ragged_to_floats(samples, h, w, bs):
+    """the val transform (Resize, Normalize; trains.py:269-272) of ragged samples on the device -> float32 (images, masks)"""
+    D = nunet_amd.dataset
+    xs, ts = [], []
+    for k in range(0, len(samples), bs):
+        part = samples[k:k + bs]
+        xs.append(D.resize_images(*D.pack_ragged([p[0] for p in part]), (h, w)))
+        ts.append(D.resize_masks(*D.pack_ragged([p[1] for p in part]), (h, w), channels=part[0][1].shape[2]))
+    return torch.cat(xs), torch.cat(ts)
 
 
 def make_split(n, h, w, cin, ncls, seed):
@@ -187,15 +226,25 @@ def main():
                                            dtype=config['dtype'])
     model = model.cuda()
     h, w, bs = config['input_h'], config['input_w'], config['batch_size']
-    # the synthetic splits live in HBM (a few MB); batches are gathered on the device
-    train = tuple(v.cuda() for v in make_split(config['train_size'], h, w, config['input_channels'], config['num_classes'], 1000))
-    val = tuple(v.cuda() for v in make_split(config['val_size'], h, w, config['input_channels'], config['num_classes'], 2000))
-    steps = config['train_size'] // (bs * world)          # drop_last=True (trains.py:296); global batch = world x bs
-
     fused = not (config['loss'] == 'LovaszHingeLoss' and config['num_classes'] != 1)   # TrainStep: SGD or Adam, any loss
     if world > 1 and not fused:
         raise SystemExit('data parallel runs the fused step: multi-class LovaszHingeLoss is not fused')
-    u8 = fused and config['device_pipeline'] and config['input_channels'] == 3 and config['num_classes'] == 1
+    # ragged sources (a folder dataset, or --source_size): decoded samples at their own sizes, resized on the device
+    ragged = config['dataset'] != 'synthetic_blobs' or config['source_size'] is not None
+    if ragged:
+        if not (fused and config['device_pipeline'] and config['input_channels'] == 3):
+            raise SystemExit('a folder dataset / --source_size runs in the device pipeline (fused step, --device_pipeline, 3 input channels)')
+        train_rag, val_rag = ragged_sets(config)
+        config['train_size'], config['val_size'] = len(train_rag), len(val_rag)
+        train = None
+        val = ragged_to_floats(val_rag, h, w, bs)
+    else:
+        # the synthetic splits live in HBM (a few MB); batches are gathered on the device
+        train = tuple(v.cuda() for v in make_split(config['train_size'], h, w, config['input_channels'], config['num_classes'], 1000))
+        val = tuple(v.cuda() for v in make_split(config['val_size'], h, w, config['input_channels'], config['num_classes'], 2000))
+    steps = config['train_size'] // (bs * world)          # drop_last=True (trains.py:296); global batch = world x bs
+
+    u8 = ragged or (fused and config['device_pipeline'] and config['input_channels'] == 3 and config['num_classes'] == 1)
     color = bool(config['color_augment'] and u8)
     if config['color_augment'] and not u8:
         raise SystemExit('--color_augment runs in the device pipeline (fused step, --device_pipeline, 3 input channels, 1 class)')
@@ -206,15 +255,21 @@ def main():
         raise SystemExit('--ema_decay averages inside the fused step: multi-class LovaszHingeLoss is not fused')
     if fused:
         model.train()
+        # the largest batch of sources either pool can be handed: the bs largest samples
+        rag = dict(resize=True, source_capacity=max(sum(sorted((p[k].size for p in train_rag), reverse=True)[:bs]) for k in (0, 1))) if ragged else {}
         if config['optimizer'] == 'Adam':      # torch.optim.Adam(params, lr, weight_decay) with its default betas / eps (trains.py:225-227)
             ts = TrainStep(model, (bs, config['input_channels'], h, w), lr=config['lr'], weight_decay=config['weight_decay'],
                            loss=config['loss'], input_u8=u8, optimizer='Adam', loss_scale=scaling,
-                           clip_grad_norm=clip, ema_decay=ema, ema_warmup=config['ema_warmup'], color_aug=color)
+                           clip_grad_norm=clip, ema_decay=ema, ema_warmup=config['ema_warmup'], color_aug=color, **rag)
         else:
             ts = TrainStep(model, (bs, config['input_channels'], h, w), lr=config['lr'], momentum=config['momentum'],
                            weight_decay=config['weight_decay'], nesterov=config['nesterov'], loss=config['loss'], input_u8=u8,
-                           loss_scale=scaling, clip_grad_norm=clip, ema_decay=ema, ema_warmup=config['ema_warmup'], color_aug=color)
-        if u8:
+                           loss_scale=scaling, clip_grad_norm=clip, ema_decay=ema, ema_warmup=config['ema_warmup'], color_aug=color, **rag)
+        if ragged:
+            pack = nunet_amd.dataset.pack_ragged
+            ts.capture(pack([p[0] for p in train_rag[:bs]]), pack([p[1] for p in train_rag[:bs]]))
+            aug_gen = torch.Generator().manual_seed(config['seed'] + 1)
+        elif u8:
             # the decoded set (what the reference's Dataset holds after cv2.imread, dataset.py:56-64) lives in HBM as uint8
             raw, m8 = nunet_amd.synth.synth_blob_pairs_u8(config['train_size'], h, w, seed=1000)
             train_u8 = (torch.from_numpy(raw).cuda(), torch.from_numpy(m8).cuda())
@@ -274,7 +329,11 @@ def main():
                 if u8:
                     aug = nunet_amd.dataset.draw_augmentation(bs, aug_gen, 'cuda') if config['augment'] else None
                     col = nunet_amd.dataset.draw_color_augmentation(bs, aug_gen, 'cuda') if color else None
-                    ts.step_u8(train_u8[0][idx], train_u8[1][idx], aug, col)
+                    if ragged:
+                        part = [train_rag[i] for i in idx.tolist()]
+                        ts.step_u8_ragged(*(pack([p[0] for p in part]) + pack([p[1] for p in part])), aug=aug, color=col)
+                    else:
+                        ts.step_u8(train_u8[0][idx], train_u8[1][idx], aug, col)
                 else:
                     ts.step(train[0][idx], train[1][idx])
             tl, ti = ts.epoch_stats()

@@ -34,6 +34,8 @@ def main():
                     help='also print IoU / Dice / Acc / loss of every head (needs --deep_supervision true)')
     ap.add_argument('--ema', default=False, type=str2bool,
                     help='evaluate model_ema.pth, the weight EMA of a run trained with --ema_decay, instead of model.pth')
+    ap.add_argument('--img_ext', default=None, help='image file extension of a folder dataset (default: the training run\'s)')
+    ap.add_argument('--mask_ext', default=None, help='mask file extension of a folder dataset (default: the training run\'s)')
     args = ap.parse_args()
     with open('models/%s/config.yml' % args.name) as f:
         config = yaml.load(f, Loader=yaml.FullLoader)
@@ -54,9 +56,20 @@ def main():
     model.load_state_dict(torch.load(ckpt, map_location='cpu'))
     model = model.cuda()
     model.eval()
-    img, msk = nunet_amd.synth.synth_split(config['val_size'], config['input_h'], config['input_w'],
-                                           config['input_channels'], config['num_classes'], seed=2000)
-    x, t = torch.from_numpy(img), torch.from_numpy(msk)
+    for k in ('img_ext', 'mask_ext'):
+        if getattr(args, k) is not None:
+            config[k] = getattr(args, k)
+    if config.get('dataset', 'synthetic_blobs') != 'synthetic_blobs' or config.get('source_size') is not None:
+        # samples at their own sizes (the folder's validation split of val.py:53-56, or the synthetic blobs of --source_size):
+        # Resize + Normalize on the device, floats into the EvalStep
+        from train import ragged_sets, ragged_to_floats
+        config.setdefault('img_ext', '.png')
+        config.setdefault('mask_ext', '.png')
+        x, t = ragged_to_floats(ragged_sets(config)[1], config['input_h'], config['input_w'], config['batch_size'])
+    else:
+        img, msk = nunet_amd.synth.synth_split(config['val_size'], config['input_h'], config['input_w'],
+                                               config['input_channels'], config['num_classes'], seed=2000)
+        x, t = torch.from_numpy(img), torch.from_numpy(msk)
     for c in range(config['num_classes']):
         os.makedirs(os.path.join('outputs', config['name'], str(c)), exist_ok=True)
     bs = config['batch_size']
