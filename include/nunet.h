@@ -582,6 +582,36 @@ int nunet_resize_u8(const uint8_t* pool, int64_t pool_bytes, const nunet_u8_samp
 int nunet_preprocess_u8_resize(const uint8_t* pool, int64_t pool_bytes, const nunet_u8_sample* samples, int32_t N, int32_t C,
                                int32_t Hd, int32_t Wd, const float* mean, const float* stdv, const int32_t* aug,
                                float post_scale, float* out_nchw, nunet_stream_t s);
+/* Full-resolution tiled inference (tiled inference): fixed-size windows cut out of ragged sources, and
+ * the overlapping windows' logits blended back into a mask of the source's size. All descriptors live in DEVICE memory and are
+ * read at run time, so a captured step replays with new ones. Geometry, along one axis with source extent S, tile extent T and
+ * overlap O (0 <= O <= T/2): S <= T gives one tile at origin 0; otherwise stride = T - O, n = ceil((S - T) / stride) + 1 and
+ * origin j = min(j * stride, S - T) - the last tile is flush with the edge, and no coordinate lies in more than 3 tiles.
+ * Tile coordinates at or past the source extent S (only a source smaller than the tile has them) are fetched through
+ * BORDER_REFLECT_101, repeated: S == 1 gives 0; otherwise p = 2(S - 1), m = i mod p, and the index is m if m < S, else p - m.
+ * Tile t is the Th x Tw window of sample tiles[t].sample at (y0, x0); sample < 0 is a null tile: it reads nothing and yields
+ * zero bytes. The kernels trust no descriptor: a sample descriptor nunet_resize_u8 would refuse, a sample index >= n_samples or
+ * an origin outside 0 .. H-1 / 0 .. W-1 gives a zero tile as well. */
+typedef struct nunet_tile { int32_t sample, y0, x0, reserved; } nunet_tile;                  /* 16 bytes, DEVICE memory, one per tile */
+/* ragged uint8 HWC sources -> uint8 [N][Th][Tw][C], N tiles */
+int nunet_crop_tiles_u8(const uint8_t* pool, int64_t pool_bytes, const nunet_u8_sample* samples, int32_t n_samples,
+                        const nunet_tile* tiles, int32_t N, int32_t C, int32_t Th, int32_t Tw, uint8_t* dst_u8_nhwc, nunet_stream_t s);
+/* One per sample: the sample's tiles are first_tile + j * nx + i (j < ny, i < nx), their origins min(j * stride_y, max(H - Th, 0))
+ * and min(i * stride_x, max(W - Tw, 0)); out_offset is the ELEMENT offset of the sample's [K][H][W] block in the outputs. */
+typedef struct nunet_tile_grid { int64_t out_offset; int32_t first_tile, ny, nx, stride_y, stride_x, reserved; } nunet_tile_grid;   /* 32 bytes, DEVICE memory */
+enum { NUNET_WINDOW_TENT = 0, NUNET_WINDOW_UNIFORM = 1 };
+/* Blend fp32 tile logits [n_tiles][K][Th][Tw] into every sample's [K][H][W] block (H, W from samples[n]): each source pixel
+ * finds the tiles that cover it in closed form from its grid and takes sum(w_t * l_t) / sum(w_t), accumulated in fp32 in
+ * ascending tile index; w_t = (float)(wy * wx), the integer product of the separable window at the pixel's place in tile t:
+ * TENT w[i] = min(i + 1, T - i), UNIFORM w[i] = 1. A gather: no atomics, no pre-zeroed output, the same bits on every run. A
+ * pixel that exactly one tile covers takes that tile's logit unchanged; tile pixels at or past H / W are never read.
+ * out_logits (fp32) and out_u8 are flat arrays of out_elems elements with the same element offsets; either may be NULL, not
+ * both. out_u8 holds the byte nunet_sigmoid_u8 gives for the blended logit with the same `thresholds` (needed with out_u8).
+ * A grid with ny, nx or a stride < 1, or tiles outside 0 .. n_tiles, writes zeros for its sample (so does a pixel no tile
+ * covers); a sample whose extents are outside 1 .. NUNET_RESIZE_MAX_EXTENT or whose block leaves 0 .. out_elems writes nothing. */
+int nunet_stitch_tiles(const float* tile_logits, int32_t n_tiles, int32_t K, int32_t Th, int32_t Tw, const nunet_u8_sample* samples,
+                       const nunet_tile_grid* grids, int32_t n_samples, int32_t window, const float* thresholds, float* out_logits,
+                       uint8_t* out_u8, int64_t out_elems, nunet_stream_t s);
 /* NCHW fp32 -> NHWC dtype with channel padding (zeros) up to cpad */
 int nunet_nchw_to_nhwc(const float* x, int32_t N, int32_t C, int32_t H, int32_t W,
                        int32_t dtype, void* y, int32_t cpad, nunet_stream_t s);
@@ -648,6 +678,12 @@ int nunet_plan_stage_u8_color(nunet_plan* p, const uint8_t* u8_nhwc, const float
 int nunet_plan_stage_u8_resize(nunet_plan* p, const uint8_t* pool, int64_t pool_bytes, const nunet_u8_sample* samples,
                                const float* mean, const float* stdv, const int32_t* aug, const nunet_color_aug* color,
                                float post_scale, void* arena, size_t arena_bytes, nunet_stream_t s);
+/* The staging launch on tiles of ragged sources: tiles[0 .. N) (N = the plan's N, tile = the plan's H x W) of input_channels
+ * channels, normalised and stored as nunet_plan_stage_u8 stores. One launch: bit for bit nunet_crop_tiles_u8 followed by
+ * nunet_plan_stage_u8 with aug NULL (a null tile stages the bytes 0). mean and stdv may be NULL. */
+int nunet_plan_stage_u8_tiles(nunet_plan* p, const uint8_t* pool, int64_t pool_bytes, const nunet_u8_sample* samples, int32_t n_samples,
+                              const nunet_tile* tiles, const float* mean, const float* stdv, float post_scale, void* arena,
+                              size_t arena_bytes, nunet_stream_t s);
 /* grads: flat fp32 in params order. accumulate: += instead of assign. */
 int nunet_plan_backward(nunet_plan* p, const float* params, const float* dlogits, void* arena, size_t arena_bytes,
                         float* grads, int32_t accumulate, nunet_stream_t s);

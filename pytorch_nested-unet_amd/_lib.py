@@ -191,6 +191,9 @@ COLOR_NONE, COLOR_HSV, COLOR_BRIGHTNESS, COLOR_CONTRAST = 0, 1, 2, 3      # NUNE
 SAMPLE_WORDS = 4    # nunet_u8_sample: 16 bytes of device memory per sample, [offset i64 (2 words), H i32, W i32] - an int32 [N,4] tensor
 RESIZE_LINEAR, RESIZE_NEAREST = 0, 1        # NUNET_RESIZE_* in include/nunet.h
 RESIZE_MAX_EXTENT = 16384                   # NUNET_RESIZE_MAX_EXTENT
+TILE_WORDS = 4      # nunet_tile: 16 bytes of device memory per tile, [sample i32, y0 i32, x0 i32, reserved] - an int32 [n,4] tensor
+GRID_WORDS = 8      # nunet_tile_grid: 32 bytes per sample, [out_offset i64 (2 words), first_tile, ny, nx, stride_y, stride_x, reserved]
+WINDOW_TENT, WINDOW_UNIFORM = 0, 1          # NUNET_WINDOW_* in include/nunet.h
 
 
 class PlanCfg(C.Structure):
@@ -268,6 +271,8 @@ _SIG = {
     "nunet_preprocess_u8_color": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp]),
     "nunet_resize_u8": (_i32, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "nunet_preprocess_u8_resize": (_i32, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
+    "nunet_crop_tiles_u8": (_i32, [_vp, _i64, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "nunet_stitch_tiles": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "nunet_nchw_to_nhwc": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "nunet_plan_create": (_vp, [C.POINTER(PlanCfg)]),
     "nunet_plan_create_pruned": (_vp, [C.POINTER(PlanCfg), _i32]),
@@ -282,6 +287,7 @@ _SIG = {
     "nunet_plan_stage_u8": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _sz, _vp]),
     "nunet_plan_stage_u8_color": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _sz, _vp]),
     "nunet_plan_stage_u8_resize": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _sz, _vp]),
+    "nunet_plan_stage_u8_tiles": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _f32, _vp, _sz, _vp]),
     "nunet_plan_backward": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _i32, _vp]),
     "nunet_plan_backward_phase": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _i32, _i32, _vp]),
     "nunet_plan_grad_scratch": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),

@@ -431,6 +431,40 @@ __device__ __forceinline__ void resize_rgb_color(const uint8_t* __restrict__ poo
   for (int c = 0; c < 3; ++c) px[c] = resize_lerp(p[0][0][c], p[0][1][c], p[1][0][c], p[1][1][c], t.ax1, t.ay1);
 }
 
+// ---------------------------------------------------------------------------
+// Tiled inference (include/nunet.h, nunet_tile): pixel (y, x) of tile t <- a byte offset into the pool, or -1 for a pixel that
+// reads nothing (null tile, bad sample index, bad descriptor, origin outside the source). nunet_crop_tiles_u8 (tiles.hip) and
+// nunet_plan_stage_u8_tiles (plan.hip) share it.
+// ---------------------------------------------------------------------------
+// BORDER_REFLECT_101, repeated, of index i >= 0 into an axis of extent S >= 1 (np.pad(mode='reflect'))
+__device__ __forceinline__ int reflect101(int i, int S) {
+  if (S == 1) return 0;
+  const int p = 2 * (S - 1), m = i % p;
+  return m < S ? m : p - m;
+}
+__device__ __forceinline__ long long tile_pixel_offset(const nunet_u8_sample* __restrict__ samples, int n_samples, const nunet_tile& t, int C,
+                                                       long long pool_bytes, int y, int x) {
+  if (t.sample < 0 || t.sample >= n_samples) return -1;
+  const nunet_u8_sample d = samples[t.sample];
+  if (!resize_sample_ok(d, C, pool_bytes)) return -1;
+  if (t.y0 < 0 || t.y0 >= d.H || t.x0 < 0 || t.x0 >= d.W) return -1;
+  int sy = t.y0 + y, sx = t.x0 + x;              // (y < Th, x < Tw <= NUNET_RESIZE_MAX_EXTENT: no overflow)
+  if (sy >= d.H) sy = reflect101(sy, d.H);
+  if (sx >= d.W) sx = reflect101(sx, d.W);
+  return d.offset + ((long long)sy * d.W + sx) * C;
+}
+
+// byte = number of thresholds <= x (nunet_sigmoid_u8, elementwise.hip): branch-free 8-step binary search over 255 thresholds in LDS
+__device__ __forceinline__ uint32_t sigmoid_byte(const float* s_thr, float x) {
+  int lo = 0;                                   // invariant: thr[lo-1] <= x (or lo == 0), answer in [lo, lo + span]
+#pragma unroll
+  for (int span = 128; span > 0; span >>= 1) {
+    const int mid = lo + span;                  // candidate count
+    if (mid <= 255 && s_thr[mid - 1] <= x) lo = mid;
+  }
+  return (uint32_t)lo;
+}
+
 template <typename T> struct Vec16 {
   // zero-initialised: set() of a 16-bit element read-modify-writes its 32-bit word, and doing that on an
   // indeterminate word is undefined (it miscompiled for fp16 on the odd elements of words 0 and 1)

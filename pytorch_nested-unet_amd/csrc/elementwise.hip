@@ -2147,16 +2147,8 @@ extern "C" int nunet_eval_step_heads(const float* logits, const float* target, i
 // byte = number of thresholds <= x: thr[k-1] (k = 1..255) is the smallest fp32 logit whose reference byte is >= k, found
 // by the caller with the reference's own sigmoid (bisection over fp32 bit patterns, metrics.sigmoid_u8_thresholds), so
 // the byte matches `(torch.sigmoid(x) * 255).astype('uint8')` EXACTLY - a device expf one ulp away from the host's would
-// flip bytes whose sigmoid * 255 sits next to an integer. Branch-free 8-step binary search in LDS.
-__device__ __forceinline__ uint32_t sigmoid_byte(const float* s_thr, float x) {
-  int lo = 0;                                   // invariant: thr[lo-1] <= x (or lo == 0), answer in [lo, lo + span]
-#pragma unroll
-  for (int span = 128; span > 0; span >>= 1) {
-    const int mid = lo + span;                  // candidate count
-    if (mid <= 255 && s_thr[mid - 1] <= x) lo = mid;
-  }
-  return (uint32_t)lo;
-}
+// flip bytes whose sigmoid * 255 sits next to an integer. Branch-free 8-step binary search in LDS (common.h, sigmoid_byte; the
+// stitch kernel of tiles.hip exports its blended logits through the same function).
 __global__ __launch_bounds__(256) void sigmoid_u8_kernel(const float* __restrict__ logits, const float* __restrict__ thr, uint8_t* __restrict__ out, int64_t n) {
   __shared__ float s_thr[256];
   if (threadIdx.x < 255) s_thr[threadIdx.x] = thr[threadIdx.x];

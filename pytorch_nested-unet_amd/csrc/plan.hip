@@ -1587,6 +1587,64 @@ extern "C" int nunet_plan_stage_u8_resize(nunet_plan* P, const uint8_t* pool, in
   return NUNET_DISPATCH(c.dtype, launch_stage_u8_resize, pool, (long long)pool_bytes, samples, c.N, c.H, c.W, c.input_channels, mean, stdv, aug, color,
                         post_scale, (void*)AB(arena, P->off_img), (hipStream_t)s);
 }
+// stage_u8_kernel on tiles of ragged sources (nunet_plan_stage_u8_tiles): the pixel's bytes come from the border-reflected window
+// tiles[n] names (common.h, tile_pixel_offset; a pixel that may read nothing stages the byte 0) instead of a dense batch; the
+// arithmetic behind the byte and the stores are stage_u8_kernel's. One thread per tile pixel.
+template <typename T>
+__global__ __launch_bounds__(256) void stage_u8_tiles_kernel(const uint8_t* __restrict__ pool, long long pool_bytes,
+                                                             const nunet_u8_sample* __restrict__ samples, int n_samples,
+                                                             const nunet_tile* __restrict__ tiles, int N, int H, int W, int C,
+                                                             const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                             float post_scale, T* __restrict__ img) {
+  constexpr int EPV = Tr<T>::EPV;
+  const long long npix = (long long)N * H * W;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < npix; i += (long long)gridDim.x * blockDim.x) {
+    const int x = (int)(i % W);
+    long long q = i / W;
+    const int y = (int)(q % H);
+    const int n = (int)(q / H);
+    const long long o = tile_pixel_offset(samples, n_samples, tiles[n], C, pool_bytes, y, x);
+    T* dst = img + i * 32;
+#pragma unroll
+    for (int v = 0; v < 32 / EPV; ++v) {
+      Vec16<T> out;
+#pragma unroll
+      for (int e = 0; e < EPV; ++e) {
+        const int c = v * EPV + e;
+        float f = 0.f;
+        if (c < C) {
+          const float m = mean ? mean[c] : 0.f, sd = stdv ? stdv[c] : 1.f;
+          const uint8_t b = o < 0 ? (uint8_t)0 : pool[o + c];
+          f = (((float)b / 255.f - m) / sd) * post_scale;
+        }
+        out.set(e, f);
+      }
+      st16(dst + v * EPV, out);
+    }
+  }
+}
+template <typename T> static int launch_stage_u8_tiles(const uint8_t* pool, long long pool_bytes, const nunet_u8_sample* samples, int n_samples,
+                                                       const nunet_tile* tiles, int N, int H, int W, int C, const float* mean, const float* stdv,
+                                                       float post_scale, void* img, hipStream_t st) {
+  const long long npix = (long long)N * H * W;
+  long long g = (npix + 255) / 256; if (g > 4096) g = 4096;
+  ProfScope ps(PC_LAYOUT, 0, (double)npix * (C + 32.0 * sizeof(T)), st);
+  NUNET_LAUNCH((stage_u8_tiles_kernel<T>), dim3((unsigned)g), dim3(256), 0, st, pool, pool_bytes, samples, n_samples, tiles, N, H, W, C, mean, stdv,
+               post_scale, (T*)img);
+  return nunet_check_launch("plan_stage_u8_tiles");
+}
+extern "C" int nunet_plan_stage_u8_tiles(nunet_plan* P, const uint8_t* pool, int64_t pool_bytes, const nunet_u8_sample* samples, int32_t n_samples,
+                                         const nunet_tile* tiles, const float* mean, const float* stdv, float post_scale, void* arena,
+                                         size_t arena_bytes, nunet_stream_t s) {
+  NUNET_REQUIRE(P && pool && samples && tiles && arena, "plan_stage_u8_tiles: null pointer");
+  ARENA_CHECK("plan_stage_u8_tiles");
+  const nunet_plan_cfg& c = P->cfg;
+  NUNET_REQUIRE(pool_bytes > 0 && n_samples > 0, "plan_stage_u8_tiles: pool_bytes=%lld n_samples=%d must be positive", (long long)pool_bytes, n_samples);
+  NUNET_REQUIRE(c.H <= NUNET_RESIZE_MAX_EXTENT && c.W <= NUNET_RESIZE_MAX_EXTENT, "plan_stage_u8_tiles: tile %d x %d: extents are 1 .. %d",
+                c.H, c.W, NUNET_RESIZE_MAX_EXTENT);
+  return NUNET_DISPATCH(c.dtype, launch_stage_u8_tiles, pool, (long long)pool_bytes, samples, n_samples, tiles, c.N, c.H, c.W, c.input_channels, mean, stdv,
+                        post_scale, (void*)AB(arena, P->off_img), (hipStream_t)s);
+}
 
 extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, const float* dlogits, void* arena, size_t arena_bytes, float* grads, int32_t accumulate, int32_t phases, nunet_stream_t s);
 extern "C" int nunet_plan_backward(nunet_plan* P, const float* params, const float* dlogits, void* arena, size_t arena_bytes, float* grads, int32_t accumulate, nunet_stream_t s) {

@@ -8,7 +8,11 @@ A checkpoint trained with --deep_supervision true can be cut back at inference t
 masks from the network pruned to the blocks that feed head L; --per_head true adds one IoU / Dice / Acc / loss line per head
 of the whole network, so one validation pass shows which depth would do.
 
---ema true evaluates models/<name>/model_ema.pth, the averaged weights train.py --ema_decay saved at their best val IoU."""
+--ema true evaluates models/<name>/model_ema.pth, the averaged weights train.py --ema_decay saved at their best val IoU.
+
+--full_res true (a folder dataset or a --source_size run) leaves the reference's Resize out: every validation image is predicted
+at its own size from overlapping input_h x input_w tiles (nunet_amd.tiled.TiledPredictor, --tile_overlap O), the masks have the
+sources' sizes and IoU / Dice / Acc are means over images at that resolution. Composes with --depth and --ema."""
 import argparse
 import os
 import sys
@@ -24,6 +28,59 @@ from nunet_amd.trainer import EvalStep
 from nunet_amd.utils import str2bool
 
 
+FULL_RES_GROUP_BYTES = 32 << 20      # sources of one TiledPredictor.predict call (one more image always fits)
+
+
+def full_res(args, config, model, samples):
+    """--full_res true: every validation image at its own size through TiledPredictor (tile = input_h x input_w, N = batch_size,
+    one captured graph), masks of the sources' sizes under the names the resized path uses, IoU / Dice / Acc as the mean over
+    images and the dataset-level per-class table."""
+    from nunet_amd.dataset import pack_ragged
+    from nunet_amd.metrics import scores_from_counts
+    from nunet_amd.tiled import TiledPredictor
+    K = config['num_classes']
+    for c in range(K):
+        os.makedirs(os.path.join('outputs', config['name'], str(c)), exist_ok=True)
+    groups, size = [[]], 0
+    for i, (img, _) in enumerate(samples):
+        if groups[-1] and size + img.size > FULL_RES_GROUP_BYTES:
+            groups.append([])
+            size = 0
+        groups[-1].append(i)
+        size += img.size
+    cap = max(sum(samples[i][0].size for i in g) for g in groups)
+    tp = TiledPredictor(model, (config['batch_size'], config['input_channels'], config['input_h'], config['input_w']),
+                        overlap=args.tile_overlap, source_capacity=cap, depth=args.depth)
+    iou, dice, acc, tiles = [], [], [], 0
+    counts = {nm: [0] * K for nm in ('tp', 'fp', 'fn', 'tn')}
+    with torch.no_grad():
+        for g in groups:
+            r = tp.predict(*(pack_ragged([samples[i][0] for i in g]) + pack_ragged([samples[i][1] for i in g])))
+            iou, dice, acc, tiles = iou + r['iou'], dice + r['dice'], acc + r['acc'], tiles + sum(r['tiles'])
+            for nm in counts:
+                counts[nm] = [a + b for a, b in zip(counts[nm], r['counts'][nm])]
+            if not args.no_images:
+                from PIL import Image
+                for i, m in zip(g, r['masks']):
+                    m = m.cpu().numpy()
+                    for c in range(K):
+                        Image.fromarray(m[c]).save(os.path.join('outputs', config['name'], str(c), 'val_%04d.jpg' % i))
+    if args.depth is not None:
+        print('depth: %d' % args.depth)
+    if args.ema:
+        print('weights: EMA (model_ema.pth)')
+    print('full resolution: %d images, %d tiles of %d x %d, overlap %d' % (len(samples), tiles, tp.th, tp.tw, tp.overlap))
+    print('IoU: %.4f' % np.mean(iou))
+    print('Dice: %.4f' % np.mean(dice))
+    print('Acc: %.4f' % np.mean(acc))
+    per = scores_from_counts(*(counts[nm] for nm in ('tp', 'fp', 'fn', 'tn')))
+    names = list(per)
+    print('class ' + ' '.join('%11s' % nm for nm in names))
+    for c in range(K):
+        print('%5d ' % c + ' '.join('%11.4f' % per[nm][0][c] for nm in names))
+    print('micro ' + ' '.join('%11.4f' % per[nm][1] for nm in names))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--name', default=None, help='model name')
@@ -36,6 +93,11 @@ def main():
                     help='evaluate model_ema.pth, the weight EMA of a run trained with --ema_decay, instead of model.pth')
     ap.add_argument('--img_ext', default=None, help='image file extension of a folder dataset (default: the training run\'s)')
     ap.add_argument('--mask_ext', default=None, help='mask file extension of a folder dataset (default: the training run\'s)')
+    ap.add_argument('--full_res', default=False, type=str2bool,
+                    help='predict every validation image at its own size from overlapping input_h x input_w tiles (a folder dataset or a '
+                         '--source_size run): masks and metrics at the sources\' resolution')
+    ap.add_argument('--tile_overlap', default=None, type=int,
+                    help='overlap of neighbouring tiles under --full_res, 0 .. min(input_h, input_w) / 2 (default: a quarter of the smaller side)')
     args = ap.parse_args()
     with open('models/%s/config.yml' % args.name) as f:
         config = yaml.load(f, Loader=yaml.FullLoader)
@@ -59,7 +121,17 @@ def main():
     for k in ('img_ext', 'mask_ext'):
         if getattr(args, k) is not None:
             config[k] = getattr(args, k)
-    if config.get('dataset', 'synthetic_blobs') != 'synthetic_blobs' or config.get('source_size') is not None:
+    ragged = config.get('dataset', 'synthetic_blobs') != 'synthetic_blobs' or config.get('source_size') is not None
+    if args.full_res:
+        if not ragged or args.per_head:
+            print('error: --full_res true needs sources at their own sizes (a folder dataset, or a run trained with --source_size LO,HI) '
+                  'and does not combine with --per_head')
+            sys.exit(2)
+        from train import ragged_sets
+        config.setdefault('img_ext', '.png')
+        config.setdefault('mask_ext', '.png')
+        return full_res(args, config, model, ragged_sets(config)[1])
+    if ragged:
         # samples at their own sizes (the folder's validation split of val.py:53-56, or the synthetic blobs of --source_size):
         # Resize + Normalize on the device, floats into the EvalStep
         from train import ragged_sets, ragged_to_floats
