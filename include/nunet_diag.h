@@ -74,8 +74,8 @@ int nunet_conv3x3_wgrad_launch_info(const nunet_wgrad_desc* d, nunet_wgrad_launc
  * every slot still holds the complete gradient its block's backward started from. Returns -1 when the plan has no block (i, j). */
 int64_t nunet_plan_feature_grad(const nunet_plan* p, int32_t i, int32_t j, int32_t* pitch, int32_t* channels);
 /* Read-only accessor of the staged input image, the sibling of nunet_plan_feature: arena byte offset of the padded NHWC image
- * [N][H][W][32] the first convolution reads (STORAGE dtype), written by nunet_plan_stage_u8(_color) or by the layout launch of
- * nunet_plan_forward; *pitch = 32, *channels = the plan's input_channels (channels input_channels .. 31 are zeros). Pruned
+ * [N][H][W][32] the first convolution reads (STORAGE dtype), written by a staging entry of the sample pipeline (nunet_plan_stage_u8*:
+ * any source under StageSink, csrc/pipeline.h) or by the layout launch of nunet_plan_forward; *pitch = 32, *channels = the plan's input_channels (channels input_channels .. 31 are zeros). Pruned
  * plans have it too. Returns -1 for a NULL plan. */
 int64_t nunet_plan_image(const nunet_plan* p, int32_t* pitch, int32_t* channels);
 /* a1 = relu(bn1(conv1(input))) of block (i, j), the activation between its two convolutions. No pass stores it: conv2 and the

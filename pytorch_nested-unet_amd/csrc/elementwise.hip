@@ -39,13 +39,6 @@ int nunet_check_launch(const char* what) {
 extern "C" const char* nunet_last_error(void) { return g_err; }
 extern "C" int nunet_version(void) { return 104; }
 
-static inline int grid_for(int64_t items, int block, int cap = 256 * 16) {
-  int64_t g = ceil_div64(items, block);
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 __global__ __launch_bounds__(256) void zero_kernel(u32x4* __restrict__ p16, size_t n16, uint32_t* __restrict__ tail, int ntail) {
   const u32x4 z = {0u, 0u, 0u, 0u};
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) p16[i] = z;
@@ -96,171 +89,6 @@ template <typename T> static int launch_nchw_to_nhwc(const float* x, int N, int 
 extern "C" int nunet_nchw_to_nhwc(const float* x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t dtype, void* y, int32_t cpad, nunet_stream_t s) {
   NUNET_REQUIRE(x && y && N > 0 && C > 0 && H > 0 && W > 0 && cpad >= C, "nchw_to_nhwc: bad args");
   return NUNET_DISPATCH(dtype, launch_nchw_to_nhwc, x, N, C, H, W, y, cpad, (hipStream_t)s);
-}
-
-// ---------------------------------------------------------------------------
-// Device-side input pipeline: what reference dataset.py:66-74 does on the host
-// after decoding — albumentations Normalize() (trains.py:266), the extra /255 (dataset.py:71),
-// HWC -> CHW (dataset.py:72) — plus the geometric augmentations of trains.py:258-259
-// (RandomRotate90 / Flip) applied per sample from host-drawn codes. Input stays uint8 over PCIe.
-//   aug[n] = rot90 count (bits 0-1, counter-clockwise like np.rot90) | hflip (bit 2) | vflip (bit 3)
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void preprocess_u8_kernel(const uint8_t* __restrict__ u, int N, int H, int W, int C,
-                                                             const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                             const int32_t* __restrict__ aug, float post_scale, float* __restrict__ out) {
-  const int64_t total = (int64_t)N * C * H * W;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int x = (int)(i % W);
-    int64_t t = i / W;
-    const int y = (int)(t % H); t /= H;
-    const int c = (int)(t % C);
-    const int n = (int)(t / C);
-    int ry, rx;                               // destination (y, x) <- source (ry, rx); H == W when the rot90 count is odd
-    aug_source_pixel(aug ? aug[n] : 0, H, W, y, x, ry, rx);
-    const float v = (float)u[(((int64_t)n * H + ry) * W + rx) * C + c];
-    const float m = mean ? mean[c] : 0.f, sd = stdv ? stdv[c] : 1.f;
-    out[i] = ((v / 255.f - m) / sd) * post_scale;
-  }
-}
-extern "C" int nunet_preprocess_u8(const uint8_t* u8_nhwc, int32_t N, int32_t H, int32_t W, int32_t C, const float* mean, const float* stdv,
-                                   const int32_t* aug, float post_scale, float* out_nchw, nunet_stream_t s) {
-  NUNET_REQUIRE(u8_nhwc && out_nchw && N > 0 && H > 0 && W > 0 && C > 0, "preprocess_u8: bad args");
-  const int64_t total = (int64_t)N * C * H * W;
-  hipStream_t st = (hipStream_t)s;
-  ProfScope ps(PC_LAYOUT, 0, (double)total * 5, st);
-  NUNET_LAUNCH(preprocess_u8_kernel, dim3(grid_for(total, 256 * 4, 2048)), dim3(256), 0, st, u8_nhwc, N, H, W, C, mean, stdv, aug, post_scale, out_nchw);
-  return nunet_check_launch("preprocess_u8");
-}
-
-// Colour augmentation (common.h, color_aug_pixel). One thread per pixel: it reads its three bytes before it writes them, so
-// the stand-alone pass may run in place.
-__global__ __launch_bounds__(256) void color_aug_u8_kernel(const uint8_t* u, long long npix, long long hw,
-                                                            const nunet_color_aug* __restrict__ color, uint8_t* out) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < npix; i += (long long)gridDim.x * blockDim.x) {
-    uint8_t r = u[i * 3], g = u[i * 3 + 1], b = u[i * 3 + 2];
-    color_aug_sample(color, (int)(i / hw), r, g, b);
-    out[i * 3] = r; out[i * 3 + 1] = g; out[i * 3 + 2] = b;
-  }
-}
-extern "C" int nunet_color_aug_u8(const uint8_t* src, int32_t N, int32_t H, int32_t W, int32_t C, const nunet_color_aug* color, uint8_t* dst,
-                                  nunet_stream_t s) {
-  NUNET_REQUIRE(src && dst && color, "color_aug_u8: null pointer");
-  NUNET_REQUIRE(N > 0 && H > 0 && W > 0, "color_aug_u8: N=%d H=%d W=%d must be positive", N, H, W);
-  NUNET_REQUIRE(C == 3, "color_aug_u8: the colour ops are defined on RGB: C=%d must be 3", C);
-  const long long hw = (long long)H * W, npix = (long long)N * hw;
-  hipStream_t st = (hipStream_t)s;
-  ProfScope ps(PC_LAYOUT, 0, (double)npix * 6, st);
-  NUNET_LAUNCH(color_aug_u8_kernel, dim3(grid_for(npix, 256, 4096)), dim3(256), 0, st, src, npix, hw, color, dst);
-  return nunet_check_launch("color_aug_u8");
-}
-// preprocess_u8_kernel's arithmetic on the colour-augmented source pixel: one thread per destination pixel, which fetches the
-// source pixel's three bytes once and writes the three planes.
-__global__ __launch_bounds__(256) void preprocess_u8_color_kernel(const uint8_t* __restrict__ u, int N, int H, int W,
-                                                                   const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                                   const int32_t* __restrict__ aug, const nunet_color_aug* __restrict__ color,
-                                                                   float post_scale, float* __restrict__ out) {
-  const int64_t hw = (int64_t)H * W, npix = (int64_t)N * hw;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
-    const int x = (int)(i % W);
-    const int64_t t = i / W;
-    const int y = (int)(t % H);
-    const int n = (int)(t / H);
-    int ry, rx;                                // destination (y, x) <- source (ry, rx); H == W when the rot90 count is odd
-    aug_source_pixel(aug ? aug[n] : 0, H, W, y, x, ry, rx);
-    const uint8_t* src = u + (((int64_t)n * H + ry) * W + rx) * 3;
-    uint8_t px[3] = {src[0], src[1], src[2]};
-    color_aug_sample(color, n, px[0], px[1], px[2]);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out[((int64_t)n * 3 + c) * hw + (int64_t)y * W + x] = (((float)px[c] / 255.f - mean[c]) / stdv[c]) * post_scale;
-  }
-}
-extern "C" int nunet_preprocess_u8_color(const uint8_t* u8_nhwc, int32_t N, int32_t H, int32_t W, int32_t C, const float* mean, const float* stdv,
-                                         const int32_t* aug, const nunet_color_aug* color, float post_scale, float* out_nchw, nunet_stream_t s) {
-  NUNET_REQUIRE(u8_nhwc && out_nchw && N > 0 && H > 0 && W > 0, "preprocess_u8_color: bad args");
-  NUNET_REQUIRE(C == 3 && mean && stdv, "preprocess_u8_color: images only: C=%d must be 3, mean and stdv given", C);
-  if (!color) return nunet_preprocess_u8(u8_nhwc, N, H, W, C, mean, stdv, aug, post_scale, out_nchw, s);
-  const int64_t npix = (int64_t)N * H * W;
-  hipStream_t st = (hipStream_t)s;
-  ProfScope ps(PC_LAYOUT, 0, (double)npix * 15, st);
-  NUNET_LAUNCH(preprocess_u8_color_kernel, dim3(grid_for(npix, 256, 4096)), dim3(256), 0, st, u8_nhwc, N, H, W, mean, stdv, aug, color, post_scale, out_nchw);
-  return nunet_check_launch("preprocess_u8_color");
-}
-
-// Resize on ragged sources (common.h, resize_taps): one thread per DESTINATION pixel - the destination is small, and of a
-// large source only the four taps behind each pixel are touched. The thread forms its taps once and walks the channels.
-template <bool NEAREST, bool COLOR>
-__global__ __launch_bounds__(256) void resize_u8_kernel(const uint8_t* __restrict__ pool, long long pool_bytes,
-                                                         const nunet_u8_sample* __restrict__ samples, int N, int C, int Hd, int Wd,
-                                                         const int32_t* __restrict__ aug, const nunet_color_aug* __restrict__ color,
-                                                         uint8_t* __restrict__ out) {
-  const int64_t npix = (int64_t)N * Hd * Wd;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
-    const int x = (int)(i % Wd);
-    const int64_t q = i / Wd;
-    const int y = (int)(q % Hd);
-    const int n = (int)(q / Hd);
-    const ResizeTaps t = resize_taps<NEAREST>(samples[n], C, pool_bytes, aug ? aug[n] : 0, Hd, Wd, y, x);
-    uint8_t* o = out + i * C;
-    if constexpr (COLOR) {
-      uint8_t px[3];
-      resize_rgb_color(pool, t, color[n], px);
-      o[0] = px[0]; o[1] = px[1]; o[2] = px[2];
-    } else {
-      for (int c = 0; c < C; ++c) o[c] = resize_channel<NEAREST>(pool, t, c);
-    }
-  }
-}
-static int resize_args_ok(const char* what, const void* pool, int64_t pool_bytes, const void* samples, int32_t N, int32_t C, int32_t Hd, int32_t Wd) {
-  NUNET_REQUIRE(pool && samples, "%s: null pointer", what);
-  NUNET_REQUIRE(N > 0 && C > 0 && pool_bytes > 0, "%s: N=%d C=%d pool_bytes=%lld must be positive", what, N, C, (long long)pool_bytes);
-  NUNET_REQUIRE(Hd >= 1 && Wd >= 1 && Hd <= NUNET_RESIZE_MAX_EXTENT && Wd <= NUNET_RESIZE_MAX_EXTENT,
-                "%s: destination %d x %d: extents are 1 .. %d", what, Hd, Wd, NUNET_RESIZE_MAX_EXTENT);
-  return NUNET_OK;
-}
-extern "C" int nunet_resize_u8(const uint8_t* pool, int64_t pool_bytes, const nunet_u8_sample* samples, int32_t N, int32_t C, int32_t Hd,
-                               int32_t Wd, int32_t mode, const int32_t* aug, const nunet_color_aug* color, uint8_t* dst, nunet_stream_t s) {
-  if (int rc = resize_args_ok("resize_u8", pool, pool_bytes, samples, N, C, Hd, Wd)) return rc;
-  NUNET_REQUIRE(dst, "resize_u8: null pointer");
-  NUNET_REQUIRE(mode == NUNET_RESIZE_LINEAR || mode == NUNET_RESIZE_NEAREST, "resize_u8: mode %d is neither LINEAR (0) nor NEAREST (1)", mode);
-  NUNET_REQUIRE(!color || (mode == NUNET_RESIZE_LINEAR && C == 3), "resize_u8: the colour ops are defined on RGB images under LINEAR: mode=%d C=%d", mode, C);
-  const int64_t npix = (int64_t)N * Hd * Wd;
-  hipStream_t st = (hipStream_t)s;
-  ProfScope ps(PC_LAYOUT, 0, (double)npix * C * (mode == NUNET_RESIZE_LINEAR ? 5 : 2), st);
-  const dim3 grid(grid_for(npix, 256, 4096)), block(256);
-  if (mode == NUNET_RESIZE_NEAREST) NUNET_LAUNCH((resize_u8_kernel<true, false>), grid, block, 0, st, pool, (long long)pool_bytes, samples, N, C, Hd, Wd, aug, color, dst);
-  else if (color) NUNET_LAUNCH((resize_u8_kernel<false, true>), grid, block, 0, st, pool, (long long)pool_bytes, samples, N, C, Hd, Wd, aug, color, dst);
-  else NUNET_LAUNCH((resize_u8_kernel<false, false>), grid, block, 0, st, pool, (long long)pool_bytes, samples, N, C, Hd, Wd, aug, color, dst);
-  return nunet_check_launch("resize_u8");
-}
-// preprocess_u8_kernel's arithmetic on the NEAREST tap of a ragged source: one thread per output element
-__global__ __launch_bounds__(256) void preprocess_u8_resize_kernel(const uint8_t* __restrict__ pool, long long pool_bytes,
-                                                                    const nunet_u8_sample* __restrict__ samples, int N, int C, int Hd, int Wd,
-                                                                    const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                                    const int32_t* __restrict__ aug, float post_scale, float* __restrict__ out) {
-  const int64_t total = (int64_t)N * C * Hd * Wd;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int x = (int)(i % Wd);
-    int64_t q = i / Wd;
-    const int y = (int)(q % Hd); q /= Hd;
-    const int c = (int)(q % C);
-    const int n = (int)(q / C);
-    const ResizeTaps t = resize_taps<true>(samples[n], C, pool_bytes, aug ? aug[n] : 0, Hd, Wd, y, x);
-    const float v = (float)resize_channel<true>(pool, t, c);
-    const float m = mean ? mean[c] : 0.f, sd = stdv ? stdv[c] : 1.f;
-    out[i] = ((v / 255.f - m) / sd) * post_scale;
-  }
-}
-extern "C" int nunet_preprocess_u8_resize(const uint8_t* pool, int64_t pool_bytes, const nunet_u8_sample* samples, int32_t N, int32_t C,
-                                          int32_t Hd, int32_t Wd, const float* mean, const float* stdv, const int32_t* aug,
-                                          float post_scale, float* out_nchw, nunet_stream_t s) {
-  if (int rc = resize_args_ok("preprocess_u8_resize", pool, pool_bytes, samples, N, C, Hd, Wd)) return rc;
-  NUNET_REQUIRE(out_nchw, "preprocess_u8_resize: null pointer");
-  const int64_t total = (int64_t)N * C * Hd * Wd;
-  hipStream_t st = (hipStream_t)s;
-  ProfScope ps(PC_LAYOUT, 0, (double)total * 5, st);
-  NUNET_LAUNCH(preprocess_u8_resize_kernel, dim3(grid_for(total, 256, 4096)), dim3(256), 0, st, pool, (long long)pool_bytes, samples, N, C, Hd, Wd,
-               mean, stdv, aug, post_scale, out_nchw);
-  return nunet_check_launch("preprocess_u8_resize");
 }
 
 // ---------------------------------------------------------------------------

@@ -18,7 +18,7 @@
 #include <vector>
 #include <stdarg.h>
 
-#include "common.h"
+#include "pipeline.h"
 
 static const int NBF[5] = {32, 64, 128, 256, 512};  // archs1.py:78
 
@@ -1459,191 +1459,50 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
 // to the storage type, as the padded NHWC tile the first conv reads. One thread per pixel writes the pixel's 32 channels
 // (zeros beyond C) as 16-byte stores. The arithmetic is nunet_preprocess_u8's followed by nunet_nchw_to_nhwc's rounding, so
 // the staged image is bit-identical to the float path's; only uint8 crosses PCIe and the per-step layout launch goes away.
+// The four entries are pipeline.h's sources under StageSink: the dense batch (with the colour op: _color), the bilinear resize
+// of ragged sources (_resize), border-reflected tile windows (_tiles). src_bytes: what the source reads per pixel.
 // ---------------------------------------------------------------------------------------------------------
-// COLOR (nunet_plan_stage_u8_color): the colour op of color[n] (common.h, color_aug_pixel) on the fetched source pixel first; C == 3.
-template <typename T, bool COLOR>
-__global__ __launch_bounds__(256) void stage_u8_kernel(const uint8_t* __restrict__ u, int N, int H, int W, int C, const float* __restrict__ mean,
-                                                       const float* __restrict__ stdv, const int32_t* __restrict__ aug,
-                                                       const nunet_color_aug* __restrict__ color, float post_scale, T* __restrict__ img) {
-  constexpr int EPV = Tr<T>::EPV;
-  const long long npix = (long long)N * H * W;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < npix; i += (long long)gridDim.x * blockDim.x) {
-    const int x = (int)(i % W);
-    long long t = i / W;
-    const int y = (int)(t % H);
-    const int n = (int)(t / H);
-    int ry, rx;                                // destination (y, x) <- source (ry, rx); H == W when the rot90 count is odd
-    aug_source_pixel(aug ? aug[n] : 0, H, W, y, x, ry, rx);
-    const uint8_t* src = u + (((long long)n * H + ry) * W + rx) * C;
-    uint8_t px[3];
-    if constexpr (COLOR) {
-      px[0] = src[0]; px[1] = src[1]; px[2] = src[2];
-      color_aug_sample(color, n, px[0], px[1], px[2]);
-      src = px;
-    }
-    T* dst = img + i * 32;
-#pragma unroll
-    for (int v = 0; v < 32 / EPV; ++v) {
-      Vec16<T> o;
-#pragma unroll
-      for (int e = 0; e < EPV; ++e) {
-        const int c = v * EPV + e;
-        float f = 0.f;
-        if (c < C) {
-          const float m = mean ? mean[c] : 0.f, sd = stdv ? stdv[c] : 1.f;
-          f = (((float)src[c] / 255.f - m) / sd) * post_scale;
-        }
-        o.set(e, f);
-      }
-      st16(dst + v * EPV, o);
-    }
-  }
+template <typename T, class Src> static int launch_stage(const char* name, const Src& src, double src_bytes, const nunet_plan* P, const float* mean,
+                                                         const float* stdv, float post_scale, void* arena, nunet_stream_t s) {
+  const nunet_plan_cfg& c = P->cfg;
+  return launch_pipeline(name, src, StageSink<T>{(T*)AB(arena, P->off_img), c.input_channels, mean, stdv, post_scale}, c.N, c.H, c.W,
+                         (double)c.N * c.H * c.W * (src_bytes + 32.0 * sizeof(T)), (hipStream_t)s);
 }
-template <typename T> static int launch_stage_u8(const uint8_t* u, int N, int H, int W, int C, const float* mean, const float* stdv, const int32_t* aug,
-                                                 const nunet_color_aug* color, float post_scale, void* img, hipStream_t st) {
-  const long long npix = (long long)N * H * W;
-  long long g = (npix + 255) / 256; if (g > 4096) g = 4096;
-  ProfScope ps(PC_LAYOUT, 0, (double)npix * (C + 32.0 * sizeof(T)), st);
-  if (color) NUNET_LAUNCH((stage_u8_kernel<T, true>), dim3((unsigned)g), dim3(256), 0, st, u, N, H, W, C, mean, stdv, aug, color, post_scale, (T*)img);
-  else NUNET_LAUNCH((stage_u8_kernel<T, false>), dim3((unsigned)g), dim3(256), 0, st, u, N, H, W, C, mean, stdv, aug, color, post_scale, (T*)img);
-  return nunet_check_launch("plan_stage_u8");
-}
+// what the four ask first (P before anything reads the plan's extents); leaves c = P->cfg and C = c.input_channels behind
+#define STAGE_CHECK(what, ptrs, ...)                                                                            \
+  NUNET_REQUIRE(P, what ": null pointer");                                                                      \
+  const nunet_plan_cfg& c = P->cfg;                                                                             \
+  const int C = c.input_channels;                                                                               \
+  if (int rc = pipeline_args_ok(what, (ptrs) && arena, c.N, C, c.H, c.W, ##__VA_ARGS__)) return rc;             \
+  ARENA_CHECK(what)
 extern "C" int nunet_plan_stage_u8(nunet_plan* P, const uint8_t* u8_nhwc, const float* mean, const float* stdv, const int32_t* aug, float post_scale,
                                    void* arena, size_t arena_bytes, nunet_stream_t s) {
-  NUNET_REQUIRE(P && u8_nhwc && arena, "plan_stage_u8: null pointer");
-  ARENA_CHECK("plan_stage_u8");
-  const nunet_plan_cfg& c = P->cfg;
-  return NUNET_DISPATCH(c.dtype, launch_stage_u8, u8_nhwc, c.N, c.H, c.W, c.input_channels, mean, stdv, aug, nullptr, post_scale, (void*)AB(arena, P->off_img), (hipStream_t)s);
+  STAGE_CHECK("plan_stage_u8", u8_nhwc);
+  return NUNET_DISPATCH(c.dtype, launch_stage, "plan_stage_u8", DenseSrc<false>{u8_nhwc, c.H, c.W, C, aug, nullptr}, C, P, mean, stdv, post_scale, arena, s);
 }
 extern "C" int nunet_plan_stage_u8_color(nunet_plan* P, const uint8_t* u8_nhwc, const float* mean, const float* stdv, const int32_t* aug,
                                          const nunet_color_aug* color, float post_scale, void* arena, size_t arena_bytes, nunet_stream_t s) {
-  NUNET_REQUIRE(P && u8_nhwc && arena, "plan_stage_u8_color: null pointer");
-  ARENA_CHECK("plan_stage_u8_color");
-  const nunet_plan_cfg& c = P->cfg;
-  NUNET_REQUIRE(c.input_channels == 3 && mean && stdv, "plan_stage_u8_color: images only: input_channels=%d must be 3, mean and stdv given", c.input_channels);
-  return NUNET_DISPATCH(c.dtype, launch_stage_u8, u8_nhwc, c.N, c.H, c.W, c.input_channels, mean, stdv, aug, color, post_scale, (void*)AB(arena, P->off_img), (hipStream_t)s);
-}
-// stage_u8_kernel on ragged sources (nunet_plan_stage_u8_resize): the pixel's bytes come from the bilinear resize of the
-// augmented source (common.h, resize_taps) instead of one fetch; the arithmetic behind the byte and the stores are stage_u8_kernel's.
-// One thread per destination pixel: it forms its four taps once, and of a large source only those taps are read.
-template <typename T, bool COLOR>
-__global__ __launch_bounds__(256) void stage_u8_resize_kernel(const uint8_t* __restrict__ pool, long long pool_bytes,
-                                                              const nunet_u8_sample* __restrict__ samples, int N, int H, int W, int C,
-                                                              const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                              const int32_t* __restrict__ aug, const nunet_color_aug* __restrict__ color,
-                                                              float post_scale, T* __restrict__ img) {
-  constexpr int EPV = Tr<T>::EPV;
-  const long long npix = (long long)N * H * W;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < npix; i += (long long)gridDim.x * blockDim.x) {
-    const int x = (int)(i % W);
-    long long q = i / W;
-    const int y = (int)(q % H);
-    const int n = (int)(q / H);
-    const ResizeTaps t = resize_taps<false>(samples[n], C, pool_bytes, aug ? aug[n] : 0, H, W, y, x);
-    uint8_t px[3];
-    if constexpr (COLOR) resize_rgb_color(pool, t, color[n], px);
-    T* dst = img + i * 32;
-#pragma unroll
-    for (int v = 0; v < 32 / EPV; ++v) {
-      Vec16<T> o;
-#pragma unroll
-      for (int e = 0; e < EPV; ++e) {
-        const int c = v * EPV + e;
-        float f = 0.f;
-        if (c < C) {
-          const float m = mean ? mean[c] : 0.f, sd = stdv ? stdv[c] : 1.f;
-          uint8_t b;
-          if constexpr (COLOR) b = px[c < 3 ? c : 0];
-          else b = resize_channel<false>(pool, t, c);
-          f = (((float)b / 255.f - m) / sd) * post_scale;
-        }
-        o.set(e, f);
-      }
-      st16(dst + v * EPV, o);
-    }
-  }
-}
-template <typename T> static int launch_stage_u8_resize(const uint8_t* pool, long long pool_bytes, const nunet_u8_sample* samples, int N, int H, int W, int C,
-                                                        const float* mean, const float* stdv, const int32_t* aug, const nunet_color_aug* color,
-                                                        float post_scale, void* img, hipStream_t st) {
-  const long long npix = (long long)N * H * W;
-  long long g = (npix + 255) / 256; if (g > 4096) g = 4096;
-  ProfScope ps(PC_LAYOUT, 0, (double)npix * (4.0 * C + 32.0 * sizeof(T)), st);
-  if (color) NUNET_LAUNCH((stage_u8_resize_kernel<T, true>), dim3((unsigned)g), dim3(256), 0, st, pool, pool_bytes, samples, N, H, W, C, mean, stdv, aug, color, post_scale, (T*)img);
-  else NUNET_LAUNCH((stage_u8_resize_kernel<T, false>), dim3((unsigned)g), dim3(256), 0, st, pool, pool_bytes, samples, N, H, W, C, mean, stdv, aug, color, post_scale, (T*)img);
-  return nunet_check_launch("plan_stage_u8_resize");
+  STAGE_CHECK("plan_stage_u8_color", u8_nhwc);
+  NUNET_REQUIRE(C == 3 && mean && stdv, "plan_stage_u8_color: images only: input_channels=%d must be 3, mean and stdv given", C);
+  if (!color) return nunet_plan_stage_u8(P, u8_nhwc, mean, stdv, aug, post_scale, arena, arena_bytes, s);
+  return NUNET_DISPATCH(c.dtype, launch_stage, "plan_stage_u8_color", DenseSrc<true>{u8_nhwc, c.H, c.W, C, aug, color}, C, P, mean, stdv, post_scale, arena, s);
 }
 extern "C" int nunet_plan_stage_u8_resize(nunet_plan* P, const uint8_t* pool, int64_t pool_bytes, const nunet_u8_sample* samples, const float* mean,
                                           const float* stdv, const int32_t* aug, const nunet_color_aug* color, float post_scale, void* arena,
                                           size_t arena_bytes, nunet_stream_t s) {
-  NUNET_REQUIRE(P && pool && samples && arena, "plan_stage_u8_resize: null pointer");
-  ARENA_CHECK("plan_stage_u8_resize");
-  const nunet_plan_cfg& c = P->cfg;
-  NUNET_REQUIRE(pool_bytes > 0, "plan_stage_u8_resize: pool_bytes=%lld must be positive", (long long)pool_bytes);
-  NUNET_REQUIRE(c.H <= NUNET_RESIZE_MAX_EXTENT && c.W <= NUNET_RESIZE_MAX_EXTENT, "plan_stage_u8_resize: destination %d x %d: extents are 1 .. %d",
-                c.H, c.W, NUNET_RESIZE_MAX_EXTENT);
-  NUNET_REQUIRE(!color || (c.input_channels == 3 && mean && stdv), "plan_stage_u8_resize: colour ops need images: input_channels=%d must be 3, mean and stdv given",
-                c.input_channels);
-  return NUNET_DISPATCH(c.dtype, launch_stage_u8_resize, pool, (long long)pool_bytes, samples, c.N, c.H, c.W, c.input_channels, mean, stdv, aug, color,
-                        post_scale, (void*)AB(arena, P->off_img), (hipStream_t)s);
-}
-// stage_u8_kernel on tiles of ragged sources (nunet_plan_stage_u8_tiles): the pixel's bytes come from the border-reflected window
-// tiles[n] names (common.h, tile_pixel_offset; a pixel that may read nothing stages the byte 0) instead of a dense batch; the
-// arithmetic behind the byte and the stores are stage_u8_kernel's. One thread per tile pixel.
-template <typename T>
-__global__ __launch_bounds__(256) void stage_u8_tiles_kernel(const uint8_t* __restrict__ pool, long long pool_bytes,
-                                                             const nunet_u8_sample* __restrict__ samples, int n_samples,
-                                                             const nunet_tile* __restrict__ tiles, int N, int H, int W, int C,
-                                                             const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                             float post_scale, T* __restrict__ img) {
-  constexpr int EPV = Tr<T>::EPV;
-  const long long npix = (long long)N * H * W;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < npix; i += (long long)gridDim.x * blockDim.x) {
-    const int x = (int)(i % W);
-    long long q = i / W;
-    const int y = (int)(q % H);
-    const int n = (int)(q / H);
-    const long long o = tile_pixel_offset(samples, n_samples, tiles[n], C, pool_bytes, y, x);
-    T* dst = img + i * 32;
-#pragma unroll
-    for (int v = 0; v < 32 / EPV; ++v) {
-      Vec16<T> out;
-#pragma unroll
-      for (int e = 0; e < EPV; ++e) {
-        const int c = v * EPV + e;
-        float f = 0.f;
-        if (c < C) {
-          const float m = mean ? mean[c] : 0.f, sd = stdv ? stdv[c] : 1.f;
-          const uint8_t b = o < 0 ? (uint8_t)0 : pool[o + c];
-          f = (((float)b / 255.f - m) / sd) * post_scale;
-        }
-        out.set(e, f);
-      }
-      st16(dst + v * EPV, out);
-    }
-  }
-}
-template <typename T> static int launch_stage_u8_tiles(const uint8_t* pool, long long pool_bytes, const nunet_u8_sample* samples, int n_samples,
-                                                       const nunet_tile* tiles, int N, int H, int W, int C, const float* mean, const float* stdv,
-                                                       float post_scale, void* img, hipStream_t st) {
-  const long long npix = (long long)N * H * W;
-  long long g = (npix + 255) / 256; if (g > 4096) g = 4096;
-  ProfScope ps(PC_LAYOUT, 0, (double)npix * (C + 32.0 * sizeof(T)), st);
-  NUNET_LAUNCH((stage_u8_tiles_kernel<T>), dim3((unsigned)g), dim3(256), 0, st, pool, pool_bytes, samples, n_samples, tiles, N, H, W, C, mean, stdv,
-               post_scale, (T*)img);
-  return nunet_check_launch("plan_stage_u8_tiles");
+  STAGE_CHECK("plan_stage_u8_resize", pool && samples, "destination", pool_bytes);
+  NUNET_REQUIRE(!color || (C == 3 && mean && stdv), "plan_stage_u8_resize: colour ops need images: input_channels=%d must be 3, mean and stdv given", C);
+  if (color) return NUNET_DISPATCH(c.dtype, launch_stage, "plan_stage_u8_resize", ResizeSrc<false, true>{pool, pool_bytes, samples, C, c.H, c.W, aug, color}, 4.0 * C, P,
+                                   mean, stdv, post_scale, arena, s);
+  return NUNET_DISPATCH(c.dtype, launch_stage, "plan_stage_u8_resize", ResizeSrc<false, false>{pool, pool_bytes, samples, C, c.H, c.W, aug, nullptr}, 4.0 * C, P, mean,
+                        stdv, post_scale, arena, s);
 }
 extern "C" int nunet_plan_stage_u8_tiles(nunet_plan* P, const uint8_t* pool, int64_t pool_bytes, const nunet_u8_sample* samples, int32_t n_samples,
                                          const nunet_tile* tiles, const float* mean, const float* stdv, float post_scale, void* arena,
                                          size_t arena_bytes, nunet_stream_t s) {
-  NUNET_REQUIRE(P && pool && samples && tiles && arena, "plan_stage_u8_tiles: null pointer");
-  ARENA_CHECK("plan_stage_u8_tiles");
-  const nunet_plan_cfg& c = P->cfg;
-  NUNET_REQUIRE(pool_bytes > 0 && n_samples > 0, "plan_stage_u8_tiles: pool_bytes=%lld n_samples=%d must be positive", (long long)pool_bytes, n_samples);
-  NUNET_REQUIRE(c.H <= NUNET_RESIZE_MAX_EXTENT && c.W <= NUNET_RESIZE_MAX_EXTENT, "plan_stage_u8_tiles: tile %d x %d: extents are 1 .. %d",
-                c.H, c.W, NUNET_RESIZE_MAX_EXTENT);
-  return NUNET_DISPATCH(c.dtype, launch_stage_u8_tiles, pool, (long long)pool_bytes, samples, n_samples, tiles, c.N, c.H, c.W, c.input_channels, mean, stdv,
-                        post_scale, (void*)AB(arena, P->off_img), (hipStream_t)s);
+  STAGE_CHECK("plan_stage_u8_tiles", pool && samples && tiles, "tile", pool_bytes);
+  NUNET_REQUIRE(n_samples > 0, "plan_stage_u8_tiles: n_samples=%d must be positive", n_samples);
+  return NUNET_DISPATCH(c.dtype, launch_stage, "plan_stage_u8_tiles", TileSrc{pool, pool_bytes, samples, n_samples, tiles, C}, C, P, mean, stdv, post_scale, arena, s);
 }
 
 extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, const float* dlogits, void* arena, size_t arena_bytes, float* grads, int32_t accumulate, int32_t phases, nunet_stream_t s);

@@ -1,43 +1,10 @@
 // tiles.hip - full-resolution tiled inference (include/nunet.h, nunet_tile / nunet_tile_grid):
-//   nunet_crop_tiles_u8: fixed-size, border-reflected windows cut out of ragged uint8 sources,
-//   nunet_stitch_tiles:  the overlapping windows' fp32 logits blended back into masks of the sources' sizes.
-// (The staging launch that crops straight into a plan's image, nunet_plan_stage_u8_tiles, sits with the other staging
-// launches in plan.hip; the pixel -> source byte map, tile_pixel_offset, is shared through common.h.)
-// Both kernels are element-wise over their DESTINATION with a capped grid and a grid-stride loop; every descriptor is device
+//   nunet_stitch_tiles: the overlapping windows' fp32 logits blended back into masks of the sources' sizes.
+// (The way in - fixed-size, border-reflected windows cut out of ragged uint8 sources, nunet_crop_tiles_u8 and
+// nunet_plan_stage_u8_tiles - is the sample pipeline's TileSrc: pipeline.h.)
+// The kernel is element-wise over its DESTINATION with a capped grid and a grid-stride loop; every descriptor is device
 // memory read at run time and none is trusted.
 #include "common.h"
-
-// One thread per tile pixel: it resolves its source pixel once and walks the channels.
-__global__ __launch_bounds__(256) void crop_tiles_u8_kernel(const uint8_t* __restrict__ pool, long long pool_bytes,
-                                                            const nunet_u8_sample* __restrict__ samples, int n_samples,
-                                                            const nunet_tile* __restrict__ tiles, int N, int C, int Th, int Tw,
-                                                            uint8_t* __restrict__ out) {
-  const int64_t npix = (int64_t)N * Th * Tw;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
-    const int x = (int)(i % Tw);
-    const int64_t q = i / Tw;
-    const int y = (int)(q % Th);
-    const int t = (int)(q / Th);
-    const long long o = tile_pixel_offset(samples, n_samples, tiles[t], C, pool_bytes, y, x);
-    uint8_t* dst = out + i * C;
-    for (int c = 0; c < C; ++c) dst[c] = o < 0 ? (uint8_t)0 : pool[o + c];
-  }
-}
-extern "C" int nunet_crop_tiles_u8(const uint8_t* pool, int64_t pool_bytes, const nunet_u8_sample* samples, int32_t n_samples,
-                                   const nunet_tile* tiles, int32_t N, int32_t C, int32_t Th, int32_t Tw, uint8_t* dst, nunet_stream_t s) {
-  NUNET_REQUIRE(pool && samples && tiles && dst, "crop_tiles_u8: null pointer");
-  NUNET_REQUIRE(N > 0 && C > 0 && n_samples > 0 && pool_bytes > 0, "crop_tiles_u8: N=%d C=%d n_samples=%d pool_bytes=%lld must be positive", N, C,
-                n_samples, (long long)pool_bytes);
-  NUNET_REQUIRE(Th >= 1 && Tw >= 1 && Th <= NUNET_RESIZE_MAX_EXTENT && Tw <= NUNET_RESIZE_MAX_EXTENT, "crop_tiles_u8: tile %d x %d: extents are 1 .. %d",
-                Th, Tw, NUNET_RESIZE_MAX_EXTENT);
-  const int64_t npix = (int64_t)N * Th * Tw;
-  hipStream_t st = (hipStream_t)s;
-  ProfScope ps(PC_LAYOUT, 0, (double)npix * C * 2, st);
-  int64_t g = ceil_div64(npix, 256);
-  if (g > 4096) g = 4096;
-  NUNET_LAUNCH(crop_tiles_u8_kernel, dim3((unsigned)g), dim3(256), 0, st, pool, (long long)pool_bytes, samples, n_samples, tiles, N, C, Th, Tw, dst);
-  return nunet_check_launch("crop_tiles_u8");
-}
 
 // ---------------------------------------------------------------------------
 // Stitch. Workgroups (x, y): y walks the samples, x the sample's K * H * W output elements, both with a stride of the grid, so
@@ -125,9 +92,7 @@ extern "C" int nunet_stitch_tiles(const float* tile_logits, int32_t n_tiles, int
   // every source pixel lies in a tile, so the n_samples sources hold at most n_tiles * Th * Tw pixels: the x extent is sized for
   // the mean sample (larger ones take more trips), capped so that the launch has at most STITCH_MAX_WG workgroups
   const int gy = n_samples < STITCH_MAX_WG ? n_samples : STITCH_MAX_WG;
-  int64_t gx = ceil_div64(ceil_div64((int64_t)n_tiles * Th * Tw * K, n_samples), 256);
-  if (gx > STITCH_MAX_WG / gy) gx = STITCH_MAX_WG / gy;
-  if (gx < 1) gx = 1;
+  const int gx = grid_for(ceil_div64((int64_t)n_tiles * Th * Tw * K, n_samples), 256, STITCH_MAX_WG / gy);
   hipStream_t st = (hipStream_t)s;
   ProfScope ps(PC_LAYOUT, 0, (double)n_tiles * K * Th * Tw * 4, st);
   NUNET_LAUNCH(stitch_tiles_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, tile_logits, n_tiles, K, Th, Tw, samples, grids, n_samples,

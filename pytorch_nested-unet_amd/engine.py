@@ -56,8 +56,8 @@ class Plan:
         return self._slot(L.lib().nunet_plan_feature_grad, i, j)
 
     def image(self):
-        """The staged input image as an [N,H,W,32] NHWC view in the storage dtype: what nunet_plan_stage_u8(_color) or the
-        layout launch of the last forward left for the first convolution; channels past input_channels are zeros (tests/debug)."""
+        """The staged input image as an [N,H,W,32] NHWC view in the storage dtype: what a staging entry of the sample pipeline
+        (nunet_plan_stage_u8*: csrc/pipeline.h, StageSink) or the layout launch of the last forward left for the first convolution; channels past input_channels are zeros (tests/debug)."""
         pitch, ch = C.c_int32(), C.c_int32()
         off = L.lib().nunet_plan_image(self.handle, C.byref(pitch), C.byref(ch))
         if off < 0:

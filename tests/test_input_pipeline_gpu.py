@@ -286,11 +286,12 @@ def test_capped_grid_preprocess_u8_color(large_free):
 
 
 def test_capped_grid_preprocess_u8():
-    """its grid is capped at 2048 blocks of 256 threads that take four elements each at any size: 5 x 460 x 457 x 4 = 4,204,400
-    elements is more than 2 x 2,097,152, so threads take up to nine trips and the last trip is partial"""
+    """one thread per destination pixel under the pipeline's one grid cap, 4096 blocks of 256 threads: 5 x 460 x 457 = 1,051,100
+    pixels of four channels each are more than the 1,048,576 the grid holds, so the last 2,524 pixels are a thread's second
+    trip and that trip ends inside a block"""
     n, h, w = PC.LARGE_SHAPES["free"]
     u = PC.tagged_large(n, h, w, 4)
-    assert u.size > 2 * 2048 * 256 * 4
+    assert n * h * w > PC.GRID_CAP_PIXELS and (n * h * w) % 256
     got = preprocess_u8(u, PC.LARGE_CODES, None, None, 1.0)
     assert_bytes(got, "fp32", PC.ref_batch(u, PC.LARGE_CODES), "preprocess_u8 5x460x457x4", PC.decode_large)
 

@@ -293,6 +293,20 @@ def test_capped_grid_resize_u8(large):
     assert np.array_equal(got, (expm // 255).astype(np.float32))
 
 
+def test_capped_grid_preprocess_u8_resize_partial_last_block():
+    """5 x 460 x 457 = 1,051,100 one-channel destination pixels against the 1,048,576 the grid holds: the last 2,524 are a thread's
+    second trip, and that trip ends inside a block (the cases above are multiples of 256). Five small ragged masks, one of
+    them a single pixel, a different rot90 / flip code each; NEAREST, then the mask preprocessing (NULL mean / std, post_scale 1)."""
+    n, h, w = PC.LARGE_SHAPES["free"]
+    assert n * h * w > PC.GRID_CAP_PIXELS and (n * h * w) % 256
+    masks = RC.binary_sources([(5, 7), (40, 33), (1, 1), (17, 29), (33, 12)], 1, seed=14)
+    codes = [1 | 4, 0, 3 | 8, 2, 1 | 4 | 8]
+    exp = RC.reference_batch(masks, h, w, RC.NEAREST, codes)
+    got = preprocess_u8_resize(Ragged(masks), h, w, codes, None, None, 1.0).cpu().numpy().transpose(0, 2, 3, 1)
+    assert_batch_equal(PC.decode_bytes(got, "fp32"), exp.astype(np.int16), "preprocess_u8_resize 5x460x457")
+    assert np.array_equal(got, PC.f32_values(exp, None, None, 1.0)) and set(np.unique(got)) <= {0.0, 1.0}
+
+
 def test_capped_grid_stage_u8_resize(large):
     samples, colors, exp = large
     n, h, w = RC.LARGE_DST

@@ -22,6 +22,7 @@ from nunet_amd import tiled as T  # noqa: E402
 from nunet_amd.engine import Plan  # noqa: E402
 from nunet_amd.metrics import iou_logit_threshold, sigmoid_masks_u8, sigmoid_u8_thresholds  # noqa: E402
 from nunet_amd.trainer import EvalStep  # noqa: E402
+import pipeline_cases as PC  # noqa: E402
 import resize_cases as RC  # noqa: E402
 import tile_cases as TC  # noqa: E402
 
@@ -159,6 +160,40 @@ def test_stage_u8_tiles_equals_crop_then_stage(kind, case):
     L.check(L.lib().nunet_plan_stage_u8(pl.handle, L.ptr(dev(exp)), L.ptr(m), L.ptr(s), None, 1.0 / 255.0, L.ptr(pl.arena), L.nbytes(pl.arena), L.stream()),
             "nunet_plan_stage_u8")
     assert np.array_equal(fused, _image_bits(pl))
+
+
+# -- 2b. past the pipeline's grid cap (4096 workgroups x 256 threads, one thread per tile pixel) ----------------------------------
+def test_capped_grid_crop_tiles_u8():
+    """5 tiles of 460 x 457 = 1,051,100 pixels against the 1,048,576 the grid holds: the last 2,524 pixels are a thread's second
+    trip, which ends inside a block. Every source is smaller than the tile, so the reflection turns many times along both axes;
+    tile 2 is null and tile 4's origin lies outside its source."""
+    n, th, tw = PC.LARGE_SHAPES["free"]
+    assert n * th * tw > PC.GRID_CAP_PIXELS and (n * th * tw) % 256
+    samples = TC.sources([(33, 70), (1, 1), (17, 16)], 3)
+    tiles = np.asarray([[0, 0, 0, 0], [1, 0, 0, 0], [-1, 0, 0, 0], [2, 16, 15, 0], [0, 33, 0, 0]], np.int32)
+    exp = oracle_crops(samples, np.concatenate([tiles[:4], NULL_TILE]), th, tw)
+    r = Ragged(samples)
+    assert_tiles_equal(crop(r, r.desc, tiles, th, tw), exp, "crop 5x460x457")
+
+
+def test_capped_grid_stage_u8_tiles():
+    """the plan of test_input_pipeline_gpu's capped-grid staging case (N = 5, 464 x 464, bf16, pruned to depth 1): 1,076,480
+    pixels, 27,904 of them a second trip. Five windows of two small sources; the staged image decodes to the oracle's crop
+    (NULL mean / std, post_scale = 1) and the padding channels of every pixel are zero bits."""
+    n, h, w = PC.LARGE_SHAPES["plan"]
+    assert n * h * w > PC.GRID_CAP_PIXELS
+    samples = TC.sources([(40, 56), (17, 16)], 3)
+    tiles = np.asarray([[0, 0, 0, 0], [1, 0, 0, 0], [0, 39, 55, 0], [1, 5, 9, 0], [0, 8, 24, 0]], np.int32)
+    r = Ragged(samples)
+    pl = Plan(n, h, w, 3, 1, True, L.BF16, False, DEV, depth=1)
+    L.check(L.lib().nunet_plan_stage_u8_tiles(pl.handle, L.ptr(r.pool), r.bytes, L.ptr(r.desc), r.n, L.ptr(dev(tiles)), None, None, 1.0,
+                                              L.ptr(pl.arena), L.nbytes(pl.arena), L.stream()), "nunet_plan_stage_u8_tiles")
+    torch.cuda.synchronize()
+    host = pl.image().cpu().contiguous()
+    assert tuple(host.shape) == (n, h, w, 32)
+    got = PC.decode_bytes(host.float().numpy()[..., :3], "bf16")
+    assert_tiles_equal(got, oracle_crops(samples, tiles, h, w).astype(got.dtype), "stage_u8_tiles 5x464x464")
+    assert not host.view(torch.int16).numpy()[..., 3:].any(), "padding channels are zero bits"
 
 
 # -- 3. nunet_stitch_tiles against the fp64 oracle ------------------------------------------------------------------------------

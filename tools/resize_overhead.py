@@ -1,7 +1,7 @@
 """Cost of the device-side Resize in the captured training step: ms per replay of the captured step, bf16, SGD, 96 x 96, batch 16,
 rot90 / flip codes on, the one-hipGraph executor forced (the modes are compared on one executor).
 
-    python tools/resize_overhead.py --parent DIR [--procs 3] [--steps 200] [--rounds 3] [--out FILE]     the comparison
+    python tools/resize_overhead.py --parent DIR [--parent_modes u8] [--procs 3] [--steps 200] [--rounds 3] [--out FILE]     the comparison
     python tools/resize_overhead.py --modes u8,equal,ragged,ragged_hsv [--steps 200] [--rounds 3]        one process (also runs
                                                                                                          on a checkout without
                                                                                                          the resize: --modes u8)
@@ -10,9 +10,11 @@ Modes: u8 = TrainStep(input_u8=True) (resize=False on this commit, all there is 
 of the plan's own size; ragged = resize=True fed sources of 2 - 6 times the linear size (192 .. 576 pixels a side, drawn per
 sample and per axis from a seeded generator); ragged_hsv = the same with every colour op HSV (13.7, -22.4, 9.2). The static
 buffers are loaded once and the captured step is replayed: the timed window holds the step's launches and no host copy, so the
-modes differ by their two head launches only. --parent DIR (a built checkout of the parent commit) alternates processes: parent
-u8, this commit's four modes, --procs times; (b) against (a) is this commit's u8 against the parent's u8, judged against the
-parent's own round-to-round and process-to-process spread. Prints one line per process, then a JSON summary (also written to --out).
+modes differ by their two head launches only. --parent DIR (a built checkout of the parent commit) alternates processes: the
+parent's --parent_modes (u8 is all a parent without the resize has; a parent that has it takes all four), this commit's --modes,
+--procs times. Every mode both trees ran is judged on its own: the difference of this commit's median and the parent's must lie
+inside the parent's own round-to-round and process-to-process spread of that mode (<mode>_inside_parent_spread). Prints one line
+per process, then a JSON summary (also written to --out).
 """
 import argparse
 import json
@@ -98,6 +100,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--modes", default="u8,equal,ragged,ragged_hsv")
     ap.add_argument("--parent", default=None, help="a built checkout of the parent commit: alternate processes of it and of this commit")
+    ap.add_argument("--parent_modes", default="u8", help="the modes the parent checkout runs")
     ap.add_argument("--tree", default=None, help="(child) the checkout whose package is measured")
     ap.add_argument("--procs", type=int, default=3)
     ap.add_argument("--steps", type=int, default=200)
@@ -111,10 +114,10 @@ def main():
         return
     acc = {}
     for p in range(a.procs):
-        for name, tree, modes in (("parent_u8", os.path.abspath(a.parent), "u8"), ("this", HERE, a.modes)):
+        for prefix, tree, modes in (("parent_", os.path.abspath(a.parent), a.parent_modes), ("", HERE, a.modes)):
             res = child(tree, modes, a.steps, a.rounds)
             for mo, v in res.items():
-                key = "parent_u8" if name == "parent_u8" else mo
+                key = prefix + mo
                 e = acc.setdefault(key, {"ms_by_process": [], "nodes": v["nodes"], "source_bytes": v["source_bytes"]})
                 e["ms_by_process"].append(v["ms"])
                 print("process %d %s: %s ms/step, %d graph nodes" % (p, key, " ".join("%.4f" % x for x in v["ms"]), v["nodes"]), flush=True)
@@ -128,11 +131,12 @@ def main():
                      % (HW, HW, BS, a.procs, a.rounds, a.steps),
            "modes": acc}
     for mo in acc:
-        if mo != "parent_u8":
+        if not mo.startswith("parent_"):
             acc[mo]["minus_parent_u8_ms"] = acc[mo]["min_ms"] - base["min_ms"]
             acc[mo]["median_minus_parent_u8_ms"] = acc[mo]["median_ms"] - base["median_ms"]
-    if "u8" in acc:
-        out["u8_inside_parent_spread"] = abs(acc["u8"]["median_minus_parent_u8_ms"]) <= base["spread_ms"]
+            if "parent_" + mo in acc:
+                acc[mo]["median_minus_parent_ms"] = acc[mo]["median_ms"] - acc["parent_" + mo]["median_ms"]
+                out[mo + "_inside_parent_spread"] = abs(acc[mo]["median_minus_parent_ms"]) <= acc["parent_" + mo]["spread_ms"]
     print(json.dumps(out))
     if a.out:
         with open(a.out, "w") as f:

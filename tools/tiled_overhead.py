@@ -4,6 +4,7 @@ train.py / val.py hold them; device events around whole passes; the forms altern
 
     python tools/tiled_overhead.py [--images 32] [--source_size 192,576] [--tile 96] [--batch 16] [--overlap O] [--rounds 7]
                                    [--out profiles/tiled_overhead.json]
+    python tools/tiled_overhead.py --parent DIR [--procs 3] [the options above]      against a built checkout of the parent commit
 
 Reports, per image: ms of the full-resolution pass (predict(): host tables, copies, one replay per N tiles, one stitch), ms of
 the resized pass (device Resize + EvalStep), tiles per image. The full-resolution time is then split on the device: the same
@@ -11,7 +12,9 @@ number of replays of the captured crop/stage + forward graph, of a captured forw
 the stitch launch on the same tile store - crop/stage = graph - forward. `outside_forward_share` is (crop/stage + stitch) /
 (crop/stage + forward + stitch); `host_and_copies_share` is what predict() spends beyond those replays and the stitch. The
 stitch's bytes/s come from its algorithmic traffic: every tile-logit element that lies inside its source read once (4 bytes),
-every output element written once (4 + 1 bytes).
+every output element written once (4 + 1 bytes). --parent DIR alternates processes of this file on the two checkouts
+(tools/parent_compare.py) and judges the full-resolution ms per image and the per-round outside-forward share against the
+parent's own spread; the summary written is this commit's last process with the comparison under "against_parent".
 """
 import argparse
 import json
@@ -22,7 +25,9 @@ import sys
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import parent_compare  # noqa: E402
+
+sys.path.insert(0, parent_compare.tree())
 import nunet_amd  # noqa: E402
 from nunet_amd import _lib as L  # noqa: E402
 from nunet_amd import dataset as D  # noqa: E402
@@ -40,6 +45,15 @@ def timed(run):
     return e0.elapsed_time(e1), r
 
 
+def write(out, path):
+    print(json.dumps(out))
+    if path:
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=32)
@@ -51,7 +65,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--out", default=os.path.join("profiles", "tiled_overhead.json"))
+    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit: alternate processes of it and of this commit")
+    ap.add_argument("--procs", type=int, default=3)
+    ap.add_argument("--tree", default=None, help="(child) the checkout whose package is measured")
     a = ap.parse_args()
+    if a.parent:
+        argv = ["--images", str(a.images), "--source_size", a.source_size, "--tile", str(a.tile), "--batch", str(a.batch), "--dtype", a.dtype,
+                "--warmup", str(a.warmup), "--rounds", str(a.rounds), "--out", ""] + (["--overlap", str(a.overlap)] if a.overlap is not None else [])
+        runs = parent_compare.alternate(__file__, a.parent, argv, a.procs)
+        out = runs["this"][-1]
+        out["against_parent"] = cmp = {"processes_each": a.procs}
+        for k, pick in (("full_res_ms_per_image", lambda r: [v / a.images for v in r["ms"]["full_res"]]), ("outside_forward_share", lambda r: r["outside_forward_share_rounds"])):
+            cmp[k] = parent_compare.judge([pick(r) for r in runs["parent"]], [pick(r) for r in runs["this"]])
+            print("%s: %+.5f against a parent spread of %.5f" % (k, cmp[k]["median_minus_parent"], cmp[k]["parent_spread"]))
+        cmp["all_inside_parent_spread"] = all(cmp[k]["inside_parent_spread"] for k in ("full_res_ms_per_image", "outside_forward_share"))
+        write(out, a.out)
+        return
     from train import ragged_sets
     samples = ragged_sets({"dataset": "synthetic_blobs", "source_size": a.source_size, "train_size": 0, "val_size": a.images})[1]
     st = nunet_amd.synth.closed_form_state(1, 3, False, False)
@@ -123,17 +152,13 @@ def main():
            "full_res_ms_per_image": med["full_res"] / a.images, "resized_ms_per_image": med["resized"] / a.images,
            "forward_ms": med["forward_replays"], "crop_stage_ms": stage, "stitch_ms": med["stitch"],
            "outside_forward_share": (stage + med["stitch"]) / dev_total,
+           "outside_forward_share_rounds": [(g - f + s_) / (g + s_) for g, f, s_ in zip(ms["graph_replays"], ms["forward_replays"], ms["stitch"])],
            "host_and_copies_share": (med["full_res"] - dev_total) / med["full_res"],
            "crop_plus_stitch_exceeds_forward": bool(stage + med["stitch"] > med["forward_replays"]),
            "stitch_algorithmic_bytes": traffic, "stitch_bytes_per_s": traffic / (med["stitch"] * 1e-3)}
     for k in forms:
         print("%-16s %s ms; median %.3f, spread %.3f" % (k, " ".join("%.3f" % v for v in ms[k]), med[k], spread[k]))
-    print(json.dumps(out))
-    if a.out:
-        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(out, f, indent=1)
-            f.write("\n")
+    write(out, a.out)
 
 
 if __name__ == "__main__":
