@@ -263,7 +263,7 @@ __device__ __forceinline__ void bn_running_update(float* rm, float* rv, int c, f
   rv[c] = cc + d;
 }
 
-// byte = number of thresholds <= x (nunet_sigmoid_u8, elementwise.hip): branch-free 8-step binary search over 255 thresholds in LDS
+// byte = number of thresholds <= x (nunet_sigmoid_u8, loss.hip): branch-free 8-step binary search over 255 thresholds in LDS
 __device__ __forceinline__ uint32_t sigmoid_byte(const float* s_thr, float x) {
   int lo = 0;                                   // invariant: thr[lo-1] <= x (or lo == 0), answer in [lo, lo + span]
 #pragma unroll
@@ -379,6 +379,96 @@ __device__ __forceinline__ double block256_sum_f64(double v, double* s_w4) {
   if ((threadIdx.x & 63) == 0) s_w4[threadIdx.x >> 6] = v;
   __syncthreads();
   return ((s_w4[0] + s_w4[1]) + s_w4[2]) + s_w4[3];
+}
+// The slab epilogue of the per-block partial sums (loss.hip), in its two halves around the workgroup's one barrier.
+// slab_park: NV values of one type per thread, each reduced over its wave by the butterfly of its type (counts: uint32), the
+// four wave totals parked in LDS (s_w: [4][NV], the caller's). slab_store, after __syncthreads(): the thread with 0 <= q < NV
+// stores ((w0 + w1) + w2) + w3 to dst[q] with a plain store; D != T converts the total on the way out (counts kept as
+// float). A kernel that mixes types parks both arrays in one call, one with several slabs parks them all; it syncs once and gives each array its own threads
+// through q; block256_slab_store is the whole epilogue of a kernel with one array.
+__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+template <int NV, typename T>
+__device__ __forceinline__ void wave_totals(const T (&v)[NV], T (&w)[NV]) {
+#pragma unroll
+  for (int q = 0; q < NV; ++q) {
+    if constexpr (std::is_same<T, float>::value) w[q] = wave_sum(v[q]);
+    else if constexpr (std::is_same<T, double>::value) w[q] = wave_sum_f64(v[q]);
+    else w[q] = wave_sum_u32(v[q]);
+  }
+}
+// (all butterflies first, then one branch for the stores: the shuffle chains of all values overlap)
+template <int NV, typename T>
+__device__ __forceinline__ void slab_park(const T (&v)[NV], T (*s_w)[NV]) {
+  T w[NV];
+  wave_totals(v, w);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < NV; ++q) s_w[threadIdx.x >> 6][q] = w[q];
+  }
+}
+template <int NA, typename TA, int NB, typename TB>     // two arrays of different types
+__device__ __forceinline__ void slab_park(const TA (&a)[NA], TA (*s_a)[NA], const TB (&b)[NB], TB (*s_b)[NB]) {
+  TA wa[NA]; TB wb[NB];
+  wave_totals(a, wa); wave_totals(b, wb);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < NA; ++q) s_a[threadIdx.x >> 6][q] = wa[q];
+#pragma unroll
+    for (int q = 0; q < NB; ++q) s_b[threadIdx.x >> 6][q] = wb[q];
+  }
+}
+template <int NV, typename T, typename D>
+__device__ __forceinline__ void slab_store(T (*s_w)[NV], D* __restrict__ dst, int q) {
+  if ((unsigned)q < (unsigned)NV) dst[q] = (D)(((s_w[0][q] + s_w[1][q]) + s_w[2][q]) + s_w[3][q]);
+}
+template <int NV, typename T, typename D>
+__device__ __forceinline__ void block256_slab_store(const T (&v)[NV], T (*s_w)[NV], D* __restrict__ dst) {
+  slab_park(v, s_w);
+  __syncthreads();
+  slab_store(s_w, dst, (int)threadIdx.x);
+}
+
+// Foreground counts of the metrics (metrics.py:10-14,31-44): predicted iff x >= thr (NaN: not), labelled iff t > 0.5.
+__device__ __forceinline__ void fg_count2(float xv, float tv, float thr, unsigned& inter, unsigned& uni) {
+  const bool a = xv >= thr, b = tv > 0.5f;
+  inter += (a && b) ? 1u : 0u; uni += (a || b) ? 1u : 0u;
+}
+__device__ __forceinline__ void fg_count4(float xv, float tv, float thr, unsigned& tp, unsigned& fp, unsigned& fn, unsigned& tn) {
+  const bool a = xv >= thr, b = tv > 0.5f;
+  tp += (a && b) ? 1u : 0u; fp += (a && !b) ? 1u : 0u; fn += (!a && b) ? 1u : 0u; tn += (!a && !b) ? 1u : 0u;
+}
+
+// What one thread of every loss step's last launch writes (trains.py:120-128): the loss of each head (loss_of(k)), their mean -
+// added left to right from 0, divided once - and the epoch meters from the last head's IoU intersection and union.
+template <class F>
+__device__ __forceinline__ void write_losses_meters(float* loss_out, int heads, double* meters, double inter, double uni, F&& loss_of) {
+  float mean = 0.f;
+  for (int k = 0; k < heads; ++k) {
+    const float lk = loss_of(k);
+    loss_out[k] = lk;
+    mean += lk;
+  }
+  mean /= (float)heads;
+  loss_out[heads] = mean;
+  if (meters) {
+    meters[0] += (double)mean;
+    meters[1] += (inter + 1e-5) / (uni + 1e-5);
+    meters[2] = inter; meters[3] = uni;
+  }
+}
+
+// launch geometry of a grid-stride loop `for (i = block * per_block + lane item; i < items; i += grid.x * per_block)`
+// (include/nunet_diag.h): thread 0 of block 0 takes the most trips, the last thread of the last block the fewest
+static inline void fill_launch_info(nunet_loss_launch_info_t* out, int gx, int gy, int gz, int64_t items, int per_block = 256) {
+  const int64_t per_pass = (int64_t)gx * per_block;
+  out->grid_x = gx; out->grid_y = gy; out->grid_z = gz; out->block = 256;
+  out->items = items;
+  out->trips_max = ceil_div64(items, per_pass);
+  out->trips_min = items / per_pass;
 }
 
 // dispatch a templated launcher on dtype

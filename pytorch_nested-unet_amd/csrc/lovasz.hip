@@ -317,23 +317,14 @@ __global__ __launch_bounds__(256) void lovasz_step_scale_kernel(float* __restric
   const float sc = seed_scale ? seed_scale[0] : 1.f;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n_all; i += (int64_t)gridDim.x * blockDim.x) {
     dx[i] = dx[i] * inv_heads * sc;
-    if (i < n_img) { const bool a = x_last[i] >= thr, b = t[i] > 0.5f; ci += (a && b) ? 1u : 0u; cu += (a || b) ? 1u : 0u; }
+    if (i < n_img) fg_count2(x_last[i], t[i], thr, ci, cu);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { ci += __shfl_xor(ci, o); cu += __shfl_xor(cu, o); }
+  ci = wave_sum_u32(ci); cu = wave_sum_u32(cu);
   if ((threadIdx.x & 63) == 0 && (ci | cu)) { atomicAdd(&cnt[0], (unsigned long long)ci); atomicAdd(&cnt[1], (unsigned long long)cu); }
 }
 __global__ void lovasz_step_final_kernel(float* __restrict__ loss_out, int heads, const unsigned long long* __restrict__ cnt, double* __restrict__ meters) {
-  float mean = 0.f;
-  for (int k = 0; k < heads; ++k) mean += loss_out[k];
-  mean /= (float)heads;
-  loss_out[heads] = mean;
-  if (meters) {
-    const double inter = (double)cnt[0], uni = (double)cnt[1];
-    meters[0] += (double)mean;
-    meters[1] += (inter + 1e-5) / (uni + 1e-5);
-    meters[2] = inter; meters[3] = uni;
-  }
+  // (the forwards have written loss_out[k]; the write-out stores each value back unchanged)
+  write_losses_meters(loss_out, heads, meters, (double)cnt[0], (double)cnt[1], [&](int k) { return loss_out[k]; });
 }
 int lovasz_loss_step(const float* logits, const float* target, int32_t N, int64_t per, int32_t heads, float* ws, float* dlogits,
                      float* loss_out, double* meters, float iou_thr, const float* seed_scale, hipStream_t st) {

@@ -1,4 +1,4 @@
-"""The BCE-Dice loss (stand-alone and inside nunet_loss_step), the IoU counts and the mask export of csrc/elementwise.hip
+"""The BCE-Dice loss (stand-alone and inside nunet_loss_step), the IoU counts and the mask export of csrc/loss.hip
 against fp64 / the host expressions, in every launch regime of their grid-stride loops. The cases, the fp64 reference and the
 per-pixel gradient bound are those of tests/loss_cases.py (pinned on the CPU by tests/test_bce_dice_cpu.py); every case first
 asserts, from the library's own nunet_loss_launch_info, the regime it is named for - blocks per image, the most grid-stride
@@ -292,7 +292,7 @@ def test_fused_step_size_limit():
     (two distinct pixel values). 2^24 + 1 is refused with a message and writes nothing.
 
     Measured on an MI355X: loss 0.312586188 against 0.312588151, a difference of -1.96e-6 where 2e-6 is allowed. It is the
-    kernel's, not the test's: every thread of loss_step_partial_kernel adds 1024 pixels one after the other in fp32, and with
+    kernel's, not the test's: every thread of bce_dice_partial_kernel<true> adds 1024 pixels one after the other in fp32, and with
     all of them equal (0.7310586) the roundings do not average out: sum p comes out 5.2e-6 too large and the BCE sum 3.4e-6, as an
     fp32 evaluation of the same summation order on the CPU reproduces to three digits. The workload's largest images
     (512 x 512) take 16 trips per thread."""

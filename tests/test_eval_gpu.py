@@ -137,6 +137,34 @@ def test_seg_metrics(case, thr, golden):
     assert torch.equal(again, sums)
 
 
+@pytest.mark.parametrize("case", [(2, 1, 1, "rand"), (33, 8, 300, "rand")], ids=EC.case_id)
+def test_seg_metrics_writes_one_slab(case, thr):
+    """nunet_seg_metrics launches the one-slab form of the kernel that nunet_eval_step_heads runs with up to four slabs: on a
+    workspace of exactly nunet_seg_metrics_ws_bytes between two NaN bands of a slab's size and more (what a second slab would
+    overwrite), the bands keep every bit and the sums equal the restatement."""
+    lib = L.lib()
+    n, k, hw, pattern = case
+    need = lib.nunet_seg_metrics_ws_bytes(n, k, hw)
+    assert need > 0 and need % 8 == 0
+    band = need // 8 + 512
+    buf = torch.full((2 * band + need // 8,), float("nan"), dtype=torch.float64, device=DEV)
+    before = buf.view(torch.int64).clone()
+    x, t = EC.build(case)
+    xd, td = x.to(DEV), t.to(DEV)
+    sums = torch.full((C.sizeof(L.SegSums),), 0xEE, dtype=torch.uint8, device=DEV)
+    L.check(lib.nunet_seg_metrics(L.ptr(xd), L.ptr(td), n, k, hw, thr, L.ptr(buf, 8 * band), need, L.ptr(sums), 0, L.stream()), "nunet_seg_metrics")
+    torch.cuda.synchronize()
+    after = buf.view(torch.int64)
+    assert torch.equal(after[:band], before[:band]), "write before the workspace"
+    assert torch.equal(after[band + need // 8:], before[band + need // 8:]), "write past the workspace"
+    got, ref = L.read_struct(sums, L.SegSums), EC.reference(case, thr)
+    for nm in COUNTS:
+        assert list(getattr(got, nm))[:k] == ref[nm], nm
+    for nm in COUNTS + SOFTS:
+        assert all(v == 0 for v in list(getattr(got, nm))[k:]), (nm, "classes >= K")
+    _check_soft(EC.case_id(case), got, ref, pattern)
+
+
 def _heads_of(case, heads):
     """logits [heads, N, K, hw]: the last head is the case's own tensor, the others are deterministic variations of it"""
     x, t = EC.build(case)
@@ -163,7 +191,7 @@ def _standalone_loss(xd, td, n, k, hw, kind):
 SEQUENCES = {"k1": [(3, 1, 257, "rand"), (2, 1, 16385, "rand"), (3, 1, 16385, "edges")], "k4": [(3, 4, 300, "rand"), (3, 4, 300, "rand"), (3, 4, 300, "rand")]}
 
 
-@pytest.mark.parametrize("heads", [1, 4])
+@pytest.mark.parametrize("heads", [1, 4, 8])    # (8: above nunet_eval_step_heads' limit, the last-head form alone reaches it)
 @pytest.mark.parametrize("loss,seq", [("BCEDiceLoss", "k1"), ("BCEDiceLoss", "k4"), ("BCEWithLogitsLoss", "k1"), ("BCEWithLogitsLoss", "k4"),
                                       ("LovaszHingeLoss", "k1")])
 def test_eval_step(heads, loss, seq, thr, golden):
