@@ -612,6 +612,25 @@ enum { NUNET_WINDOW_TENT = 0, NUNET_WINDOW_UNIFORM = 1 };
 int nunet_stitch_tiles(const float* tile_logits, int32_t n_tiles, int32_t K, int32_t Th, int32_t Tw, const nunet_u8_sample* samples,
                        const nunet_tile_grid* grids, int32_t n_samples, int32_t window, const float* thresholds, float* out_logits,
                        uint8_t* out_u8, int64_t out_elems, nunet_stream_t s);
+/* Test-time augmentation (EvalStep(tta=...)): `code` has exactly the meaning of aug[n] above - rot90 count in bits 0-1
+ * (np.rot90 sense), hflip in bit 2, vflip in bit 3, values 0 .. 15; an odd rotation count needs H == W - and both entries map
+ * pixels through the pipeline's one index function (aug_source_pixel), so the merge undoes exactly what the view did. Both
+ * move 32 x 32 tiles of a plane through LDS: global reads and writes run along rows for every code. Every argument is checked
+ * before the launch (NUNET_EINVAL): null pointers, non-positive extents, a code outside 0 .. 15, an odd rotation with H != W,
+ * the two buffers being one, and for the merge view_index outside 0 .. views-1, views < 1, an unknown mode. */
+/* dst[n][c] = the view of src[n][c] under `code` (dst[y][x] = src[ry][rx], aug_source_pixel). fp32 planes, a bit copy. */
+int nunet_dihedral_nchw(const float* src, int32_t N, int32_t C, int32_t H, int32_t W, int32_t code, float* dst, nunet_stream_t s);
+/* One view of a TTA merge. view: logits [N][K][Hv][Wv] computed on the view `code` of an [H][W] batch.
+ * acc: [N][K][H][W] in the SOURCE frame. Pixel (y,x) of the view goes to (ry,rx) = aug_source_pixel(code,H,W,y,x).
+ *   view_index == 0: acc = f(v)   (no pre-zeroing by the caller)      otherwise: acc = acc + f(v)   (fp32, one rounding)
+ *   view_index == views-1, after the add: acc = finish(acc)
+ * NUNET_TTA_LOGIT: f(v) = v;           finish(a) = a / (float)views               (IEEE division, no contraction)
+ * NUNET_TTA_PROB:  f(v) = sigmoid(v) with the fp32 sigmoid of the loss kernels;
+ *                  finish(a): p = clamp(a / (float)views, 2^-23, 1 - 2^-23); logf(p) - log1pf(-p)
+ * Views are merged by successive calls on one stream, in index order: no atomics, bit-identical from run to run. */
+enum { NUNET_TTA_LOGIT = 0, NUNET_TTA_PROB = 1 };
+int nunet_tta_merge(const float* view, int32_t N, int32_t K, int32_t H, int32_t W, int32_t code, int32_t mode,
+                    int32_t view_index, int32_t views, float* acc, nunet_stream_t s);
 /* NCHW fp32 -> NHWC dtype with channel padding (zeros) up to cpad */
 int nunet_nchw_to_nhwc(const float* x, int32_t N, int32_t C, int32_t H, int32_t W,
                        int32_t dtype, void* y, int32_t cpad, nunet_stream_t s);

@@ -194,6 +194,7 @@ RESIZE_MAX_EXTENT = 16384                   # NUNET_RESIZE_MAX_EXTENT
 TILE_WORDS = 4      # nunet_tile: 16 bytes of device memory per tile, [sample i32, y0 i32, x0 i32, reserved] - an int32 [n,4] tensor
 GRID_WORDS = 8      # nunet_tile_grid: 32 bytes per sample, [out_offset i64 (2 words), first_tile, ny, nx, stride_y, stride_x, reserved]
 WINDOW_TENT, WINDOW_UNIFORM = 0, 1          # NUNET_WINDOW_* in include/nunet.h
+TTA_LOGIT, TTA_PROB = 0, 1                  # NUNET_TTA_* in include/nunet.h
 
 
 class PlanCfg(C.Structure):
@@ -273,6 +274,8 @@ _SIG = {
     "nunet_preprocess_u8_resize": (_i32, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
     "nunet_crop_tiles_u8": (_i32, [_vp, _i64, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "nunet_stitch_tiles": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "nunet_dihedral_nchw": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "nunet_tta_merge": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "nunet_nchw_to_nhwc": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "nunet_plan_create": (_vp, [C.POINTER(PlanCfg)]),
     "nunet_plan_create_pruned": (_vp, [C.POINTER(PlanCfg), _i32]),

@@ -936,9 +936,36 @@ class TrainStep:
 LOSS_KINDS = {"BCEDiceLoss": L.LOSS_BCE_DICE, "LovaszHingeLoss": L.LOSS_LOVASZ_HINGE, "BCEWithLogitsLoss": L.LOSS_BCE_LOGITS}
 
 
+TTA_SETS = {"flips": (0, 4, 8, 12), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}      # geometric codes as the input pipeline's aug
+TTA_MERGES = {"logit": L.TTA_LOGIT, "prob": L.TTA_PROB}
+
+
+def tta_codes(tta, h, w):
+    """EvalStep's tta argument -> None (off) or the tuple of geometric codes, one per view, in merge order. Host only."""
+    if tta is None:
+        return None
+    if isinstance(tta, str):
+        if tta not in TTA_SETS:
+            raise L.NunetError("EvalStep: tta %r is not one of %s, None or a tuple of codes 0 .. 15" % (tta, sorted(TTA_SETS)))
+        codes = TTA_SETS[tta]
+    elif isinstance(tta, (tuple, list)):
+        codes = tuple(tta)
+    else:
+        raise L.NunetError("EvalStep: tta %r is not one of %s, None or a tuple of codes 0 .. 15" % (tta, sorted(TTA_SETS)))
+    if not codes:
+        raise L.NunetError("EvalStep: tta is an empty tuple: at least one view (None switches test-time augmentation off)")
+    for c in codes:
+        if isinstance(c, bool) or not isinstance(c, int) or not 0 <= c <= 15:
+            raise L.NunetError("EvalStep: tta code %r is outside 0 .. 15 (rot90 count | hflip << 2 | vflip << 3)" % (c,))
+        if c & 1 and h != w:
+            raise L.NunetError("EvalStep: tta code %d has an odd rot90 count, which needs H == W (got %d x %d)" % (c, h, w))
+    return codes
+
+
 class _EvalBatch:
     """The buffers of one validation batch size: a Plan of its own (not Engine.plans: the training step's recorded program and
-    lane state live on the cached plan of the same key), static input / target / logits, the loss workspace and outputs."""
+    lane state live on the cached plan of the same key), static input / target / logits, the loss workspace and outputs; under
+    test-time augmentation also the view of the input and the logits of one view."""
 
     def __init__(self, ev, n):
         from .engine import Plan
@@ -956,16 +983,34 @@ class _EvalBatch:
         nb = ws_query(n, ev.ncls, ev.h * ev.w, self.heads, ev.loss_kind)
         self.ws = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)        # (the caching allocator hands out 512-byte aligned blocks)
         self.loss_out = torch.zeros(self.heads + 1, dtype=torch.float32, device=dev)    # per head, then their mean
+        if ev.tta is not None:      # (an odd rot90 count has H == W: the view's extents are the source's, one plan serves every view)
+            self.x_view = torch.zeros_like(self.x)
+            self.view_logits = torch.zeros_like(self.logits)
         self.graph = None
 
     def repack(self, ev):
         L.check(L.lib().nunet_plan_repack(self.pl.handle, L.ptr(ev.flat_params), L.ptr(self.pl.arena), L.nbytes(self.pl.arena), L.stream()), "plan_repack")
 
     def issue(self, ev):
-        """forward in eval mode on the packed weights of this plan's arena (training = 2), then the validation step"""
+        """forward in eval mode on the packed weights of this plan's arena (training = 2), then the validation step. Under
+        test-time augmentation, per view in order: the view of the input (code 0: the input itself), its forward, and the merge
+        of all heads' logits ([heads][n][K][hw] is contiguous: heads * n samples) into self.logits in the source frame."""
         lib, eng, pl, st = L.lib(), ev.eng, self.pl, L.stream()
-        L.check(lib.nunet_plan_forward(pl.handle, L.ptr(ev.flat_params), L.ptr(ev.bnbuf), L.ptr(eng.nbt), L.ptr(self.x), L.ptr(pl.arena),
-                                       L.nbytes(pl.arena), L.ptr(self.logits), 2, st), "plan_forward")
+
+        def forward(x, logits):
+            L.check(lib.nunet_plan_forward(pl.handle, L.ptr(ev.flat_params), L.ptr(ev.bnbuf), L.ptr(eng.nbt), L.ptr(x), L.ptr(pl.arena),
+                                           L.nbytes(pl.arena), L.ptr(logits), 2, st), "plan_forward")
+
+        if ev.tta is None:
+            forward(self.x, self.logits)
+        for i, code in enumerate(ev.tta or ()):
+            x = self.x
+            if code:
+                L.check(lib.nunet_dihedral_nchw(L.ptr(self.x), self.n, ev.cin, ev.h, ev.w, code, L.ptr(self.x_view), st), "dihedral_nchw")
+                x = self.x_view
+            forward(x, self.view_logits)
+            L.check(lib.nunet_tta_merge(L.ptr(self.view_logits), self.heads * self.n, ev.ncls, ev.h, ev.w, code, ev.tta_mode, i, len(ev.tta),
+                                        L.ptr(self.logits), st), "tta_merge")
         if ev.per_head:
             L.check(lib.nunet_eval_step_heads(L.ptr(self.logits), L.ptr(self.t), self.n, ev.ncls, ev.h * ev.w, self.heads, ev.loss_kind,
                                               L.ptr(self.ws), L.nbytes(self.ws), L.ptr(self.loss_out), L.ptr(ev.meters), L.ptr(ev.head_meters),
@@ -997,9 +1042,23 @@ class EvalStep:
     weights=(flat_params, bnbuf): the step reads these arenas - flat fp32 device tensors in the order and size of
     Engine.flat_params / Engine.bnbuf, e.g. (ts.ema_params, ts.ema_bnbuf) of a TrainStep with a weight EMA - instead of the
     module's own: repack and forward take the parameter and BatchNorm arenas as arguments, so another set of weights needs no
-    second module. num_batches_tracked stays the engine's (eval never reads it). depth= and per_head= work as without."""
+    second module. num_batches_tracked stays the engine's (eval never reads it). depth= and per_head= work as without.
 
-    def __init__(self, model, batch_shape, loss="BCEDiceLoss", use_graph=True, depth=None, per_head=False, weights=None):
+    tta="flips" (codes 0, 4, 8, 12; any H, W), "d4" (codes 0 .. 7, the eight distinct maps; H == W) or a tuple of geometric
+    codes 0 .. 15 (the input pipeline's aug: rot90 count | hflip << 2 | vflip << 3): test-time augmentation. Per view, in order,
+    the step forms the view of the input (nunet_dihedral_nchw), runs the forward on it and merges the logits of every head back
+    into the source frame (nunet_tta_merge) - all inside the one captured graph. tta_merge="logit": the fp32 sum in view order
+    divided once by the number of views; "prob": the mean of the sigmoids, clamped to [2^-23, 1 - 2^-23] and taken back to a
+    logit. The merged prediction stays in logit space, so logits, last_logits, last_loss, result(), depth=, per_head=, weights=
+    and the tail batch mean what they mean without it. None (default): no new launch."""
+
+    def __init__(self, model, batch_shape, loss="BCEDiceLoss", use_graph=True, depth=None, per_head=False, weights=None, tta=None,
+                 tta_merge="logit"):
+        # (host-only checks first: a refused tta never touches the device)
+        if tta_merge not in TTA_MERGES:
+            raise L.NunetError("EvalStep: tta_merge %r is not one of %s" % (tta_merge, sorted(TTA_MERGES)))
+        self.tta = tta_codes(tta, batch_shape[2], batch_shape[3])
+        self.tta_merge, self.tta_mode = tta_merge, TTA_MERGES[tta_merge]
         if depth is not None:
             model.check_depth(depth, need_eval=False)     # (the step always runs the eval forward, whatever mode the module is in)
         if per_head:

@@ -10,7 +10,8 @@ models/<name>/log.csv with columns epoch, lr, loss, iou, val_loss, val_iou (:304
 models/<name>/model.pth = state_dict at the best val IoU (:344-349), early stopping (:351-354).
 The `lr` column logs the scheduler's current lr (the reference logs the constant initial lr, :332).
 Beside the fused step, validation (trains.py:150-188) runs as the captured EvalStep (--eval_step false: the module loop; the
-same val_loss and val_iou to the bit); --val_metrics true appends val_dice, val_acc to the epoch line and to log.csv.
+same val_loss and val_iou to the bit); --val_metrics true appends val_dice, val_acc to the epoch line and to log.csv;
+--val_tta flips|d4 validates under test-time augmentation (EvalStep(tta=...)).
 
 Data parallel (new capability; the reference is single-device, trains.py:223): launch one process per GPU,
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port 29500 \
@@ -96,6 +97,9 @@ def parse_args():
                         'meters on the device, one read per pass; same val_loss and val_iou to the bit); False: the module loop')
     p.add_argument('--val_metrics', default=False, type=str2bool,
                    help='also log val_dice (reference metrics.py dice_coef) and val_acc (pixel accuracy) per epoch, after images_per_sec')
+    p.add_argument('--val_tta', default='none', choices=('none', 'flips', 'd4'),
+                   help='validate under test-time augmentation inside the EvalStep: the 4 flips, or the 8 rotations and flips of a square '
+                        'input, merged in logit space on the device (needs --eval_step true)')
     p.add_argument('--augment', default=False, type=str2bool, help='RandomRotate90 + Flip per sample (trains.py:258-259), device pipeline only')
     p.add_argument('--color_augment', default=False, type=str2bool,
                    help='OneOf([HueSaturationValue, RandomBrightness, RandomContrast], p=1) per sample (trains.py:260-264; modelled on '
@@ -229,6 +233,11 @@ def main():
     fused = not (config['loss'] == 'LovaszHingeLoss' and config['num_classes'] != 1)   # TrainStep: SGD or Adam, any loss
     if world > 1 and not fused:
         raise SystemExit('data parallel runs the fused step: multi-class LovaszHingeLoss is not fused')
+    val_tta = None if config['val_tta'] == 'none' else config['val_tta']
+    if val_tta is not None and not (fused and config['eval_step']):
+        raise SystemExit('--val_tta %s merges the views inside the captured EvalStep: it needs the fused step and --eval_step true' % val_tta)
+    if val_tta == 'd4' and h != w:
+        raise SystemExit('--val_tta d4 rotates by 90 degrees: input_h %d must equal input_w %d (use --val_tta flips)' % (h, w))
     # ragged sources (a folder dataset, or --source_size): decoded samples at their own sizes, resized on the device
     ragged = config['dataset'] != 'synthetic_blobs' or config['source_size'] is not None
     if ragged:
@@ -294,11 +303,11 @@ def main():
         clip_params = [p for p in model.parameters() if p.requires_grad]
 
     # validation: the captured EvalStep beside the fused step (its own plan and arena; built behind ts.capture)
-    ev = EvalStep(model, (bs, config['input_channels'], h, w), loss=config['loss']) if fused and config['eval_step'] else None
+    ev = EvalStep(model, (bs, config['input_channels'], h, w), loss=config['loss'], tta=val_tta) if fused and config['eval_step'] else None
     if ev is not None and rank == 0:
-        print('=> captured validation step (EvalStep)')
+        print('=> captured validation step (EvalStep)' + (', test-time augmentation %s (%d views)' % (val_tta, len(ev.tta)) if val_tta else ''))
     # the averaged weights through a second EvalStep that reads the TrainStep's averaged arenas (no second module)
-    ev_ema = (EvalStep(model, (bs, config['input_channels'], h, w), loss=config['loss'], weights=(ts.ema_params, ts.ema_bnbuf))
+    ev_ema = (EvalStep(model, (bs, config['input_channels'], h, w), loss=config['loss'], weights=(ts.ema_params, ts.ema_bnbuf), tta=val_tta)
               if ema is not None else None)
     log_keys = (('epoch', 'lr', 'loss', 'iou', 'val_loss', 'val_iou', 'images_per_sec') + (('val_dice', 'val_acc') if config['val_metrics'] else ())
                 + (('ema_val_loss', 'ema_val_iou') if ema is not None else ()))

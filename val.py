@@ -12,7 +12,12 @@ of the whole network, so one validation pass shows which depth would do.
 
 --full_res true (a folder dataset or a --source_size run) leaves the reference's Resize out: every validation image is predicted
 at its own size from overlapping input_h x input_w tiles (nunet_amd.tiled.TiledPredictor, --tile_overlap O), the masks have the
-sources' sizes and IoU / Dice / Acc are means over images at that resolution. Composes with --depth and --ema."""
+sources' sizes and IoU / Dice / Acc are means over images at that resolution. Composes with --depth and --ema.
+
+--tta flips|d4 evaluates under test-time augmentation (EvalStep(tta=...)): the four flips, or the eight rotations and flips of a
+square input, merged on the device in logit space (--tta_merge logit) or as probabilities (--tta_merge prob); the metrics, the
+per-head table and the exported masks come from the merged logits. Composes with --depth, --per_head and --ema, not with
+--full_res."""
 import argparse
 import os
 import sys
@@ -98,7 +103,14 @@ def main():
                          '--source_size run): masks and metrics at the sources\' resolution')
     ap.add_argument('--tile_overlap', default=None, type=int,
                     help='overlap of neighbouring tiles under --full_res, 0 .. min(input_h, input_w) / 2 (default: a quarter of the smaller side)')
+    ap.add_argument('--tta', default='none', choices=('none', 'flips', 'd4'),
+                    help='test-time augmentation: merge the predictions of the 4 flips / the 8 rotations and flips (d4: input_h == input_w)')
+    ap.add_argument('--tta_merge', default='logit', choices=('logit', 'prob'),
+                    help='merge the views as the mean logit, or as the mean probability taken back to a logit')
     args = ap.parse_args()
+    if args.full_res and args.tta != 'none':
+        print('error: --full_res true does not combine with --tta %s: test-time augmentation of tiled inference is not implemented' % args.tta)
+        sys.exit(2)
     with open('models/%s/config.yml' % args.name) as f:
         config = yaml.load(f, Loader=yaml.FullLoader)
     print('-' * 20)
@@ -150,9 +162,13 @@ def main():
         loss = 'BCEDiceLoss'                                             # (the metrics do not depend on it)
     # the validation step of train.py: forward, IoU / Dice / accuracy of the last head (val.py:92-93) and the meters on the device
     shape = (min(bs, x.size(0)), config['input_channels'], config['input_h'], config['input_w'])
-    ev = EvalStep(model, shape, loss=loss, depth=args.depth)
+    tta = None if args.tta == 'none' else args.tta
+    if tta == 'd4' and config['input_h'] != config['input_w']:
+        print('error: --tta d4 rotates by 90 degrees: input_h %d must equal input_w %d (use --tta flips)' % (config['input_h'], config['input_w']))
+        sys.exit(2)
+    ev = EvalStep(model, shape, loss=loss, depth=args.depth, tta=tta, tta_merge=args.tta_merge)
     # (the per-head table comes from the whole network: a pass of its own beside the pruned one)
-    ev_heads = EvalStep(model, shape, loss=loss, per_head=True) if args.per_head else None
+    ev_heads = EvalStep(model, shape, loss=loss, per_head=True, tta=tta, tta_merge=args.tta_merge) if args.per_head else None
     bs = ev.n
     with torch.no_grad():
         ev.begin()
@@ -171,6 +187,8 @@ def main():
         print('depth: %d' % args.depth)
     if args.ema:
         print('weights: EMA (model_ema.pth)')
+    if tta is not None:
+        print('tta: %s (%d views, merged as %s)' % (tta, len(ev.tta), args.tta_merge))
     print('IoU: %.4f' % r['iou'])
     print('Dice: %.4f' % r['dice'])
     print('Acc: %.4f' % r['acc'])
