@@ -172,6 +172,12 @@ int nunet_plan_set_wait_prune(nunet_plan* p, int32_t enable);
  * are in-order) asks to wait for the ops edge_src[edge_off[b] .. edge_off[b + 1]), each issued before b. keep[e] = 1: the wait is
  * made; 0: it is implied by lane order and the waits kept so far (a producer on b's own lane always is). At most 16 lanes. */
 int nunet_wait_prune_host(int32_t nlanes, int32_t nops, const int32_t* op_lane, const int32_t* edge_off, const int32_t* edge_src, uint8_t* keep);
+/* The list scheduler's placement over plain arrays (a pure host function: no plan, no HIP call). nops ops in program order, op b
+ * of estimated cost cost[b] (us) reads the resource ids rd[rd_off[b] .. rd_off[b + 1]) and writes wr[wr_off[b] .. wr_off[b + 1]);
+ * ids are 0..511, at most 12 reads and 8 writes per op. The hazards of that order (read after write, write after write, write
+ * after read) form a DAG; order[q] = the op issued q-th (a topological order of the DAG), lane[b] = the lane (0..2) of op b. */
+int nunet_list_schedule_host(int32_t nops, const float* cost, const int32_t* rd_off, const int32_t* rd, const int32_t* wr_off, const int32_t* wr,
+                             int32_t* order, int32_t* lane);
 /* The work item that workgroup b of G takes first (common.h, xcd_remap: one contiguous item range per XCD), evaluated on the host. */
 int32_t nunet_xcd_remap_host(int32_t b, int32_t G);
 

@@ -231,6 +231,7 @@ _SIG = {
     "nunet_plan_set_bn_up": (_i32, [_vp, _i32]),
     "nunet_plan_set_wait_prune": (_i32, [_vp, _i32]),
     "nunet_wait_prune_host": (_i32, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_uint8)]),
+    "nunet_list_schedule_host": (_i32, [_i32, C.POINTER(C.c_float)] + [C.POINTER(_i32)] * 6),
     "nunet_head_bwd": (_i32, [_i32] * 6 + [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp]),
     "nunet_head_bwd_bnr": (_i32, [_i32] * 6 + [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, C.POINTER(BnrDesc), _vp]),
     "nunet_bce_dice_ws_bytes": (C.c_size_t, [_i32]),

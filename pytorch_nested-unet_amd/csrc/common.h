@@ -82,7 +82,7 @@ int nunet_zero_async(void* p, size_t bytes, hipStream_t st);
 // node after node with a synchronisation of its own (2.6-5 us per node, tools/graph_gap_probe.py), while a single-stream
 // graph replays as one batch of pre-built packets (0.7 us per node). So the plan's lanes are NOT captured as branches of one
 // graph: every lane keeps a real stream, its ops are captured into ONE single-stream graph, and the cross-lane
-// dependencies become device-side flags inside those graphs. The lane scheduler (plan.hip, Sched) routes its
+// dependencies become device-side flags inside those graphs. The lane scheduler (sched.hip, Sched) routes its
 // stream waits, event records and "about to launch on this stream" through these hooks; they return false when no
 // recording is active (the caller then does the real HIP call).
 // ---------------------------------------------------------------------------
@@ -479,7 +479,7 @@ static inline void fill_launch_info(nunet_loss_launch_info_t* out, int gx, int g
                         : (nunet_set_error("bad dtype %d", (int)(dt)), NUNET_EINVAL))
 
 // ---------------------------------------------------------------------------
-// Optimiser functors of the fused update kernels (plan.hip) and the flat Adam step (elementwise.hip): the per-element step
+// Optimiser functors of the fused update kernels (weights.hip) and the flat Adam step (elementwise.hip): the per-element step
 // with its state pointers (NS fp32 buffers in flat parameter order). begin(gscale) reads the device scalars once per thread;
 // one(p, g, s) takes the (scaled, undecayed) gradient and the element's state, updates the state in place and returns the
 // new parameter. Built on the host from a nunet_optim by opt_sgd() / opt_adam() below, which every entry reaches through
@@ -548,7 +548,7 @@ struct OptAdam {  // torch.optim.Adam, amsgrad=False, maximize=False, L2 decay i
 // state stream. one() runs the wrapped step, then moves the last stream towards the parameter it returns - copied on the
 // first update, lerped with this step's w otherwise; both words were written by ema_prepare_kernel in an earlier launch, so
 // the choice is uniform over the launch. A skipped step is the wrapped functor's: begin() returns false and nothing is stored.
-// The plan's tile kernel (plan.hip) runs it as it is; the flat step (elementwise.hip launch_flat) unwraps it.
+// The plan's tile kernel (weights.hip) runs it as it is; the flat step (elementwise.hip launch_flat) unwraps it.
 template <typename O> struct OptEma {
   static constexpr int NS = O::NS + 1;
   float* st[O::NS + 1];     // the wrapped functor's streams, then ema_params

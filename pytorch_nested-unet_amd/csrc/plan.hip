@@ -6,390 +6,35 @@
 //   * packed KRSC weights (forward + flipped/transposed dgrad copies);
 //   * native-layout fp32 gradient scratch that a single kernel unpacks into the
 //     caller's flat OIHW gradient arena (reference parameters() order).
-#include <stdlib.h>
-#include <string.h>
-
-#include <initializer_list>
-#include <functional>
-#include <algorithm>
-
-#include <map>
-#include <string>
-#include <vector>
-#include <stdarg.h>
-
+// The plan's types are plan.h's; the weight-layout kernels live in weights.hip, the lane scheduler in sched.h / sched.hip.
 #include "pipeline.h"
-
-static const int NBF[5] = {32, 64, 128, 256, 512};  // archs1.py:78
-
-// ---------------------------------------------------------------------------
-// batched weight pack / gradient unpack
-// ---------------------------------------------------------------------------
-#define MAXENT 40
-#define HEAD_SLABS 256
-struct PackEnt { long long src, wf, wd; int cout, cin, cinpad; };
-struct PackTab { int n; int ntiles; PackEnt e[MAXENT]; int tile0[MAXENT + 1]; };
-struct UnpackEnt { long long src, dst; int cout, cin, cinpad, taps, nvec, nslab; };   // nslab > 1: sum of partial slabs (heads)
-struct UnpackTab { int n; int accumulate; UnpackEnt e[MAXENT]; };
-
-// ---------------------------------------------------------------------------------------------------------
-// The walk every weight-layout kernel below shares. One block per (layer, 32 Cout x 32 Cin tile); PackTab carries a
-// prefix sum of tiles per entry for the block -> tile map. A tile lives in LDS as s[co_local][ci_local * 9 + tap]:
-// its OIHW rows (parameters, flat gradients) are contiguous runs of 32 * 9 floats, the native gradient scratch
-// [tap][co][cinpad] and both packed layouts are contiguous along ci (wf) or co (wd). The unpack kernels' blocks past
-// the last tile own one UnpackTab entry each (tail_entry).
-// ---------------------------------------------------------------------------------------------------------
-constexpr int TILE_LD = 32 * 9 + 1;
-struct Tile { int e, co0, ci0, cw, rw; };   // table entry, tile origin; cw / rw: real input channels / output rows in the tile (cw <= 0: pure padding)
-
-__device__ __forceinline__ Tile tile_of(const PackTab& tab, int bid) {
-  Tile t;
-  t.e = 0;
-  while (t.e + 1 < tab.n && bid >= tab.tile0[t.e + 1]) ++t.e;
-  const int i = bid - tab.tile0[t.e];
-  const int cout = tab.e[t.e].cout, cin = tab.e[t.e].cin, nci = (tab.e[t.e].cinpad + 31) / 32;
-  t.co0 = (i / nci) * 32; t.ci0 = (i % nci) * 32;
-  t.cw = min(32, cin - t.ci0); t.rw = min(32, cout - t.co0);
-  return t;
-}
-
-// 1x1 head: [nslab][tot] partial slabs (already OIHW order, tot <= 8 classes * 33 = 264), summed by one block of B = 256 threads in a
-// fixed order: B / ne threads share an element's slabs (a single thread walking all 256 slabs is a chain of 256
-// dependent-latency loads: that loop alone made the earlier fused kernels 100 us long), thread (part, e) adds slabs part,
-// part + parts, ... in order, the parts meet in LDS (B floats) and are added in order q = 0 .. parts - 1. The owning thread
-// calls f(element, sum). The order depends on B, so every caller is a 256-thread block.
-template <typename F>
-__device__ __forceinline__ void head_slab_sum(const float* __restrict__ dw, int tot, int nslab, float* lds, F f) {
-  constexpr int B = 256;
-  for (int e0 = 0; e0 < tot; e0 += B) {
-    const int ne = min(B, tot - e0);
-    const int parts = B / ne;                     // threads per element
-    const int e = threadIdx.x % ne, part = threadIdx.x / ne;
-    float v = 0.f;
-    if (part < parts) {
-#pragma unroll 8
-      for (int sl = part; sl < nslab; sl += parts) v += dw[(long long)sl * tot + e0 + e];
-    }
-    lds[threadIdx.x] = part < parts ? v : 0.f;
-    __syncthreads();
-    if ((int)threadIdx.x < ne) {
-      float t = 0.f;
-      for (int q = 0; q < parts; ++q) t += lds[q * ne + threadIdx.x];
-      f(e0 + (int)threadIdx.x, t);
-    }
-    __syncthreads();
-  }
-}
-
-// A 256-thread block past the last tile: the slab sum of a 1x1 head, or a conv layer's bias / BatchNorm vectors (they follow the
-// weights in the scratch entry and in the flat arenas). f(index relative to the entry's dst, value).
-template <typename F>
-__device__ __forceinline__ void tail_entry(const UnpackEnt& en, const float* __restrict__ scratch, float* lds, F f) {
-  const float* dw = scratch + en.src;
-  const int nw = en.cout * en.cin * en.taps;
-  if (en.nslab > 1) {
-    head_slab_sum(dw, nw + en.nvec * en.cout, en.nslab, lds, f);
-    return;
-  }
-  const float* vsrc = dw + (long long)en.taps * en.cout * en.cinpad;
-  for (int i = threadIdx.x; i < en.nvec * en.cout; i += blockDim.x) f(nw + i, vsrc[i]);
-}
-
-// scratch dw[tap][co][cinpad] -> LDS tile: 16-byte loads along ci for a full tile (an element-wise gather touches nine
-// 128-byte lines per wave load); a ragged tile element-wise, entries outside rw x cw left unwritten
-__device__ __forceinline__ void gather_scratch_tile(float (*s)[TILE_LD], const float* __restrict__ dw, const PackEnt& en, const Tile& t) {
-  if (t.rw == 32 && t.cw == 32 && en.cinpad % 4 == 0 && ((uintptr_t)dw & 15) == 0) {
-    for (int i = threadIdx.x; i < 9 * 32 * 8; i += blockDim.x) {
-      const int c4 = i & 7, ro = (i >> 3) & 31, tap = i >> 8;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(dw + ((long long)tap * en.cout + t.co0 + ro) * en.cinpad + t.ci0 + c4 * 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s[ro][(c4 * 4 + j) * 9 + tap] = v[j];
-    }
-  } else {
-    for (int i = threadIdx.x; i < 9 * 32 * 32; i += blockDim.x) {
-      const int ci = i & 31, ro = (i >> 5) & 31, tap = i >> 10;
-      if (ro < t.rw && ci < t.cw) s[ro][ci * 9 + tap] = dw[((long long)tap * en.cout + t.co0 + ro) * en.cinpad + t.ci0 + ci];
-    }
-  }
-}
-
-// OIHW rows w[co][cin][9] -> LDS tile: 16-byte loads for a full tile; a ragged one (the first layer's) element-wise, zero
-// outside rw x cw (the ci >= cin columns are written to wf as zeros)
-__device__ __forceinline__ void load_oihw_tile(float (*s)[TILE_LD], const float* __restrict__ w, const PackEnt& en, const Tile& t) {
-  const float* wrow = w + ((long long)t.co0 * en.cin + t.ci0) * 9;
-  if (t.rw == 32 && t.cw == 32 && en.cin % 4 == 0 && ((uintptr_t)wrow & 15) == 0) {
-    for (int i = threadIdx.x; i < 32 * 72; i += blockDim.x) {
-      const int ro = i / 72, k4 = i - ro * 72;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(wrow + (long long)ro * en.cin * 9 + k4 * 4);
-      float* d = &s[ro][k4 * 4];
-      d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
-    }
-  } else {
-    for (int i = threadIdx.x; i < 32 * 288; i += blockDim.x) {
-      const int ro = i / 288, k = i - ro * 288;      // k = ci_local*9 + tap
-      float v = 0.f;
-      if (ro < t.rw && k < t.cw * 9) v = wrow[(long long)ro * en.cin * 9 + k];
-      s[ro][k] = v;
-    }
-  }
-}
-
-// LDS tile -> both packed layouts of T, wf[tap][co][cinpad] and (en.wd >= 0) the flipped / transposed wd[8 - tap][ci][co]:
-// 16-byte stores (8 packed elements per thread) where rows and alignment allow, element-wise otherwise
-template <typename T>
-__device__ __forceinline__ void store_packed_tile(const float (*s)[TILE_LD], T* __restrict__ arena, const PackEnt& en, const Tile& t) {
-  constexpr int EPV = Tr<T>::EPV;
-  T* wf = arena + en.wf;
-  T* wd = en.wd >= 0 ? arena + en.wd : nullptr;
-  if (t.rw == 32 && en.cinpad % 8 == 0 && en.cout % 8 == 0 && ((uintptr_t)wf & 15) == 0 && ((uintptr_t)wd & 15) == 0) {
-    for (int i = threadIdx.x; i < 9 * 32 * 4; i += blockDim.x) {    // wf[tap][co][ci], ci fastest: 8 ci per thread
-      const int g = i & 3, ro = (i >> 2) & 31, tap = i >> 7;
-      if (t.ci0 + g * 8 < en.cinpad) {
-        T* q = wf + ((long long)tap * en.cout + t.co0 + ro) * en.cinpad + t.ci0 + g * 8;
-#pragma unroll
-        for (int h = 0; h < 8 / EPV; ++h) {
-          Vec16<T> o;
-#pragma unroll
-          for (int e = 0; e < EPV; ++e) o.set(e, s[ro][(g * 8 + h * EPV + e) * 9 + tap]);
-          st16(q + h * EPV, o);
-        }
-      }
-    }
-    if (wd) {
-      for (int i = threadIdx.x; i < 9 * 32 * 4; i += blockDim.x) {  // wd[8-tap][ci][co], co fastest: 8 co per thread
-        const int g = i & 3, ci = (i >> 2) & 31, tap = i >> 7;
-        if (ci < t.cw) {
-          T* q = wd + ((long long)(8 - tap) * en.cin + t.ci0 + ci) * en.cout + t.co0 + g * 8;
-#pragma unroll
-          for (int h = 0; h < 8 / EPV; ++h) {
-            Vec16<T> o;
-#pragma unroll
-            for (int e = 0; e < EPV; ++e) o.set(e, s[g * 8 + h * EPV + e][ci * 9 + tap]);
-            st16(q + h * EPV, o);
-          }
-        }
-      }
-    }
-    return;
-  }
-  for (int i = threadIdx.x; i < 9 * 32 * 32; i += blockDim.x) {   // wf[tap][co][ci], ci fastest
-    const int ci = i & 31, ro = (i >> 5) & 31, tap = i >> 10;
-    if (ro < t.rw && t.ci0 + ci < en.cinpad)
-      wf[((long long)tap * en.cout + t.co0 + ro) * en.cinpad + t.ci0 + ci] = from_f32<T>(s[ro][ci * 9 + tap]);
-  }
-  if (wd) {
-    for (int i = threadIdx.x; i < 9 * 32 * 32; i += blockDim.x) { // wd[8-tap][ci][co], co fastest
-      const int ro = i & 31, ci = (i >> 5) & 31, tap = i >> 10;
-      if (ro < t.rw && ci < t.cw)
-        wd[((long long)(8 - tap) * en.cin + t.ci0 + ci) * en.cout + t.co0 + ro] = from_f32<T>(s[ro][ci * 9 + tap]);
-    }
-  }
-}
-
-// fp32 parameters -> both packed layouts
-template <typename T>
-__global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ params, T* __restrict__ arena, PackTab tab) {
-  __shared__ float s_t[32][TILE_LD];
-  const Tile t = tile_of(tab, blockIdx.x);
-  const PackEnt en = tab.e[t.e];
-  load_oihw_tile(s_t, params + en.src, en, t);
-  __syncthreads();
-  store_packed_tile(s_t, arena, en, t);
-}
-
-// Gradient scratch -> flat OIHW gradient arena (overwritten or accumulated into), the OIHW rows written as 16-byte runs
-__global__ __launch_bounds__(256) void unpack_tiled_kernel(const float* __restrict__ scratch, float* __restrict__ grads, PackTab tab, UnpackTab ut) {
-  __shared__ float s_t[32][TILE_LD];
-  if ((int)blockIdx.x >= tab.ntiles) {
-    const UnpackEnt en = ut.e[(int)blockIdx.x - tab.ntiles];
-    float* g = grads + en.dst;
-    tail_entry(en, scratch, &s_t[0][0], [&](int i, float v) { g[i] = ut.accumulate ? g[i] + v : v; });
-    return;
-  }
-  const Tile t = tile_of(tab, blockIdx.x);
-  if (t.cw <= 0) return;                                 // pure padding tile
-  const PackEnt en = tab.e[t.e];
-  const UnpackEnt ue = ut.e[t.e];
-  float* grow = grads + ue.dst + ((long long)t.co0 * en.cin + t.ci0) * 9;
-  gather_scratch_tile(s_t, scratch + ue.src, en, t);
-  __syncthreads();
-  if (t.rw == 32 && t.cw == 32 && en.cin % 4 == 0 && ((uintptr_t)grow & 15) == 0) {
-    for (int i = threadIdx.x; i < 32 * 72; i += blockDim.x) {
-      const int ro = i / 72, k4 = i - ro * 72;
-      f32x4* q = reinterpret_cast<f32x4*>(grow + (long long)ro * en.cin * 9 + k4 * 4);
-      const float* sp = &s_t[ro][k4 * 4];
-      f32x4 v = {sp[0], sp[1], sp[2], sp[3]};
-      if (ut.accumulate) { const f32x4 o = *q; v[0] += o[0]; v[1] += o[1]; v[2] += o[2]; v[3] += o[3]; }
-      *q = v;
-    }
-  } else {
-    for (int i = threadIdx.x; i < 32 * 288; i += blockDim.x) {
-      const int ro = i / 288, k = i - ro * 288;
-      if (ro < t.rw && k < t.cw * 9) {
-        float* q = grow + (long long)ro * en.cin * 9 + k;
-        *q = ut.accumulate ? *q + s_t[ro][k] : s_t[ro][k];
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Fused optimiser step (unpack_sgd_tiled_kernel, below the plan): native-layout gradient scratch -> optimiser step on
-// the fp32 master parameters, one launch; the next forward repacks the 16-bit weight layouts. torch.optim.SGD
-// semantics (reference trains.py:229-231).
-// ---------------------------------------------------------------------------------------------------------
-struct UpdP { float* params; const float* scratch; float* grads; float gscale; };
-
-// one element of the fused kernels outside the LDS tiles, at flat index idx: the scaled gradient to the flat arena when the
-// caller wants it, then the step unless loss scaling skipped it (live false)
-template <typename O>
-__device__ __forceinline__ void step_elem(const UpdP& u, const O& o, bool live, float gs, long long idx, float g) {
-  g *= gs;
-  if (u.grads) u.grads[idx] = g;
-  if (live) u.params[idx] = opt_elem(o, u.params[idx], g, idx);
-}
-
-// block -> tile prefix table of a PackTab: entry i owns blocks [tile0[i], tile0[i + 1]) of the tile kernels, one per 32 x 32
-// (cout, cinpad) tile. Filled once, when the table is built.
-static void pack_tiles(PackTab& tab) {
-  int nt = 0;
-  for (int i = 0; i < tab.n; ++i) { tab.tile0[i] = nt; nt += ((tab.e[i].cout + 31) / 32) * ((tab.e[i].cinpad + 31) / 32); }
-  tab.tile0[tab.n] = nt; tab.ntiles = nt;
-}
-
-template <typename T> static int launch_pack(const float* params, void* arena_t, const PackTab& tab, hipStream_t st) {
-  double pb = 0;
-  for (int i = 0; i < tab.n; ++i) pb += 9.0 * tab.e[i].cout * tab.e[i].cin * (4 + (tab.e[i].wd >= 0 ? 2 : 1) * sizeof(T));
-  ProfScope ps(PC_PACK, 0, pb, st);
-  NUNET_LAUNCH((pack_kernel<T>), dim3(tab.ntiles), dim3(256), 0, st, params, (T*)arena_t, tab);
-  return nunet_check_launch("pack_weights");
-}
-
-extern "C" int nunet_pack_weights(const float* w, int32_t cout, int32_t cin, int32_t cin_pad, int32_t dtype, void* wf, void* wd, nunet_stream_t s) {
-  NUNET_REQUIRE(w && wf && cout > 0 && cin > 0 && cin_pad >= cin, "pack_weights: bad args");
-  NUNET_REQUIRE(dtype >= 0 && dtype <= 2, "pack_weights: bad dtype");
-  PackTab tab; memset(&tab, 0, sizeof(tab));
-  tab.n = 1;
-  const int es = dtype_size(dtype);
-  char* base = (wd && (char*)wd < (char*)wf) ? (char*)wd : (char*)wf;
-  NUNET_REQUIRE(((char*)wf - base) % es == 0 && (!wd || ((char*)wd - base) % es == 0), "pack_weights: wf/wd misaligned");
-  tab.e[0].src = 0;
-  tab.e[0].wf = ((char*)wf - base) / es;
-  tab.e[0].wd = wd ? ((char*)wd - base) / es : -1;
-  tab.e[0].cout = cout; tab.e[0].cin = cin; tab.e[0].cinpad = cin_pad;
-  pack_tiles(tab);
-  return NUNET_DISPATCH(dtype, launch_pack, w, (void*)base, tab, (hipStream_t)s);
-}
-
-extern "C" int nunet_unpack_wgrad(const float* dw, int32_t cout, int32_t cin, int32_t cin_pad, float* g, int32_t accumulate, nunet_stream_t s) {
-  NUNET_REQUIRE(dw && g && cout > 0 && cin > 0 && cin_pad >= cin, "unpack_wgrad: bad args");
-  PackTab tab; memset(&tab, 0, sizeof(tab));
-  UnpackTab ut; memset(&ut, 0, sizeof(ut));
-  tab.n = ut.n = 1; ut.accumulate = accumulate;
-  tab.e[0].wd = -1; tab.e[0].cout = cout; tab.e[0].cin = cin; tab.e[0].cinpad = cin_pad;
-  ut.e[0].cout = cout; ut.e[0].cin = cin; ut.e[0].cinpad = cin_pad; ut.e[0].taps = 9; ut.e[0].nvec = 0; ut.e[0].nslab = 1;
-  pack_tiles(tab);
-  NUNET_LAUNCH(unpack_tiled_kernel, dim3(tab.ntiles), dim3(256), 0, (hipStream_t)s, dw, g, tab, ut);   // no vectors: no tail block
-  return nunet_check_launch("unpack_wgrad");
-}
+#include "sched.h"
 
 // ---------------------------------------------------------------------------
 // plan
 // ---------------------------------------------------------------------------
-struct ConvL {
-  int cin, cinpad, cout;
-  long long w_off, b_off, g_off, be_off;  // floats into flat params
-  long long rm_off, rv_off; int bn_index; // floats into bnbuf / index into nbt
-  long long wf, wd;                       // elements of T into the packed-weight region (wd -1: none)
-  long long gs;                           // floats into grad scratch: [dw 9*cout*cinpad][db][dgamma][dbeta]
-  long long stats, save, bsum;            // floats into the fp32 small-vector regions (x REPLICAS x 2 int64 words in the fixed-point regions)
-  long long slab; int ks, wg_target;      // weight-gradient K-split slabs: floats into the slab region, slices, workgroup target
-};
-struct Node {
-  int i, j;
-  int in_prefix;   // number of level slots concatenated in front (0: encoder input)
-  int out_slot;    // slot of X_i receiving the block output
-  int up_slot;     // slot of X_{i+1} that is upsampled into the concat, -1: none
-  ConvL c1, c2;
-  size_t y1, y2, up, pin;      // arena byte offsets (a1 = relu(bn1(y1)) is never stored: its two readers form it in their loaders)
-  size_t dy[2], da1, gup, gpin;   // ... backward scratch (dY of conv2 / conv1) of the BLOCK, so blocks of one level can run on different lanes
-  size_t sk; long long sk_floats; // ... fp32 K-split slabs of the BLOCK (blocks of the grid-starved levels; 0 floats: none)
-  // backward pass, decided at creation (plan_backward_facts): destinations that an earlier op of the pass wrote first are accumulated into
-  unsigned acc0_mask;             // dgrad1: bit q = slot q of the concat prefix's gradient
-  int acc_pool, acc_up;           // pool-backward / upsample-backward
-  bool bn2_in_head;               // the reduce pass of BatchNorm2's backward rides in a head's backward (Head::bnr_block)
-};
-struct Head { long long w_off, b_off, gs; int slot; int acc, bnr_block; };   // backward: accumulate flag, block whose BN2 reduce it carries (-1: none)
-// what the resource ids of the lane scheduler are laid out for (NestedUNet has 15 blocks, UNet 9)
-#define NUNET_MAX_BLOCKS 15
-#define NUNET_MAX_HEADS 4
-
-#define NLANES 10
-struct PlanRt {  // runtime objects owned by the plan (host side only)
-  hipStream_t lanes[NLANES];
-  bool lanes_ok;
-  std::vector<hipEvent_t> events[2];   // [0] forward, [1] backward: an event is never re-recorded within one capture
-  size_t events_used[2];
-  int multistream;
-  int schedule;                            // NUNET_SCHEDULE_LANES: an op runs on its block's lane; NUNET_SCHEDULE_LIST: Sched::run_list picks
-  int wgrad_dy;                            // nunet_plan_set_wgrad_dy: the weight gradients form dy1 / dy2 in their loaders (no side stores)
-  int head_bn;                             // nunet_plan_set_head_bn: BatchNorm2 of a head-only block output rides in the head's launch (default 1)
-  int bn_up;                               // nunet_plan_set_bn_up: NUNET_BN_UP_* - which producers' BatchNorm2 launch also upsamples
-  int wait_prune;                          // nunet_plan_set_wait_prune: cross-lane waits that lane order already implies are dropped (default 1)
-  bool lanes_external;
-  std::vector<hipStream_t> cap_streams;   // never-reused streams for capture-time lane continuation
-  size_t cap_next;
-  // NUNET_STAMPS=1 diagnostic: a 1-thread kernel after every scheduled op writes the 100 MHz wall clock,
-  // so the real timeline of an (unprofiled) hipGraph replay can be read back (tools/stamp_timeline.py)
-  unsigned long long* stamps;              // device, [2][STAMP_CAP]
-  int lane_low_priority;                   // side lanes of the flag-synchronised program at the lowest stream priority (default 1)
-  int calibrating;                         // nunet_plan_calibrate: single lane + stamps, to measure every op's isolated cost
-  std::map<std::string, float> op_cost[2]; // measured cost (us) by op name, per pass; empty: the built-in estimates
-  hipStream_t seg_lanes[3];                // side-lane streams of the segmented recording (created together: distinct hardware queues)
-  std::vector<hipStream_t> seg_owned;      // every stream seg_pick_lanes created and kept (destroyed with the plan)
-  struct Sched* open_sched;                // backward pass left open after phase 1 (nunet_plan_backward_phase 1|8): lanes, dependency state
-  std::vector<hipEvent_t> b0_events;       // ... and the last-writer events of the first bucket's gradients, for nunet_plan_bucket0_wait
-  std::vector<std::string> stamp_labels[2];
-  std::vector<nunet_plan_census_entry> census[2];   // nunet_plan_census_*: the convolutions / weight-gradient pairs of the last forward [0] / backward [1]
-};
-void graph_tag_tail(hipStream_t st, int lane);   // graph.hip: lane bookkeeping of an active nunet_graph capture
-#define STAMP_CAP 512
-__global__ void stamp_kernel(unsigned long long* p) { *p = wall_clock64(); }
-struct nunet_plan;
-static PlanRt* rt_of(nunet_plan* P);
-struct nunet_plan {
-  nunet_plan_cfg cfg;
-  int depth;                    // 0: the whole network; 1..4: pruned to the blocks x_{i,j}, i + j <= depth, that feed head `depth` (eval forward only)
-  int es;                       // element size of T
-  int hl[5], wl[5]; long long px[5];
-  int nslots[5], PX[5];
-  std::vector<Node> exec;       // execution order
-  std::vector<int> reg;         // registration (parameter) order -> index into exec
-  std::vector<Head> heads;
-  long long nparams, nbnbuf; int nbn;
-  int first_phase_nodes; long long gs_bucket0;   // backward phase 1 = heads + this many last nodes; its gradient-scratch prefix
-  // arena regions (byte offsets)
-  size_t off_fx, stats_floats;  // fixed-point per-channel sums: [BatchNorm statistics | BatchNorm-backward sums], zeroed by every training forward
-  size_t off_gs, gs_floats;     // reduced gradient scratch (native layout, gradient-ready order): what a data-parallel job exchanges
-  size_t off_slab; long long slab_floats;   // K-split slabs of the weight gradients (summed into the scratch by reduce_kernel)
-  size_t off_save;
-  size_t off_wpack; long long wpack_elems;
-  size_t off_img;
-  size_t X[5], GX[5];
-  struct PlanRt* rt;
-  size_t total;
-  PackTab ptab;
-  UnpackTab utab;
-};
-
-static size_t fx_region_bytes(const nunet_plan* P) { return P->stats_floats * NUNET_BN_SUM_REPLICAS * NUNET_FX_WORDS * sizeof(long long); }
-static long long* fx_of(void* arena, const nunet_plan* P, int region, long long off) {   // region 0: BN statistics, 1: BN-backward sums
-  return (long long*)((char*)arena + P->off_fx + (size_t)region * fx_region_bytes(P)) + off * NUNET_BN_SUM_REPLICAS * NUNET_FX_WORDS;
-}
 static size_t bump(size_t& cur, size_t bytes) {
   size_t o = align_up(cur, 256);
   cur = o + bytes;
   return o;
+}
+static int block_at(const nunet_plan* p, int i, int j) {   // index into exec of x_{i,j}, -1: none
+  for (size_t k = 0; p && k < p->exec.size(); ++k) if (p->exec[k].i == i && p->exec[k].j == j) return (int)k;
+  return -1;
+}
+// registration order of the execution list: by column j, then row i (archs1.py:45-56 / 85-103)
+static void registration_order(nunet_plan* P) {
+  P->reg.clear();
+  for (int j = 0; j < 5; ++j)
+    for (int i = 0; i < 5; ++i)
+      if (const int k = block_at(P, i, j); k >= 0) P->reg.push_back(k);
+}
+static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+// a zeroed conv / weight-gradient / BatchNorm descriptor with the plan's dtype and the extents of pyramid level l
+template <typename D> static D level_desc(const nunet_plan* P, int l) {
+  D d; memset(&d, 0, sizeof(d));
+  d.dtype = P->cfg.dtype; d.N = P->cfg.N; d.H = P->hl[l]; d.W = P->wl[l];
+  return d;
 }
 
 // The static facts of the backward pass. A gradient destination is assigned by its first writer and accumulated into by the later
@@ -458,11 +103,7 @@ static nunet_plan* plan_create_impl(const nunet_plan_cfg* cfg, int depth) {
       P->exec.push_back(n);
     }
   }
-  // registration order: by column j, then row i (archs1.py:45-56 / 85-103)
-  for (int j = 0; j < 5; ++j)
-    for (int i = 0; i < 5; ++i)
-      for (size_t k = 0; k < P->exec.size(); ++k)
-        if (P->exec[k].i == i && P->exec[k].j == j) P->reg.push_back((int)k);
+  registration_order(P);
 
   // ---- parameter / buffer offsets in registration order -------------------------
   long long po = 0, bo = 0, gs = 0, sv = 0; int bn = 0;
@@ -505,11 +146,7 @@ static nunet_plan* plan_create_impl(const nunet_plan_cfg* cfg, int depth) {
     std::vector<Node> keep;
     for (const Node& n : P->exec) if (kept(n)) keep.push_back(n);
     P->exec.swap(keep);
-    P->reg.clear();
-    for (int j = 0; j < 5; ++j)
-      for (int i = 0; i < 5; ++i)
-        for (size_t k = 0; k < P->exec.size(); ++k)
-          if (P->exec[k].i == i && P->exec[k].j == j) P->reg.push_back((int)k);
+    registration_order(P);
   }
   if (P->exec.size() > NUNET_MAX_BLOCKS || P->heads.size() > NUNET_MAX_HEADS) {
     nunet_set_error("plan_create: %zu blocks / %zu heads, the lane scheduler's resource ids cover %d / %d", P->exec.size(), P->heads.size(), NUNET_MAX_BLOCKS, NUNET_MAX_HEADS);
@@ -540,8 +177,8 @@ static nunet_plan* plan_create_impl(const nunet_plan_cfg* cfg, int depth) {
       //  9146-9247, 9107 images/s: a little fewer workgroups leave the chain's kernels more room: 96/192.)
       const bool big = (long long)cfg->N * cfg->H * cfg->W >= (1LL << 20);
       c.wg_target = big ? (c.cinpad < o.cinpad ? 256 : 512) : (c.cinpad < o.cinpad ? 96 : 192);
-      nunet_wgrad_desc wd; memset(&wd, 0, sizeof(wd));
-      wd.N = cfg->N; wd.H = P->hl[n.i]; wd.W = P->wl[n.i]; wd.C0 = c.cinpad; wd.Cout = c.cout; wd.target_wgs = c.wg_target;
+      nunet_wgrad_desc wd = level_desc<nunet_wgrad_desc>(P, n.i);
+      wd.C0 = c.cinpad; wd.Cout = c.cout; wd.target_wgs = c.wg_target;
       c.ks = nunet_conv3x3_wgrad_slabs(&wd);
       c.slab = slab; slab += (long long)c.ks * 9LL * c.cout * c.cinpad;
     }
@@ -613,25 +250,13 @@ static nunet_plan* plan_create_impl(const nunet_plan_cfg* cfg, int depth) {
     UnpackEnt& ue = P->utab.e[P->utab.n++];
     ue.src = P->heads[k].gs; ue.dst = P->heads[k].w_off; ue.cout = cfg->num_classes; ue.cin = NBF[0]; ue.cinpad = NBF[0]; ue.taps = 1; ue.nvec = 1; ue.nslab = HEAD_SLABS;
   }
-  PlanRt* rt = new PlanRt();
-  rt->lanes_ok = true;
-  rt->lanes_external = false;
-  rt->cap_next = 0;
-  rt->stamps = nullptr;
-  rt->calibrating = 0;
-  rt->lane_low_priority = 1;
-  rt->open_sched = nullptr;
-  rt->seg_lanes[0] = rt->seg_lanes[1] = rt->seg_lanes[2] = nullptr;
-  rt->events_used[0] = rt->events_used[1] = 0;
-  { const char* e = getenv("NUNET_MULTISTREAM"); rt->multistream = e ? atoi(e) : 1; }
-  rt->schedule = NUNET_SCHEDULE_LANES;
-  { const char* e = getenv("NUNET_WGRAD_DY"); rt->wgrad_dy = e ? (atoi(e) != 0) : 0; }
-  // (the three below: environment overrides for A/B runs of unchanged programs, as the two above)
-  { const char* e = getenv("NUNET_HEAD_BN"); rt->head_bn = e ? (atoi(e) != 0) : 1; }
-  { const char* e = getenv("NUNET_BN_UP"); const int v = e ? atoi(e) : NUNET_BN_UP_NONE; rt->bn_up = v >= NUNET_BN_UP_NONE && v <= NUNET_BN_UP_ALL ? v : NUNET_BN_UP_NONE; }
-  { const char* e = getenv("NUNET_WAIT_PRUNE"); rt->wait_prune = e ? (atoi(e) != 0) : 1; }
+  PlanRt* rt = new PlanRt();   // (defaults: the member initialisers; the five below: environment overrides for A/B runs of unchanged programs)
+  rt->multistream = env_int("NUNET_MULTISTREAM", rt->multistream);
+  rt->wgrad_dy = env_int("NUNET_WGRAD_DY", rt->wgrad_dy) != 0;
+  rt->head_bn = env_int("NUNET_HEAD_BN", rt->head_bn) != 0;
+  if (const int v = env_int("NUNET_BN_UP", rt->bn_up); v >= NUNET_BN_UP_NONE && v <= NUNET_BN_UP_ALL) rt->bn_up = v;
+  rt->wait_prune = env_int("NUNET_WAIT_PRUNE", rt->wait_prune) != 0;
   for (int l = 0; l < NLANES; ++l) {
-    rt->lanes[l] = nullptr;
     if (hipStreamCreateWithFlags(&rt->lanes[l], hipStreamNonBlocking) != hipSuccess) { rt->lanes_ok = false; (void)hipGetLastError(); }
   }
   P->rt = rt;
@@ -649,18 +274,10 @@ extern "C" nunet_plan* nunet_plan_create_pruned(const nunet_plan_cfg* cfg, int32
 }
 extern "C" int32_t nunet_plan_depth(const nunet_plan* p) { return p ? p->depth : 0; }
 
-// Entries of the training path on a pruned plan: refused before any launch and before any buffer is looked at
-#define REFUSE_PRUNED(what) \
-  NUNET_REQUIRE(P->depth == 0, what ": the plan is pruned to depth %d (nunet_plan_create_pruned): it runs eval forwards only", P->depth)
-
-
-static PlanRt* rt_of(nunet_plan* P) { return P->rt; }
-
-static void sched_free(struct Sched* s);
 extern "C" void nunet_plan_destroy(nunet_plan* p) {
   if (!p) return;
   if (p->rt) {
-    if (p->rt->open_sched) { sched_free(p->rt->open_sched); p->rt->open_sched = nullptr; }
+    if (p->rt->open_sched) { delete p->rt->open_sched; p->rt->open_sched = nullptr; }
     if (!p->rt->lanes_external)
       for (int l = 0; l < NLANES; ++l) if (p->rt->lanes[l]) (void)hipStreamDestroy(p->rt->lanes[l]);
     for (size_t k = 0; k < p->rt->cap_streams.size(); ++k) (void)hipStreamDestroy(p->rt->cap_streams[k]);
@@ -677,10 +294,6 @@ extern "C" int64_t nunet_plan_param_count(const nunet_plan* p) { return p ? p->n
 extern "C" int64_t nunet_plan_bnbuf_count(const nunet_plan* p) { return p ? p->nbnbuf : 0; }
 extern "C" int32_t nunet_plan_bn_layers(const nunet_plan* p) { return p ? p->nbn : 0; }
 extern "C" int32_t nunet_plan_num_heads(const nunet_plan* p) { return p ? (int32_t)p->heads.size() : 0; }
-static int block_at(const nunet_plan* p, int i, int j) {   // index into exec of x_{i,j}, -1: none
-  for (size_t k = 0; p && k < p->exec.size(); ++k) if (p->exec[k].i == i && p->exec[k].j == j) return (int)k;
-  return -1;
-}
 static int64_t slot_offset(const nunet_plan* p, const size_t* level, int32_t i, int32_t j, int32_t* pitch, int32_t* channels) {
   const int k = block_at(p, i, j);
   if (k < 0) return -1;
@@ -704,523 +317,6 @@ extern "C" int nunet_plan_census_get(const nunet_plan* p, int32_t pass, int32_t 
   NUNET_REQUIRE(index >= 0 && (size_t)index < p->rt->census[pass].size(), "plan_census_get: index out of range");
   *out = p->rt->census[pass][index];
   return NUNET_OK;
-}
-
-#define CK(expr)                \
-  do {                          \
-    int rc_ = (expr);           \
-    if (rc_ != NUNET_OK) return rc_; \
-  } while (0)
-
-static inline char* AB(void* arena, size_t off) { return (char*)arena + off; }
-
-// ---------------------------------------------------------------------------
-// Lane scheduler. The x_{i,j} grid has natural concurrency: blocks of level i depend only
-// on levels i and i+-1, and weight gradients depend on nothing downstream. Every kernel
-// here is latency-bound on its own (short contractions, grid-starved deep levels), so the
-// plan issues every op on a stream of its own choosing - a block's ops on the block's lane
-// (lane_of: the critical chain on lane 0, the side blocks on lanes 1-3 by anti-diagonal; a
-// block's weight gradients on that same lane), or wherever the list scheduler (Sched::run_list)
-// places them -, forked from and joined to the caller's stream with events. Exact RAW / WAW /
-// WAR dependencies come from a per-buffer tracker (last-writer event, last-reader event per
-// lane). Captured by the caller, the lanes become parallel branches of ONE hipGraph.
-// ---------------------------------------------------------------------------
-// Resource ids of the tracker in numeric order, with what each range spans (B = NUNET_MAX_BLOCKS blocks)
-#define NRES 512
-enum {
-  R_X = 0, R_GX = 25,                            // 5 levels x 5 slots each: block outputs (slot s of X_l: R_X + 5 l + s); their gradients
-  R_BLK = 50,                                    // B x B_STRIDE: the forward buffers of a block (B_*)
-  R_IMG = 230, R_LOGITS = 231, R_DLOGITS = 232,  // 1 each
-  R_WP = 233,                                    // 5 levels: packed weights
-  R_GSW = 240, R_GSV = 280,                      // B x 2 each (conv1, conv2): weight gradients; BatchNorm-backward sums + small-vector gradients
-  R_GSH = 310,                                   // NUNET_MAX_HEADS: the gradients of a head
-  R_LVL = 330,                                   // B x L_STRIDE: the backward scratch of a block (L_*)
-  R_SK = 470                                     // B: split-K workspace
-};
-enum { B_Y1 = 0, B_Y2, B_UP, B_PIN, B_ST1, B_ST2, B_STRIDE = 8 };
-enum { L_DY0 = 0, L_DY1, L_DA1, L_GUP, L_GPIN, L_STRIDE = 8 };
-static_assert(B_ST2 < B_STRIDE && L_GPIN < L_STRIDE && R_X + 5 * 5 <= R_GX && R_GX + 5 * 5 <= R_BLK && R_BLK + NUNET_MAX_BLOCKS * B_STRIDE <= R_IMG &&
-              R_IMG < R_LOGITS && R_LOGITS < R_DLOGITS && R_DLOGITS < R_WP && R_WP + 5 <= R_GSW && R_GSW + 2 * NUNET_MAX_BLOCKS <= R_GSV &&
-              R_GSV + 2 * NUNET_MAX_BLOCKS <= R_GSH && R_GSH + NUNET_MAX_HEADS <= R_LVL && R_LVL + NUNET_MAX_BLOCKS * L_STRIDE <= R_SK &&
-              R_SK + NUNET_MAX_BLOCKS <= NRES, "resource-id ranges overlap at this capacity");
-
-// ---- Which cross-lane waits an op still needs -------------------------------------------------------------------------------
-// Lanes are in-order (a stream; while capturing, a chain of streams each forked from the lane's tail), and what a kernel wrote
-// is visible device-wide once it has ended (flag executor) - so "ends before" is transitive: an op that starts after
-// op B has ended, where B started after A had ended, needs no wait of its own for A. Every issued op gets a stamp: its lane, its
-// number on that lane, and the vector clock of its lane at that point - per lane, the number of the last op known to have ended
-// before this one starts. A requested wait (read after write, write after write, write after read alike) whose producer the
-// waiting lane's clock already covers is dropped; so is one that another wait of the same op covers; every wait that is kept
-// merges the producer's clock into the lane's. Host bookkeeping only; nunet_wait_prune_host runs it over plain arrays.
-#define WP_MAXL 16
-static_assert(NLANES <= WP_MAXL, "the wait pruner's clocks cover every lane");
-struct LaneStamp { int lane, seq; int clock[WP_MAXL]; };
-struct WaitPruner {
-  int know[WP_MAXL][WP_MAXL], seq[WP_MAXL];
-  void reset() { memset(know, 0, sizeof(know)); memset(seq, 0, sizeof(seq)); }
-  void absorb(int L, const LaneStamp& s) { for (int l = 0; l < WP_MAXL; ++l) know[L][l] = std::max(know[L][l], s.clock[l]); }
-  // the op about to start on lane L asks to wait for c[0..n): keep[q] = 1 for the waits it must make
-  void decide(int L, const LaneStamp* const* c, int n, unsigned char* keep) {
-    for (int q = 0; q < n; ++q) keep[q] = know[L][c[q]->lane] < c[q]->seq;
-    for (int q = 0; q < n; ++q) {
-      if (!keep[q]) continue;
-      for (int r = 0; r < n && keep[q]; ++r) {
-        if (r == q || !keep[r] || c[r]->clock[c[q]->lane] < c[q]->seq) continue;
-        const bool same = c[r]->lane == c[q]->lane && c[r]->seq == c[q]->seq;   // the same op asked for twice: the first stays
-        if (!same || r < q) keep[q] = 0;
-      }
-    }
-    for (int q = 0; q < n; ++q) if (keep[q]) absorb(L, *c[q]);
-  }
-  LaneStamp done(int L) {        // the op on lane L has been issued
-    LaneStamp s; s.lane = L; s.seq = ++seq[L]; know[L][L] = s.seq;
-    memcpy(s.clock, know[L], sizeof(s.clock));
-    return s;
-  }
-};
-extern "C" int nunet_wait_prune_host(int32_t nlanes, int32_t nops, const int32_t* op_lane, const int32_t* edge_off, const int32_t* edge_src, uint8_t* keep) {
-  NUNET_REQUIRE(op_lane && edge_off && keep && nlanes >= 1 && nlanes <= WP_MAXL && nops >= 0, "wait_prune_host: bad args (1..%d lanes)", WP_MAXL);
-  WaitPruner wp; wp.reset();
-  std::vector<LaneStamp> stamp((size_t)nops);
-  std::vector<const LaneStamp*> c;
-  for (int b = 0; b < nops; ++b) {
-    const int L = op_lane[b], e0 = edge_off[b], e1 = edge_off[b + 1];
-    NUNET_REQUIRE(L >= 0 && L < nlanes && e0 <= e1 && (e0 == e1 || edge_src), "wait_prune_host: op %d: lane %d, edges [%d, %d)", b, L, e0, e1);
-    c.clear();
-    for (int e = e0; e < e1; ++e) {
-      NUNET_REQUIRE(edge_src[e] >= 0 && edge_src[e] < b, "wait_prune_host: edge %d of op %d names op %d, which is not issued before it", e, b, edge_src[e]);
-      c.push_back(&stamp[edge_src[e]]);
-    }
-    if (!c.empty()) wp.decide(L, c.data(), (int)c.size(), keep + e0);
-    stamp[b] = wp.done(L);
-  }
-  return NUNET_OK;
-}
-
-struct Sched {
-  hipStream_t main_s;
-  WaitPruner wp; bool prune;                       // see above; prune off: every requested wait is made (nunet_plan_set_wait_prune)
-  std::map<hipEvent_t, LaneStamp> stamp_of;        // the op each event of this pass marks the end of
-  hipStream_t lane_s[NLANES];      // stream currently carrying each lane (fixed lanes when not capturing)
-  hipEvent_t lane_tail[NLANES];    // event after the last op issued on the lane
-  bool multi, capturing, failed;
-  bool used[NLANES];
-  PlanRt* rt;
-  std::vector<hipEvent_t>* pool;
-  size_t* pool_used;
-  struct Res { hipEvent_t w_ev; hipStream_t w_st; hipEvent_t r_ev[NLANES]; hipStream_t r_st[NLANES]; };
-  Res res[NRES];
-  int cur_lane; int nreads, nwrites; int reads[16], writes[16];
-  hipEvent_t fork_ev;
-  hipEvent_t pend[64]; int npend;
-  int lane_map[NLANES];
-  int pass;
-  char cur_name[32];
-  void name(const char* fmt, ...) {
-    va_list ap; va_start(ap, fmt); vsnprintf(cur_name, sizeof(cur_name), fmt, ap); va_end(ap);
-  }
-  void stamp(hipStream_t st, int lane) {
-    if (!rt->stamps) return;
-    std::vector<std::string>& lab = rt->stamp_labels[pass];
-    if ((int)lab.size() >= STAMP_CAP) return;
-    NUNET_LAUNCH(stamp_kernel, dim3(1), dim3(1), 0, st, rt->stamps + (size_t)pass * STAMP_CAP + lab.size());
-    char b[48]; snprintf(b, sizeof(b), "L%d %s", lane, cur_name);
-    lab.push_back(b);
-  }
-
-  hipEvent_t new_event() {
-    if (*pool_used == pool->size()) {
-      hipEvent_t e;
-      (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
-      pool->push_back(e);
-    }
-    return (*pool)[(*pool_used)++];
-  }
-  void init(nunet_plan* P, hipStream_t s, int pass);
-  // One wait per distinct event, never on an event of the stream itself.
-  void want(hipEvent_t ev, hipStream_t ev_st, hipStream_t st) {
-    if (!ev) return;
-    if (ev_st == st) { if (prune) wp.absorb(cur_lane, stamp_of[ev]); return; }   // (stream order: what that op knew, this one knows)
-    for (int k = 0; k < npend; ++k) if (pend[k] == ev) return;
-    if (npend < 64) pend[npend++] = ev;
-    else failed = true;        // a dropped wait would be a silent race between lanes: reported by the caller after the join
-  }
-  // ROCm 7.2: inside a stream capture, a stream that waits on an event DESCENDING from its
-  // own tail node crashes hipStreamEndCapture (regression test: tests/test_capture_gpu.py). The x_{i,j}
-  // grid ping-pongs between levels all the time, so while capturing a lane with cross-lane
-  // waits continues on a never-used stream that waits on the lane's tail event AND the
-  // cross-lane events (no own tail -> plain fork semantics). Eager issue keeps fixed lanes.
-  hipStream_t fresh_stream() {
-    if (rt->cap_next >= rt->cap_streams.size()) { failed = true; return nullptr; }
-    return rt->cap_streams[rt->cap_next++];
-  }
-  // stream waits / event records: real HIP calls, or instructions of the segmented program being recorded (graph.hip)
-  static void wait_on(hipStream_t st, hipEvent_t ev) { if (!seg_wait(st, ev)) (void)hipStreamWaitEvent(st, ev, 0); }
-  static void record_on(hipEvent_t ev, hipStream_t st) { if (!seg_record(ev, st)) (void)hipEventRecord(ev, st); }
-  // begin an op on `lane` (already mapped) reading `rd` and writing `wr` resources; returns the stream to launch on
-  hipStream_t begin_v(int lane, const int* rd, int nrd, const int* wr, int nwr) {
-    if (!multi) return main_s;
-    cur_lane = lane; nreads = 0; nwrites = 0; npend = 0;
-    hipStream_t st = lane_s[lane];      // may be null while capturing (lane not started yet)
-    for (int q = 0; q < nrd; ++q) {
-      const int r = rd[q];
-      reads[nreads++] = r;
-      Res& R = res[r];
-      want(R.w_ev, R.w_st, st);
-    }
-    for (int q = 0; q < nwr; ++q) {
-      const int w = wr[q];
-      writes[nwrites++] = w;
-      Res& R = res[w];
-      want(R.w_ev, R.w_st, st);
-      for (int l = 0; l < NLANES; ++l) want(R.r_ev[l], R.r_st[l], st);
-    }
-    if (prune && npend > 0) {
-      const LaneStamp* c[64]; unsigned char keep[64];
-      for (int k = 0; k < npend; ++k) c[k] = &stamp_of[pend[k]];
-      wp.decide(lane, c, npend, keep);
-      int m = 0;
-      for (int k = 0; k < npend; ++k) if (keep[k]) pend[m++] = pend[k];
-      npend = m;
-    }
-    if (capturing) {
-      if (!used[lane] || npend > 0) {
-        hipStream_t ns = fresh_stream();
-        if (!ns) return main_s;   // pool exhausted: flagged, caller gets an error after the join
-        if (used[lane] && lane_tail[lane]) (void)hipStreamWaitEvent(ns, lane_tail[lane], 0);
-        else (void)hipStreamWaitEvent(ns, fork_ev, 0);
-        st = ns; lane_s[lane] = ns; used[lane] = true;
-      }
-    } else if (!used[lane]) {
-      used[lane] = true;
-      if (st != main_s) wait_on(st, fork_ev);
-    }
-    for (int k = 0; k < npend; ++k) wait_on(st, pend[k]);
-    seg_touch(st);                       // (segmented recording: the op's launches open / continue this stream's segment)
-    return st;
-  }
-
-  // ---- deferred ops: the backward pass collects its ops first (descriptors captured by value), then issues them
-  struct Op { int lane, leaf; float cost; int nrd, nwr; int rd[12], wr[8]; char name[32]; std::function<int(hipStream_t)> fn; };
-  std::vector<Op> ops;
-  // launch census (nunet_diag.h): the geometry the launch's own host queries report for the descriptor handed to the scheduler
-  void census_conv(const nunet_conv_desc& d) {
-    nunet_plan_census_entry e; memset(&e, 0, sizeof(e));
-    memcpy(e.label, cur_name, sizeof(e.label)); e.label[sizeof(e.label) - 1] = 0;
-    e.kind = NUNET_CENSUS_CONV; e.N = d.N; e.H = d.H; e.W = d.W;
-    e.C0 = d.C0; e.C1 = d.C1; e.D0 = d.D0; e.D1 = d.D1; e.in_tf = d.in_tf; e.has_bn_y = d.bn_y != nullptr; e.acc0_mask = d.acc0_mask;
-    e.splitk_ws_floats = d.splitk_ws ? d.splitk_ws_floats : 0; e.has_tf_store = d.tf_store != nullptr;
-    if (nunet_conv3x3_launch_info(&d, &e.conv) == NUNET_OK) rt->census[pass & 1].push_back(e);
-  }
-  void census_wgrad(const nunet_wgrad_desc& a, const nunet_wgrad_desc& b) {
-    nunet_plan_census_entry e; memset(&e, 0, sizeof(e));
-    memcpy(e.label, cur_name, sizeof(e.label)); e.label[sizeof(e.label) - 1] = 0;
-    e.kind = NUNET_CENSUS_WGRAD_PAIR; e.N = a.N; e.H = a.H; e.W = a.W;
-    e.wgrad_tf[0] = (a.x_tf ? 1 : 0) | (a.d_tf ? 2 : 0); e.wgrad_tf[1] = (b.x_tf ? 1 : 0) | (b.d_tf ? 2 : 0);
-    if (nunet_conv3x3_wgrad_launch_info(&a, &e.wgrad[0]) == NUNET_OK && nunet_conv3x3_wgrad_launch_info(&b, &e.wgrad[1]) == NUNET_OK)
-      rt->census[pass & 1].push_back(e);
-  }
-  // a 3x3 convolution (forward or input gradient)
-  void add_conv(int lane, std::initializer_list<int> rd, std::initializer_list<int> wr, const nunet_conv_desc& d, int alg_cin = 0) {
-    census_conv(d);
-    const double px = (double)d.N * d.H * d.W;
-    add(lane, 0, 6.f + (float)(2.0 * 9 * (d.C0 + d.C1) * (d.D0 + d.D1) * px / 4e8), rd, wr, [d, alg_cin](hipStream_t ls) {
-      g_prof_alg_cin = alg_cin; const int r = nunet_conv3x3_fwd(&d, ls); g_prof_alg_cin = 0; return r; });
-  }
-  void add(int lane, int leaf, float cost, std::initializer_list<int> rd, std::initializer_list<int> wr, std::function<int(hipStream_t)> fn) {
-    add_v(lane, leaf, cost, rd.begin(), (int)rd.size(), wr.begin(), (int)wr.size(), std::move(fn));
-  }
-  void add_v(int lane, int leaf, float cost, const int* rd, int nrd, const int* wr, int nwr, std::function<int(hipStream_t)> fn) {
-    Op o; o.lane = lane_map[lane]; o.leaf = leaf; o.cost = cost; o.nrd = o.nwr = 0;
-    for (int q = 0; q < nrd; ++q) if (rd[q] >= 0) { if (o.nrd < 12) o.rd[o.nrd++] = rd[q]; else failed = true; }
-    for (int q = 0; q < nwr; ++q) if (wr[q] >= 0) { if (o.nwr < 8) o.wr[o.nwr++] = wr[q]; else failed = true; }
-    memcpy(o.name, cur_name, sizeof(o.name)); cur_name[0] = 0;
-    measured_cost(o);
-    o.fn = std::move(fn);
-    ops.push_back(std::move(o));
-  }
-  // the op's isolated cost as nunet_plan_calibrate measured it (by name), instead of the built-in estimate
-  void measured_cost(Op& o) {
-    const std::map<std::string, float>& m = rt->op_cost[pass & 1];
-    if (m.empty() || !o.name[0]) return;
-    const auto it = m.find(o.name);
-    if (it != m.end()) o.cost = it->second;
-  }
-  int issue(const int* order, const int* lane, int n);
-  int run_ops();
-  int run_list();
-  bool list;                           // lanes assigned by a list scheduler over the dependency graph (run_list) instead of by block
-  int run() { return (list && multi) ? run_list() : run_ops(); }
-  void end() {
-    if (!multi) { stamp(main_s, 0); cur_name[0] = 0; return; }
-    hipStream_t st = lane_s[cur_lane];
-    if (!st) return;
-    stamp(st, cur_lane); cur_name[0] = 0;
-    if (capturing) graph_tag_tail(st, cur_lane);
-    hipEvent_t ev = new_event();
-    record_on(ev, st);
-    stamp_of[ev] = wp.done(cur_lane);
-    lane_tail[cur_lane] = ev;
-    for (int k = 0; k < nreads; ++k) { res[reads[k]].r_ev[cur_lane] = ev; res[reads[k]].r_st[cur_lane] = st; }
-    for (int k = 0; k < nwrites; ++k) {
-      Res& R = res[writes[k]];
-      R.w_ev = ev; R.w_st = st;
-      for (int l = 0; l < NLANES; ++l) { R.r_ev[l] = nullptr; R.r_st[l] = nullptr; }
-    }
-  }
-  void join() {
-    if (!multi) return;
-    for (int l = 0; l < NLANES; ++l)
-      if (used[l] && lane_tail[l] && lane_s[l] != main_s) wait_on(main_s, lane_tail[l]);
-    seg_touch(main_s);                   // what the caller launches next on its stream opens a new segment
-  }
-};
-
-static void sched_free(Sched* s) { delete s; }
-
-// Side-lane streams of the segmented program. ROCm maps every stream onto one of 4 hardware queues at creation and offers no way
-// to ask which (tools/seg_overlap_probe.py: of 8 fresh streams some pairs share a queue, and two lanes that share a queue run
-// strictly one after the other). So the lanes are CHOSEN BY MEASUREMENT: a 100 us single-workgroup spin kernel on two streams at
-// once takes 100 us when they sit on different queues and 200 us when not. Three candidates that overlap with the caller's
-// stream and with each other become lanes 1-3 (the rest are destroyed). Called outside any capture, once per plan.
-int nunet_debug_spin(int32_t us, int32_t tag, nunet_stream_t s);
-static void seg_pick_lanes(PlanRt* rt, hipStream_t main_s) {
-  const int NC = 12, SPIN_US = 100;
-  hipStream_t cand[NC];
-  int nc = 0;
-  // the side lanes get the LOWEST stream priority: the chain lane's workgroups are dispatched ahead of theirs (+1.4 % on the
-  // flag-synchronised step) - unless the caller says otherwise (nunet_plan_set_lane_priority): with RCCL's high-priority stream in
-  // the process, lowest-priority lanes are served in time slices (every kernel on one of them took 100-190 us in the
-  // data-parallel rehearsal: 3.4-4.4 ms per step against 1.82 at default priority).
-  const int side_prio = rt->lane_low_priority;
-  int pr_least = 0, pr_greatest = 0;
-  (void)hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest);
-  // (measured and not kept: side lanes on CU-masked streams - hipExtStreamCreateWithCUMask, 16 to 96 CUs kept free for the chain -
-  //  and the chain on a high-priority stream both run the step at 5.3 ms instead of 1.85)
-  for (int k = 0; k < NC; ++k) {
-    const hipError_t ce = side_prio ? hipStreamCreateWithPriority(&cand[nc], hipStreamNonBlocking, pr_least) : hipStreamCreateWithFlags(&cand[nc], hipStreamNonBlocking);
-    if (ce == hipSuccess) ++nc; else (void)hipGetLastError();
-  }
-  hipEvent_t e0 = nullptr, e1 = nullptr, eb = nullptr;
-  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventCreateWithFlags(&eb, hipEventDisableTiming);
-  auto overlap = [&](hipStream_t a, hipStream_t b) {          // true: a and b run side by side
-    (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b);
-    (void)hipEventRecord(e0, a);
-    (void)nunet_debug_spin(SPIN_US, 1, a);
-    (void)nunet_debug_spin(SPIN_US, 1, b);
-    (void)hipEventRecord(eb, b);
-    (void)hipStreamWaitEvent(a, eb, 0);
-    (void)hipEventRecord(e1, a);
-    (void)hipStreamSynchronize(a);
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return ms * 1000.f < 1.5f * SPIN_US;
-  };
-  // A lane must also DISPATCH at the caller's stream's rate: with RCCL initialised in the process, some streams sit on queues that
-  // the hardware scheduler serves in time slices - every kernel on such a lane took 100-190 us in the data-parallel rehearsal
-  // (4.1 ms per step). Eight back-to-back 2 us kernels, timed on the candidate against the same on the caller's stream.
-  auto chain_us = [&](hipStream_t a) {
-    (void)hipStreamSynchronize(a);
-    (void)nunet_debug_spin(2, 1, a);
-    (void)hipEventRecord(e0, a);
-    for (int q = 0; q < 8; ++q) (void)nunet_debug_spin(2, 1, a);
-    (void)hipEventRecord(e1, a);
-    (void)hipStreamSynchronize(a);
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { (void)hipGetLastError(); return 1e9f; }
-    return ms * 1000.f;
-  };
-  const float base_us = std::min(chain_us(main_s), chain_us(main_s));
-  hipStream_t pick[3]; int np = 0;
-  bool usedc[NC] = {false};
-  for (int k = 0; k < nc && np < 3; ++k) {
-    // (also clear of the process's default stream: the copies of the next batch are usually queued there)
-    bool ok = overlap(main_s, cand[k]) && overlap((hipStream_t)nullptr, cand[k]);
-    if (ok) { const float c_us = std::min(chain_us(cand[k]), chain_us(cand[k])); ok = c_us < 2.5f * base_us + 20.f; }
-    for (int q = 0; q < np && ok; ++q) ok = overlap(pick[q], cand[k]);
-    if (ok) { pick[np++] = cand[k]; usedc[k] = true; }
-  }
-  for (int k = 0; k < nc; ++k) { if (!usedc[k]) (void)hipStreamDestroy(cand[k]); else rt->seg_owned.push_back(cand[k]); }
-  // (fewer than three distinct queues found: lanes share a STREAM - never two streams of one queue, which the flag-synchronised
-  //  program could not survive: a polling kernel ahead of its signal in the same queue)
-  for (int q = 0; q < 3; ++q) rt->seg_lanes[q] = q < np ? pick[q] : (np > 0 ? pick[q % np] : main_s);
-  if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); if (eb) (void)hipEventDestroy(eb);
-}
-
-void Sched::init(nunet_plan* P, hipStream_t s, int pass_) {
-  const int pass = pass_;
-  this->pass = pass_;
-  cur_name[0] = 0;
-  rt = rt_of(P);
-  main_s = s;
-  {
-    static int want_stamps = -1;
-    if (want_stamps < 0) { const char* e = getenv("NUNET_STAMPS"); want_stamps = e ? atoi(e) : 0; }
-    hipStreamCaptureStatus cs0 = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &cs0);
-    if (want_stamps && !rt->stamps && cs0 != hipStreamCaptureStatusActive) {
-      if (hipMalloc((void**)&rt->stamps, 2 * STAMP_CAP * sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); rt->stamps = nullptr; }
-    }
-    rt->stamp_labels[pass].clear();
-    rt->census[pass].clear();
-    if (rt->stamps) { snprintf(cur_name, sizeof(cur_name), "start"); stamp(s, 0); cur_name[0] = 0; }
-  }
-  multi = rt->multistream != 0 && rt->lanes_ok && !rt->calibrating;
-  list = rt->schedule == NUNET_SCHEDULE_LIST && !rt->calibrating;
-  failed = false;
-  capturing = false;
-  prune = rt->wait_prune != 0; wp.reset(); stamp_of.clear();
-  pool = &rt->events[pass]; pool_used = &rt->events_used[pass];
-  *pool_used = 0;
-  memset(res, 0, sizeof(res));
-  cur_lane = 0; nreads = nwrites = 0; npend = 0;
-  fork_ev = nullptr;
-  if (multi) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) capturing = true;
-    else (void)hipGetLastError();
-    if (seg_active()) capturing = false;   // segmented recording: fixed lanes on real streams (the caller's stream is merely inside a segment)
-    if (!capturing && rt->cap_streams.empty()) {
-      // pool for later captures, created outside any capture (warm-up passes run eagerly first)
-      for (int k = 0; k < 320; ++k) {
-        hipStream_t q;
-        if (hipStreamCreateWithFlags(&q, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); break; }
-        rt->cap_streams.push_back(q);
-      }
-    }
-    if (capturing && (rt->cap_streams.empty())) multi = false;     // never warmed up eagerly: stay on one stream
-    if (capturing && pass == 0) rt->cap_next = 0;                   // forward + backward of one capture share the pool
-  }
-  // lane of (level 0..4, weight gradients of level 0..4): one lane per pyramid level, weight gradients on their
-  // block's lane (measured best on MI355X: separate weight-gradient lanes add cross-queue edges that cost more than the
-  // overlap they buy; the exception is the deferral of the shallow chain blocks' weight gradients, see the backward pass)
-  for (int l = 0; l < NLANES; ++l) { lane_map[l] = l % 5; lane_s[l] = capturing ? nullptr : rt->lanes[l]; used[l] = false; lane_tail[l] = nullptr; }
-  if (multi && seg_active()) {
-    // four real streams = ROCm's four hardware queues: the critical chain (lane 0) runs on the caller's stream itself - no
-    // fork / join edge on the chain -, the side lanes on three streams of the plan's, the deferred weight gradients share lane 3's
-    lane_s[0] = main_s; used[0] = true;
-    if (!rt->seg_lanes[0]) {
-      // (the dry pass of a recording comes first and captures nothing: the only moment the calibration kernels may run on `s`)
-      hipStreamCaptureStatus cs2 = hipStreamCaptureStatusNone;
-      (void)hipStreamIsCapturing(main_s, &cs2);
-      if (cs2 != hipStreamCaptureStatusActive) { const bool keep = g_dry_run; g_dry_run = false; seg_pick_lanes(rt, main_s); g_dry_run = keep; }
-      else for (int q = 0; q < 3; ++q) rt->seg_lanes[q] = rt->lanes[q + 1];
-    }
-    for (int q = 0; q < 3; ++q) lane_s[q + 1] = rt->seg_lanes[q];
-    // (the deferred weight gradients of the chain blocks go to the stream of lane 1: its own block, x0_1, is the LAST of the
-    //  level-0 row's backward chain B04 -> B03 -> B02 -> B01, so that stream idles for the first 500 us of the backward pass; on
-    //  lane 3's stream they sat in front of B03 and held the whole row back by 280 us)
-    lane_s[4] = lane_s[1];
-  }
-  if (multi) {
-    fork_ev = new_event();
-    record_on(fork_ev, main_s);
-    if (capturing) graph_tag_tail(main_s, -1);   // launches made so far on the caller's stream are not ours to place
-  }
-}
-
-// Issue the collected ops: op order[q] on lane lane[order[q]], for q = 0 .. n-1; stops at the first launch that fails.
-int Sched::issue(const int* order, const int* lane, int n) {
-  int rc = NUNET_OK;
-  for (int q = 0; q < n && rc == NUNET_OK; ++q) {
-    Op& o = ops[order[q]];
-    hipStream_t st = begin_v(lane[order[q]], o.rd, o.nrd, o.wr, o.nwr);
-    rc = o.fn(st);
-    memcpy(cur_name, o.name, sizeof(cur_name));
-    end();
-  }
-  ops.clear();
-  return rc;
-}
-
-int Sched::run_ops() {
-  // ops are issued in program order, each on its block's lane (a simulated list schedule and a rewrite of the captured graph's
-  // edge order were both measured slower than the plain capture order on ROCm 7.2, see DESIGN.md, and are not kept)
-  const int n = (int)ops.size();
-  std::vector<int> order(n), lane(n);
-  for (int i = 0; i < n; ++i) { order[i] = i; lane[i] = ops[i].lane; }
-  return issue(order.data(), lane.data(), n);
-}
-
-// List schedule: the lane of every op is CHOSEN here instead of following its block. The hazards of the program order (read after
-// write, write after write - the accumulation order into the shared gradient slots -, write after read) are the edges of a DAG;
-// ops are taken by critical-path priority (cost + longest path to the end) and each goes to the lane on which it can start
-// earliest in a simulation with the ops' cost estimates (a dependency that crosses lanes costs XSYNC), then issued in simulated
-// start order. Any topological order of that DAG keeps every conflicting pair in program order, so the resource tracker sees
-// the same hazards and the results are bit-identical to the block-lane schedule (tests assert it). Meant for lanes that are
-// real in-order streams (the flag-synchronised program), where the issue order on a lane IS its execution order: the
-// block-lane order put leaf work (weight gradients) in front of critical ops of the same lane.
-int Sched::run_list() {
-  const int n = (int)ops.size();
-  // three lanes: measured on MI355X (96x96 bs16, flag-synchronised lanes) 2 / 3 / 4 lanes = 8640 / 9270 / 8950 images/s - the fourth
-  // concurrent stream costs the critical chain more than its overlap buys; limiting the summed chip share of the concurrent ops
-  // instead (a capacity model over the launch grids) only lost: 1.5 / 2.0 / 2.5 / 3.0 full-chip ops at once = 6610 / 8480 / 8720 /
-  // 9260. A crossing dependency costs one sync kernel on each side (XSYNC; 0 / 3 / 10 us in the model: no difference).
-  constexpr int NL = 3; constexpr float XSYNC = 3.f;
-  std::vector<std::vector<int>> succ(n), pred(n);
-  std::vector<int> indeg(n, 0);
-  {
-    std::vector<int> lastw(NRES, -1);
-    std::vector<std::vector<int>> readers(NRES);
-    auto edge = [&](int a, int b) { if (a >= 0 && a != b && std::find(succ[a].begin(), succ[a].end(), b) == succ[a].end()) { succ[a].push_back(b); pred[b].push_back(a); ++indeg[b]; } };
-    for (int i = 0; i < n; ++i) {
-      const Op& o = ops[i];
-      for (int q = 0; q < o.nrd; ++q) edge(lastw[o.rd[q]], i);
-      for (int q = 0; q < o.nwr; ++q) { edge(lastw[o.wr[q]], i); for (int r : readers[o.wr[q]]) edge(r, i); }
-      for (int q = 0; q < o.nrd; ++q) readers[o.rd[q]].push_back(i);
-      for (int q = 0; q < o.nwr; ++q) { lastw[o.wr[q]] = i; readers[o.wr[q]].clear(); }
-    }
-  }
-  std::vector<float> prio(n, 0.f), tend(n, 0.f);
-  for (int i = n - 1; i >= 0; --i) { float m = 0.f; for (int s : succ[i]) m = std::max(m, prio[s]); prio[i] = ops[i].cost + m; }
-  // (measured, no effect or worse: a priority bias for the weight gradients (-100 / 0: the same, +300 us: -3 %), the cost of the
-  //  grid-starved levels 2-4 scaled by 1.5 / 2 / 3 as a model of their in-step inflation (-0.5 / -2 / -2 %): the isolated costs
-  //  schedule best)
-  std::vector<int> ready, lane(n, 0), order;
-  float lane_free[NL] = {0.f, 0.f, 0.f};
-  for (int i = 0; i < n; ++i) if (indeg[i] == 0) ready.push_back(i);
-  // event-driven: the lane that falls idle first takes the most urgent op that could start on it by then; when nothing could, the
-  // lane's clock moves on to the next moment something can (so leaf work fills the holes of a lane instead of queueing at its end)
-  auto est = [&](int p, int l) { float t = 0.f; for (int q : pred[p]) t = std::max(t, tend[q] + (lane[q] != l ? XSYNC : 0.f)); return t; };
-  int guard = 0;
-  while (!ready.empty() && guard++ < 100000) {
-    int l = 0;
-    for (int k = 1; k < NL; ++k) if (lane_free[k] < lane_free[l]) l = k;
-    const float T = lane_free[l];
-    int best = -1;
-    for (int q = 0; q < (int)ready.size(); ++q) {
-      if (est(ready[q], l) > T + 0.01f) continue;
-      if (best < 0 || prio[ready[q]] > prio[ready[best]] || (prio[ready[q]] == prio[ready[best]] && ready[q] < ready[best])) best = q;
-    }
-    if (best < 0) {
-      // nothing can start on this lane yet: wait for the earliest of (an op becoming startable here, another lane falling idle)
-      float nt = 1e30f;
-      for (int q : ready) nt = std::min(nt, est(q, l));
-      for (int k = 0; k < NL; ++k) if (k != l && lane_free[k] > T) nt = std::min(nt, lane_free[k]);
-      lane_free[l] = nt > T ? nt : T + 0.5f;
-      continue;
-    }
-    const int p = ready[best];
-    ready.erase(ready.begin() + best);
-    lane[p] = l; tend[p] = T + ops[p].cost; lane_free[l] = tend[p];
-    order.push_back(p);
-    for (int s2 : succ[p]) if (--indeg[s2] == 0) ready.push_back(s2);
-  }
-  if ((int)order.size() != n) { nunet_set_error("plan: list schedule placed %d of %d ops (dependency cycle)", (int)order.size(), n); ops.clear(); return NUNET_EINVAL; }
-  // issue in simulated start order (stable: a topological order of the hazard DAG)
-  std::vector<int> idx(order);
-  std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return tend[a] - ops[a].cost < tend[b] - ops[b].cost; });
-  // (the sort by start time keeps predecessors first: a successor starts at or after its predecessor's end)
-  {
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = getenv("NUNET_LIST_DEBUG"); dbg = e ? atoi(e) : 0; }
-    if (dbg && !g_dry_run) {
-      float mk = 0.f; for (int i = 0; i < n; ++i) mk = std::max(mk, tend[i]);
-      fprintf(stderr, "list schedule pass %d: %d ops, simulated makespan %.1f us, critical path %.1f us%s\n", pass, n, mk, n ? prio[0] : 0.f, rt->op_cost[pass & 1].empty() ? " (built-in costs)" : " (measured costs)");
-      if (dbg > 1) for (int i : idx) fprintf(stderr, "  %8.1f %6.1f  L%d %s\n", tend[i] - ops[i].cost, ops[i].cost, lane[i], ops[i].name);
-    }
-  }
-  return issue(idx.data(), lane.data(), n);
 }
 
 // Lane of a block. Crossing hardware queues costs 5-10 us of dispatch latency per dependency edge, so the assignment
@@ -1288,11 +384,55 @@ static int set_splitk(nunet_conv_desc& d, const nunet_plan* P, void* arena, int 
   if (n.sk_floats > 0) { d.splitk_ws = (float*)AB(arena, n.sk); d.splitk_ws_floats = n.sk_floats; }
   return n.sk_floats > 0 ? R_SK + k : -1;
 }
+// BatchNorm + ReLU of layer cv + 1 of block k (v: its forward view) as the stand-alone kernel runs it, into a of pitch PA; bnbuf /
+// nbt null: no running statistics. The caller adds the kernel's other outputs (pooled, up).
+static nunet_bn_fwd_desc bn_fwd_desc(const nunet_plan* P, const float* params, float* bnbuf, int64_t* nbt, int k, int cv, const BnView& v, int training, void* a, int PA) {
+  const Node& n = P->exec[k];
+  const ConvL& L = cv ? n.c2 : n.c1;
+  nunet_bn_fwd_desc b = level_desc<nunet_bn_fwd_desc>(P, n.i);
+  b.C = v.C;
+  b.y = v.y; b.PY = v.C; b.conv_bias = params + L.b_off; b.stats = v.fx;
+  b.gamma = v.gamma; b.beta = v.beta;
+  if (bnbuf) { b.running_mean = bnbuf + L.rm_off; b.running_var = bnbuf + L.rv_off; }
+  b.num_batches_tracked = nbt ? nbt + L.bn_index : nullptr;
+  b.save_mean_invstd = v.mean_invstd; b.training = training; b.momentum = 0.1f; b.eps = 1e-5f;
+  b.a = a; b.PA = PA;
+  return b;
+}
 
-// every plan entry that touches the arena checks what the caller says it owns against the plan's own layout
-#define ARENA_CHECK(what) \
-  NUNET_REQUIRE(arena_bytes >= P->total, what ": arena of %zu bytes, nunet_plan_arena_bytes() = %zu", (size_t)arena_bytes, P->total); \
-  NUNET_REQUIRE(((uintptr_t)arena & 255) == 0, what ": arena must be 256-byte aligned")
+// The facts of a forward pass that follow from the plan and from PlanRt's bn_up and head_bn - so they are worked out per pass, not
+// at creation. A head whose slot no block reads in the forward pass (the last head of a full plan, final<L> of a pruned one) takes
+// its block's BatchNorm2 + ReLU into its own launch (nunet_head_fwd_bn).
+struct FwdFacts {
+  int up_reader[NUNET_MAX_BLOCKS];   // the block that upsamples block k's output (-1: none)
+  int up_writer[NUNET_MAX_BLOCKS];   // the block whose output block k upsamples (-1: none)
+  bool up_in_bn[NUNET_MAX_BLOCKS];   // block k's BatchNorm2 launch writes that upsample for its reader
+  int head_block[NUNET_MAX_HEADS];   // the block whose BatchNorm2 + ReLU rides in head h's launch (-1: none)
+};
+static FwdFacts plan_forward_facts(const nunet_plan* P) {
+  FwdFacts F;
+  const PlanRt* const rt = P->rt;
+  const int nb = (int)P->exec.size();
+  for (int k = 0; k < nb; ++k) {
+    const Node& n = P->exec[k];
+    F.up_reader[k] = F.up_writer[k] = -1;
+    for (int q = nb - 1; q >= 0; --q)
+      if (P->exec[q].up_slot >= 0 && P->exec[q].i + 1 == n.i && P->exec[q].up_slot == n.out_slot) F.up_reader[k] = q;
+    for (int q = 0; q < k && n.up_slot >= 0; ++q)
+      if (P->exec[q].i == n.i + 1 && P->exec[q].out_slot == n.up_slot) F.up_writer[k] = q;
+    F.up_in_bn[k] = rt->bn_up != NUNET_BN_UP_NONE && F.up_reader[k] >= 0 &&
+                    (rt->bn_up == NUNET_BN_UP_ALL || P->cfg.unet || n.i + n.j == (P->depth ? P->depth : 4));   // _CHAIN: the row ends B40, B31, B22, B13
+  }
+  for (size_t h = 0; h < P->heads.size(); ++h) {
+    F.head_block[h] = -1;
+    if (!rt->head_bn) continue;
+    bool read = false;
+    for (const Node& q : P->exec) read |= q.i == 0 && q.in_prefix > P->heads[h].slot;
+    for (int k = 0; k < nb && !read; ++k)
+      if (P->exec[k].i == 0 && P->exec[k].out_slot == P->heads[h].slot && P->exec[k].in_prefix > 0) F.head_block[h] = k;
+  }
+  return F;
+}
 
 extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnbuf, int64_t* nbt, const float* input, void* arena, size_t arena_bytes, float* logits, int32_t training_flags, nunet_stream_t s) {
   const int32_t training = training_flags & 1;
@@ -1311,54 +451,27 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
   if (training) CK(nunet_zero_async(AB(arena, P->off_fx), 2 * fx_region_bytes(P), st));
   if (!staged) CK(nunet_nchw_to_nhwc(input, c.N, c.input_channels, c.H, c.W, dt, AB(arena, P->off_img), 32, (nunet_stream_t)st));
 
-  Sched S; S.init(P, st, 0);
+  Sched S; S.init(P->rt, st, 0);
   const bool skip_pack = (training_flags & 2) != 0;   // the caller vouches that nunet_plan_repack left the packed weights current
   if (!skip_pack) {
     S.name("pack");
-    S.add(0, 0, 15.f, {}, {R_WP + 0, R_WP + 1, R_WP + 2, R_WP + 3, R_WP + 4}, [=](hipStream_t ls) {
-      return NUNET_DISPATCH(dt, launch_pack, params, wpack, P->ptab, ls);
-    });
+    S.add(0, 0, 15.f, {}, {R_WP + 0, R_WP + 1, R_WP + 2, R_WP + 3, R_WP + 4}, [=](hipStream_t ls) { return plan_pack_weights(P, params, arena, ls); });
   }
   // (The x2 upsample of a block output can ride in the producer's BatchNorm launch as a second block role - nunet_bn_fwd_desc.up,
   // bit-identical; which producers do is rt->bn_up. Measured on MI355X under the flag-synchronised, list-scheduled executor, 96x96
   // batch 16 bf16, six alternating runs of 200 steps each: none / the chain's four row ends / all ten = 1.586 / 1.601 / 1.636 ms per
   // step (min-max spread of one configuration 0.012 ms); 256x256 batch 32: none / chain = 15.25 / 15.63 ms. The fused launch pays
   // the coefficient prologue in every upsample workgroup and holds the chain longer than the launch it saves: the default is none.)
-  const PlanRt* const prt = rt_of(P);
-  // the block that upsamples block k's output (-1: none), and whether k's BatchNorm2 launch does it for that block
-  auto up_reader = [&](int k) {
-    const Node& n = P->exec[k];
-    for (int q = 0; q < (int)P->exec.size(); ++q)
-      if (P->exec[q].up_slot >= 0 && P->exec[q].i + 1 == n.i && P->exec[q].up_slot == n.out_slot) return q;
-    return -1;
-  };
-  auto up_in_bn = [&](int k) {
-    const Node& n = P->exec[k];
-    if (prt->bn_up == NUNET_BN_UP_NONE || up_reader(k) < 0) return false;
-    return prt->bn_up == NUNET_BN_UP_ALL || P->cfg.unet || n.i + n.j == (P->depth ? P->depth : 4);   // _CHAIN: the row ends B40, B31, B22, B13
-  };
-  // A head whose slot no block reads in the forward pass (the last head of a full plan, final<L> of a pruned one) takes its
-  // block's BatchNorm2 + ReLU into its own launch (nunet_head_fwd_bn): head_block[k] = that block, or -1.
-  int head_block[NUNET_MAX_HEADS];
-  for (size_t h = 0; h < P->heads.size(); ++h) {
-    head_block[h] = -1;
-    if (!prt->head_bn) continue;
-    bool read = false;
-    for (const Node& q : P->exec) read |= q.i == 0 && q.in_prefix > P->heads[h].slot;
-    for (int k = 0; k < (int)P->exec.size() && !read; ++k)
-      if (P->exec[k].i == 0 && P->exec[k].out_slot == P->heads[h].slot && P->exec[k].in_prefix > 0) head_block[h] = k;
-  }
+  const FwdFacts F = plan_forward_facts(P);
   nunet_bn_fwd_desc head_bn[NUNET_MAX_HEADS];
   for (int k = 0; k < (int)P->exec.size(); ++k) {
     const Node& n = P->exec[k];
-    const int i = n.i, f = NBF[i], H = P->hl[i], W = P->wl[i];
-    const int lane = lane_of(P, n), rb = R_BLK + k * B_STRIDE;
+    const int i = n.i, f = NBF[i];
+    const int lane = lane_of(P, n);
     const Cat in = block_in(P, arena, k, false);
     const BnView bn1 = bn_view(P, arena, params, k, 0, 0), bn2 = bn_view(P, arena, params, k, 1, 0);
-    int up_writer = -1;      // the block whose output this one upsamples
-    for (int q = 0; q < k && n.up_slot >= 0; ++q)
-      if (P->exec[q].i == i + 1 && P->exec[q].out_slot == n.up_slot) up_writer = q;
-    if (n.up_slot >= 0 && !(up_writer >= 0 && up_reader(up_writer) == k && up_in_bn(up_writer))) {
+    const int uw = F.up_writer[k];
+    if (n.up_slot >= 0 && !(uw >= 0 && F.up_reader[uw] == k && F.up_in_bn[uw])) {
       const Buf x = slot_of(P, arena, false, i + 1, n.up_slot);
       S.name("B%d%d.upF", n.i, n.j);
       S.add(lane, 0, 7.f, {x.r}, {in.r[4]}, [=](hipStream_t ls) {
@@ -1367,8 +480,7 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
     }
     // ---- conv1: raw output y1 + its BatchNorm sums (fixed point) ---------------------------------------------
     {
-      nunet_conv_desc d; memset(&d, 0, sizeof(d));
-      d.dtype = dt; d.N = c.N; d.H = H; d.W = W;
+      nunet_conv_desc d = level_desc<nunet_conv_desc>(P, i);
       set_src(d, in);
       d.wpack = wpack + (size_t)n.c1.wf * es;
       d.bias = nullptr;  // absorbed by the BatchNorm that follows (bn_stat_coeffs)
@@ -1383,8 +495,7 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
     // its other reader, the weight gradient of conv2, forms it from y1 in its own loader (nunet_wgrad_desc.x_tf) --------
     {
       const ConvL& L = n.c2; const ConvL& L1 = n.c1;
-      nunet_conv_desc d; memset(&d, 0, sizeof(d));
-      d.dtype = dt; d.N = c.N; d.H = H; d.W = W;
+      nunet_conv_desc d = level_desc<nunet_conv_desc>(P, i);
       d.src0 = bn1.y; d.C0 = f; d.P0 = f;
       d.in_tf = NUNET_TF_BN_RELU; d.tf_training = training;
       d.tf_fx = training ? bn1.fx : nullptr;
@@ -1401,29 +512,21 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
     // ---- BatchNorm2 + ReLU (+ 2x2 max-pool for the encoder column): the block output has many consumers
     // (convs of the same level, the upsample, the pool, a head) and is materialised once in its level-buffer slot ------
     {
-      const ConvL& L = n.c2;
       const Buf out = slot_of(P, arena, false, i, n.out_slot);
-      nunet_bn_fwd_desc b; memset(&b, 0, sizeof(b));
-      b.dtype = dt; b.N = c.N; b.H = H; b.W = W; b.C = f;
-      b.y = bn2.y; b.PY = f; b.conv_bias = params + L.b_off; b.stats = bn2.fx;
-      b.gamma = bn2.gamma; b.beta = bn2.beta;
-      b.running_mean = bnbuf + L.rm_off; b.running_var = bnbuf + L.rv_off;
-      b.num_batches_tracked = nbt ? nbt + L.bn_index : nullptr;
-      b.save_mean_invstd = bn2.mean_invstd; b.training = training; b.momentum = 0.1f; b.eps = 1e-5f;
-      b.a = out.p; b.PA = P->PX[i];
+      nunet_bn_fwd_desc b = bn_fwd_desc(P, params, bnbuf, nbt, k, 1, bn2, training, out.p, P->PX[i]);
       int rpin = -1;
       if (n.in_prefix == 0 && i < 4) {  // encoder column: feed the next level (archs1.py:115,118,122,127)
         const int q = block_at(P, i + 1, 0);
         if (q >= 0) { const Cat nx = block_in(P, arena, q, false); b.pooled = nx.p[0]; b.PP = f; rpin = nx.r[0]; }
       }
       int rup = -1;
-      if (up_in_bn(k)) {                // the reader's upsampled input, written here instead of by its stand-alone launch
-        const Cat nx = block_in(P, arena, up_reader(k), false);
+      if (F.up_in_bn[k]) {              // the reader's upsampled input, written here instead of by its stand-alone launch
+        const Cat nx = block_in(P, arena, F.up_reader[k], false);
         b.up = nx.p[1]; b.PU = f; rup = nx.r[4];
       }
       bool in_head = false;
       for (size_t h = 0; h < P->heads.size(); ++h)
-        if (head_block[h] == k) { head_bn[h] = b; in_head = true; }
+        if (F.head_block[h] == k) { head_bn[h] = b; in_head = true; }
       if (in_head) continue;            // issued with the head below
       S.name("B%d%d.bnF2", n.i, n.j);
       S.add(lane, 0, 6.f, {bn2.r_y, bn2.r_fx}, {out.r, rpin, rup}, [=](hipStream_t ls) { return nunet_bn_relu_fwd(&b, ls); });
@@ -1434,10 +537,10 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
     const Head hd = P->heads[k];
     const Buf x = slot_of(P, arena, false, 0, hd.slot);
     S.name("head%d.F", (int)k);
-    if (head_block[k] >= 0) {
+    if (F.head_block[k] >= 0) {
       // (the union of the two launches' resource ids; the slot stays materialised for Plan.feature and the backward pass)
       const nunet_bn_fwd_desc b = head_bn[k];
-      const BnView bn2 = bn_view(P, arena, params, head_block[k], 1, 0);
+      const BnView bn2 = bn_view(P, arena, params, F.head_block[k], 1, 0);
       S.add(0, 0, 8.f, {bn2.r_y, bn2.r_fx}, {x.r, R_LOGITS + 0}, [=](hipStream_t ls) {
         return nunet_head_fwd_bn(&b, c.num_classes, params + hd.w_off, params + hd.b_off, logits + plane * k, ls);
       });
@@ -1447,10 +550,7 @@ extern "C" int nunet_plan_forward(nunet_plan* P, const float* params, float* bnb
       return nunet_head_fwd(dt, c.N, c.H, c.W, NBF[0], c.num_classes, x.p, P->PX[0], params + hd.w_off, params + hd.b_off, logits + plane * k, ls);
     });
   }
-  int rc = S.run();
-  S.join();  // always rejoin the caller's stream (also on error: a capture must not be left forked)
-  if (rc == NUNET_OK && S.failed) { nunet_set_error("plan_forward: lane scheduler overflow (capture stream pool / dependency lists)"); rc = NUNET_EINVAL; }
-  return rc;
+  return S.finish(S.run(), "plan_forward");
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1520,205 +620,6 @@ extern "C" int nunet_plan_grad_scratch(const nunet_plan* P, int64_t* byte_offset
   return NUNET_OK;
 }
 
-// Optimiser step straight from the gradient scratch: replaces nunet_plan_backward_phase bit 2 +
-// nunet_opt_step; the weights are repacked by the next nunet_plan_forward as usual.
-// unpack_tiled_kernel with the optimiser step as the epilogue of its store phase: the tile's gradients meet the OIHW
-// parameters and the optimiser state as 16-byte runs, the flat gradient arena is written only when the caller wants it.
-template <typename O>
-__global__ __launch_bounds__(256) void unpack_sgd_tiled_kernel(UpdP u, O o, PackTab tab, UnpackTab ut) {
-  __shared__ float s_t[32][TILE_LD];
-  float gs = u.gscale;
-  const bool live = o.begin(gs);   // false: a step skipped by loss scaling, which stores the unscaled gradients only
-  if (!live && !u.grads) return;
-  if ((int)blockIdx.x >= tab.ntiles) {
-    const UnpackEnt en = ut.e[(int)blockIdx.x - tab.ntiles];
-    tail_entry(en, u.scratch, &s_t[0][0], [&](int i, float g) { step_elem(u, o, live, gs, en.dst + i, g); });
-    return;
-  }
-  const Tile t = tile_of(tab, blockIdx.x);
-  if (t.cw <= 0) return;
-  const PackEnt en = tab.e[t.e];
-  const UnpackEnt ue = ut.e[t.e];
-  const long long row0 = ue.dst + ((long long)t.co0 * en.cin + t.ci0) * 9;
-  gather_scratch_tile(s_t, u.scratch + ue.src, en, t);
-  __syncthreads();
-  bool al = ((uintptr_t)(u.params + row0) & 15) == 0 && (!u.grads || ((uintptr_t)(u.grads + row0) & 15) == 0);
-#pragma unroll
-  for (int q = 0; q < O::NS; ++q) al = al && ((uintptr_t)(o.st[q] + row0) & 15) == 0;
-  if (t.rw == 32 && t.cw == 32 && en.cin % 4 == 0 && al) {
-    for (int i = threadIdx.x; i < 32 * 72; i += blockDim.x) {
-      const int ro = i / 72, k4 = i - ro * 72;
-      const long long idx = row0 + (long long)ro * en.cin * 9 + k4 * 4;
-      const float* sp = &s_t[ro][k4 * 4];
-      f32x4 g = {sp[0] * gs, sp[1] * gs, sp[2] * gs, sp[3] * gs};
-      if (!live) {
-        *reinterpret_cast<f32x4*>(u.grads + idx) = g;
-        continue;
-      }
-      f32x4 pv = *reinterpret_cast<const f32x4*>(u.params + idx);
-      f32x4 sv[O::NS];
-#pragma unroll
-      for (int q = 0; q < O::NS; ++q) sv[q] = *reinterpret_cast<const f32x4*>(o.st[q] + idx);
-      if (u.grads) *reinterpret_cast<f32x4*>(u.grads + idx) = g;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float s[O::NS];
-#pragma unroll
-        for (int q = 0; q < O::NS; ++q) s[q] = sv[q][j];
-        pv[j] = o.one(pv[j], g[j], s);
-#pragma unroll
-        for (int q = 0; q < O::NS; ++q) sv[q][j] = s[q];
-      }
-#pragma unroll
-      for (int q = 0; q < O::NS; ++q) *reinterpret_cast<f32x4*>(o.st[q] + idx) = sv[q];
-      *reinterpret_cast<f32x4*>(u.params + idx) = pv;
-    }
-  } else {
-    for (int i = threadIdx.x; i < 32 * 288; i += blockDim.x) {
-      const int ro = i / 288, k = i - ro * 288;
-      if (ro < t.rw && k < t.cw * 9) step_elem(u, o, live, gs, row0 + (long long)ro * en.cin * 9 + k, s_t[ro][k]);
-    }
-  }
-}
-
-template <typename O> static int launch_unpack_step(nunet_plan* P, void* arena, float* params, const O& o, float grad_scale, float* grads,
-                                                    double bytes, hipStream_t st) {
-  UpdP u;
-  u.params = params; u.scratch = (const float*)AB(arena, P->off_gs); u.grads = grads;
-  u.gscale = grad_scale;
-  ProfScope ps(PC_SGD, 0, bytes, st);
-  NUNET_LAUNCH((unpack_sgd_tiled_kernel<O>), dim3(P->ptab.ntiles + P->utab.n), dim3(256), 0, st, u, o, P->ptab, P->utab);
-  return nunet_check_launch("plan_opt_step");
-}
-
-// The fused step on the plan's own buffers with any optimiser, gradient scratch -> step -> fp32 master parameters
-// (unpack_sgd_tiled_kernel; the next forward repacks). `grads` (flat OIHW arena) is optional: when given it receives the
-// (scaled) gradients as nunet_plan_backward would have left them. Adam streams its second state buffer on top.
-extern "C" int nunet_plan_opt_step(nunet_plan* P, float* params, const nunet_optim* opt, void* arena, size_t arena_bytes, float grad_scale,
-                                   float* grads, nunet_stream_t s) {
-  NUNET_REQUIRE(P, "plan_opt_step: null plan");
-  CK(opt_check(opt, "plan_opt_step", true));      // (the caller's descriptor first: a bad one is reported whatever the plan is)
-  REFUSE_PRUNED("plan_opt_step");
-  NUNET_REQUIRE(params && arena, "plan_opt_step: null pointer");
-  ARENA_CHECK("plan_opt_step");
-  return opt_dispatch(opt, [&](const auto& o) {
-    const double bytes = (double)P->nparams * (20.0 + (grads ? 4.0 : 0.0) + 8.0 * (o.NS - 1));
-    return launch_unpack_step(P, arena, params, o, grad_scale, grads, bytes, (hipStream_t)s);
-  });
-}
-
-// Square norm of the gradient scratch for gradient clipping (include/nunet.h nunet_clip): the unpack kernels'
-// block -> (layer, 32 x 32 tile | vector tail | head) map, read-only. A conv tile sums the squares of its real [tap][co][ci]
-// entries (ci < cin: the padding up to cinpad does not count) straight from the scratch, 16-byte loads along ci; a tail block
-// takes the layer's conv bias, gamma and beta; a head block sums the slabs first (head_slab_sum, so in unpack_sgd_tiled_kernel's order) and
-// squares the sum. Products exact in double, a thread's elements in index order, then block256_sum_f64: one partial per
-// workgroup, plain store (a pure-padding tile stores 0).
-__global__ __launch_bounds__(256) void plan_sqnorm_kernel(const float* __restrict__ scratch, PackTab tab, UnpackTab ut, double* __restrict__ ws) {
-  __shared__ float s_p[256];
-  __shared__ double s_w[4];
-  double acc = 0.0;
-  if ((int)blockIdx.x >= tab.ntiles) {
-    tail_entry(ut.e[(int)blockIdx.x - tab.ntiles], scratch, s_p, [&](int, float g) { acc += (double)g * (double)g; });
-  } else {
-    const Tile t = tile_of(tab, blockIdx.x);
-    const PackEnt en = tab.e[t.e];
-    const float* dw = scratch + ut.e[t.e].src;
-    if (t.cw > 0 && en.cinpad % 4 == 0 && ((uintptr_t)dw & 15) == 0) {
-      for (int i = threadIdx.x; i < 9 * 32 * 8; i += blockDim.x) {
-        const int c4 = i & 7, ro = (i >> 3) & 31, tap = i >> 8;
-        if (ro >= t.rw || c4 * 4 >= t.cw) continue;      // (t.ci0 + c4 * 4 < cin <= cinpad, a multiple of 4: the run is inside the row)
-        const f32x4 v = *reinterpret_cast<const f32x4*>(dw + ((long long)tap * en.cout + t.co0 + ro) * en.cinpad + t.ci0 + c4 * 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (c4 * 4 + j < t.cw) acc += (double)v[j] * (double)v[j];
-      }
-    } else if (t.cw > 0) {
-      for (int i = threadIdx.x; i < 9 * 32 * 32; i += blockDim.x) {
-        const int ci = i & 31, ro = (i >> 5) & 31, tap = i >> 10;
-        if (ro < t.rw && ci < t.cw) {
-          const float v = dw[((long long)tap * en.cout + t.co0 + ro) * en.cinpad + t.ci0 + ci];
-          acc += (double)v * (double)v;
-        }
-      }
-    }
-  }
-  const double tot = block256_sum_f64(acc, s_w);
-  if (threadIdx.x == 0) ws[blockIdx.x] = tot;
-}
-extern "C" size_t nunet_plan_grad_sqnorm_ws_bytes(const nunet_plan* P) { return (P && !P->depth) ? (size_t)(P->ptab.ntiles + P->utab.n) * sizeof(double) : 0; }
-extern "C" int nunet_plan_grad_sqnorm(nunet_plan* P, const void* arena, size_t arena_bytes, double* ws, size_t ws_bytes, nunet_stream_t s) {
-  NUNET_REQUIRE(P, "plan_grad_sqnorm: null plan");
-  REFUSE_PRUNED("plan_grad_sqnorm");
-  NUNET_REQUIRE(arena && ws, "plan_grad_sqnorm: null pointer");
-  ARENA_CHECK("plan_grad_sqnorm");
-  NUNET_REQUIRE(((uintptr_t)ws & 7) == 0, "plan_grad_sqnorm: ws must be 8-byte aligned");
-  NUNET_REQUIRE(ws_bytes >= nunet_plan_grad_sqnorm_ws_bytes(P), "plan_grad_sqnorm: workspace of %zu bytes, nunet_plan_grad_sqnorm_ws_bytes = %zu",
-                ws_bytes, nunet_plan_grad_sqnorm_ws_bytes(P));
-  ProfScope ps(PC_SGD, 0, (double)P->nparams * 4, (hipStream_t)s);
-  NUNET_LAUNCH(plan_sqnorm_kernel, dim3(P->ptab.ntiles + P->utab.n), dim3(256), 0, (hipStream_t)s,
-               (const float*)AB(const_cast<void*>(arena), P->off_gs), P->ptab, P->utab, ws);
-  return nunet_check_launch("plan_grad_sqnorm");
-}
-
-// Repack the 16-bit weight layouts from the fp32 master parameters (what nunet_plan_forward does first unless told
-// that they are current): needed before a forward that is told so (bit 1 of its `training` flags).
-extern "C" int nunet_plan_repack(nunet_plan* P, const float* params, void* arena, size_t arena_bytes, nunet_stream_t s) {
-  NUNET_REQUIRE(P && params && arena, "plan_repack: null pointer");
-  ARENA_CHECK("plan_repack");
-  char* wpack = AB(arena, P->off_wpack);
-  return NUNET_DISPATCH(P->cfg.dtype, launch_pack, params, wpack, P->ptab, (hipStream_t)s);
-}
-
-// Sum of the weight gradients' K-split slabs into the native-layout gradient scratch, all layers of a phase in one
-// launch. A block owns 64 float4 outputs of one layer; thread (part, e) adds slabs part, part + 4, ... in order, the
-// four parts meet in LDS in order: a fixed summation tree, so the gradient is bit-identical from run to run.
-#define MAXRED 40
-struct RedEnt { long long slab, dst, stride, n4; int ks, blk0; };
-struct RedTab { int n, nblocks; RedEnt e[MAXRED]; };
-__global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ slabs, float* __restrict__ gs, RedTab tab) {
-  __shared__ f32x4 s_p[4][64];
-  int e = 0;
-  while (e + 1 < tab.n && (int)blockIdx.x >= tab.e[e + 1].blk0) ++e;
-  const RedEnt en = tab.e[e];
-  const int part = threadIdx.x >> 6, el = threadIdx.x & 63;
-  const long long i = ((long long)blockIdx.x - en.blk0) * 64 + el;
-  f32x4 a = {0.f, 0.f, 0.f, 0.f};
-  if (i < en.n4) {
-    const float* q = slabs + en.slab + i * 4;
-#pragma unroll 4
-    for (int sl = part; sl < en.ks; sl += 4) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(q + (size_t)sl * en.stride);
-      a[0] += v[0]; a[1] += v[1]; a[2] += v[2]; a[3] += v[3];
-    }
-  }
-  s_p[part][el] = a;
-  __syncthreads();
-  if (part == 0 && i < en.n4) {
-    f32x4 r = s_p[0][el];
-#pragma unroll
-    for (int q = 1; q < 4; ++q) { const f32x4 v = s_p[q][el]; r[0] += v[0]; r[1] += v[1]; r[2] += v[2]; r[3] += v[3]; }
-    *reinterpret_cast<f32x4*>(gs + en.dst + i * 4) = r;
-  }
-}
-// layers of exec nodes [k_lo, k_hi] whose gradient was split (ks > 1; unsplit layers write the scratch directly)
-static int launch_reduce(nunet_plan* P, void* arena, int k_lo, int k_hi, hipStream_t st) {
-  RedTab tab; tab.n = 0; tab.nblocks = 0;
-  double bytes = 0;
-  for (int k = k_hi; k >= k_lo; --k)
-    for (int cv = 1; cv >= 0; --cv) {
-      const ConvL& c = cv ? P->exec[k].c2 : P->exec[k].c1;
-      if (c.ks <= 1) continue;
-      RedEnt& en = tab.e[tab.n++];
-      en.slab = c.slab; en.dst = c.gs; en.stride = 9LL * c.cout * c.cinpad; en.n4 = en.stride / 4; en.ks = c.ks; en.blk0 = tab.nblocks;
-      tab.nblocks += (int)((en.n4 + 63) / 64);
-      bytes += (double)en.stride * 4 * (c.ks + 1);
-    }
-  if (tab.n == 0) return NUNET_OK;
-  ProfScope ps(PC_UNPACK, 0, bytes, st);
-  NUNET_LAUNCH(reduce_kernel, dim3(tab.nblocks), dim3(256), 0, st, (const float*)AB(arena, P->off_slab), (float*)AB(arena, P->off_gs), tab);
-  return nunet_check_launch("wgrad slab reduce");
-}
-
 // phases (bit 0 = heads and the last anti-diagonal's blocks, 75 % of the gradient bytes; bit 1 = the remaining blocks; bit 2 = unpack
 // into the flat OIHW gradient arena; bit 3 = leave the pass open; bit 4 = continue the open pass) - five values, any other is refused:
 //   3     whole pass                    7      whole pass + unpack (nunet_plan_backward)        4   unpack only
@@ -1747,16 +648,16 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
   // the end. Together they let a data-parallel caller put the first bucket's exchange BESIDE phase 2 inside one captured graph
   // without a fork / join barrier between the phases.
   const bool leave_open = (phases & 8) != 0, cont = (phases & 16) != 0;
-  PlanRt* const rt = rt_of(P);
+  PlanRt* const rt = P->rt;
   NUNET_REQUIRE(!cont || rt->open_sched, "plan_backward: phase bit 4 (continue) without an open pass");
   NUNET_REQUIRE(!(leave_open && (phases & 4)), "plan_backward: an open pass cannot unpack (bit 2)");
-  if (!cont && rt->open_sched) { sched_free(rt->open_sched); rt->open_sched = nullptr; }     // an abandoned open pass
+  if (!cont && rt->open_sched) { delete rt->open_sched; rt->open_sched = nullptr; }     // an abandoned open pass
   Sched* const Sp = cont ? rt->open_sched : new Sched();
   Sched& S = *Sp;
-  if (!cont) S.init(P, st, 1);
+  if (!cont) S.init(rt, st, 1);
   else NUNET_REQUIRE(S.main_s == st, "plan_backward: continue on the stream the open pass was started on");
   rt->open_sched = nullptr;
-  struct Owner { Sched* s; PlanRt* rt; bool keep; ~Owner() { if (keep) rt->open_sched = s; else sched_free(s); } } owner{Sp, rt, false};
+  struct Owner { Sched* s; PlanRt* rt; bool keep; ~Owner() { if (keep) rt->open_sched = s; else delete s; } } owner{Sp, rt, false};
   const long long plane = (long long)c.N * c.num_classes * c.H * c.W;
   for (size_t k = 0; k < P->heads.size() && (phases & 1); ++k) {
     const Head h = P->heads[k];
@@ -1797,8 +698,8 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
     // ---- BatchNorm2 + ReLU backward, REDUCE pass: sum dz, sum dz * xhat over the block-output gradient (which several
     // consumers accumulated into its level-buffer slot) -> fixed-point sums; not when a head backward took it
     if (!n.bn2_in_head) {
-      nunet_bn_bwd_desc b2; memset(&b2, 0, sizeof(b2));
-      b2.dtype = dt; b2.N = c.N; b2.H = H; b2.W = W; b2.C = f;
+      nunet_bn_bwd_desc b2 = level_desc<nunet_bn_bwd_desc>(P, i);
+      b2.C = f;
       b2.da = gxo.p; b2.PDA = P->PX[i]; set_bn(b2, bn2);
       S.name("B%d%d.bnR2", n.i, n.j);
       S.add(lane, 0, 9.f, {gxo.r, bn2.r_y}, {bn2.r_fx}, [=](hipStream_t ls) { return nunet_bn_relu_bwd_reduce(&b2, ls); });
@@ -1808,8 +709,7 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
     // side for the weight gradient unless that forms it itself); the epilogue takes BatchNorm1's reduce pass on the da1 it
     // stores (archs1.py:23-30)
     {
-      nunet_conv_desc d; memset(&d, 0, sizeof(d));
-      d.dtype = dt; d.N = c.N; d.H = H; d.W = W;
+      nunet_conv_desc d = level_desc<nunet_conv_desc>(P, i);
       d.src0 = gxo.p; d.C0 = f; d.P0 = P->PX[i];
       set_tf_bn_bwd(d, bn2);
       d.tf_store = dy2_in_wgrad ? nullptr : dy2.p; d.tf_ps = f;
@@ -1825,8 +725,7 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
     // (and the three small gradient vectors of BatchNorm1) are taken by its weight gradient's loader
     if (has_dgrad1) {
       const Cat g = block_in(P, arena, k, true);
-      nunet_conv_desc d; memset(&d, 0, sizeof(d));
-      d.dtype = dt; d.N = c.N; d.H = H; d.W = W;
+      nunet_conv_desc d = level_desc<nunet_conv_desc>(P, i);
       d.src0 = da1.p; d.C0 = f; d.P0 = f;
       set_tf_bn_bwd(d, bn1);
       d.tf_store = dy1_in_wgrad ? nullptr : dy1.p; d.tf_ps = f;
@@ -1857,8 +756,7 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
     // reads them); conv1's problem first: it may carry the first layer's algorithmic Cin for the profiler
     {
       const Cat in = block_in(P, arena, k, false);
-      nunet_wgrad_desc w1, w2; memset(&w1, 0, sizeof(w1)); memset(&w2, 0, sizeof(w2));
-      w1.dtype = w2.dtype = dt; w1.N = w2.N = c.N; w1.H = w2.H = H; w1.W = w2.W = W;
+      nunet_wgrad_desc w1 = level_desc<nunet_wgrad_desc>(P, i), w2 = w1;
       // conv2's input a1 = relu(bn1(y1)), formed in the loader from the raw y1 and the statistics the forward saved
       w2.src0 = bn1.y; w2.C0 = f; w2.P0 = f;
       w2.x_tf = NUNET_TF_BN_RELU; w2.x_mean_invstd = bn1.mean_invstd; w2.x_gamma = bn1.gamma; w2.x_beta = bn1.beta;
@@ -1912,14 +810,10 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
     owner.keep = true;
     return NUNET_OK;
   }
-  S.join();
-  if (rc == NUNET_OK && S.failed) { nunet_set_error("plan_backward: lane scheduler overflow (capture stream pool / dependency lists)"); rc = NUNET_EINVAL; }
+  rc = S.finish(rc, "plan_backward");
   if (rc) return rc;
   if (!(phases & 4)) return NUNET_OK;
-  P->utab.accumulate = accumulate;
-  ProfScope ps(PC_UNPACK, 0, (double)P->nparams * (accumulate ? 12 : 8), st);
-  NUNET_LAUNCH(unpack_tiled_kernel, dim3(P->ptab.ntiles + P->utab.n), dim3(256), 0, st, gsr, grads, P->ptab, P->utab);
-  return nunet_check_launch("unpack_grads");
+  return plan_unpack_grads(P, arena, grads, accumulate, st);
 }
 
 // Data-parallel exchange beside the backward pass: with the pass left open (phases 1|8), `s` waits for the kernels that complete
@@ -1928,15 +822,15 @@ extern "C" int nunet_plan_backward_phase(nunet_plan* P, const float* params, con
 extern "C" int nunet_plan_bucket0_wait(nunet_plan* P, nunet_stream_t s) {
   NUNET_REQUIRE(P, "plan_bucket0_wait: null plan");
   REFUSE_PRUNED("plan_bucket0_wait");
-  NUNET_REQUIRE(rt_of(P)->open_sched, "plan_bucket0_wait: no open pass (nunet_plan_backward_phase 1|8 comes first)");
-  for (hipEvent_t e : rt_of(P)->b0_events)
+  NUNET_REQUIRE(P->rt->open_sched, "plan_bucket0_wait: no open pass (nunet_plan_backward_phase 1|8 comes first)");
+  for (hipEvent_t e : P->rt->b0_events)
     if (hipStreamWaitEvent((hipStream_t)s, e, 0) != hipSuccess) { nunet_set_error("plan_bucket0_wait: %s", hipGetErrorString(hipGetLastError())); return NUNET_ELAUNCH; }
   return NUNET_OK;
 }
 
 extern "C" int nunet_plan_stamps_read(nunet_plan* P, int32_t pass, uint64_t* ticks, int32_t cap, int32_t* n_out, char* labels, int32_t label_bytes) {
   NUNET_REQUIRE(P && ticks && n_out && labels && (pass == 0 || pass == 1) && label_bytes > 0, "plan_stamps_read: bad args");
-  PlanRt* rt = rt_of(P);
+  PlanRt* rt = P->rt;
   *n_out = 0; labels[0] = 0;
   if (!rt->stamps) return NUNET_OK;                    // NUNET_STAMPS not set
   const std::vector<std::string>& lab = rt->stamp_labels[pass];
@@ -1965,20 +859,20 @@ extern "C" int nunet_plan_stamps_read(nunet_plan* P, int32_t pass, uint64_t* tic
 // the streams live on; it just keeps its lanes.
 extern "C" int nunet_plan_reset_lanes(nunet_plan* P) {
   NUNET_REQUIRE(P, "plan_reset_lanes: null plan");
-  PlanRt* rt = rt_of(P);
+  PlanRt* rt = P->rt;
   rt->seg_lanes[0] = rt->seg_lanes[1] = rt->seg_lanes[2] = nullptr;
   return NUNET_OK;
 }
 
 extern "C" int nunet_plan_set_lane_priority(nunet_plan* P, int32_t lowest) {
   NUNET_REQUIRE(P, "plan_set_lane_priority: null plan");
-  rt_of(P)->lane_low_priority = lowest ? 1 : 0;
+  P->rt->lane_low_priority = lowest ? 1 : 0;
   return NUNET_OK;
 }
 
 extern "C" int nunet_plan_calibrate(nunet_plan* P, int32_t begin) {
   NUNET_REQUIRE(P, "plan_calibrate: null plan");
-  PlanRt* rt = rt_of(P);
+  PlanRt* rt = P->rt;
   if (begin) {
     if (!rt->stamps && hipMalloc((void**)&rt->stamps, 2 * STAMP_CAP * sizeof(unsigned long long)) != hipSuccess) {
       (void)hipGetLastError(); rt->stamps = nullptr;
@@ -2013,15 +907,9 @@ extern "C" int nunet_plan_calibrate(nunet_plan* P, int32_t begin) {
   return rc;
 }
 
-extern "C" int nunet_debug_stamp(uint64_t* dst, nunet_stream_t s) {
-  NUNET_REQUIRE(dst, "debug_stamp: null pointer");
-  NUNET_LAUNCH(stamp_kernel, dim3(1), dim3(1), 0, (hipStream_t)s, (unsigned long long*)dst);
-  return nunet_check_launch("debug_stamp");
-}
-
 extern "C" int nunet_plan_set_lanes(nunet_plan* P, nunet_stream_t* lanes, int32_t n) {
   NUNET_REQUIRE(P && lanes && n >= 1, "plan_set_lanes: bad args");
-  PlanRt* rt = rt_of(P);
+  PlanRt* rt = P->rt;
   for (int l = 0; l < NLANES; ++l) rt->lanes[l] = (hipStream_t)lanes[l % n];   // caller-owned streams
   rt->lanes_ok = true;
   rt->lanes_external = true;
@@ -2032,7 +920,7 @@ extern "C" int nunet_plan_set_schedule(nunet_plan* P, int32_t schedule) {
   NUNET_REQUIRE(P, "plan_set_schedule: null plan");
   NUNET_REQUIRE(schedule == NUNET_SCHEDULE_LANES || schedule == NUNET_SCHEDULE_LIST,
                 "plan_set_schedule: schedule %d is neither NUNET_SCHEDULE_LANES (0) nor NUNET_SCHEDULE_LIST (2)", schedule);
-  rt_of(P)->schedule = schedule;
+  P->rt->schedule = schedule;
   return NUNET_OK;
 }
 
@@ -2040,8 +928,8 @@ extern "C" int nunet_plan_set_wgrad_dy(nunet_plan* P, int32_t in_loader) {
   NUNET_REQUIRE(P, "plan_set_wgrad_dy: null plan");
   REFUSE_PRUNED("plan_set_wgrad_dy");
   NUNET_REQUIRE(in_loader == 0 || in_loader == 1, "plan_set_wgrad_dy: %d is neither 0 (side stores) nor 1 (weight-gradient loaders)", in_loader);
-  NUNET_REQUIRE(!rt_of(P)->open_sched, "plan_set_wgrad_dy: a backward pass is open (nunet_plan_backward_phase 1|8): its second phase reads what the first stored");
-  rt_of(P)->wgrad_dy = in_loader;
+  NUNET_REQUIRE(!P->rt->open_sched, "plan_set_wgrad_dy: a backward pass is open (nunet_plan_backward_phase 1|8): its second phase reads what the first stored");
+  P->rt->wgrad_dy = in_loader;
   return NUNET_OK;
 }
 
@@ -2054,21 +942,13 @@ extern "C" int nunet_plan_block_act1(nunet_plan* P, const float* params, void* a
   ARENA_CHECK("plan_block_act1");
   const int k = block_at(P, i, j);
   NUNET_REQUIRE(k >= 0, "plan_block_act1: the plan has no block (%d, %d)", (int)i, (int)j);
-  const nunet_plan_cfg& c = P->cfg;
-  const Node& n = P->exec[k];
-  const BnView bn1 = bn_view(P, arena, params, k, 0, 0);
-  nunet_bn_fwd_desc b; memset(&b, 0, sizeof(b));
-  b.dtype = c.dtype; b.N = c.N; b.H = P->hl[i]; b.W = P->wl[i]; b.C = NBF[i];
-  b.y = bn1.y; b.PY = NBF[i]; b.conv_bias = params + n.c1.b_off; b.stats = bn1.fx;
-  b.gamma = bn1.gamma; b.beta = bn1.beta;
-  b.save_mean_invstd = bn1.mean_invstd; b.training = 1; b.momentum = 0.1f; b.eps = 1e-5f;
-  b.a = out; b.PA = NBF[i];
+  const nunet_bn_fwd_desc b = bn_fwd_desc(P, params, nullptr, nullptr, k, 0, bn_view(P, arena, params, k, 0, 0), 1, out, NBF[i]);
   return nunet_bn_relu_fwd(&b, s);
 }
 
 extern "C" int nunet_plan_set_multistream(nunet_plan* P, int32_t enable) {
   NUNET_REQUIRE(P, "plan_set_multistream: null plan");
-  rt_of(P)->multistream = enable;
+  P->rt->multistream = enable;
   return NUNET_OK;
 }
 
@@ -2076,19 +956,19 @@ extern "C" int nunet_plan_set_multistream(nunet_plan* P, int32_t enable) {
 extern "C" int nunet_plan_set_head_bn(nunet_plan* P, int32_t enable) {
   NUNET_REQUIRE(P, "plan_set_head_bn: null plan");
   NUNET_REQUIRE(enable == 0 || enable == 1, "plan_set_head_bn: %d is neither 0 (two launches) nor 1 (nunet_head_fwd_bn)", enable);
-  rt_of(P)->head_bn = enable;
+  P->rt->head_bn = enable;
   return NUNET_OK;
 }
 extern "C" int nunet_plan_set_bn_up(nunet_plan* P, int32_t mode) {
   NUNET_REQUIRE(P, "plan_set_bn_up: null plan");
   NUNET_REQUIRE(mode >= NUNET_BN_UP_NONE && mode <= NUNET_BN_UP_ALL, "plan_set_bn_up: %d is not one of NUNET_BN_UP_NONE (0), _CHAIN (1), _ALL (2)", mode);
-  rt_of(P)->bn_up = mode;
+  P->rt->bn_up = mode;
   return NUNET_OK;
 }
 extern "C" int nunet_plan_set_wait_prune(nunet_plan* P, int32_t enable) {
   NUNET_REQUIRE(P, "plan_set_wait_prune: null plan");
   NUNET_REQUIRE(enable == 0 || enable == 1, "plan_set_wait_prune: %d is neither 0 (every requested wait) nor 1 (implied waits dropped)", enable);
-  NUNET_REQUIRE(!rt_of(P)->open_sched, "plan_set_wait_prune: a backward pass is open (nunet_plan_backward_phase 1|8)");
-  rt_of(P)->wait_prune = enable;
+  NUNET_REQUIRE(!P->rt->open_sched, "plan_set_wait_prune: a backward pass is open (nunet_plan_backward_phase 1|8)");
+  P->rt->wait_prune = enable;
   return NUNET_OK;
 }

@@ -1,7 +1,7 @@
 """Stream-capture regression (ROCm 7.2): a capturing stream that waits on an event DESCENDING from its own tail node
 crashes hipStreamEndCapture (a host segfault, round-1 record gpurun_out/ms_test.log). The plan's lane scheduler never
 produces that pattern: while capturing, a lane with cross-lane waits continues on a never-used stream
-(csrc/plan.hip Sched::begin_v). These tests run in a CHILD process, so that a scheduler change which re-introduces the
+(csrc/sched.hip Sched::begin_v). These tests run in a CHILD process, so that a scheduler change which re-introduces the
 pattern fails a test instead of taking the pytest process down."""
 import os
 import subprocess

@@ -562,7 +562,7 @@ def test_fused_update_equals_unpack_sgd_pack(dtype, mode, synth):
 
 
 def _head_slab_sum_host(slabs, B):
-    """The documented order of the 1x1 head's slab sum for a block of B threads (plan.hip head_slab_sum), in float32 with
+    """The documented order of the 1x1 head's slab sum for a block of B threads (weights.hip head_slab_sum), in float32 with
     sequential adds: elements in chunks of B; in a chunk of ne elements parts = B // ne threads share an element, thread
     (part, e) adds slabs part, part + parts, ... in order from 0, and the parts are added in order 0 .. parts - 1 from 0."""
     nslab, tot = slabs.shape

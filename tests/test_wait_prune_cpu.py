@@ -1,4 +1,4 @@
-"""The lane scheduler's wait pruning (csrc/plan.hip, WaitPruner) through its host-only entry nunet_wait_prune_host, on seeded
+"""The lane scheduler's wait pruning (csrc/sched.h, WaitPruner) through its host-only entry nunet_wait_prune_host, on seeded
 random DAGs: what it keeps is a subset of what was asked, and every requested cross-lane dependency is still enforced by
 lane order plus the kept waits. No GPU."""
 import ctypes as C

@@ -5,7 +5,7 @@ set -e
 cd "$(dirname "$0")/.."
 mkdir -p tools/_diag
 S=pytorch_nested-unet_amd/csrc
-for f in conv3x3 elementwise plan prof lovasz graph tiles pipeline; do
+for f in conv3x3 elementwise loss tta plan weights sched prof lovasz graph tiles pipeline; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DNUNET_KSTAMP -Wno-unused-variable -c $S/$f.hip -o tools/_diag/$f.o &
 done
 wait
